@@ -2,6 +2,18 @@
 """bench.py -- MSM + NTT throughput of the halo2 hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--curve pallas|bn254|vesta] [--workload ...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step and the roofline of the timed
+region).  Everything else -- the sharded-vs-whole check and its timing (N > 1), phases_ms / overlap / roofline_ntt,
+two_steps_in_flight, the modmul ceiling, cpu_baseline, the sub-records and proof_gen -- runs only with --full (and there
+the --no-* options drop parts of it); the line keeps those keys, null in a plain run.
+
+--dump-outputs DIR writes what the last timed step computed, rank 0's view, as float64 arrays of 32-bit words
+(little-endian, exact): DIR/commitments.npy = the step's MSM results in column order as affine (x, y), canonical
+integers, (columns, 16) with (0, 0) for the identity; DIR/ntt_<group>.npy = the transformed columns of each NTT group
+(in place, so after warmup + steps transforms), a fixed sample of DUMP_ROWS rows (numpy default_rng(DUMP_SEED + j)
+over group j's rows, sorted) as canonical integers out of Montgomery form, (rows, 8).
 
 One "step" = one pass of the hot path over the MSM/NTT calls of ONE Poseidon k=16 proof
 (BASELINE.json metric "MSM+NTT field-ops/s ... Poseidon k=16"; call counts from SURVEY.md
@@ -50,6 +62,7 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
 # multiply-adds of one mixed XYZZ addition in units of a full product's 117 (Pasta): 6 products + 2 squarings (81) + y3's
 # two products with one reduction (198) = 1062 / 117
 PRODUCT_EQUIVALENTS_PER_ADD = (6 * 117 + 2 * 81 + 198) / 117.0
+DUMP_ROWS, DUMP_SEED = 16384, 0x48324D53   # --dump-outputs: rows sampled per NTT group
 
 
 def ops_msm(n):
@@ -156,6 +169,31 @@ BASE_FIELD = {"bn254": 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C1
               "pallas": MODULI["pasta_fp"], "vesta": MODULI["pasta_fq"]}
 
 
+def words32(values):
+    """list of non-negative ints < 2^256 -> (len, 8) float64 of their 32-bit words, least significant first (exact)"""
+    return np.array([[(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] for v in values], dtype=np.float64).reshape(-1, 8)
+
+
+def dump_outputs(out_dir, results, ntt_bufs, ntt_names, q, p):
+    """--dump-outputs: the last timed step's commitments and transformed columns (format in the module docstring)"""
+    os.makedirs(out_dir, exist_ok=True)
+    if results:
+        pts = [pt for r in results for pt in jac_to_affine_ints(r.cpu().numpy().view(np.uint64), q)]
+        xy = [words32(pt if pt is not None else (0, 0)).reshape(16) for pt in pts]
+        np.save(os.path.join(out_dir, "commitments.npy"), np.stack(xy))
+    rinv = pow(1 << 256, -1, p)
+    for j, name in enumerate(ntt_names):
+        if name not in ntt_bufs:
+            continue
+        import torch
+        buf = ntt_bufs[name][0]
+        idx = np.sort(np.random.default_rng(DUMP_SEED + j).choice(buf.shape[0], size=min(DUMP_ROWS, buf.shape[0]),
+                                                                  replace=False))
+        rows = buf.index_select(0, torch.as_tensor(idx, device=buf.device)).cpu().numpy().view(np.uint64)
+        vals = [sum(int(r[i]) << (64 * i) for i in range(4)) * rinv % p for r in rows]
+        np.save(os.path.join(out_dir, "ntt_%s.npy" % name), words32(vals))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -178,6 +216,10 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="rehearsal: take the N > 1 code paths (range split, all-gather, partial-sum addition, config 5) even "
                          "with one rank -- run under torch.distributed.run with one rank to exercise RCCL on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks, sub-records and extra measurements beyond the timed steps (see the docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float64, see the docstring)")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args, sys.argv[1:])
@@ -300,7 +342,7 @@ def main():
     # all-gathered (the path's one exchange step: m x 96 bytes per rank and phase).  The north star's other reading, ONE
     # proof's columns spread over the N GPUs (total work fixed), is the sub-record `one_proof_sharded`.
     ntt_bufs = build_ntt_bufs(False)
-    ntt_bufs_shared = build_ntt_bufs(True) if world > 1 else ntt_bufs
+    ntt_bufs_shared = build_ntt_bufs(True) if world > 1 and args.full else ntt_bufs   # the one-proof job's (--full)
     results = [None] * len(phases)
 
     class Lane:
@@ -421,11 +463,13 @@ def main():
             t = t.to(dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, ntt_bufs, [name for name, *_ in ntts], BASE_FIELD[args.curve], p)
 
     # one proof's job spread over the ranks (total work fixed): sharded == whole as group elements, then its time
     sharded_ok = None
     one_proof = None
-    if multi and phases:
+    if args.full and multi and phases:
         q = BASE_FIELD[args.curve]
         step(shared=True)
         torch.cuda.synchronize()
@@ -458,7 +502,7 @@ def main():
     # handed torch's current stream)
     phases_ms = {}
     prof_alone = None
-    for name, fn in (("msm", msm_phase), ("ntt", ntt_phase)):
+    for name, fn in (("msm", msm_phase), ("ntt", ntt_phase)) if args.full else ():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         fn()                                    # (scratch sized for this stream's calls before the clock starts)
         barrier()
@@ -480,7 +524,7 @@ def main():
     # stream its own MSM / NTT scratch -- so that one step's sorts and small-grid tails run beside the other's
     # chip-filling kernels.  Each step keeps its own Fiat-Shamir order.
     two_in_flight = None
-    if args.workload == "poseidon" and world == 1 and not args.no_extras:
+    if args.full and args.workload == "poseidon" and world == 1 and not args.no_extras:
         # (normal priority: a SECOND high-priority stream in the process left every later small kernel of the run 3-5 x
         # slower -- 50 us for a 13 us kernel; profiles/r03_second_high_priority_stream.txt)
         lane1 = Lane(torch.cuda.Stream(device=dev, priority=0),
@@ -511,7 +555,7 @@ def main():
                          "lanes_agree": same}
 
     overlap = None
-    if args.workload == "poseidon":
+    if args.workload == "poseidon" and phases_ms:
         overlap = {"ms_per_step": round(dt / args.steps * 1e3, 4), "msm_plus_ntt_serial_ms": round(phases_ms["msm"] + phases_ms["ntt"], 4),
                    "what": "phases_ms times the MSM phases and the NTTs alone, one after the other on one stream; in the "
                            "step the transforms that wait for no challenge run on a second stream beside the MSMs' "
@@ -520,7 +564,7 @@ def main():
     # NTT roofline: algorithmic bytes = m * n * 64 per transform (SURVEY.md 8(d) bytes_ntt: each element read and
     # written once, whatever the number of passes); the per-pass figure the kernels actually move is reported beside it
     roofline_ntt = None
-    if ntt_bufs:
+    if ntt_bufs and phases_ms:
         ntt_bytes = sum(m * (1 << lg) * 64 for _, lg, m, _ in ntt_bufs.values())
         pass_bytes = sum(m * (1 << lg) * 64 * ((lg + 9) // 10) for _, lg, m, _ in ntt_bufs.values())
         ach = ntt_bytes / (phases_ms["ntt"] * 1e-3) / 1e9
@@ -555,7 +599,7 @@ def main():
     # the integer ceiling: dependent working-form products on every CU (a few ms), at the chunk kernel's occupancy
     # and at the best occupancy
     modmul = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         r3, r8 = ctypes.c_double(0), ctypes.c_double(0)
         h2lib.check(L.h2_selftest_modmul_rate(cid, 3, 512, ctypes.byref(r3)), "h2_selftest_modmul_rate")
         h2lib.check(L.h2_selftest_modmul_rate(cid, 8, 512, ctypes.byref(r8)), "h2_selftest_modmul_rate")
@@ -608,11 +652,11 @@ def main():
             return {"error": repr(exc)[:400]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = sub(cpu_baseline, args, cols_np, n, k, ext, p, gen, two_adicity, R)
 
     extras = {}
-    if not args.no_extras and args.workload == "poseidon":
+    if args.full and not args.no_extras and args.workload == "poseidon":
         for b in (g, g_lagrange):
             b.release()
         del msm_cols
@@ -631,9 +675,9 @@ def main():
     # h2_generate_proof is one process on this rank's GPU(s): rank 0 runs and reports it; n_gpus in the record says what
     # ran (the C++ prover shards its commit phases over the contexts of h2_init_devices, not over ranks)
     proof_gen_multi = None
-    if not args.no_proof and args.workload == "poseidon" and rank == 0:
+    if args.full and not args.no_proof and args.workload == "poseidon" and rank == 0:
         proof_gen = sub(proof_generation, k)
-    if not args.no_proof and args.workload == "poseidon" and world > 1 and ndev >= world:
+    if args.full and not args.no_proof and args.workload == "poseidon" and world > 1 and ndev >= world:
         # the N-GPU proof: ONE process with N contexts (h2_init_devices), started by rank 0 while the other ranks wait at
         # the barrier below with their GPUs idle; its commit phases are split by point range over the N GPUs
         if rank == 0:

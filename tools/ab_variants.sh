@@ -11,7 +11,7 @@ for v in variants/lib_*.so; do
 import json,sys
 d=json.loads(sys.stdin.read()); print("'$v' msm 2^'$kk': ms %.4f  chunk %.4f" % (d["ms_per_step"], d["roofline"]["avg_kernel_ms"]))'
   done
-  H2_NO_BUILD=1 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-proof --no-extras 2>/dev/null | python3 -c '
+  H2_NO_BUILD=1 python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-proof --no-extras 2>/dev/null | python3 -c '
 import json,sys
 d=json.loads(sys.stdin.read()); print("'$v' step: ms %.4f median %.4f chunk %.4f msm %.4f" % (d["ms_per_step"], d["ms_per_step_median"], d["roofline"]["avg_kernel_ms"], d["phases_ms"]["msm"]))'
 done

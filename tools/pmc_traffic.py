@@ -1,9 +1,9 @@
 """Summarise two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) into profiles/<name>.json.
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_f -o run --output-format csv -- python3 bench.py ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_w -o run --output-format csv -- python3 bench.py ...
-    python3 tools/pmc_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w profiles/pmc_traffic.json [step_executions]
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_f -o run --output-format csv -- python3 bench.py ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_w -o run --output-format csv -- python3 bench.py ...
+    python3 tools/pmc_traffic.py $OUT/pmc_f $OUT/pmc_w profiles/pmc_traffic.json [step_executions]
 
 The summary is stamped with a hash of the kernel sources (bench.py's source_hash) and H2_GIT_HEAD from the
 environment: bench.py reports `traffic` from it only while the sources are the ones that were profiled.
@@ -70,7 +70,7 @@ def main():
     dom = next(k for k in kernels if "msm_chunk_kernel" in k)
     doc = {"source_hash": bench.source_hash(), "git_head": os.environ.get("H2_GIT_HEAD", "?"), "steps_profiled": step_execs,
            "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (two separate passes) -- python3 "
-                      "bench.py --steps 3 --warmup 0 --no-cpu-baseline --no-proof --no-extras",
+                      "bench.py --steps 3 --warmup 0 --full --no-cpu-baseline --no-proof --no-extras",
            "workload": "poseidon_k16_proof_shape, pallas", "units": "KB as reported by rocprofv3",
            "correction": "per access shape, factors from profiles/pmc_calibration.json (tools/pmc_calib.hip): stream x%.2f, "
                          "64-byte row gather x%.2f, 64-byte runs x%.2f, >= 128-byte runs x%.2f; WRITE_SIZE as reported"

@@ -1,10 +1,11 @@
 #!/bin/bash
 # usage (on the GPU box): bash tools/ptimeline.sh  -- kernel timeline of the LAST of 3 key-cached Poseidon k=16 proofs: gaps and kernels
 cd "$GRAFT_REPO_ROOT" && export TMPDIR=/tmp
-rm -rf gpurun_out/ptl
-H2_PROFILE_KEY_CACHE=1 rocprofv3 --kernel-trace -d gpurun_out/ptl -o run --output-format csv -- python3 tools/proof_profile.py 3 > gpurun_out/ptl_out.txt 2> gpurun_out/ptl_err.txt
-f=$(find gpurun_out/ptl -name '*kernel_trace.csv' | head -1)
-python3 - "$f" > gpurun_out/ptimeline.txt <<'P'
+export OUT=${OUT:-out}; mkdir -p "$OUT"   # where the artefacts go (relative to the repository root)
+rm -rf $OUT/ptl
+H2_PROFILE_KEY_CACHE=1 rocprofv3 --kernel-trace -d $OUT/ptl -o run --output-format csv -- python3 tools/proof_profile.py 3 > $OUT/ptl_out.txt 2> $OUT/ptl_err.txt
+f=$(find $OUT/ptl -name '*kernel_trace.csv' | head -1)
+python3 - "$f" > $OUT/ptimeline.txt <<'P'
 import csv, sys
 rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name']) for r in csv.DictReader(open(sys.argv[1]))]
 rows.sort()
@@ -25,5 +26,5 @@ for s, e, name in g:
     end = max(end, e)
 print("span %.1f us, GPU busy (union) %.1f us, kernels %d" % ((end - t0) / 1000, busy / 1000, len(g)))
 P
-rm -rf gpurun_out/ptl
-tail -1 gpurun_out/ptimeline.txt
+rm -rf $OUT/ptl
+tail -1 $OUT/ptimeline.txt

@@ -1,9 +1,10 @@
 #!/bin/bash
-# BASELINE.json configs 3-5, one GPU's share each, appended as bench.py JSON lines to $1 (default gpurun_out/cfg.jsonl)
+# BASELINE.json configs 3-5, one GPU's share each, appended as bench.py JSON lines to $1 (default $OUT/cfg.jsonl)
 set -e
-O=${1:-gpurun_out/cfg.jsonl}
+export OUT=${OUT:-out}; mkdir -p "$OUT"
+O=${1:-$OUT/cfg.jsonl}
 : > $O
-run() { python bench.py "$@" --no-cpu-baseline --no-proof >> $O; tail -1 $O | python -c '
+run() { python bench.py "$@" --full --no-cpu-baseline --no-proof >> $O; tail -1 $O | python -c '
 import json, sys
 d = json.loads(sys.stdin.read())
 print(d["config"]["workload"], "ms/step %.3f" % d["ms_per_step"], "field-ops/s %.3e" % d["value"])'; }

@@ -1,10 +1,11 @@
 #!/bin/bash
 # usage (on the GPU box): bash tools/step_timeline.sh -- kernel timeline of the LAST bench step (start, duration, queue, kernel)
 cd "$GRAFT_REPO_ROOT" && export TMPDIR=/tmp
-rm -rf gpurun_out/stl
-rocprofv3 --kernel-trace -d gpurun_out/stl -o run --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-proof --no-extras > gpurun_out/stl_out.txt 2> gpurun_out/stl_err.txt
-f=$(find gpurun_out/stl -name '*kernel_trace.csv' | head -1)
-python3 - "$f" > gpurun_out/step_timeline.txt <<'P'
+export OUT=${OUT:-out}; mkdir -p "$OUT"   # where the artefacts go (relative to the repository root)
+rm -rf $OUT/stl
+rocprofv3 --kernel-trace -d $OUT/stl -o run --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-proof --no-extras > $OUT/stl_out.txt 2> $OUT/stl_err.txt
+f=$(find $OUT/stl -name '*kernel_trace.csv' | head -1)
+python3 - "$f" > $OUT/step_timeline.txt <<'P'
 import csv, sys
 rows = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'], r.get('Queue_Id', '?')) for r in csv.DictReader(open(sys.argv[1]))]
 rows.sort()
@@ -19,5 +20,5 @@ for s, e, name, q in rows[start:end]:
     print("%8.1f %7.1f  q%-3s %s" % ((s - t0) / 1000, (e - s) / 1000, q, nm))
 print("step span %.1f us" % ((rows[end][0] - t0) / 1000))
 P
-rm -rf gpurun_out/stl
-cat gpurun_out/step_timeline.txt
+rm -rf $OUT/stl
+cat $OUT/step_timeline.txt

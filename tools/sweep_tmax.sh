@@ -11,7 +11,7 @@ d=json.loads(sys.stdin.read()); print("  msm 2^20 ms/step %.4f  chunk kernel %.4
 done
 for t in 64 96; do
   echo "TMAX=$t k16 step"
-  H2_TUNE_TMAX=$t python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-proof --no-extras | python3 -c '
+  H2_TUNE_TMAX=$t python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-proof --no-extras | python3 -c '
 import json,sys
 d=json.loads(sys.stdin.read()); print("  step ms %.4f  chunk kernel %.4f  msm phase %.4f ntt %.4f" % (d["ms_per_step"], d["roofline"]["avg_kernel_ms"], d["phases_ms"]["msm"], d["phases_ms"]["ntt"]))'
 done

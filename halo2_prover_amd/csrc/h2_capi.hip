@@ -9,6 +9,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <optional>
 
 #include "h2_host.hpp"
 #include "h2_ntt.hpp"
@@ -84,9 +85,21 @@ DevCtx* ctx_current() {
 }
 size_t ctx_index(const DevCtx* c) { return (size_t)(c - &g_h2.ctx[0]); }
 
+int device_alloc(void** p, size_t bytes, const char* what) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) return H2_OK;
+  (void)hipGetLastError();
+  *p = nullptr;
+  g_h2.last_error = std::string("hipMalloc(") + what + "): " + hipGetErrorString(e);
+  return H2_ENOMEM;
+}
+
 // ---- arenas ----------------------------------------------------------------------------------
 static uint64_t g_arena_growths = 0, g_arena_waits = 0;
-int arena_acquire(Arena& a, size_t want, hipStream_t s) {
+ArenaLease::ArenaLease(Arena& arena, size_t want, hipStream_t stream) : a(arena), s(stream) { rc = acquire(want); }
+int ArenaLease::acquire(size_t want) {
+  clean_bytes = a.bytes < want ? 0 : a.clean_bytes;   // this user takes over the region and may overwrite it
+  a.clean_bytes = 0;
   if (a.bytes < want) {
     g_arena_growths++;
     if (a.p) {
@@ -97,14 +110,8 @@ int arena_acquire(Arena& a, size_t want, hipStream_t s) {
       a.bytes = 0;
       a.used = false;
     }
-    a.clean_bytes = 0;
     const size_t sz = want + (want >> 3);  // head-room so slightly larger calls do not reallocate
-    hipError_t e = hipMalloc(&a.p, sz);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      g_h2.last_error = std::string("hipMalloc: ") + hipGetErrorString(e);
-      return H2_ENOMEM;
-    }
+    if (int st = device_alloc(&a.p, sz, "arena"); st != H2_OK) return st;
     a.bytes = sz;
   }
   if (!a.ev) H2_TRY(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
@@ -114,11 +121,26 @@ int arena_acquire(Arena& a, size_t want, hipStream_t s) {
   }
   return H2_OK;
 }
-int arena_release(Arena& a, hipStream_t s) {
+int ArenaLease::release() {
+  released = true;
   H2_TRY(hipEventRecord(a.ev, s));
   a.last = s;
   a.used = true;
   return H2_OK;
+}
+int ArenaLease::wait() {
+  H2_TRY(hipStreamSynchronize(s));
+  released = true;   // the arena is idle: no event has to order a later user behind this use
+  return H2_OK;
+}
+ArenaLease::~ArenaLease() noexcept {
+  if (rc != H2_OK || released) return;
+  if (hipEventRecord(a.ev, s) == hipSuccess) {
+    a.last = s;
+    a.used = true;
+  } else {
+    (void)hipGetLastError();
+  }
 }
 static void arena_free(Arena& a) {
   if (a.p) (void)hipFree(a.p);
@@ -149,34 +171,26 @@ static int register_device(DevCtx& src, int curve, const void* d_affine, size_t 
   };
   for (size_t i = 0; i < g_h2.ctx.size(); i++) {
     DeviceGuard dg(g_h2.ctx[i].device);
-    hipError_t e = hipMalloc(&be.table[i], be.table_bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      be.table[i] = nullptr;
-      g_h2.last_error = std::string("hipMalloc(table): ") + hipGetErrorString(e);
-      return fail(H2_ENOMEM);
-    }
+    if (int rc = device_alloc(&be.table[i], be.table_bytes, "table"); rc != H2_OK) return fail(rc);
   }
   const size_t si = ctx_index(&src);
   {
     DeviceGuard dg(src.device);
     // the points are checked while the table is built: a counter in the (otherwise idle) scan arena
-    int rc = arena_acquire(src.div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, src.stream);
-    if (rc != H2_OK) return fail(rc);
+    ArenaLease scan_ws(src.div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, src.stream);
+    if (scan_ws.rc != H2_OK) return fail(scan_ws.rc);
     uint32_t* d_bad = (uint32_t*)src.div_ws.p;
     uint32_t bad = 0;
     // the table kernel's scratch (80 bytes per table entry) is the MSM workspace, idle while bases are being registered
-    Arena& table_ws = src.msm_ws.of(src.stream);
-    table_ws.clean_bytes = 0;                      // the table kernel's scratch overwrites what an MSM left zeroed
-    rc = arena_acquire(table_ws, be.table_bytes / 64 * MSM_TABLE_SCRATCH, src.stream);
-    if (rc != H2_OK) return fail(rc);
+    ArenaLease table_ws(src.msm_ws.of(src.stream), be.table_bytes / 64 * MSM_TABLE_SCRATCH, src.stream);
+    if (table_ws.rc != H2_OK) return fail(table_ws.rc);
     hipError_t e = hipMemsetAsync(d_bad, 0, 4, src.stream);
-    if (e == hipSuccess) e = ops->table_build(d_affine, be.table[si], table_ws.p, (uint32_t)n, g, d_bad, src.stream);
+    if (e == hipSuccess) e = ops->table_build(d_affine, be.table[si], table_ws.a.p, (uint32_t)n, g, d_bad, src.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, src.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(src.stream);
     if (e != hipSuccess) return fail(dev_fail(e, "msm_table_kernel"));
-    (void)arena_release(src.div_ws, src.stream);
-    (void)arena_release(table_ws, src.stream);
+    (void)scan_ws.release();
+    (void)table_ws.release();
     if (bad) {
       g_h2.last_error = "bases: " + std::to_string(bad) + " point(s) not on the curve";
       return fail(H2_EINVAL);
@@ -249,9 +263,9 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
     const size_t mm = m - j0 < group ? m - j0 : group;
     MsmWorkspace ws = msm_workspace(n, mm, be.geom, g_msm_guard ? 256u : 0u, be.n, g_sort2_pack);
     if (ws.E >= (1ull << 31) || ws.K >= (1ull << 31)) return H2_EINVAL;
-    Arena& A = c.msm_ws.of(stream);
-    int rc = arena_acquire(A, ws.total, stream);
-    if (rc != H2_OK) return rc;
+    ArenaLease lease(c.msm_ws.of(stream), ws.total, stream);
+    if (lease.rc != H2_OK) return lease.rc;
+    Arena& A = lease.a;
     // every kernel's index range against the region it indexes, before anything is enqueued.  (n_bases is the
     // REGISTERED length whatever the range: a sorted entry is w * be.n + i relative to the table row of first_base)
     if (const char* broken = msm_check(ws, be.geom, n, mm, col_stride, (uint32_t)be.n, A.bytes)) {
@@ -275,8 +289,7 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
     if (c.tail_wanted && !c.tail_event) H2_TRY(hipEventCreateWithFlags(&c.tail_event, hipEventDisableTiming));
     void* dst = (char*)d_out + j0 * out_sz;
     // the previous launch sequence on this workspace left its counter region zero: no memset when this one's fits in it
-    const bool zeroed = !g_msm_guard && A.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
-    A.clean_bytes = 0;                             // (until this sequence is enqueued whole)
+    const bool zeroed = !g_msm_guard && lease.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
     hipError_t e = ops->msm_launch(table, per_column ? col_tables : nullptr, (uint32_t)be.n,
                                    (const char*)d_scalars + j0 * col_stride * 32, n, col_stride,
                                    mm, be.geom, (char*)A.p, ws, stream, ev0, ev1, (c.tail_wanted && !ev1) ? c.tail_event : nullptr,
@@ -289,16 +302,16 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
       A.clean_bytes = ws.zero_bytes;
     }
     if (g_msm_guard) {
-      uint32_t* d_bad = nullptr;
+      void* d_bad = nullptr;
+      if (int rc = device_alloc(&d_bad, ws.n_regions * 4, "guard"); rc != H2_OK) return rc;
+      DeviceBuffer owner(d_bad);
       std::vector<uint32_t> bad(ws.n_regions, 0);
-      H2_TRY(hipMalloc(&d_bad, ws.n_regions * 4));
       H2_TRY(hipMemsetAsync(d_bad, 0, ws.n_regions * 4, stream));
       if (g_msm_guard_poke)        // the checker's own test: one byte just behind the second region
         H2_TRY(hipMemsetAsync((char*)A.p + ws.regions[1].off + ws.regions[1].bytes, 0, 1, stream));
-      hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)A.p, ws, d_bad);
+      hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)A.p, ws, (uint32_t*)d_bad);
       H2_TRY(hipMemcpyAsync(bad.data(), d_bad, ws.n_regions * 4, hipMemcpyDeviceToHost, stream));
       H2_TRY(hipStreamSynchronize(stream));
-      (void)hipFree(d_bad);
       g_guard_launches++;
       for (uint32_t r = 0; r < ws.n_regions; r++)
         if (bad[r]) {
@@ -312,8 +325,7 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
       e = ops->to_affine((char*)A.p + ws.off_tree2, dst, (uint32_t)mm, stream);
       if (e != hipSuccess) return dev_fail(e, "msm finish kernel");
     }
-    rc = arena_release(A, stream);
-    if (rc != H2_OK) return rc;
+    if (int rc = lease.release(); rc != H2_OK) return rc;
   }
   return H2_OK;
 }
@@ -343,19 +355,14 @@ static int get_twiddles(DevCtx& c, const CurveOps* ops, const uint64_t omega[4],
   memcpy(te.omega, omega, 32);
   te.scaled = scale != nullptr;
   if (scale) memcpy(te.scale, scale, 32);
-  hipError_t e = hipMalloc(&te.tw, ops->ntt_table_bytes(log_n));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return H2_ENOMEM;
-  }
+  if (int rc = device_alloc(&te.tw, ops->ntt_table_bytes(log_n), "twiddles"); rc != H2_OK) return rc;
+  DeviceBuffer owner(te.tw);      // until the table is in the cache
   // built on the library's stream and finished before anybody uses it: a table is shared by every later caller,
   // whatever stream they bring (once per (field, omega, log n, constant))
-  e = ops->ntt_twiddles(te.tw, omega, log_n, c.stream, scale);
+  hipError_t e = ops->ntt_twiddles(te.tw, omega, log_n, c.stream, scale);
   if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-  if (e != hipSuccess) {
-    (void)hipFree(te.tw);
-    return dev_fail(e, "ntt_build_tables");
-  }
+  if (e != hipSuccess) return dev_fail(e, "ntt_build_tables");
+  (void)owner.release();
   te.stamp = ++c.stamp;
   c.twiddles.push_back(te);
   *out = te.tw;
@@ -370,27 +377,23 @@ int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[
   // a constant that rides in the inter-pass twiddles needs tables built with it
   int rc = get_twiddles(c, ops, omega, log_n, (scale && ops->ntt_scale_in_table(log_n)) ? scale : nullptr, &tw);
   if (rc != H2_OK) return rc;
-  NttPlan pl = ntt_make_plan(log_n);
-  void* scratch = nullptr;
-  Arena* A = nullptr;
-  if (pl.npass > 1) {
-    A = &c.ntt_ws.of(stream);
-    rc = arena_acquire(*A, m * ((size_t)32 << log_n), stream);
-    if (rc != H2_OK) return rc;
-    scratch = A->p;
+  std::optional<ArenaLease> A;     // the second buffer of a two-pass transform
+  if (ntt_make_plan(log_n).npass > 1) {
+    A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << log_n), stream);
+    if (A->rc != H2_OK) return A->rc;
   }
-  hipError_t e = ops->ntt_launch(d_a, scratch, tw, log_n, m, stream, scale);
+  hipError_t e = ops->ntt_launch(d_a, A ? A->a.p : nullptr, tw, log_n, m, stream, scale);
   if (e != hipSuccess) return dev_fail(e, "ntt_launch");
-  if (A) return arena_release(*A, stream);
-  return H2_OK;
+  return A ? A->release() : H2_OK;
 }
 
 }  // namespace h2
 
 namespace {
 
-// every *_device entry point: the context of the current device, and the stream the work goes to
+// every *_device entry point: the library lock, the context of the current device, and the stream the work goes to
 struct Call {
+  std::lock_guard<std::recursive_mutex> lk{g_h2_mu};
   DevCtx* c = nullptr;
   hipStream_t stream = nullptr;
   int rc = H2_OK;
@@ -512,7 +515,6 @@ int h2_shutdown(void) {
 }
 
 int h2_bases_register_device(h2_curve_t curve, const void* d_affine, size_t n, uint64_t* handle_out) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(nullptr);
   if (k.rc != H2_OK) return k.rc;
   // the caller's copy / kernel that produced d_affine may still be in flight on another stream
@@ -526,11 +528,10 @@ int h2_bases_register(h2_curve_t curve, const uint64_t* affine, size_t n, uint64
   if (!curve_ok((int)curve) || !affine || !handle_out || n == 0) return H2_EINVAL;
   DevCtx& c = g_h2.ctx[0];
   DeviceGuard dg(c.device);
-  int rc = arena_acquire(c.stage, n * 64, c.stream);
-  if (rc != H2_OK) return rc;
+  ArenaLease stage(c.stage, n * 64, c.stream);
+  if (stage.rc != H2_OK) return stage.rc;
   H2_TRY(hipMemcpyAsync(c.stage.p, affine, n * 64, hipMemcpyHostToDevice, c.stream));
-  rc = register_device(c, (int)curve, c.stage.p, n, handle_out);   // synchronises c.stream
-  return rc;
+  return register_device(c, (int)curve, c.stage.p, n, handle_out);   // synchronises c.stream
 }
 
 int h2_bases_release(uint64_t handle) {
@@ -570,12 +571,11 @@ int h2_msm_plan(uint64_t handle, h2_msm_plan_t* out) {
 
 int h2_msm_device_range(h2_curve_t curve, uint64_t handle, const void* d_scalars, size_t first_base, size_t n,
                         size_t col_stride, size_t m, void* d_out_jac, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  Call k(stream_);
   const BasesEntry* be = nullptr;
   int rc = msm_common_checks((int)curve, handle, first_base, n, m, &be);
   if (rc != H2_OK) return rc;
   if (!d_out_jac || (n && !d_scalars) || (m > 1 && col_stride < n)) return H2_EINVAL;
-  Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (n == 0) {
     H2_TRY(hipMemsetAsync(d_out_jac, 0, m * 96, k.stream));
@@ -586,7 +586,7 @@ int h2_msm_device_range(h2_curve_t curve, uint64_t handle, const void* d_scalars
 
 int h2_msm_device_multi(h2_curve_t curve, const uint64_t* handles, const void* d_scalars, size_t first_base, size_t n,
                         size_t col_stride, size_t m, void* d_out_jac, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  Call k(stream_);
   if (!handles || m == 0 || m > MSM_MAX_MULTI) return H2_EINVAL;
   const BasesEntry* bes[MSM_MAX_MULTI];
   for (size_t j = 0; j < m; j++) {
@@ -594,7 +594,6 @@ int h2_msm_device_multi(h2_curve_t curve, const uint64_t* handles, const void* d
     if (rc != H2_OK) return rc;
   }
   if (!d_out_jac || (n && !d_scalars) || (m > 1 && col_stride < n)) return H2_EINVAL;
-  Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (n == 0) {
     H2_TRY(hipMemsetAsync(d_out_jac, 0, m * 96, k.stream));
@@ -609,7 +608,6 @@ int h2_msm_device(h2_curve_t curve, uint64_t handle, const void* d_scalars, size
 }
 
 int h2_stream_wait_msm_tail(void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (k.c->tail_recorded && k.c->tail_wait) H2_TRY(hipStreamWaitEvent(k.stream, k.c->tail_wait, 0));
@@ -619,7 +617,6 @@ int h2_stream_wait_msm_tail(void* stream_) {
 
 int h2_points_sum_device(h2_curve_t curve, const void* d_in_jac, size_t groups, size_t count, void* d_out_jac,
                          void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_in_jac || !d_out_jac || groups == 0 || groups > (1u << 20) || count > (1u << 24))
@@ -651,13 +648,13 @@ static int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* co
   if (m == 1 && G > 1 && n >= 4096 * G) {
     // point-range split of one MSM: context g takes bases [lo_g, hi_g)
     std::vector<uint64_t> partial(G * 12);
+    std::vector<std::optional<ArenaLease>> stages(G);
     for (size_t g = 0; g < G; g++) {
       DevCtx& c = g_h2.ctx[g];
       DeviceGuard dg(c.device);
       const size_t lo = n * g / G, hi = n * (g + 1) / G, cnt = hi - lo;
       const size_t res_off = h2_align256(cnt * 32);
-      rc = arena_acquire(c.stage, res_off + 96, c.stream);
-      if (rc != H2_OK) return rc;
+      if (int st = stages[g].emplace(c.stage, res_off + 96, c.stream).rc; st != H2_OK) return st;
       H2_TRY(hipMemcpyAsync(c.stage.p, (const char*)cols[0] + lo * 32, cnt * 32, hipMemcpyHostToDevice, c.stream));
       void* d_res = (char*)c.stage.p + res_off;
       rc = msm_device_run(c, (int)curve, *be, c.stage.p, lo, cnt, cnt, 1, d_res, false, c.stream);
@@ -666,34 +663,33 @@ static int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* co
     }
     for (size_t g = 0; g < G; g++) {
       DeviceGuard dg(g_h2.ctx[g].device);
-      H2_TRY(hipStreamSynchronize(g_h2.ctx[g].stream));
+      if (int st = stages[g]->wait(); st != H2_OK) return st;
     }
     // add the G partial sums on context 0 (they are 96 bytes each)
     DevCtx& c = g_h2.ctx[0];
     DeviceGuard dg(c.device);
     const size_t res_off = h2_align256(G * 96);
-    rc = arena_acquire(c.stage, res_off + 96, c.stream);
-    if (rc != H2_OK) return rc;
+    ArenaLease stage(c.stage, res_off + 96, c.stream);
+    if (stage.rc != H2_OK) return stage.rc;
     H2_TRY(hipMemcpyAsync(c.stage.p, partial.data(), G * 96, hipMemcpyHostToDevice, c.stream));
     void* d_res = (char*)c.stage.p + res_off;
     hipError_t e = ops_of((int)curve)->points_sum(c.stage.p, d_res, (uint32_t)G, 1, c.stream);
     if (e != hipSuccess) return dev_fail(e, "points_sum_kernel");
     if (affine_out) return H2_EINVAL;   // not reached: h2_msm asks for Jacobian
     H2_TRY(hipMemcpyAsync(out, d_res, 96, hipMemcpyDeviceToHost, c.stream));
-    H2_TRY(hipStreamSynchronize(c.stream));
-    return H2_OK;
+    return stage.wait();
   }
   // column sharding: context g takes columns g, g + G, ...; the results come back as Jacobian points and are
   // normalised on the host when the caller wants affine ones
   std::vector<uint8_t> jac(affine_out ? m * 96 : 0);
   uint8_t* dst = affine_out ? jac.data() : (uint8_t*)out;
+  std::vector<std::optional<ArenaLease>> stages(G);
   for (size_t g = 0; g < G && g < m; g++) {
     DevCtx& c = g_h2.ctx[g];
     DeviceGuard dg(c.device);
     const size_t mine = (m - g + G - 1) / G;
     const size_t res_off = h2_align256(mine * col_bytes);
-    rc = arena_acquire(c.stage, res_off + mine * 96, c.stream);
-    if (rc != H2_OK) return rc;
+    if (int st = stages[g].emplace(c.stage, res_off + mine * 96, c.stream).rc; st != H2_OK) return st;
     for (size_t i = 0; i < mine; i++)
       H2_TRY(hipMemcpyAsync((char*)c.stage.p + i * col_bytes, cols[g + i * G], col_bytes, hipMemcpyHostToDevice,
                             c.stream));
@@ -709,7 +705,7 @@ static int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* co
   }
   for (size_t g = 0; g < G && g < m; g++) {
     DeviceGuard dg(g_h2.ctx[g].device);
-    H2_TRY(hipStreamSynchronize(g_h2.ctx[g].stream));
+    if (int st = stages[g]->wait(); st != H2_OK) return st;
   }
   if (affine_out) jac_to_affine_host((int)curve, jac.data(), m, (uint8_t*)out);
   return H2_OK;
@@ -729,7 +725,6 @@ int h2_msm_batch(h2_curve_t curve, uint64_t handle, const uint64_t* const* scala
 }
 
 int h2_srs_generate(h2_curve_t curve, const uint64_t s[4], size_t n, void* d_out_affine, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   const CurveOps* ops = ops_of((int)curve);
@@ -740,7 +735,6 @@ int h2_srs_generate(h2_curve_t curve, const uint64_t s[4], size_t n, void* d_out
 }
 
 int h2_fixed_base_mul(h2_curve_t curve, const void* d_scalars, size_t n, void* d_out_affine, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   const CurveOps* ops = ops_of((int)curve);
@@ -785,7 +779,6 @@ int h2_profile_read(h2_profile_t* out) {
 }
 
 int h2_ntt_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !omega || m == 0 || log_n > 30) return H2_EINVAL;
@@ -795,7 +788,6 @@ int h2_ntt_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t omega[4]
 
 int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n,
                          const uint64_t scale[4], void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !omega || !scale || m == 0 || log_n > 30) return H2_EINVAL;
@@ -808,7 +800,6 @@ int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t o
 }
 
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !c) return H2_EINVAL;
@@ -819,7 +810,6 @@ int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const 
 }
 
 int h2_poly_coset_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t g[4], void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !g) return H2_EINVAL;
@@ -831,7 +821,6 @@ int h2_poly_coset_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const 
 
 int h2_poly_mul_periodic_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const void* d_t, size_t period,
                                 void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_t || period == 0 || (period & (period - 1))) return H2_EINVAL;
@@ -842,7 +831,6 @@ int h2_poly_mul_periodic_device(h2_curve_t curve, void* d_a, size_t n, size_t m,
 }
 
 int h2_poly_inverse_device(h2_curve_t curve, void* d_a, size_t n, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a) return H2_EINVAL;
@@ -854,34 +842,31 @@ int h2_poly_inverse_device(h2_curve_t curve, void* d_a, size_t n, void* stream_)
 
 int h2_poly_divide_linear_device(h2_curve_t curve, const void* d_a, size_t n, const uint64_t z[4], void* d_q,
                                  void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_q || !z || d_a == d_q) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  int rc = arena_acquire(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
-  if (rc != H2_OK) return rc;
-  hipError_t e = ops_of((int)curve)->poly_divide_linear(d_a, n, z, d_q, k.c->div_ws.p, k.stream);
+  ArenaLease A(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  hipError_t e = ops_of((int)curve)->poly_divide_linear(d_a, n, z, d_q, A.a.p, k.stream);
   if (e != hipSuccess) return dev_fail(e, "poly_divide kernels");
-  return arena_release(k.c->div_ws, k.stream);
+  return A.release();
 }
 
 int h2_poly_prefix_product_device(h2_curve_t curve, const void* d_a, size_t n, void* d_out, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_out) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  int rc = arena_acquire(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
-  if (rc != H2_OK) return rc;
-  hipError_t e = ops_of((int)curve)->poly_prefix_product(d_a, n, d_out, k.c->div_ws.p, k.stream);
+  ArenaLease A(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  hipError_t e = ops_of((int)curve)->poly_prefix_product(d_a, n, d_out, A.a.p, k.stream);
   if (e != hipSuccess) return dev_fail(e, "poly_prefix kernels");
-  return arena_release(k.c->div_ws, k.stream);
+  return A.release();
 }
 
 int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_t first_block, size_t n, void* d_out,
                                void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !seed || !d_out) return H2_EINVAL;
@@ -896,7 +881,6 @@ int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_b || op < 0 || op > 2) return H2_EINVAL;
@@ -917,16 +901,16 @@ int h2_ntt_batch(h2_curve_t curve, uint64_t* const* cols, size_t m, const uint64
   if (log_n == 0) return H2_OK;
   const size_t col_bytes = (size_t)32 << log_n;
   const size_t G = g_h2.ctx.size();
+  std::vector<std::optional<ArenaLease>> stages(G);
   for (size_t g = 0; g < G && g < m; g++) {
     DevCtx& c = g_h2.ctx[g];
     DeviceGuard dg(c.device);
     const size_t mine = (m - g + G - 1) / G;
-    int rc = arena_acquire(c.stage, mine * col_bytes, c.stream);
-    if (rc != H2_OK) return rc;
+    if (int st = stages[g].emplace(c.stage, mine * col_bytes, c.stream).rc; st != H2_OK) return st;
     for (size_t i = 0; i < mine; i++)
       H2_TRY(hipMemcpyAsync((char*)c.stage.p + i * col_bytes, cols[g + i * G], col_bytes, hipMemcpyHostToDevice,
                             c.stream));
-    rc = ntt_enqueue(c, (int)curve, c.stage.p, mine, omega, log_n, c.stream);
+    int rc = ntt_enqueue(c, (int)curve, c.stage.p, mine, omega, log_n, c.stream);
     if (rc != H2_OK) return rc;
     for (size_t i = 0; i < mine; i++)
       H2_TRY(hipMemcpyAsync(cols[g + i * G], (char*)c.stage.p + i * col_bytes, col_bytes, hipMemcpyDeviceToHost,
@@ -934,26 +918,23 @@ int h2_ntt_batch(h2_curve_t curve, uint64_t* const* cols, size_t m, const uint64
   }
   for (size_t g = 0; g < G && g < m; g++) {
     DeviceGuard dg(g_h2.ctx[g].device);
-    H2_TRY(hipStreamSynchronize(g_h2.ctx[g].stream));
+    if (int st = stages[g]->wait(); st != H2_OK) return st;
   }
   return H2_OK;
 }
 
 // best_fft over group elements (FftGroup for C::Curve): n = 2^log_n Jacobian points in place, natural order, unscaled
 int h2_fft_group_device(h2_curve_t curve, void* d_points_jac, const uint64_t omega[4], uint32_t log_n, void* stream_) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_points_jac || !omega || log_n > 26) return H2_EINVAL;
   if (log_n == 0) return H2_OK;
   const CurveOps* ops = ops_of((int)curve);
-  Arena& A = k.c->msm_ws.of(k.stream);
-  A.clean_bytes = 0;
-  int rc = arena_acquire(A, ops->group_fft_scratch(log_n), k.stream);      // the MSM workspace, idle here
-  if (rc != H2_OK) return rc;
-  hipError_t e = ops->group_fft(d_points_jac, d_points_jac, A.p, omega, log_n, k.stream);
+  ArenaLease A(k.c->msm_ws.of(k.stream), ops->group_fft_scratch(log_n), k.stream);      // the MSM workspace, idle here
+  if (A.rc != H2_OK) return A.rc;
+  hipError_t e = ops->group_fft(d_points_jac, d_points_jac, A.a.p, omega, log_n, k.stream);
   if (e != hipSuccess) return dev_fail(e, "group fft kernels");
-  return arena_release(A, k.stream);
+  return A.release();
 }
 
 int h2_fft_group(h2_curve_t curve, uint64_t* points_jac, const uint64_t omega[4], uint32_t log_n) {
@@ -964,14 +945,13 @@ int h2_fft_group(h2_curve_t curve, uint64_t* points_jac, const uint64_t omega[4]
   DevCtx& c = g_h2.ctx[0];
   DeviceGuard dg(c.device);
   const size_t bytes = ((size_t)96) << log_n;
-  int rc = arena_acquire(c.stage, bytes, c.stream);
-  if (rc != H2_OK) return rc;
+  ArenaLease stage(c.stage, bytes, c.stream);
+  if (stage.rc != H2_OK) return stage.rc;
   H2_TRY(hipMemcpyAsync(c.stage.p, points_jac, bytes, hipMemcpyHostToDevice, c.stream));
-  rc = h2_fft_group_device(curve, c.stage.p, omega, log_n, c.stream);
+  int rc = h2_fft_group_device(curve, c.stage.p, omega, log_n, c.stream);
   if (rc != H2_OK) return rc;
   H2_TRY(hipMemcpyAsync(points_jac, c.stage.p, bytes, hipMemcpyDeviceToHost, c.stream));
-  H2_TRY(hipStreamSynchronize(c.stream));
-  return arena_release(c.stage, c.stream);
+  return stage.wait();
 }
 
 int h2_ntt(h2_curve_t curve, uint64_t* a, const uint64_t omega[4], uint32_t log_n) {
@@ -1014,16 +994,15 @@ extern "C" int h2_selftest_curve_op_device(int curve, int op, const uint64_t* p,
   if (!ops || !p || !q || !out || n == 0 || n > (1u << 20)) return H2_EINVAL;
   DevCtx& g_ctx = g_h2.ctx[0];
   DeviceGuard dg(g_ctx.device);
-  int rc = arena_acquire(g_ctx.stage, 3 * n * 64, g_ctx.stream);
-  if (rc != H2_OK) return rc;
+  ArenaLease stage(g_ctx.stage, 3 * n * 64, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
   char* d = (char*)g_ctx.stage.p;
   H2_TRY(hipMemcpyAsync(d, p, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
   H2_TRY(hipMemcpyAsync(d + n * 64, q, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
   hipError_t e = ops->selftest_curve_device(op, d, d + n * 64, d + 2 * n * 64, (uint32_t)n, g_ctx.stream);
   if (e != hipSuccess) return dev_fail(e, "selftest_curve_kernel");
   H2_TRY(hipMemcpyAsync(out, d + 2 * n * 64, n * 64, hipMemcpyDeviceToHost, g_ctx.stream));
-  H2_TRY(hipStreamSynchronize(g_ctx.stream));
-  return H2_OK;
+  return stage.wait();
 }
 
 extern "C" int h2_selftest_field_op_device(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
@@ -1035,16 +1014,15 @@ extern "C" int h2_selftest_field_op_device(int field, int op, const uint64_t* a,
   const int which = field & 1;
   DevCtx& g_ctx = g_h2.ctx[0];
   DeviceGuard dg(g_ctx.device);
-  int rc = arena_acquire(g_ctx.stage, 3 * n * 32, g_ctx.stream);
-  if (rc != H2_OK) return rc;
+  ArenaLease stage(g_ctx.stage, 3 * n * 32, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
   char* d = (char*)g_ctx.stage.p;
   H2_TRY(hipMemcpyAsync(d, a, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
   H2_TRY(hipMemcpyAsync(d + n * 32, b, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
   hipError_t e = ops->selftest_field_device(which, op, d, d + n * 32, d + 2 * n * 32, (uint32_t)n, g_ctx.stream);
   if (e != hipSuccess) return dev_fail(e, "selftest_field_kernel");
   H2_TRY(hipMemcpyAsync(out, d + 2 * n * 32, n * 32, hipMemcpyDeviceToHost, g_ctx.stream));
-  H2_TRY(hipStreamSynchronize(g_ctx.stream));
-  return H2_OK;
+  return stage.wait();
 }
 
 // test hooks around the MSM workspace (include/h2hip_selftest.h)

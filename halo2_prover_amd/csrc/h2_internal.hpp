@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -25,14 +26,15 @@ struct Arena {
   hipStream_t last = nullptr;
   bool used = false;
   // MSM workspace: [clean_off, clean_off + clean_bytes) is zero when the work enqueued so far has run -- the previous MSM
-  // launch sequence zeroed its counter region again on its way out (msm_rowcol_kernel) -- so the next one skips its memset
+  // launch sequence zeroed its counter region again on its way out (msm_rowcol_kernel) -- so the next one skips its memset.
+  // Each ArenaLease hands this to its user and clears it; an MSM sets it again once its launch sequence is enqueued whole
   size_t clean_off = 0, clean_bytes = 0;
 };
 
 // Scratch that a launch sequence owns from its first kernel to its last (the MSM workspace, the NTT's second buffer): one
 // arena per stream for up to H2_ARENA_SLOTS streams, so that launch sequences enqueued on different streams run side by
 // side (two proofs in flight on one GPU: bench.py's `two_steps_in_flight`).  A further stream takes over the slot that
-// has been idle longest; arena_acquire orders it behind that slot's previous user (an event wait), as it ordered every
+// has been idle longest; its ArenaLease orders it behind that slot's previous user (an event wait), as it ordered every
 // stream behind every other before round 3.
 constexpr int H2_ARENA_SLOTS = 4;
 struct ArenaSet {
@@ -130,9 +132,31 @@ bool curve_ok(int c);
 DevCtx* ctx_current();
 size_t ctx_index(const DevCtx* c);
 
-// arenas: acquire = grow if needed + order `s` behind the previous user; release = record the event behind this use
-int arena_acquire(Arena& a, size_t want, hipStream_t s);
-int arena_release(Arena& a, hipStream_t s);
+// hipMalloc of the buffer named `what`: H2_ENOMEM (sticky error cleared, last_error set, *p = null) if it fails
+int device_alloc(void** p, size_t bytes, const char* what);
+// scratch device memory owned by one call: freed on every way out of it
+struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
+using DeviceBuffer = std::unique_ptr<void, HipFree>;
+
+// One use of an arena by the work a call enqueues on `s`.  The constructor grows the arena if needed and orders `s`
+// behind the previous user on another stream (status in rc); release() records the arena's event behind this use, the
+// event the next user on another stream waits on; wait() synchronises `s` instead, after which the arena is idle and
+// needs no event.  A lease ended neither way -- an error path, or a user with no status to report -- records the event
+// in its destructor, result ignored, so that work already enqueued is still waited for.
+struct ArenaLease {
+  Arena& a;
+  hipStream_t s;
+  size_t clean_bytes = 0;   // a.clean_bytes as the previous user left it
+  int rc;
+  ArenaLease(Arena& arena, size_t want, hipStream_t stream);
+  ArenaLease(const ArenaLease&) = delete;
+  ~ArenaLease() noexcept;
+  int release();
+  int wait();
+ private:
+  bool released = false;
+  int acquire(size_t want);
+};
 
 // enqueue m MSMs (columns of n scalars, col_stride elements apart, bases first_base ... first_base + n - 1 of the
 // registered vector) -> m Jacobian (96 B) or affine (64 B) points at d_out; all on `stream`

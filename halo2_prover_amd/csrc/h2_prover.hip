@@ -185,12 +185,8 @@ struct Dev {
     if (it != cache().end()) {
       p = it->second;
       cache().erase(it);
-    } else {
-      hipError_t e = hipMalloc(&p, bytes);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail(H2_ENOMEM, "hipMalloc");
-      }
+    } else if (int rc = device_alloc(&p, bytes, "block"); rc != H2_OK) {
+      fail(rc, g_h2.last_error);
     }
     live.push_back({p, bytes});
     return p;
@@ -297,14 +293,10 @@ struct Dev {
   void divide_linear(Col a, uint32_t n, const Fr& z, Col q) {
     uint64_t zl[4];
     limbs(z, zl);
-    st_ok(arena_acquire(c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, s), "arena");
-    hip_ok(ops->poly_divide_linear(a, n, zl, q, c->div_ws.p, s), "poly_divide_linear");
-    st_ok(arena_release(c->div_ws, s), "arena");
-  }
-  void prefix_product(Col a, uint32_t n, Col out) {
-    st_ok(arena_acquire(c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, s), "arena");
-    hip_ok(ops->poly_prefix_product(a, n, out, c->div_ws.p, s), "poly_prefix_product");
-    st_ok(arena_release(c->div_ws, s), "arena");
+    ArenaLease A(c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, s);
+    st_ok(A.rc, "arena");
+    hip_ok(ops->poly_divide_linear(a, n, zl, q, A.a.p, s), "poly_divide_linear");
+    st_ok(A.release(), "arena");
   }
   // mode 0: q_j = (a_j - a_j(z_j)) / (X - z_j); mode 1: out_j[i] = prod_{t < i} a_j[t] -- all jobs in one launch sequence
   void scan_batch(int mode, uint32_t n, const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
@@ -413,14 +405,18 @@ const Params& params_get(const uint8_t* bytes, size_t len) {
     if (part == PARTS - 1)
       for (q = bytes + 64 * blocks; q < bytes + len; q++) l[0] = (l[0] ^ *q) * 0x100000001B3ull;
   };
-  if (len >= (1u << 20)) {
-    std::thread th[PARTS - 1];
-    for (int t = 0; t < PARTS - 1; t++) th[t] = std::thread(hash_part, t + 1);
-    hash_part(0);
-    for (auto& t : th) t.join();
-  } else {
-    for (int t = 0; t < PARTS; t++) hash_part(t);
+  std::thread th[PARTS - 1];
+  for (int t = 1; t < PARTS; t++) {
+    try {
+      if (len >= (1u << 20)) th[t - 1] = std::thread(hash_part, t);
+      else hash_part(t);
+    } catch (const std::exception&) {   // no thread to be had: the part is hashed here, into its own lanes all the same
+      hash_part(t);
+    }
   }
+  hash_part(0);
+  for (auto& t : th)
+    if (t.joinable()) t.join();
   Blake2b h;
   h.update(lane, sizeof lane);
   h.update(&len, sizeof len);
@@ -798,7 +794,8 @@ PendingCommit commit_begin(Dev& d, const Params& P, Col cols, uint32_t n, size_t
     DeviceGuard dg(cg.device);
     const size_t lo = (size_t)n * slot / G, hi = (size_t)n * (slot + 1) / G, cnt = hi - lo;
     const size_t res_off = (m * cnt * 32 + 255) & ~(size_t)255;
-    st_ok(arena_acquire(cg.stage, res_off + m * 96, cg.stream), "arena");
+    ArenaLease stage(cg.stage, res_off + m * 96, cg.stream);
+    st_ok(stage.rc, "arena");
     hip_ok(hipStreamWaitEvent(cg.stream, d.c->shard_ev, 0), "hipStreamWaitEvent");
     for (size_t j = 0; j < m; j++)
       hip_ok(hipMemcpyPeerAsync((char*)cg.stage.p + j * cnt * 32, cg.device, (const char*)cols + (j * (size_t)n + lo) * 32,
@@ -808,7 +805,7 @@ PendingCommit commit_begin(Dev& d, const Params& P, Col cols, uint32_t n, size_t
     hip_ok(hipMemcpyPeerAsync(partials + slot * m * 96, d.c->device, d_res, cg.device, m * 96, cg.stream),
            "hipMemcpyPeerAsync(partials)");
     hip_ok(hipEventRecord(event_of(cg), cg.stream), "hipEventRecord");
-    st_ok(arena_release(cg.stage, cg.stream), "arena");
+    st_ok(stage.release(), "arena");
     slot++;
   }
   // this context's share: rows [0, n / G)

@@ -177,9 +177,9 @@ static int register_device(DevCtx& src, int curve, const void* d_affine, size_t 
   {
     DeviceGuard dg(src.device);
     // the points are checked while the table is built: a counter in the (otherwise idle) scan arena
-    ArenaLease scan_ws(src.div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, src.stream);
+    ArenaLease scan_ws(src.div_ws, sizeof(uint32_t), src.stream);
     if (scan_ws.rc != H2_OK) return fail(scan_ws.rc);
-    uint32_t* d_bad = (uint32_t*)src.div_ws.p;
+    uint32_t* d_bad = (uint32_t*)scan_ws.a.p;
     uint32_t bad = 0;
     // the table kernel's scratch (80 bytes per table entry) is the MSM workspace, idle while bases are being registered
     ArenaLease table_ws(src.msm_ws.of(src.stream), be.table_bytes / 64 * MSM_TABLE_SCRATCH, src.stream);
@@ -846,10 +846,10 @@ int h2_poly_divide_linear_device(h2_curve_t curve, const void* d_a, size_t n, co
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_q || !z || d_a == d_q) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  ArenaLease A(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
+  ArenaLease A(k.c->div_ws, SCAN_WS_BYTES, k.stream);
   if (A.rc != H2_OK) return A.rc;
-  hipError_t e = ops_of((int)curve)->poly_divide_linear(d_a, n, z, d_q, A.a.p, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_divide kernels");
+  hipError_t e = ops_of((int)curve)->poly_scan(0, &d_a, &d_q, z, 1, n, A.a.p, k.stream);
+  if (e != hipSuccess) return dev_fail(e, "poly_scan kernels");
   return A.release();
 }
 
@@ -858,10 +858,10 @@ int h2_poly_prefix_product_device(h2_curve_t curve, const void* d_a, size_t n, v
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_out) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  ArenaLease A(k.c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, k.stream);
+  ArenaLease A(k.c->div_ws, SCAN_WS_BYTES, k.stream);
   if (A.rc != H2_OK) return A.rc;
-  hipError_t e = ops_of((int)curve)->poly_prefix_product(d_a, n, d_out, A.a.p, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_prefix kernels");
+  hipError_t e = ops_of((int)curve)->poly_scan(1, &d_a, &d_out, nullptr, 1, n, A.a.p, k.stream);
+  if (e != hipSuccess) return dev_fail(e, "poly_scan kernels");
   return A.release();
 }
 

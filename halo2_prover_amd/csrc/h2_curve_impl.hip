@@ -126,13 +126,27 @@ hipError_t poly_inverse(void* d_a, size_t total, hipStream_t s) {
   hipLaunchKernelGGL(poly_inverse_kernel<FS>, dim3(poly_grid(total)), dim3(256), 0, s, (U128*)d_a, total);
   return hipGetLastError();
 }
-hipError_t poly_divide_linear(const void* d_a, size_t n, const uint64_t z[4], void* d_q, void* d_ws, hipStream_t s) {
-  Fe<FS> zv;
-  memcpy(zv.v, z, 32);
-  return poly_divide_linear_launch<FS>((const U128*)d_a, n, zv, (U128*)d_q, (U128*)d_ws, s);
-}
-hipError_t poly_prefix_product(const void* d_a, size_t n, void* d_out, void* d_ws, hipStream_t s) {
-  return poly_prefix_product_launch<FS>((const U128*)d_a, n, (U128*)d_out, (U128*)d_ws, s);
+hipError_t poly_scan(int mode, const void* const* d_a, void* const* d_out, const uint64_t* z, uint32_t jobs, size_t n,
+                     void* d_ws, hipStream_t s) {
+  if (jobs == 0 || jobs > SCAN_MAX_JOBS || n == 0) return hipErrorInvalidValue;
+  uint32_t L = (uint32_t)((n + SCAN_CHUNKS - 1) / SCAN_CHUNKS);
+  if (L < 16) L = 16;
+  const uint32_t C = (uint32_t)((n + L - 1) / L);
+  ScanBatch<FS> B{};
+  for (uint32_t j = 0; j < jobs; j++) {
+    B.a[j] = (const U128*)d_a[j];
+    B.out[j] = (U128*)d_out[j];
+    if (mode == 0) {
+      memcpy(B.z[j].v, z + 4 * j, 32);
+      B.w[j] = fe_pow_u64(B.z[j], (uint64_t)L);
+    }
+  }
+  U128* H = (U128*)d_ws;
+  U128* G = H + 2 * (size_t)jobs * SCAN_CHUNKS;
+  hipLaunchKernelGGL(poly_scan_chunk_kernel<FS>, dim3((C + 63) / 64, jobs), dim3(64), 0, s, B, mode, n, L, C, H);
+  hipLaunchKernelGGL(poly_scan_block_kernel<FS>, dim3(jobs), dim3(SCAN_BLOCK_THREADS), 0, s, B, mode, C, H, G);
+  hipLaunchKernelGGL(poly_scan_apply_kernel<FS>, dim3((C + 63) / 64, jobs), dim3(64), 0, s, B, mode, n, L, C, G);
+  return hipGetLastError();
 }
 hipError_t chacha20_scalars(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s) {
   ChaChaKey k;
@@ -354,7 +368,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_,    srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_divide_linear, poly_prefix_product, chacha20_scalars, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 
 }  // namespace

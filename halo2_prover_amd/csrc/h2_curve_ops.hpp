@@ -57,10 +57,11 @@ struct CurveOps {
   hipError_t (*poly_mul_periodic)(void* d_a, size_t total, const void* d_t, size_t period, hipStream_t s);
   hipError_t (*poly_pointwise)(void* d_a, const void* d_b, size_t total, int op, hipStream_t s);
   hipError_t (*poly_inverse)(void* d_a, size_t total, hipStream_t s);
-  // d_q = (d_a - d_a(z)) / (X - z); d_ws: 2 * 1024 elements of scratch
-  hipError_t (*poly_divide_linear)(const void* d_a, size_t n, const uint64_t z[4], void* d_q, void* d_ws, hipStream_t s);
-  // d_out[i] = prod_{j < i} d_a[j] (d_out[0] = 1; may alias d_a); d_ws as above
-  hipError_t (*poly_prefix_product)(const void* d_a, size_t n, void* d_out, void* d_ws, hipStream_t s);
+  // 1 <= jobs <= SCAN_MAX_JOBS (8) scans of n >= 1 elements side by side (h2_poly.hpp); d_ws: jobs * SCAN_WS_BYTES
+  // (2 * 4096 * 32) bytes.  mode 0: d_out[j] = (d_a[j] - d_a[j](z_j)) / (X - z_j), z: 4 limbs per job, d_out[j] != d_a[j];
+  // mode 1: d_out[j][i] = prod_{t < i} d_a[j][t] (d_out[j][0] = 1; may alias d_a[j]), z unused
+  hipError_t (*poly_scan)(int mode, const void* const* d_a, void* const* d_out, const uint64_t* z, uint32_t jobs, size_t n,
+                          void* d_ws, hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)

@@ -325,6 +325,53 @@ H2_HD Fe<FP> fe29_canonical_pack(Fe29<FP> t) {
   if (s.v[8] >= 0) t = s;
   return fe29_pack(t);
 }
+// t in (-p, 3p), any limbs within fe29_norm's reach -> canonical, packed (the API's bytes when t is x 2^256 + j p)
+template <class FP>
+H2_HD Fe<FP> w_canonical_pack(const Fe29<FP>& t0) {
+  Fe29<FP> pl;
+#pragma unroll
+  for (int i = 0; i < 9; i++) pl.v[i] = (int32_t)fe29_p<FP>(i);
+  Fe29<FP> t = fe29_norm(t0);
+  if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
+  Fe29<FP> s = fe29_norm(fe29_sub(t, pl));
+  if (s.v[8] >= 0) t = s;
+  s = fe29_norm(fe29_sub(t, pl));
+  if (s.v[8] >= 0) t = s;
+  return fe29_pack(t);
+}
+
+// A value in the API form (x 2^256, canonical) as a product operand without a conversion product: shifted left by five
+// bits while it is unpacked it is the integer x 2^261 + (a multiple of p) < 32 p, the working form of x; minus 16 p it
+// lies in (-16 p, 16 p) with limbs of magnitude < 2^29 (a valid operand of fe29_mul on either side).
+template <class FP>
+H2_HD Fe29<FP> expr_column_operand(const Fe<FP>& a) {
+  Fe29<FP> r;
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    // limb j of (a << 5): bits [29 j - 5, 29 j + 24) of a
+    const int bit = 29 * j - 5;
+    uint32_t limb;
+    if (bit < 0) {
+      limb = (a.v[0] << 5) & L29_MASK;
+    } else {
+      const int w = bit >> 5, sh = bit & 31;
+      const uint64_t lo = a.v[w], hi = w + 1 < 8 ? a.v[w + 1] : 0;
+      limb = (uint32_t)((lo | (hi << 32)) >> sh) & L29_MASK;
+    }
+    // minus 16 p = (p << 4): limb j of it is bits [29 j - 4, 29 j + 25) of p
+    const int pb = 29 * j - 4;
+    uint32_t pl;
+    if (pb < 0) {
+      pl = (FP::P(0) << 4) & L29_MASK;
+    } else {
+      const int w = pb >> 5, sh = pb & 31;
+      const uint64_t lo = w < 8 ? FP::P(w) : 0, hi = w + 1 < 8 ? FP::P(w + 1) : 0;
+      pl = (uint32_t)((lo | (hi << 32)) >> sh) & L29_MASK;
+    }
+    r.v[j] = (int32_t)limb - (int32_t)pl;
+  }
+  return r;
+}
 
 // a^(p-2) on the working form, two exponent bits at a time (254 squarings + ~96 products); a normalised, of small
 // magnitude (a product's result); the exponent is a constant, so the branches are uniform

@@ -7,6 +7,7 @@
 // device so a column never leaves HBM between its NTTs and its MSM.
 #pragma once
 #include "h2_field.hpp"
+#include "h2_field29.hpp"
 
 namespace h2 {
 
@@ -70,135 +71,209 @@ __global__ void __launch_bounds__(256) poly_inverse_kernel(U128* __restrict__ a,
   }
 }
 
-// ---- kate_division: q = (a - a(z)) / (X - z) --------------------------------------------------------------
-// halo2_proofs @6b43b6b src/arithmetic.rs `kate_division` (called by the GWC / SHPLONK provers on every opened
-// polynomial): the serial recurrence q[i-1] = a[i] + z q[i] from the top coefficient down, q[n-1] = 0.  Written
-// Q_i = sum_{j >= i} a[j] z^(j-i) it is a suffix sum with weights, done in three launches over C <= 1024 chunks of
-// L coefficients: each chunk's own Horner value, a log-step suffix scan of those values with multiplier
-// w = z^L (one block), then the recurrence inside every chunk started from the scanned value.  d_q != d_a.
-constexpr uint32_t DIV_MAX_CHUNKS = 1024;
-
+// ---- kate_division and the exclusive prefix product, several in ONE launch sequence (grid.y = job) --------------------
+// mode 0: q = (a - a(z)) / (X - z), halo2_proofs @6b43b6b src/arithmetic.rs `kate_division` (called by the GWC / SHPLONK
+// provers on every opened polynomial): the serial recurrence q[i-1] = a[i] + z q[i] from the top coefficient down,
+// q[n-1] = 0.  Written Q_i = sum_{j >= i} a[j] z^(j-i) it is a suffix sum with weights.  out != a.
+// mode 1: out[i] = prod_{j < i} a[j], out[0] = 1.  The permutation argument's grand product (halo2_proofs @6b43b6b
+// src/plonk/permutation/prover.rs `Argument::commit`: z[0] = last_z, z[i+1] = z[i] * numerator[i] / denominator[i]) is
+// this scan of the per-row ratios, times last_z.  May run in place (a thread reads a[i] before it writes out[i]).
+// Three launches over C <= SCAN_CHUNKS chunks of L >= 16 elements: each chunk's own value, a scan of the chunk values in
+// one block (for the division with multiplier w = z^L), then the recurrence inside every chunk started from the scanned
+// value.  Each scan is a latency chain on 16 waves; independent jobs side by side (the opening witnesses of the GWC
+// points, the permutation sets' grand products) cost what one costs.  Scratch: SCAN_WS_BYTES per job.
+constexpr int SCAN_MAX_JOBS = 8;
+constexpr uint32_t SCAN_CHUNKS = 4096;
+constexpr size_t SCAN_WS_BYTES = 2 * SCAN_CHUNKS * 32;   // the chunk values H and the scanned values G
+template <class FP>
+struct ScanBatch {
+  const U128* a[SCAN_MAX_JOBS];
+  U128* out[SCAN_MAX_JOBS];
+  Fe<FP> z[SCAN_MAX_JOBS];   // division only: the point
+  Fe<FP> w[SCAN_MAX_JOBS];   // division only: z^L
+};
+// Both modes on the 29-bit form (a chain of products on one wave: twice as fast there).  Mode 1 works on true values:
+// loads through expr_column_operand, one extra product (fe29_to_api) per stored element, off the chain.  Mode 0 is
+// LINEAR in the data, so the data stay in the API's form read as the working form of x / 32 (plain unpack, no conversion
+// either way): with z in the true working form, acc z / R' + a keeps that scaling, and a result only needs to be made
+// canonical to be stored.
+constexpr int SCAN_AHEAD = 4;     // elements loaded ahead of the recurrence (the chain itself cannot hide a load)
 template <class FP>
 __global__ void __launch_bounds__(64)
-poly_divide_chunk_kernel(const U128* __restrict__ a, size_t n, uint32_t L, uint32_t C, Fe<FP> z, U128* __restrict__ H) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+poly_scan_chunk_kernel(ScanBatch<FP> B, int mode, size_t n, uint32_t L, uint32_t C, U128* __restrict__ H) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, job = blockIdx.y;
   if (c >= C) return;
+  const U128* a = B.a[job];
   const size_t lo = (size_t)c * L, hi = min(n, lo + L);
-  Fe<FP> acc = Fe<FP>::zero();
-  for (size_t i = hi; i-- > lo;) acc = fe_add(fe_mul(acc, z), fe_load<FP>(a + 2 * i));
-  fe_store<FP>(H + 2 * c, acc);
-}
-
-// G[c] = sum_{d > c} H[d] w^(d-c-1)
-template <class FP>
-__global__ void __launch_bounds__(1024)
-poly_divide_scan_kernel(const U128* __restrict__ H, uint32_t C, Fe<FP> w, U128* __restrict__ G) {
-  __shared__ U128 lds[2 * DIV_MAX_CHUNKS];
-  const uint32_t c = threadIdx.x;
-  Fe<FP> y = c < C ? fe_load<FP>(H + 2 * c) : Fe<FP>::zero();
-  Fe<FP> wp = w;
-  for (uint32_t s = 1; s < C; s <<= 1) {
-    fe_store<FP>(lds + 2 * c, y);
-    __syncthreads();
-    if (c + s < C) y = fe_add(y, fe_mul(wp, fe_load<FP>(lds + 2 * (c + s))));
-    __syncthreads();
-    wp = fe_mul(wp, wp);
+  U128* dst = H + 2 * ((size_t)job * SCAN_CHUNKS + c);
+  if (mode == 0) {
+    W acc = W::zero();
+    const W z = expr_column_operand(B.z[job]);
+    for (size_t top = hi; top > lo;) {
+      const uint32_t cnt = (uint32_t)min((size_t)SCAN_AHEAD, top - lo);
+      F v[SCAN_AHEAD];
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) v[k] = fe_load<FP>(a + 2 * (top - 1 - k));
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) acc = fe29_add(fe29_mul(acc, z), fe29_unpack(v[k]));
+      top -= cnt;
+    }
+    fe_store<FP>(dst, w_canonical_pack(acc));
+  } else {
+    W acc = fe29_from_api(F::one());
+    for (size_t at = lo; at < hi;) {
+      const uint32_t cnt = (uint32_t)min((size_t)SCAN_AHEAD, hi - at);
+      F v[SCAN_AHEAD];
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) v[k] = fe_load<FP>(a + 2 * (at + k));
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) acc = fe29_mul(acc, expr_column_operand(v[k]));
+      at += cnt;
+    }
+    fe_store<FP>(dst, fe29_to_api(acc));
   }
-  fe_store<FP>(lds + 2 * c, y);
-  __syncthreads();
-  if (c < C) fe_store<FP>(G + 2 * c, c + 1 < C ? fe_load<FP>(lds + 2 * (c + 1)) : Fe<FP>::zero());
 }
-
+// Scan of the C <= SCAN_CHUNKS chunk values in one block of SCAN_BLOCK_THREADS threads: every thread takes
+// SCAN_PER_THREAD consecutive values (a short recurrence in registers), the group totals go through a log-step scan
+// in LDS (unpacked, 36 bytes each), and the thread finishes its own values.  The block is a chain of products on ONE
+// CU: measured 69 us with 1024 threads x 4 values (16 waves queue for four SIMDs), 74 us with 256 x 16 (long local
+// recurrences), 61 us with 512 x 8.  With 4096 chunks of 16 elements the three kernels take 17 + 61 + 28 us for the
+// four opening quotients of a proof; with 1024 chunks of 64 they took 58 + 40 + 65.
+constexpr int SCAN_BLOCK_THREADS = 512;
+constexpr int SCAN_PER_THREAD = SCAN_CHUNKS / SCAN_BLOCK_THREADS;
+template <class FP>
+__global__ void __launch_bounds__(SCAN_BLOCK_THREADS)
+poly_scan_block_kernel(ScanBatch<FP> B, int mode, uint32_t C, const U128* __restrict__ H, U128* __restrict__ G) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  __shared__ int32_t lds[9 * SCAN_BLOCK_THREADS];   // [limb][thread]
+  constexpr int K = SCAN_PER_THREAD;
+  const uint32_t t = threadIdx.x, job = blockIdx.x;
+  H += 2 * (size_t)job * SCAN_CHUNKS;
+  G += 2 * (size_t)job * SCAN_CHUNKS;
+  auto put = [&](uint32_t i, const W& x) {
+#pragma unroll
+    for (int l = 0; l < 9; l++) lds[l * SCAN_BLOCK_THREADS + i] = x.v[l];
+  };
+  auto get = [&](uint32_t i) {
+    W x;
+#pragma unroll
+    for (int l = 0; l < 9; l++) x.v[l] = lds[l * SCAN_BLOCK_THREADS + i];
+    return x;
+  };
+  const W one = fe29_from_api(F::one());
+  const uint32_t T = (C + K - 1) / K;               // threads that hold values
+  if (mode == 0) {
+    // data scaled like the API's bytes (see above); y_c = sum_{j >= c} w^(j-c) v_j, G[c] = y_(c+1)
+    W wk[K + 1];                                    // w^0 .. w^K, true working form, normalised
+    wk[0] = one;
+    wk[1] = fe29_mul(expr_column_operand(B.w[job]), one);
+#pragma unroll
+    for (int k = 2; k <= K; k++) wk[k] = fe29_mul(wk[k - 1], wk[1]);
+    W s[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) s[k] = t * K + k < C ? fe29_unpack(fe_load<FP>(H + 2 * (t * K + k))) : W::zero();
+#pragma unroll
+    for (int k = K - 2; k >= 0; k--) s[k] = fe29_norm(fe29_add(s[k], fe29_mul(wk[1], s[k + 1])));
+    W y = s[0];                                     // the group's total, weights counted from its first chunk
+    W wp = wk[K];
+    for (uint32_t st = 1; st < T; st <<= 1) {
+      put(t, y);
+      __syncthreads();
+      if (t + st < T) y = fe29_norm(fe29_add(y, fe29_mul(wp, get(t + st))));
+      __syncthreads();
+      wp = fe29_mul(wp, wp);
+    }
+    put(t, y);
+    __syncthreads();
+    const W next = t + 1 < T ? get(t + 1) : W::zero();    // y of the following group's first chunk
+    // y_(tK+k) = s_k + w^(K-k) next; G[tK+k] = y_(tK+k+1), and G of the group's last chunk is `next`
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const uint32_t c = t * K + k;
+      if (c >= C) break;
+      const W v = k + 1 < K ? fe29_add(s[k + 1], fe29_mul(wk[K - k - 1], next)) : fe29_mul(next, one);
+      fe_store<FP>(G + 2 * c, w_canonical_pack(k + 1 < K ? fe29_mul(fe29_norm(v), one) : v));
+    }
+  } else {
+    // G[c] = prod_{j < c} v_j
+    W p[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) p[k] = t * K + k < C ? expr_column_operand(fe_load<FP>(H + 2 * (t * K + k))) : one;
+    p[0] = fe29_mul(p[0], one);
+#pragma unroll
+    for (int k = 1; k < K; k++) p[k] = fe29_mul(p[k - 1], p[k]);
+    W y = p[K - 1];
+    for (uint32_t st = 1; st < T; st <<= 1) {
+      put(t, y);
+      __syncthreads();
+      if (t >= st) y = fe29_mul(y, get(t - st));
+      __syncthreads();
+    }
+    put(t, y);
+    __syncthreads();
+    const W before = t > 0 ? get(t - 1) : one;      // product of every group below this one
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const uint32_t c = t * K + k;
+      if (c >= C) break;
+      fe_store<FP>(G + 2 * c, fe29_to_api(k == 0 ? before : fe29_mul(before, p[k - 1])));
+    }
+  }
+}
 template <class FP>
 __global__ void __launch_bounds__(64)
-poly_divide_apply_kernel(const U128* __restrict__ a, size_t n, uint32_t L, uint32_t C, Fe<FP> z,
-                         const U128* __restrict__ G, U128* __restrict__ q) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+poly_scan_apply_kernel(ScanBatch<FP> B, int mode, size_t n, uint32_t L, uint32_t C, const U128* __restrict__ G) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, job = blockIdx.y;
   if (c >= C) return;
+  const U128* a = B.a[job];
+  U128* out = B.out[job];
   const size_t lo = (size_t)c * L, hi = min(n, lo + L);
-  Fe<FP> cur = fe_load<FP>(G + 2 * c);
-  for (size_t i = hi; i-- > lo;) {
-    cur = fe_add(fe_mul(cur, z), fe_load<FP>(a + 2 * i));
-    if (i >= 1) fe_store<FP>(q + 2 * (i - 1), cur);
+  const U128* g = G + 2 * ((size_t)job * SCAN_CHUNKS + c);
+  if (mode == 0) {
+    W cur = fe29_unpack(fe_load<FP>(g));
+    const W z = expr_column_operand(B.z[job]);
+    for (size_t top = hi; top > lo;) {
+      const uint32_t cnt = (uint32_t)min((size_t)SCAN_AHEAD, top - lo);
+      F v[SCAN_AHEAD];
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) v[k] = fe_load<FP>(a + 2 * (top - 1 - k));
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) {
+          const size_t i = top - 1 - k;
+          cur = fe29_add(fe29_mul(cur, z), fe29_unpack(v[k]));
+          if (i >= 1) fe_store<FP>(out + 2 * (i - 1), w_canonical_pack(cur));
+        }
+      top -= cnt;
+    }
+    if (c == C - 1) fe_store<FP>(out + 2 * (n - 1), F::zero());
+  } else {
+    W cur = fe29_mul(expr_column_operand(fe_load<FP>(g)), fe29_from_api(F::one()));
+    for (size_t at = lo; at < hi;) {
+      const uint32_t cnt = (uint32_t)min((size_t)SCAN_AHEAD, hi - at);
+      F v[SCAN_AHEAD];
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) v[k] = fe_load<FP>(a + 2 * (at + k));
+#pragma unroll
+      for (int k = 0; k < SCAN_AHEAD; k++)
+        if ((uint32_t)k < cnt) {
+          fe_store<FP>(out + 2 * (at + k), fe29_to_api(cur));
+          cur = fe29_mul(cur, expr_column_operand(v[k]));
+        }
+      at += cnt;
+    }
   }
-  if (c == C - 1) fe_store<FP>(q + 2 * (n - 1), Fe<FP>::zero());
-}
-
-// enqueue; d_ws holds 2 * DIV_MAX_CHUNKS elements
-template <class FP>
-inline hipError_t poly_divide_linear_launch(const U128* a, size_t n, const Fe<FP>& z, U128* q, U128* d_ws,
-                                            hipStream_t stream) {
-  uint32_t L = (uint32_t)((n + DIV_MAX_CHUNKS - 1) / DIV_MAX_CHUNKS);
-  if (L < 16) L = 16;
-  const uint32_t C = (uint32_t)((n + L - 1) / L);
-  U128* H = d_ws;
-  U128* G = d_ws + 2 * DIV_MAX_CHUNKS;
-  const Fe<FP> w = fe_pow_u64(z, (uint64_t)L);
-  hipLaunchKernelGGL(poly_divide_chunk_kernel<FP>, dim3((C + 63) / 64), dim3(64), 0, stream, a, n, L, C, z, H);
-  hipLaunchKernelGGL(poly_divide_scan_kernel<FP>, dim3(1), dim3(DIV_MAX_CHUNKS), 0, stream, H, C, w, G);
-  hipLaunchKernelGGL(poly_divide_apply_kernel<FP>, dim3((C + 63) / 64), dim3(64), 0, stream, a, n, L, C, z, G, q);
-  return hipGetLastError();
-}
-
-// ---- exclusive prefix product: out[i] = prod_{j < i} a[j], out[0] = 1 ------------------------------------------
-// The permutation argument's grand product (halo2_proofs @6b43b6b src/plonk/permutation/prover.rs `Argument::commit`:
-// z[0] = last_z, z[i+1] = z[i] * numerator[i] / denominator[i]) is this scan of the per-row ratios, times last_z.
-// Same three launches as the division: chunk products, log-step scan of the chunk products in one block, then the
-// recurrence inside every chunk.  May run in place (a thread reads a[i] before it writes out[i]).
-template <class FP>
-__global__ void __launch_bounds__(64)
-poly_prefix_chunk_kernel(const U128* __restrict__ a, size_t n, uint32_t L, uint32_t C, U128* __restrict__ H) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const size_t lo = (size_t)c * L, hi = min(n, lo + L);
-  Fe<FP> acc = Fe<FP>::one();
-  for (size_t i = lo; i < hi; i++) acc = fe_mul(acc, fe_load<FP>(a + 2 * i));
-  fe_store<FP>(H + 2 * c, acc);
-}
-
-// G[c] = prod_{d < c} H[d]
-template <class FP>
-__global__ void __launch_bounds__(1024)
-poly_prefix_scan_kernel(const U128* __restrict__ H, uint32_t C, U128* __restrict__ G) {
-  __shared__ U128 lds[2 * DIV_MAX_CHUNKS];
-  const uint32_t c = threadIdx.x;
-  Fe<FP> y = c < C ? fe_load<FP>(H + 2 * c) : Fe<FP>::one();
-  for (uint32_t s = 1; s < C; s <<= 1) {
-    fe_store<FP>(lds + 2 * c, y);
-    __syncthreads();
-    if (c >= s) y = fe_mul(y, fe_load<FP>(lds + 2 * (c - s)));
-    __syncthreads();
-  }
-  fe_store<FP>(lds + 2 * c, y);
-  __syncthreads();
-  if (c < C) fe_store<FP>(G + 2 * c, c > 0 ? fe_load<FP>(lds + 2 * (c - 1)) : Fe<FP>::one());
-}
-
-template <class FP>
-__global__ void __launch_bounds__(64)
-poly_prefix_apply_kernel(const U128* a, size_t n, uint32_t L, uint32_t C, const U128* __restrict__ G, U128* out) {
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const size_t lo = (size_t)c * L, hi = min(n, lo + L);
-  Fe<FP> cur = fe_load<FP>(G + 2 * c);
-  for (size_t i = lo; i < hi; i++) {
-    const Fe<FP> x = fe_load<FP>(a + 2 * i);
-    fe_store<FP>(out + 2 * i, cur);
-    cur = fe_mul(cur, x);
-  }
-}
-
-template <class FP>
-inline hipError_t poly_prefix_product_launch(const U128* a, size_t n, U128* out, U128* d_ws, hipStream_t stream) {
-  uint32_t L = (uint32_t)((n + DIV_MAX_CHUNKS - 1) / DIV_MAX_CHUNKS);
-  if (L < 16) L = 16;
-  const uint32_t C = (uint32_t)((n + L - 1) / L);
-  U128* H = d_ws;
-  U128* G = d_ws + 2 * DIV_MAX_CHUNKS;
-  hipLaunchKernelGGL(poly_prefix_chunk_kernel<FP>, dim3((C + 63) / 64), dim3(64), 0, stream, a, n, L, C, H);
-  hipLaunchKernelGGL(poly_prefix_scan_kernel<FP>, dim3(1), dim3(DIV_MAX_CHUNKS), 0, stream, H, C, G);
-  hipLaunchKernelGGL(poly_prefix_apply_kernel<FP>, dim3((C + 63) / 64), dim3(64), 0, stream, a, n, L, C, G, out);
-  return hipGetLastError();
 }
 
 // ---- the blinding polynomial's coefficients ------------------------------------------------------------------

@@ -289,37 +289,20 @@ struct Dev {
       accumulate = true;
     }
   }
-  // q = (a - a(z)) / (X - z)
-  void divide_linear(Col a, uint32_t n, const Fr& z, Col q) {
-    uint64_t zl[4];
-    limbs(z, zl);
-    ArenaLease A(c->div_ws, (size_t)2 * DIV_MAX_CHUNKS * 32, s);
-    st_ok(A.rc, "arena");
-    hip_ok(ops->poly_divide_linear(a, n, zl, q, A.a.p, s), "poly_divide_linear");
-    st_ok(A.release(), "arena");
-  }
   // mode 0: q_j = (a_j - a_j(z_j)) / (X - z_j); mode 1: out_j[i] = prod_{t < i} a_j[t] -- all jobs in one launch sequence
   void scan_batch(int mode, uint32_t n, const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
-    for (size_t j0 = 0; j0 < in.size(); j0 += pk::SCAN_MAX_JOBS) {
-      const size_t cnt = std::min<size_t>(pk::SCAN_MAX_JOBS, in.size() - j0);
-      uint32_t L = (n + pk::SCAN_CHUNKS - 1) / pk::SCAN_CHUNKS;
-      if (L < 16) L = 16;
-      const uint32_t C = (n + L - 1) / L;
-      pk::ScanBatch B{};
+    for (size_t j0 = 0; j0 < in.size(); j0 += SCAN_MAX_JOBS) {
+      const size_t cnt = std::min<size_t>(SCAN_MAX_JOBS, in.size() - j0);
+      const void* a[SCAN_MAX_JOBS];
+      void* o[SCAN_MAX_JOBS];
+      uint64_t zl[SCAN_MAX_JOBS][4];
       for (size_t j = 0; j < cnt; j++) {
-        B.a[j] = in[j0 + j];
-        B.out[j] = out[j0 + j];
-        if (mode == 0) {
-          B.z[j] = z[j0 + j].v;
-          B.w[j] = z[j0 + j].pow_u64(L).v;
-        }
+        a[j] = in[j0 + j];
+        o[j] = out[j0 + j];
+        if (mode == 0) limbs(z[j0 + j], zl[j]);
       }
-      Col ws = col((size_t)2 * cnt * pk::SCAN_CHUNKS);
-      Col H = ws, G = ws + 2 * cnt * (size_t)pk::SCAN_CHUNKS;
-      hipLaunchKernelGGL(pk::scan_chunk_kernel, dim3((C + 63) / 64, (unsigned)cnt), dim3(64), 0, s, B, mode, n, L, C, H);
-      hipLaunchKernelGGL(pk::scan_block_kernel, dim3((unsigned)cnt), dim3(pk::SCAN_BLOCK_THREADS), 0, s, B, mode, C, H, G);
-      hipLaunchKernelGGL(pk::scan_apply_kernel, dim3((C + 63) / 64, (unsigned)cnt), dim3(64), 0, s, B, mode, n, L, C, G);
-      hip_ok(hipGetLastError(), "scan_batch kernels");
+      void* ws = alloc(cnt * SCAN_WS_BYTES);
+      hip_ok(ops->poly_scan(mode, a, o, mode == 0 ? zl[0] : nullptr, (uint32_t)cnt, n, ws, s), "poly_scan");
       release(ws);
     }
   }
@@ -1509,7 +1492,7 @@ void shplonk_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const std
     // column's length, its top coefficients are zero)
     Col src = acc, dst = quo;
     for (auto& pt : G.points) {
-      d.divide_linear(src, n, pt, dst);
+      d.scan_batch(0, n, {src}, {dst}, {pt});
       std::swap(src, dst);
     }
     d.lincomb(h, n, gi == 0 ? std::vector<std::pair<Col, Fr>>{{src, vp}}
@@ -1546,7 +1529,7 @@ void shplonk_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const std
     hipLaunchKernelGGL(pk::sub_prefix_kernel, dim3(1), dim3(64), 0, d.s, acc, d_c, 1u);
     hip_ok(hipGetLastError(), "sub_prefix_kernel");
   }
-  d.divide_linear(acc, n, u, quo);
+  d.scan_batch(0, n, {acc}, {quo}, {u});
   hipLaunchKernelGGL(pk::scale_range_kernel, dim3((n + 255) / 256), dim3(256), 0, d.s, quo, 0u, n, z0.inv().v);
   hip_ok(hipGetLastError(), "scale_range_kernel");
   tr.write_point(commit(d, P, quo, n, 1, false)[0]);

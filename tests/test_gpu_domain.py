@@ -95,11 +95,11 @@ def test_quotient_of_a_product_k16(h2):
     assert not h_c[n:].any().item()
 
 
-@pytest.mark.parametrize("curve", ["bn254", "pallas"])
-@pytest.mark.parametrize("n", [1, 2, 15, 16, 17, 1000, 1 << 12, (1 << 14) + 5])
+@pytest.mark.parametrize("curve", ["bn254", "pallas", "vesta"])
+@pytest.mark.parametrize("n", [1, 2, 15, 16, 17, 1000, 1 << 12, (1 << 14) + 5, 1 << 16, (1 << 16) + 1])
 def test_divide_linear_matches_kate_division(h2, curve, n):
     """h2_poly_divide_linear_device against the oracle's synthetic division (halo2_ref.pdiv_linear): every chunking
-    case (one short chunk, a ragged last chunk, 1024 chunks) and q[n-1] = 0."""
+    case (one short chunk, a ragged last chunk, 4096 chunks) and q[n-1] = 0."""
     import ctypes
     import torch
     f = R.CURVES[curve].scalar
@@ -180,7 +180,7 @@ def test_chacha20_scalars_match_the_oracle_rng(h2, curve):
 
 
 @pytest.mark.parametrize("curve", ["bn254", "vesta"])
-@pytest.mark.parametrize("n", [1, 2, 16, 17, 1000, (1 << 14) + 3, 1 << 17])
+@pytest.mark.parametrize("n", [1, 2, 16, 17, 1000, (1 << 14) + 3, 1 << 16, (1 << 16) + 1, 1 << 17])
 def test_prefix_product_matches_the_running_product(h2, curve, n):
     """h2_poly_prefix_product_device against z[i+1] = z[i] * a[i], z[0] = 1 in big integers (zeros included: every
     later row becomes 0), out of place and in place."""

@@ -974,6 +974,31 @@ extern "C" int h2_selftest_field_op(int field, int op, const uint64_t a[4], cons
   }
   return rc == 0 ? H2_OK : H2_EINVAL;
 }
+template <class FP>
+static int selftest_fe29(int op, const int32_t* in, int32_t* out) {
+  Fe29<FP> a[4];
+  for (int k = 0; k < 4; k++) memcpy(a[k].v, in + 9 * k, sizeof(a[k].v));
+  Fe29<FP> r;
+  switch (op) {
+    case 0: r = fe29_mul(a[0], a[1]); break;
+    case 1: r = fe29_sqr(a[0]); break;
+    case 2: r = fe29_mul_sub(a[0], a[1], a[2], a[3]); break;
+    case 3: r = fe29_mul_up(a[0], a[1]); break;
+    default: return H2_EINVAL;
+  }
+  memcpy(out, r.v, sizeof(r.v));
+  return H2_OK;
+}
+extern "C" int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]) {
+  if (!in || !out) return H2_EINVAL;
+  switch (field) {
+    case 0: return selftest_fe29<BN254_FQ>(op, in, out);
+    case 1: return selftest_fe29<BN254_FR>(op, in, out);
+    case 2: return selftest_fe29<PASTA_FP>(op, in, out);
+    case 3: return selftest_fe29<PASTA_FQ>(op, in, out);
+  }
+  return H2_EINVAL;
+}
 extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) {
   const CurveOps* ops = ops_of(curve);
   if (!ops || !p || !q || !out) return H2_EINVAL;

@@ -26,7 +26,7 @@ struct Affine29 {
 template <class CV>
 struct Xyzz29 {
   using F = Fe29<typename CV::Base>;
-  F x, y, zz, zzz;                                       // |x| < 5p, |y| < 2p, zz, zzz in (-p/2, 3p/2)
+  F x, y, zz, zzz;                                       // |x| < 5p, |y| < 2p, zz, zzz in (-3p/2, p/2]
   H2_HD bool is_identity() const { return zz.is_zero_exact(); }
   static H2_HD Xyzz29 identity() { return Xyzz29{F::zero(), F::zero(), F::zero(), F::zero()}; }
 };
@@ -118,7 +118,7 @@ H2_HD Xyzz29<CV> xyzz29_double(const Xyzz29<CV>& p) {
   const F s = fe29_mul(p.x, v);                          // 5 * 1.5
   const F xx = fe29_sqr(p.x);                            // 25
   const F m = fe29_norm(fe29_add(fe29_add(xx, xx), xx)); // < 4.5
-  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sqr(m), s), s));                        // (-3.5, 2.5)
+  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sqr(m), s), s));                        // (-2.5, 3.5)
   const F y3 = fe29_mul_sub(m, fe29_sub(s, x3), w, p.y);                                // 4.5 * 5 + 1.5 * 2, one reduction
   return Xyzz29<CV>{x3, y3, fe29_mul(v, p.zz), fe29_mul(w, p.zzz)};
 }
@@ -131,8 +131,8 @@ H2_HD Xyzz29<CV> xyzz29_add_affine(const Xyzz29<CV>& acc, const Affine29<CV>& q)
   if (acc.is_identity()) return xyzz29_from_affine(q);
   const F u2 = fe29_mul(q.x, acc.zz);
   const F s2 = fe29_mul(q.y, acc.zzz);
-  const F p = fe29_sub(u2, acc.x);                       // (-3.5, 6.5); limbs of magnitude < 2^29
-  const F r = fe29_sub(s2, acc.y);                       // (-2.5, 3.5)
+  const F p = fe29_sub(u2, acc.x);                       // (-6.5, 3.5); limbs of magnitude < 2^29
+  const F r = fe29_sub(s2, acc.y);                       // (-3.5, 2.5)
   if (fe29_is_zero_mod_p(p)) {
     if (fe29_is_zero_mod_p(r)) return xyzz29_double_affine(q);
     return Xyzz29<CV>::identity();
@@ -140,7 +140,7 @@ H2_HD Xyzz29<CV> xyzz29_add_affine(const Xyzz29<CV>& acc, const Affine29<CV>& q)
   const F pp = fe29_sqr(p);                              // 42
   const F ppp = fe29_mul(p, pp);                         // 6.5 * 1.5
   const F qq = fe29_mul(acc.x, pp);                      // 5 * 1.5
-  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(fe29_sqr(r), ppp), qq), qq));       // (-5, 3)
+  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(fe29_sqr(r), ppp), qq), qq));       // (-3, 5)
   const F y3 = fe29_mul_sub(r, fe29_sub(qq, x3), acc.y, ppp);                            // 3.5 * 6.5 + 2 * 1.5, one reduction
   return Xyzz29<CV>{x3, y3, fe29_mul(acc.zz, pp), fe29_mul(acc.zzz, ppp)};
 }

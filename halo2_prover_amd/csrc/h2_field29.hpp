@@ -12,13 +12,26 @@
 // Invariants (the callers in h2_curve29.hpp are written against these):
 //   value   x R' mod p, as the integer  sum_i v[i] 2^(29 i)  with SIGNED limbs -- it may be negative or exceed p.
 //   fe29_mul(a, b): needs |a_i| < 2^30 and |b_j| < 2^29 (or the other way round: the sums of 18 limb products must
-//           stay below 2^63), and |a| |b| <= 64 p^2.  Returns limbs in [0, 2^29) (top limb signed, small) and a
-//           value in (-p/2, 3p/2).
+//           stay below 2^63), and |a| |b| <= 64 p^2.  Returns limbs in [0, 2^29) (top limb signed, small) and the value
+//           (a b - m p) / R' with 0 <= m < R' (the SUBTRACTIVE reduction, below): in (a b / R' - p, a b / R'], so in
+//           (-3p/2, p/2] -- the mirror image of the additive form's (-p/2, 3p/2), so every magnitude bound the callers
+//           were written against (|x| < 1.5p for a product) still holds; only what relied on the sign moved
+//           (fe29_canonical_pack, fe29_to_api, w_canonical_pack; the NTT's inter-pass store keeps the additive
+//           fe29_mul_up, in [a b / R', a b / R' + p)).  For the Pasta primes 64 p / R' exceeds 1/2 by 2^-127 relative,
+//           so "p/2" there means p/2 (1 + 2^-127); nothing below depends on that slack.
+//   fe29_sqr(a): |a_i| < 2^29, |a|^2 <= 64 p^2; fe29_mul_sub(a, b, c, d): every limb below 2^29 in magnitude,
+//           |a b - c d| <= 64 p^2.  Same output limbs and range as fe29_mul.
 //   fe29_add / fe29_sub / fe29_neg: limb-wise, no carries: limb magnitudes add up.  A difference of two normalised
 //           values has limbs of magnitude < 2^29 and can go straight into a product; anything built from three or
 //           more terms is passed through fe29_norm (carry propagation: limbs back in [0, 2^29), value unchanged).
 //   exact zero (all limbs 0) only ever arises from the identity's coordinates, so `is_zero_exact` is the identity
 //   test; `fe29_is_zero_mod_p` is the real test for the exceptional cases of the addition formulas.
+//
+// The column kernel (round 4): each column is its limb products as 64-bit multiply-adds, then the Montgomery step
+// m = acc p^-1 mod 2^29 and acc -= m p.  For p = 1 mod 2^29 (Pasta) m is acc's low 29 bits and the p[0] term is never
+// computed (acc - m only clears what the arithmetic shift drops); the top limb 2^22 is one multiply-add with a hidden
+// constant instead of a 64-bit shift and add.  What is left per column is one AND, one 64-bit shift and the one 64-bit
+// add the compiler uses to join the column's two multiply-add chains (the ISA table).
 //
 // Conversions need no new constants: the API form x 2^256 is the R' form of x / 32, so going in is five doublings
 // in the 32-bit-limb field, and going out is one product with FP::ONE (= 2^256 mod p) read as a plain integer.
@@ -118,27 +131,69 @@ H2_HD Fe29<FP> fe29_norm(const Fe29<FP>& a) {
   return r;
 }
 
+// The limb products are signed 32 x 32 -> 64 multiply-adds: ONE v_mad_i64_i32 each.  But where the optimiser can PROVE a
+// limb non-negative (a value just unpacked or masked) it rewrites that operand's sign extension as a zero extension,
+// and the back end then has neither its signed nor its unsigned pattern for sext(a) * zext(b): it multiplies 32 x 64
+// bits -- two v_mad_u64_u32, two moves, and for the signed top limbs two v_mul_lo_u32 and a v_add3_u32 more (seen in
+// msm_chunk_kernel's ISA: 1211 multiply-adds + 112 v_mul_lo_u32 per point addition against 1062 limb products).  An
+// empty asm statement per operand limb hides the range from the optimiser and costs no instruction.
+H2_HD int32_t fe29_opaque(int32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(x));
+#endif
+  return x;
+}
 namespace detail29 {
-// acc += m * p[J], the constant limb folded: 0 -> nothing, 1 -> add, 2^s -> shifted add
-template <class FP, int J>
-H2_HD void mac_p(int64_t& acc, int32_t m) {
+// a constant the optimiser may not see (it stays in a scalar register): m * 2^22 or m * (2^28 + 1) is then ONE
+// multiply-add, not the 64-bit shifts and 64-bit adds the optimiser would rewrite it into
+H2_HD int32_t fe29_hidden(int32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+s"(c));
+#endif
+  return c;
+}
+// acc -= m * p[J]: a zero limb costs nothing, every other one (2^22 included) one multiply-add with -p[J]; the sparse
+// constants are hidden, the dense ones are not worth a shift sequence to the optimiser anyway.  UP (the additive form,
+// fe29_mul_up): acc += m * p[J], the constant limb folded: 1 -> add, 2^s -> shifted add
+template <class FP, int J, bool UP>
+H2_HD void msub_p(int64_t& acc, int32_t m) {
   constexpr uint32_t pj = fe29_p<FP>(J);
-  if constexpr (pj == 0) {
-  } else if constexpr (pj == 1) {
-    acc += m;
-  } else if constexpr ((pj & (pj - 1)) == 0) {
-    acc += (int64_t)m << __builtin_ctz(pj);
+  if constexpr (UP) {
+    if constexpr (pj == 0) {
+    } else if constexpr (pj == 1) {
+      acc += m;
+    } else if constexpr ((pj & (pj - 1)) == 0) {
+      acc += (int64_t)m << __builtin_ctz(pj);
+    } else {
+      acc += (int64_t)m * (int32_t)pj;
+    }
+  } else if constexpr (pj == 0) {
+  } else if constexpr (__builtin_popcount(pj) <= 2) {
+    acc += (int64_t)m * fe29_hidden(-(int32_t)pj);
   } else {
-    acc += (int64_t)m * (int32_t)pj;
+    acc += (int64_t)m * -(int32_t)pj;
   }
 }
-// m with (acc + m p) = 0 mod 2^29: m = acc * (-p^-1) mod 2^29.  For the Pasta primes p = 1 mod 2^29, so that is -acc:
-// a subtraction instead of a quarter-rate v_mul_lo_u32, nine times per product
-template <class FP>
-H2_HD int32_t mont_m(uint32_t acc_lo) {
-  constexpr uint32_t ninv = FP::INV & L29_MASK;
-  if constexpr (ninv == L29_MASK) return (int32_t)((0u - acc_lo) & L29_MASK);
-  else return (int32_t)((acc_lo * ninv) & L29_MASK);
+// the Montgomery step of column K < 9, SUBTRACTIVE: m = acc p^-1 mod 2^29 in [0, 2^29), acc -= m p[0].  For the Pasta
+// primes p = 1 mod 2^29: m is acc's own low 29 bits (one AND, no negation, no v_mul_lo_u32) and acc - m p[0] = acc - m
+// only clears the bits that the shift after it drops -- the p[0] term is not computed at all
+// UP: m = -acc p^-1 mod 2^29 and acc += m p[0] (the form before the subtractive one, kept for fe29_mul_up)
+template <class FP, bool UP>
+H2_HD int32_t mont_step(int64_t& acc) {
+  constexpr uint32_t pinv = (0u - (FP::INV & L29_MASK)) & L29_MASK;     // p^-1 mod 2^29 (FP::INV = -p^-1 mod 2^32)
+  if constexpr (UP) {
+    constexpr uint32_t ninv = FP::INV & L29_MASK;
+    const int32_t m = ninv == L29_MASK ? (int32_t)((0u - (uint32_t)acc) & L29_MASK)
+                                       : (int32_t)(((uint32_t)acc * ninv) & L29_MASK);
+    msub_p<FP, 0, true>(acc, m);
+    return m;
+  } else if constexpr (pinv == 1) {
+    return fe29_opaque((int32_t)((uint32_t)acc & L29_MASK));
+  } else {
+    const int32_t m = fe29_opaque((int32_t)(((uint32_t)acc * pinv) & L29_MASK));
+    msub_p<FP, 0, false>(acc, m);
+    return m;
+  }
 }
 template <class FP, int K, int I, int IEND>
 H2_HD void col_ab(int64_t& acc, const int32_t* a, const int32_t* b) {
@@ -147,28 +202,33 @@ H2_HD void col_ab(int64_t& acc, const int32_t* a, const int32_t* b) {
     col_ab<FP, K, I + 1, IEND>(acc, a, b);
   }
 }
-template <class FP, int K, int I, int IEND>
+template <class FP, int K, int I, int IEND, bool UP>
 H2_HD void col_mp(int64_t& acc, const int32_t* m) {
   if constexpr (I <= IEND) {
-    mac_p<FP, K - I>(acc, m[I]);
-    col_mp<FP, K, I + 1, IEND>(acc, m);
+    msub_p<FP, K - I, UP>(acc, m[I]);
+    col_mp<FP, K, I + 1, IEND, UP>(acc, m);
   }
 }
-// column K of a*b + m*p; the low half fixes m[K] so that the column's low 29 bits vanish
-template <class FP, int K>
+// after column K's limb products: the m p terms, then (K < 9) m[K] such that the column's low 29 bits vanish, or
+// (K >= 9) output limb K - 9; the arithmetic shift hands the rest to column K + 1 (exact below K = 9)
+template <class FP, int K, bool UP = false>
+H2_HD void reduce_col(int64_t& acc, int32_t* m, int32_t* t) {
+  if constexpr (K < 9) {
+    if constexpr (K > 0) col_mp<FP, K, 0, K - 1, UP>(acc, m);
+    m[K] = mont_step<FP, UP>(acc);
+  } else {
+    col_mp<FP, K, K - 8, 8, UP>(acc, m);
+    t[K - 9] = (int32_t)((uint32_t)acc & L29_MASK);
+  }
+  acc >>= 29;
+}
+// column K of a*b - m*p (UP: a*b + m*p)
+template <class FP, int K, bool UP = false>
 H2_HD void columns(int64_t& acc, const int32_t* a, const int32_t* b, int32_t* m, int32_t* t) {
   if constexpr (K < 17) {
     col_ab<FP, K, (K < 9 ? 0 : K - 8), (K < 9 ? K : 8)>(acc, a, b);
-    if constexpr (K < 9) {
-      if constexpr (K > 0) col_mp<FP, K, 0, K - 1>(acc, m);
-      m[K] = mont_m<FP>((uint32_t)acc);
-      mac_p<FP, 0>(acc, m[K]);
-    } else {
-      col_mp<FP, K, K - 8, 8>(acc, m);
-      t[K - 9] = (int32_t)((uint32_t)acc & L29_MASK);
-    }
-    acc >>= 29;                                                               // arithmetic: exact below K = 9
-    columns<FP, K + 1>(acc, a, b, m, t);
+    reduce_col<FP, K, UP>(acc, m, t);
+    columns<FP, K + 1, UP>(acc, a, b, m, t);
   }
 }
 // column K of a^2: cross terms with the doubled operand, the square of the middle limb once
@@ -184,15 +244,7 @@ template <class FP, int K>
 H2_HD void columns_sq(int64_t& acc, const int32_t* a, const int32_t* a2, int32_t* m, int32_t* t) {
   if constexpr (K < 17) {
     col_sq<FP, K, (K < 9 ? 0 : K - 8), K / 2>(acc, a, a2);
-    if constexpr (K < 9) {
-      if constexpr (K > 0) col_mp<FP, K, 0, K - 1>(acc, m);
-      m[K] = mont_m<FP>((uint32_t)acc);
-      mac_p<FP, 0>(acc, m[K]);
-    } else {
-      col_mp<FP, K, K - 8, 8>(acc, m);
-      t[K - 9] = (int32_t)((uint32_t)acc & L29_MASK);
-    }
-    acc >>= 29;
+    reduce_col<FP, K>(acc, m, t);
     columns_sq<FP, K + 1>(acc, a, a2, m, t);
   }
 }
@@ -202,32 +254,12 @@ H2_HD void columns2(int64_t& acc, const int32_t* a, const int32_t* b, const int3
   if constexpr (K < 17) {
     col_ab<FP, K, (K < 9 ? 0 : K - 8), (K < 9 ? K : 8)>(acc, a, b);
     col_ab<FP, K, (K < 9 ? 0 : K - 8), (K < 9 ? K : 8)>(acc, c, d);
-    if constexpr (K < 9) {
-      if constexpr (K > 0) col_mp<FP, K, 0, K - 1>(acc, m);
-      m[K] = mont_m<FP>((uint32_t)acc);
-      mac_p<FP, 0>(acc, m[K]);
-    } else {
-      col_mp<FP, K, K - 8, 8>(acc, m);
-      t[K - 9] = (int32_t)((uint32_t)acc & L29_MASK);
-    }
-    acc >>= 29;
+    reduce_col<FP, K>(acc, m, t);
     columns2<FP, K + 1>(acc, a, b, c, d, m, t);
   }
 }
 }  // namespace detail29
 
-// The limb products are signed 32 x 32 -> 64 multiply-adds: ONE v_mad_i64_i32 each.  But where the optimiser can PROVE a
-// limb non-negative (a value just unpacked or masked) it rewrites that operand's sign extension as a zero extension,
-// and the back end then has neither its signed nor its unsigned pattern for sext(a) * zext(b): it multiplies 32 x 64
-// bits -- two v_mad_u64_u32, two moves, and for the signed top limbs two v_mul_lo_u32 and a v_add3_u32 more (seen in
-// msm_chunk_kernel's ISA: 1211 multiply-adds + 112 v_mul_lo_u32 per point addition against 1062 limb products).  An
-// empty asm statement per operand limb hides the range from the optimiser and costs no instruction.
-H2_HD int32_t fe29_opaque(int32_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm("" : "+v"(x));
-#endif
-  return x;
-}
 template <class FP>
 H2_HD void fe29_opaque_limbs(int32_t* o, const Fe29<FP>& a) {
 #pragma unroll
@@ -254,6 +286,20 @@ H2_HD Fe29<FP> fe29_mul_plain(const Fe29<FP>& a, const Fe29<FP>& b) {
   int32_t m[9];
   Fe29<FP> r;
   detail29::columns<FP, 0>(acc, a.v, b.v, m, r.v);
+  r.v[8] = (int32_t)acc;
+  return r;
+}
+// a b / R' rounded UP: (a b + m p) / R' in [a b / R', a b / R' + p) -- non-negative for a b >= 0.  The form of the
+// product before the subtractive one (p[0] and 2^22 terms as 64-bit adds, a negated m): where a non-negative result is
+// stored as it is (the NTT's inter-pass product) it costs less than a carry pass after the subtractive product
+template <class FP>
+H2_HD Fe29<FP> fe29_mul_up(const Fe29<FP>& a, const Fe29<FP>& b) {
+  int64_t acc = 0;
+  int32_t m[9], av[9], bv[9];
+  fe29_opaque_limbs(av, a);
+  fe29_opaque_limbs(bv, b);
+  Fe29<FP> r;
+  detail29::columns<FP, 0, true>(acc, av, bv, m, r.v);
   r.v[8] = (int32_t)acc;
   return r;
 }
@@ -298,34 +344,25 @@ H2_HD Fe29<FP> fe29_from_api(const Fe<FP>& a) {
   for (int i = 0; i < 5; i++) t = fe_dbl(t);
   return fe29_unpack(t);
 }
-// working form (any value of magnitude < 64 p, limbs of magnitude < 2^30) -> API form, canonical
-template <class FP>
-H2_HD Fe<FP> fe29_to_api(const Fe29<FP>& a) {
-  Fe<FP> one;
-#pragma unroll
-  for (int i = 0; i < 8; i++) one.v[i] = FP::ONE(i);                 // 2^256 mod p as a plain integer
-  Fe29<FP> t = fe29_mul(a, fe29_unpack(one));                        // in (-p/2, 3p/2), limbs normalised
-  Fe29<FP> pl;
-#pragma unroll
-  for (int i = 0; i < 9; i++) pl.v[i] = (int32_t)fe29_p<FP>(i);
-  if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
-  const Fe29<FP> s = fe29_norm(fe29_sub(t, pl));
-  if (s.v[8] >= 0) t = s;
-  return fe29_pack(t);
-}
-
-// t in (-p/2, 3p/2) with normalised limbs -> canonical, packed
+// t in (-2p, p) with normalised limbs (a product's result) -> canonical, packed
 template <class FP>
 H2_HD Fe<FP> fe29_canonical_pack(Fe29<FP> t) {
   Fe29<FP> pl;
 #pragma unroll
   for (int i = 0; i < 9; i++) pl.v[i] = (int32_t)fe29_p<FP>(i);
   if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
-  const Fe29<FP> s = fe29_norm(fe29_sub(t, pl));
-  if (s.v[8] >= 0) t = s;
+  if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
   return fe29_pack(t);
 }
-// t in (-p, 3p), any limbs within fe29_norm's reach -> canonical, packed (the API's bytes when t is x 2^256 + j p)
+// working form (any value of magnitude < 64 p, limbs of magnitude < 2^30) -> API form, canonical
+template <class FP>
+H2_HD Fe<FP> fe29_to_api(const Fe29<FP>& a) {
+  Fe<FP> one;
+#pragma unroll
+  for (int i = 0; i < 8; i++) one.v[i] = FP::ONE(i);                 // 2^256 mod p as a plain integer
+  return fe29_canonical_pack(fe29_mul(a, fe29_unpack(one)));        // in (-3p/2, p/2], limbs normalised
+}
+// t in (-2p, 2p), any limbs within fe29_norm's reach -> canonical, packed (the API's bytes when t is x 2^256 + j p)
 template <class FP>
 H2_HD Fe<FP> w_canonical_pack(const Fe29<FP>& t0) {
   Fe29<FP> pl;
@@ -333,9 +370,8 @@ H2_HD Fe<FP> w_canonical_pack(const Fe29<FP>& t0) {
   for (int i = 0; i < 9; i++) pl.v[i] = (int32_t)fe29_p<FP>(i);
   Fe29<FP> t = fe29_norm(t0);
   if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
-  Fe29<FP> s = fe29_norm(fe29_sub(t, pl));
-  if (s.v[8] >= 0) t = s;
-  s = fe29_norm(fe29_sub(t, pl));
+  if (t.v[8] < 0) t = fe29_norm(fe29_add(t, pl));
+  const Fe29<FP> s = fe29_norm(fe29_sub(t, pl));
   if (s.v[8] >= 0) t = s;
   return fe29_pack(t);
 }
@@ -398,8 +434,9 @@ H2_HD Fe29<FP> fe29_inv(const Fe29<FP>& a) {
   return r;
 }
 
-// x == 0 mod p for a loosely reduced x (|x| < 16 p): if x = j p then j = x[0] p^-1 mod 2^29 is tiny -- anything else
-// is rejected by that one limb; the rare survivors are reduced completely
+// x == 0 mod p for a loosely reduced x (|x| < 16 p: the callers pass differences of a few products and normalised
+// values, |x| < 4p): if x = j p then j = x[0] p^-1 mod 2^29 is in (-16, 16) -- anything else is rejected by that one
+// limb; the rare survivors are reduced completely (fe29_to_api takes any |x| < 64 p)
 template <class FP>
 H2_HD bool fe29_is_zero_mod_p(const Fe29<FP>& a) {
   constexpr uint32_t pinv = (0u - (FP::INV & L29_MASK)) & L29_MASK;  // p^-1 mod 2^29

@@ -9,14 +9,15 @@
 //     subtractions are nine limb operations without carries; every value written back to LDS is carry-normalised
 //     (limbs in [0, 2^29), the top limb takes the sign);
 //   * magnitudes: a tile's inputs are below 3p/2 (canonical API data, or what a non-final pass stored: see below); a
-//     radix-4 double stage adds at most two products (each in (-p/2, 3p/2)) to an element, the very first one (all
+//     radix-4 double stage adds at most two products (each in (-3p/2, p/2)) to an element, the very first one (all
 //     twiddles 1) at most quadruples it: <= 4 * 1.5p + 3p * 4 = 18p after the five double stages of a 1024-row tile,
 //     well inside fe29_mul's |a| |b| <= 64 p^2 with a canonical twiddle as b.
 // Round 3: what the pass did besides products:
 //   * leaving a NON-FINAL pass an element x is multiplied by the inter-pass twiddle anyway.  It is first moved to
 //     32p + x (or 32p - x where the exponent asks for -w: the negation costs nothing) -- positive, limbs below 2^30 --
-//     so the product lies in [0, 1.5p) and its limbs pack to 256 bits as they are: no carry pass, no conditional
-//     additions.  The stored value is a representative below 2^256, not the canonical one; only the next pass reads it;
+//     so the product rounded up (fe29_mul_up) lies in [0, 1.5p) and its limbs pack to 256 bits as they are: no carry
+//     pass, no conditional additions.  The stored value is a representative below 2^256, not the canonical one; only
+//     the next pass reads it;
 //   * leaving the FINAL pass nothing is multiplied (round 2: a 240-instruction product with 1 on every element of every
 //     forward transform): t = floor(x / 2^252) is read off the top limb and x - T[t] with T[t] = floor(t 2^252 / p) p
 //     from a 300-entry table lies in [0, p + 2^252): one conditional subtraction makes it canonical;
@@ -240,7 +241,8 @@ ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U12
     if (!P.is_final || P.has_scale) {
       // one product: the inter-pass twiddle w^(outer * i * k) (the table's entry 0 is 1, or the constant of a scaled
       // transform) or the final pass's scale.  32p +- x is positive (|x| <= 18p) with limbs below 2^30, so the product
-      // is in [0, 50 p / 128 + p) and its limbs are those of a non-negative integer below 2^256: packed as they are
+      // rounded up (fe29_mul_up) is in [0, 50 p / 128 + p) and its limbs are those of a non-negative integer below
+      // 2^256: packed as they are
       Fe29<FP> t;
       bool negate = false;
       if (!P.is_final) {
@@ -252,8 +254,8 @@ ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U12
         t = fe29_unpack(scale29);
       }
       x = negate ? fe29_sub(p32, x) : fe29_add(p32, x);
-      x = fe29_mul(x, t);
-      if (P.is_final) r = fe29_canonical_pack(x);       // a scaled final pass (one or three passes): canonical bytes
+      x = fe29_mul_up(x, t);
+      if (P.is_final) r = fe29_canonical_pack(fe29_norm(fe29_sub(x, pl)));   // a scaled final pass: canonical bytes
       else r = fe29_pack(x);
     } else {
       // no product: t = floor(x / 2^252) from the top limb (x is carry-normalised), x - T[t] in [0, p + 2^252)

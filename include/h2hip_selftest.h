@@ -72,6 +72,10 @@ uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */
 int h2_selftest_set_shard_min_rows(size_t rows);
 int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, size_t cap, size_t* out_len);
+/* the 29-bit working-form product (h2_field29.hpp) instantiated on the host, no GPU: field 0 bn254 Fq, 1 bn254 Fr,
+ * 2 pasta Fp, 3 pasta Fq; in = four operands a, b, c, d of 9 signed 29-bit-radix limbs; op 0: fe29_mul(a, b),
+ * 1: fe29_sqr(a), 2: fe29_mul_sub(a, b, c, d), 3: fe29_mul_up(a, b) -> the 9 limbs of the result */
+int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]);
 /* scratch arenas of the current context: out = {allocations, cross-stream hand-overs (event waits), MSM slots taken
  * over by a further stream, NTT slots taken over} since h2_init */
 int h2_selftest_arena_stats(uint64_t out[4]);

@@ -974,30 +974,62 @@ extern "C" int h2_selftest_field_op(int field, int op, const uint64_t a[4], cons
   }
   return rc == 0 ? H2_OK : H2_EINVAL;
 }
+// one operand set (a, b, c, d: 9 limbs each) through op 0..3; the host hook and the device kernel run this same source
 template <class FP>
-static int selftest_fe29(int op, const int32_t* in, int32_t* out) {
+H2_HD void selftest_fe29_run(int op, const int32_t* in, int32_t* out) {
   Fe29<FP> a[4];
-  for (int k = 0; k < 4; k++) memcpy(a[k].v, in + 9 * k, sizeof(a[k].v));
+  for (int k = 0; k < 4; k++)
+    for (int l = 0; l < 9; l++) a[k].v[l] = in[9 * k + l];
   Fe29<FP> r;
   switch (op) {
     case 0: r = fe29_mul(a[0], a[1]); break;
     case 1: r = fe29_sqr(a[0]); break;
     case 2: r = fe29_mul_sub(a[0], a[1], a[2], a[3]); break;
-    case 3: r = fe29_mul_up(a[0], a[1]); break;
-    default: return H2_EINVAL;
+    default: r = fe29_mul_up(a[0], a[1]); break;
   }
-  memcpy(out, r.v, sizeof(r.v));
-  return H2_OK;
+  for (int l = 0; l < 9; l++) out[l] = r.v[l];
+}
+template <class FP>
+__global__ void __launch_bounds__(64) selftest_fe29_kernel(int op, const int32_t* __restrict__ in, int32_t* __restrict__ out,
+                                                           uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  selftest_fe29_run<FP>(op, in + 36 * (size_t)i, out + 9 * (size_t)i);
 }
 extern "C" int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]) {
-  if (!in || !out) return H2_EINVAL;
+  if (!in || !out || op < 0 || op > 3) return H2_EINVAL;
   switch (field) {
-    case 0: return selftest_fe29<BN254_FQ>(op, in, out);
-    case 1: return selftest_fe29<BN254_FR>(op, in, out);
-    case 2: return selftest_fe29<PASTA_FP>(op, in, out);
-    case 3: return selftest_fe29<PASTA_FQ>(op, in, out);
+    case 0: selftest_fe29_run<BN254_FQ>(op, in, out); return H2_OK;
+    case 1: selftest_fe29_run<BN254_FR>(op, in, out); return H2_OK;
+    case 2: selftest_fe29_run<PASTA_FP>(op, in, out); return H2_OK;
+    case 3: selftest_fe29_run<PASTA_FQ>(op, in, out); return H2_OK;
   }
   return H2_EINVAL;
+}
+// n operand sets through the DEVICE instantiation, one kernel launch; host pointers in (36 limbs per set) and out (9)
+extern "C" int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* out, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!in || !out || n == 0 || n > (1u << 20) || field < 0 || field > 3 || op < 0 || op > 3) return H2_EINVAL;
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  const size_t in_bytes = n * 36 * 4, out_bytes = n * 9 * 4;
+  ArenaLease stage(g_ctx.stage, in_bytes + out_bytes, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  int32_t* d_in = (int32_t*)g_ctx.stage.p;
+  int32_t* d_out = (int32_t*)((char*)g_ctx.stage.p + in_bytes);
+  H2_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, g_ctx.stream));
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  switch (field) {
+    case 0: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    case 1: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FR>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    case 2: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FP>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    default: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dev_fail(e, "selftest_fe29_kernel");
+  H2_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
 }
 extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) {
   const CurveOps* ops = ops_of(curve);

@@ -11,14 +11,18 @@
 //
 // Invariants (the callers in h2_curve29.hpp are written against these):
 //   value   x R' mod p, as the integer  sum_i v[i] 2^(29 i)  with SIGNED limbs -- it may be negative or exceed p.
-//   fe29_mul(a, b): needs |a_i| < 2^30 and |b_j| < 2^29 (or the other way round: the sums of 18 limb products must
-//           stay below 2^63), and |a| |b| <= 64 p^2.  Returns limbs in [0, 2^29) (top limb signed, small) and the value
-//           (a b - m p) / R' with 0 <= m < R' (the SUBTRACTIVE reduction, below): in (a b / R' - p, a b / R'], so in
-//           (-3p/2, p/2] -- the mirror image of the additive form's (-p/2, 3p/2), so every magnitude bound the callers
-//           were written against (|x| < 1.5p for a product) still holds; only what relied on the sign moved
-//           (fe29_canonical_pack, fe29_to_api, w_canonical_pack; the NTT's inter-pass store keeps the additive
-//           fe29_mul_up, in [a b / R', a b / R' + p)).  For the Pasta primes 64 p / R' exceeds 1/2 by 2^-127 relative,
-//           so "p/2" there means p/2 (1 + 2^-127); nothing below depends on that slack.
+//   fe29_mul(a, b): needs only the limb bounds |a_i| < 2^30 and |b_j| < 2^29 (or the other way round: the sums of 18
+//           limb products must stay below 2^63).  Returns exactly (a b - m p) / R' with m = a b p^-1 mod R', 0 <= m < R'
+//           (the SUBTRACTIVE reduction, below), in the normalised form: limbs 0..7 in [0, 2^29), the top limb signed.
+//           Its value lies in (a b / R' - p, a b / R'] for ANY operands within the limb bounds (tests/
+//           test_fe29_product.py checks products up to 1024 p^2: the callers' (+-32 p)^2 in expr_kernel, (+-16 p)^2 in
+//           perm_ratio_kernel).  Only when also |a| |b| <= 64 p^2 is it in (-3p/2, p/2] -- the mirror image of the
+//           additive form's (-p/2, 3p/2), so every magnitude bound the callers were written against (|x| < 1.5p for a
+//           product of such operands) still holds; only what relied on the sign moved (fe29_canonical_pack,
+//           fe29_to_api, w_canonical_pack; the NTT's inter-pass store keeps the additive fe29_mul_up, exactly
+//           (a b + m' p) / R' with m' = -a b p^-1 mod R', in [a b / R', a b / R' + p)).  For the Pasta primes
+//           64 p / R' exceeds 1/2 by 2^-127 relative, so "p/2" there means p/2 (1 + 2^-127); nothing below depends on
+//           that slack.
 //   fe29_sqr(a): |a_i| < 2^29, |a|^2 <= 64 p^2; fe29_mul_sub(a, b, c, d): every limb below 2^29 in magnitude,
 //           |a b - c d| <= 64 p^2.  Same output limbs and range as fe29_mul.
 //   fe29_add / fe29_sub / fe29_neg: limb-wise, no carries: limb magnitudes add up.  A difference of two normalised

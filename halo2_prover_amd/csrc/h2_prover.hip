@@ -522,6 +522,9 @@ struct ExprProgram {
   // result with no other use is never stored: a slot costs 32 bytes of LDS per row and the slots of 128 rows decide
   // how many blocks share a CU (h2_prover_kernels.hpp, expr_kernel).
   void compile(int root) {
+    for (const Node& nd : nodes)                     // the operand word has 22 bits for a column and 8 for rot + 128
+      if (nd.op == 1 && (nd.col < 0 || nd.col >= (1 << 22) || nd.rot < -128 || nd.rot > 127))
+        fail(H2_EINVAL, "quotient program: column index or rotation does not fit its operand word");
     (void)constant(Fr::one());                       // the reducing product's operand: interned before the node tables are sized
     std::vector<int> need(nodes.size(), -1);
     std::function<int(int)> su = [&](int id) -> int {
@@ -609,7 +612,81 @@ struct ExprProgram {
     }
     if (nslots == 0) nslots = 1;
   }
+  // six u32 -- instructions, products, column reads, live-value slots, constants, inserted reductions -- then the code
+  // (12 bytes per instruction): what the test hooks report
+  std::vector<uint8_t> report() const {
+    uint32_t st[6] = {(uint32_t)code.size(), 0, 0, nslots, (uint32_t)consts.size(), nreduce};
+    for (auto& ins : code) {
+      if ((ins.op_dst >> 24) == 2) st[1]++;
+      if ((ins.a & (3u << 30)) == pk::X_COL) st[2]++;
+      if ((ins.b & (3u << 30)) == pk::X_COL) st[2]++;
+    }
+    std::vector<uint8_t> r(24 + code.size() * sizeof(pk::XInstr));
+    memcpy(r.data(), st, 24);
+    memcpy(r.data() + 24, code.data(), code.size() * sizeof(pk::XInstr));
+    return r;
+  }
 };
+
+// expr_kernel over en rows: the column pointers and row masks, the constant table (c, patched for the proof) in the
+// kernel's working form c 2^261, and the LDS of the slots beyond the registers -- checked against what one workgroup
+// may hold before anything is uploaded or launched.  create_proof and the test hook h2_selftest_expr_run both launch
+// the quotient program through here.
+size_t expr_lds_bytes(const ExprProgram& X) {
+  const size_t lds_slots = X.nslots > (uint32_t)pk::EXPR_REG_SLOTS ? X.nslots - pk::EXPR_REG_SLOTS : 1;
+  const size_t lds = lds_slots * 9 * pk::EXPR_BLOCK * 4;
+  if (lds > pk::EXPR_LDS_MAX) fail(H2_EINVAL, "quotient program needs too many live values");
+  return lds;
+}
+void expr_launch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, const std::vector<const U128*>& ptrs,
+                 const std::vector<uint32_t>& masks, std::vector<Fr> consts, Col out, uint32_t step, uint32_t en) {
+  const size_t lds = expr_lds_bytes(X);
+  const U128* const* d_ptrs = (const U128* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
+  const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
+  for (auto& c : consts)
+    for (int t = 0; t < 5; t++) c = c + c;            // c 2^256 -> c 2^261: the kernel's working form (R' = 2^261)
+  Col d_consts = d.upload_frs(consts);
+  if (lds > 64 * 1024)                                // past 64 KiB: raised, as the MSM and NTT kernels raise theirs
+    hip_ok(hipFuncSetAttribute((const void*)pk::expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+           "hipFuncSetAttribute(expr_kernel)");
+  hipLaunchKernelGGL(pk::expr_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK), dim3(pk::EXPR_BLOCK), lds, d.s, d_code,
+                     (uint32_t)X.code.size(), d_ptrs, d_masks, d_consts, out, step, en);
+  hip_ok(hipGetLastError(), "expr_kernel");
+}
+
+// a caller's expression DAG (the test hooks h2_selftest_host what = 7 and h2_selftest_expr_run): u32 node count, u32
+// constant count, then per node four i32 {op, a, b, x} -- op 0: constant x; 1: column a at rotation x; 2 / 3 / 4: add /
+// sub / mul of the earlier nodes a and b -- then the constants, 32 canonical little-endian bytes each.  The last node
+// is the root.  Built through ExprProgram's own methods and compiled as the prover compiles its quotient.
+void program_from_dag(const uint8_t* in, size_t in_len, ExprProgram& X) {
+  if (!in || in_len < 8) fail(H2_EINVAL, "dag: truncated");
+  uint32_t nn, nc;
+  memcpy(&nn, in, 4);
+  memcpy(&nc, in + 4, 4);
+  if (nn == 0 || nn > (1u << 20) || nc > (1u << 20) || in_len != 8 + 16 * (size_t)nn + 32 * (size_t)nc)
+    fail(H2_EINVAL, "dag: wrong length");
+  std::vector<Fr> cs(nc);
+  for (uint32_t j = 0; j < nc; j++)
+    if (!Fr::from_le_bytes_canonical(in + 8 + 16 * (size_t)nn + 32 * (size_t)j, &cs[j])) fail(H2_EINVAL, "dag: constant not canonical");
+  std::vector<int> id(nn);
+  for (uint32_t i = 0; i < nn; i++) {
+    int32_t f[4];
+    memcpy(f, in + 8 + 16 * (size_t)i, 16);
+    const int op = f[0], a = f[1], b = f[2], x = f[3];
+    if (op == 0) {
+      if (x < 0 || (uint32_t)x >= nc) fail(H2_EINVAL, "dag: no such constant");
+      id[i] = X.constant(cs[x]);
+    } else if (op == 1) {
+      id[i] = X.column(a, x);                        // compile checks the column index and the rotation
+    } else if (op >= 2 && op <= 4) {
+      if (a < 0 || b < 0 || (uint32_t)a >= i || (uint32_t)b >= i) fail(H2_EINVAL, "dag: operand is not an earlier node");
+      id[i] = op == 2 ? X.add(id[a], id[b]) : op == 3 ? X.sub(id[a], id[b]) : X.mul(id[a], id[b]);
+    } else {
+      fail(H2_EINVAL, "dag: unknown op");
+    }
+  }
+  X.compile(id[nn - 1]);
+}
 
 // pseudo-columns of the program beyond the circuit's own: indices into the pointer table handed to the kernel
 struct ColumnMap {
@@ -1253,17 +1330,7 @@ std::vector<uint8_t> create_proof(ProvingKey& K, const Circuit& C, const std::ve
     consts[K.c_beta] = beta;
     consts[K.c_gamma] = gamma;
     for (size_t j = 0; j < np; j++) consts[K.c_beta_delta[j]] = beta * delta.pow_u64((uint64_t)j);
-    const U128* const* d_ptrs = (const U128* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
-    const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
-    for (auto& c : consts)
-      for (int t = 0; t < 5; t++) c = c + c;            // c 2^256 -> c 2^261: the kernel's working form (R' = 2^261)
-    Col d_consts = d.upload_frs(consts);
-    const size_t lds_slots = K.prog.nslots > (uint32_t)pk::EXPR_REG_SLOTS ? K.prog.nslots - pk::EXPR_REG_SLOTS : 1;
-    const size_t lds = lds_slots * 9 * pk::EXPR_BLOCK * 4;
-    if (lds > 160 * 1024) fail(H2_EINVAL, "quotient program needs too many live values");
-    hipLaunchKernelGGL(pk::expr_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK), dim3(pk::EXPR_BLOCK), lds, d.s, K.d_code,
-                       (uint32_t)K.prog.code.size(), d_ptrs, d_masks, d_consts, h_ext, en / n, en);
-    hip_ok(hipGetLastError(), "expr_kernel");
+    expr_launch(d, K.prog, K.d_code, ptrs, masks, std::move(consts), h_ext, en / n, en);
   }
   d.release(ext);
   // extended -> coefficients: inverse NTT with 1 / 2^ext_k, un-shift the coset, keep n (deg - 1) coefficients
@@ -2249,15 +2316,16 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
       else K.circuit = std::make_unique<PoseidonCircuit>();
       key_shape(K);
       build_quotient_program(K);
-      uint32_t st[6] = {(uint32_t)K.prog.code.size(), 0, 0, K.prog.nslots, (uint32_t)K.prog.consts.size(), K.prog.nreduce};
-      for (auto& ins : K.prog.code) {
-        if ((ins.op_dst >> 24) == 2) st[1]++;
-        if ((ins.a & (3u << 30)) == pk::X_COL) st[2]++;
-        if ((ins.b & (3u << 30)) == pk::X_COL) st[2]++;
+      r = K.prog.report();
+    } else if (what == 7) {                // a caller's DAG (program_from_dag) compiled: what 6 reports, then the
+      ExprProgram X;                       // constant table (32 canonical LE bytes each; the one compile adds included)
+      program_from_dag(in, in_len, X);
+      r = X.report();
+      for (auto& c : X.consts) {
+        uint8_t b[32];
+        c.to_le_bytes(b);
+        r.insert(r.end(), b, b + 32);
       }
-      r.resize(24 + K.prog.code.size() * sizeof(pk::XInstr));
-      memcpy(r.data(), st, 24);
-      memcpy(r.data() + 24, K.prog.code.data(), K.prog.code.size() * sizeof(pk::XInstr));
     } else if (what == 5) {                // pairing check on two (G1, G2) pairs: 2 x (64 + 128) canonical bytes -> 1 byte
       if (in_len != 2 * 192) return H2_EINVAL;
       std::vector<std::pair<G1, bn::G2>> pairs;
@@ -2281,6 +2349,53 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
       return H2_EINVAL;
     }
     return emit(r, out, cap, out_len);
+  });
+}
+
+// a caller's DAG (program_from_dag) run by expr_kernel over en = 2^log_en rows, launched as create_proof launches it
+int h2_selftest_expr_run(const uint8_t* dag, size_t dag_len, const uint64_t* cols, const uint32_t* log_len, uint32_t ncols,
+                         uint32_t log_en, uint32_t step, uint64_t* out, uint32_t stats[6]) {
+  return guarded([&]() -> int {
+    if (!cols || !log_len || !out || !stats || ncols == 0 || ncols > (1u << 16) || log_en > 22) return H2_EINVAL;
+    ExprProgram X;
+    program_from_dag(dag, dag_len, X);
+    (void)expr_lds_bytes(X);                 // over the LDS limit: refused before a device is even looked at
+    for (auto& nd : X.nodes)
+      if (nd.op == 1 && (uint32_t)nd.col >= ncols) fail(H2_EINVAL, "dag: no such column");
+    size_t total = 0;
+    for (uint32_t c = 0; c < ncols; c++) {
+      if (log_len[c] > 24) return H2_EINVAL;
+      total += (size_t)1 << log_len[c];
+    }
+    if (total > ((size_t)1 << 24)) return H2_EINVAL;
+    // the kernel takes every column element as canonical (x 2^256 mod p below p): anything else is refused here
+    uint64_t p[4];
+    for (int w = 0; w < 4; w++) p[w] = (uint64_t)BN254_FR::P(2 * w) | ((uint64_t)BN254_FR::P(2 * w + 1) << 32);
+    for (size_t e = 0; e < total; e++) {
+      const uint64_t* v = cols + 4 * e;
+      int w = 3;
+      while (w > 0 && v[w] == p[w]) w--;
+      if (v[w] >= p[w]) return H2_EINVAL;
+    }
+    const uint32_t en = 1u << log_en;
+    const std::vector<uint8_t> rep = X.report();
+    memcpy(stats, rep.data(), 24);
+    Dev d(the_ctx());
+    const pk::XInstr* d_code = (const pk::XInstr*)d.upload(X.code.data(), X.code.size() * sizeof(pk::XInstr));
+    const U128* d_cols = (const U128*)d.upload(cols, total * 32);
+    std::vector<const U128*> ptrs(ncols);
+    std::vector<uint32_t> masks(ncols);
+    size_t off = 0;
+    for (uint32_t c = 0; c < ncols; c++) {
+      ptrs[c] = d_cols + 2 * off;
+      masks[c] = (1u << log_len[c]) - 1;
+      off += (size_t)1 << log_len[c];
+    }
+    Col d_out = d.col(en);
+    expr_launch(d, X, d_code, ptrs, masks, X.consts, d_out, step, en);
+    hip_ok(hipMemcpyAsync(out, d_out, (size_t)en * 32, hipMemcpyDeviceToHost, d.s), "hipMemcpyAsync(D2H)");
+    d.sync();
+    return H2_OK;
   });
 }
 

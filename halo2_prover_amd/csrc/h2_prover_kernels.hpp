@@ -230,6 +230,7 @@ constexpr uint32_t X_SLOT = 0u << 30, X_CONST = 1u << 30, X_COL = 2u << 30, X_PR
 constexpr uint32_t X_NO_STORE = 0xFFFFFFu;     // destination field of a result that only the next instruction reads
 constexpr int EXPR_BLOCK = 64;
 constexpr int EXPR_REG_SLOTS = 4;       // slots kept in registers (expr_kernel); the rest is LDS
+constexpr size_t EXPR_LDS_MAX = 160 * 1024;   // dynamic LDS one workgroup may hold (expr_kernel has no static LDS)
 // magnitudes, in units of p, that the host's compiler (ExprProgram::compile) assumes: a column operand after
 // expr_column_operand, and the largest value an instruction may produce before it is reduced by a product with one
 constexpr int EXPR_COLUMN_BOUND = 16, EXPR_VALUE_BOUND = 32;
@@ -239,9 +240,12 @@ constexpr int EXPR_COLUMN_BOUND = 16, EXPR_VALUE_BOUND = 32;
 //   * a column holds x 2^256 (canonical); shifted left by five bits while it is unpacked that is the integer
 //     x 2^261 + (a multiple of p) < 32 p, the working form of x -- minus 16 p it lies in (-16 p, 16 p);
 //   * the constant table is uploaded in the working form (c 2^261 mod p, canonical) and only unpacked;
-//   * sums and differences are carry-normalised, products need nothing; the compiler keeps every value below
-//     EXPR_VALUE_BOUND p (it multiplies by one where a sum would exceed it), so every product has operands far below
-//     the 64 p that fe29_mul and fe29_to_api allow;
+//   * sums and differences are carry-normalised, products need nothing; the compiler keeps every value that is stored
+//     or forwarded below EXPR_VALUE_BOUND p (it multiplies a sum by one where it would exceed that bound: the sum, at
+//     most 2 EXPR_VALUE_BOUND p, is then that product's operand).  fe29_mul needs only its limb bounds, which every
+//     normalised value of magnitude below 2^260 meets; a product of two such values, up to (32 p)^2 = 1024 p^2, is
+//     past the 64 p^2 that gives fe29_mul's (-3p/2, p/2] range, and lies in (a b / R' - p, a b / R'], |x| < 9 p;
+//     fe29_to_api takes any |x| < 64 p;
 //   * the last result goes back to the API form (one product) on its way out.
 // Operands that do not depend on the program's own results -- columns and constants -- are fetched TWO instructions
 // ahead (a global load is 0.5-2 us, an instruction 0.1-0.5).  LDS: 36 bytes per slot beyond the register slots and row.

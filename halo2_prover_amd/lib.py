@@ -92,6 +92,8 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_msm_guard_report": (_I, [_P, _P, _Z]),
     "h2_selftest_arena_stats": (_I, [_P]),
     "h2_selftest_fe29_op": (_I, [_I, _I, _P, _P]),
+    "h2_selftest_fe29_op_device": (_I, [_I, _I, _P, _P, _Z]),
+    "h2_selftest_expr_run": (_I, [_P, _Z, _P, _P, _U32, _U32, _U32, _P, _P]),
 }
 
 # the RNG callback of the product surface: void (*)(void* ctx, uint8_t* out, size_t n)

@@ -66,7 +66,13 @@ int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* mo
  *    x || y per fixed column then per permutation column, zero = identity) -> 32-byte transcript_repr || the Debug string;
  * 5: pairing check e(P1, Q1) e(P2, Q2) == 1 on two pairs of 64 + 128 canonical bytes -> one byte;
  * 6: the quotient program of circuit in[0] as the prover compiles it -> six u32 (instructions, products, column reads,
- *    live-value slots, constants, inserted reductions) followed by the instructions (3 x u32 each: op_dst, a, b). */
+ *    live-value slots, constants, inserted reductions) followed by the instructions (3 x u32 each: op_dst, a, b);
+ * 7: a caller's expression DAG compiled by the same compiler -> what 6 returns, then the program's constant table
+ *    (32-byte canonical LE each: the caller's constants merged by value, plus the one the compiler adds).  The DAG:
+ *    u32 nodes, u32 constants, then per node four i32 {op, a, b, x} -- op 0: constant x; 1: column a at rotation x;
+ *    2 / 3 / 4: add / sub / mul of the EARLIER nodes a and b -- then the constants (32-byte canonical LE, bn256::Fr).
+ *    The last node is the root.  H2_EINVAL for a later or unknown node, a rotation outside [-128, 127], a column
+ *    index of 2^22 or more, or a root that is a bare constant or column. */
 /* commit phases of the C++ prover / keygen that were spread over more than one context (h2_init_devices) so far */
 uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */
@@ -76,6 +82,16 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
  * 2 pasta Fp, 3 pasta Fq; in = four operands a, b, c, d of 9 signed 29-bit-radix limbs; op 0: fe29_mul(a, b),
  * 1: fe29_sqr(a), 2: fe29_mul_sub(a, b, c, d), 3: fe29_mul_up(a, b) -> the 9 limbs of the result */
 int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]);
+/* the same four ops through the DEVICE instantiation: n operand sets (36 limbs each, host pointer) -> n x 9 limbs,
+ * one kernel launch */
+int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* out, size_t n);
+/* the quotient program's kernel (expr_kernel) on a caller's DAG (the format of h2_selftest_host what = 7), launched
+ * as the prover launches it: ncols host columns, concatenated, column c of 2^log_len[c] elements (4 x u64, x 2^256
+ * canonical) read at row (i + rot * step) & (2^log_len[c] - 1); out = the 2^log_en results (4 x u64 each, canonical);
+ * stats = what 6's six counters.  H2_EINVAL (nothing launched) for what what 7 refuses, a column that does not exist,
+ * an element that is not canonical, or a program that needs more LDS than one workgroup may hold. */
+int h2_selftest_expr_run(const uint8_t* dag, size_t dag_len, const uint64_t* cols, const uint32_t* log_len, uint32_t ncols,
+                         uint32_t log_en, uint32_t step, uint64_t* out, uint32_t stats[6]);
 /* scratch arenas of the current context: out = {allocations, cross-stream hand-overs (event waits), MSM slots taken
  * over by a further stream, NTT slots taken over} since h2_init */
 int h2_selftest_arena_stats(uint64_t out[4]);

@@ -494,3 +494,149 @@ def synth_scalar(rng, p):
             limb &= (1 << 62) - 1
         v |= limb << (64 * i)
     return v - p if v >= p else v
+
+
+# ---- the 29-bit working form (halo2_prover_amd/csrc/h2_field29.hpp) and expr_kernel, exactly -------------------------
+# Nine signed 29-bit limbs, R' = 2^261.  These models give the very limbs the HIP code produces, not only a value mod p:
+# the normalised form has limbs 0..7 in [0, 2^29) and a signed top limb.
+
+FE29_R = 1 << 261
+FE29_MASK = (1 << 29) - 1
+_FE29_PINV = {}
+
+
+def fe29_value(limbs):
+    return sum(int(v) << (29 * i) for i, v in enumerate(limbs))
+
+
+def fe29_normalised(x):
+    """signed integer -> limbs 0..7 in [0, 2^29), the top limb x >> 232 (it has to fit the int32 the code keeps it in)"""
+    top = x >> 232
+    assert -(1 << 31) <= top < (1 << 31), "top limb overflows int32"
+    return [(x >> (29 * i)) & FE29_MASK for i in range(8)] + [top]
+
+
+def _pinv(p):
+    if p not in _FE29_PINV:
+        _FE29_PINV[p] = pow(p, -1, FE29_R)
+    return _FE29_PINV[p]
+
+
+def fe29_reduce(x, p):
+    """the subtractive Montgomery reduction of the integer x (a b for fe29_mul / fe29_sqr, a b - c d for fe29_mul_sub):
+    (x - m p) / R' with m = x p^-1 mod R', 0 <= m < R', normalised"""
+    m = x * _pinv(p) % FE29_R
+    q, rem = divmod(x - m * p, FE29_R)
+    assert rem == 0
+    return fe29_normalised(q)
+
+
+def fe29_reduce_up(x, p):
+    """fe29_mul_up's additive reduction: (x + m' p) / R' with m' = -x p^-1 mod R', 0 <= m' < R', normalised"""
+    m = -x * _pinv(p) % FE29_R
+    q, rem = divmod(x + m * p, FE29_R)
+    assert rem == 0
+    return fe29_normalised(q)
+
+
+def fe29_mul(a, b, p):
+    return fe29_reduce(fe29_value(a) * fe29_value(b), p)
+
+
+def fe29_mul_up(a, b, p):
+    return fe29_reduce_up(fe29_value(a) * fe29_value(b), p)
+
+
+def fe29_mul_limbs_ok(a, b):
+    """fe29_mul's only precondition: |a_i| < 2^30 and |b_j| < 2^29, or the other way round"""
+    def below(x, bound):
+        return all(-bound < v < bound for v in x)
+    return (below(a, 1 << 30) and below(b, 1 << 29)) or (below(a, 1 << 29) and below(b, 1 << 30))
+
+
+def _i32(v):
+    assert -(1 << 31) <= v < (1 << 31), "int32 overflow"
+    return v
+
+
+def fe29_norm(a):
+    """fe29_norm: carry propagation with int32 limbs, the value unchanged"""
+    r, carry = [], 0
+    for i in range(8):
+        x = _i32(a[i] + carry)
+        r.append(x & FE29_MASK)
+        carry = x >> 29
+    return r + [_i32(a[8] + carry)]
+
+
+def fe29_add(a, b):
+    return [_i32(x + y) for x, y in zip(a, b)]
+
+
+def fe29_sub(a, b):
+    return [_i32(x - y) for x, y in zip(a, b)]
+
+
+def fe29_unpack(x):
+    """a non-negative integer below 2^256 -> 9 x 29 bits"""
+    assert 0 <= x < 1 << 256
+    return [(x >> (29 * j)) & FE29_MASK for j in range(9)]
+
+
+def fe29_expr_column_operand(api, p):
+    """expr_column_operand: the API integer x 2^256 (canonical) -> limb j of (api << 5) minus limb j of 16 p, so the
+    value (api << 5) - 16 p, in (-16 p, 16 p), with limbs of magnitude < 2^29"""
+    assert 0 <= api < p
+    a, s = api << 5, p << 4
+    return [((a >> (29 * j)) & FE29_MASK) - ((s >> (29 * j)) & FE29_MASK) for j in range(9)]
+
+
+def fe29_to_api(t, p):
+    """fe29_to_api: one product with 2^256 mod p (as a plain integer), then p added while the top limb is negative
+    (at most twice) -> the API integer (canonical for |t| < 64 p)"""
+    r = fe29_mul(t, fe29_unpack((1 << 256) % p), p)
+    pl = fe29_unpack(p)
+    for _ in range(2):
+        if r[8] < 0:
+            r = fe29_norm(fe29_add(r, pl))
+    assert r[8] >= 0
+    return fe29_value(r) % (1 << 256)
+
+
+X_SLOT, X_CONST, X_COL, X_PREV = 0, 1, 2, 3
+X_NO_STORE = 0xFFFFFF
+
+
+def expr_kernel_row(code, consts_working, column_at, p, steps=None):
+    """One row of expr_kernel (h2_prover_kernels.hpp) on the compiled code [(op_dst, a, b)], as the kernel computes
+    it: a column operand through fe29_expr_column_operand of column_at(c, rot) (the API integer the row reads), a
+    constant unpacked from its working form consts_working[k] (c 2^261 mod p), a sum or difference through fe29_norm,
+    a product through fe29_mul; unwritten slots are zero.  Returns fe29_to_api of the last result.  `steps`, if given,
+    collects (op, a limbs, b limbs, result limbs, destination) per instruction."""
+    slots = {}
+    r = [0] * 9
+
+    def operand(code_word):
+        kind, low = code_word >> 30, code_word & 0x3FFFFFFF
+        if kind == X_SLOT:
+            return slots.get(low, [0] * 9)
+        if kind == X_PREV:
+            return r
+        if kind == X_CONST:
+            return fe29_unpack(consts_working[low])
+        return fe29_expr_column_operand(column_at(low >> 8, (low & 0xFF) - 128), p)
+
+    for op_dst, a_w, b_w in code:
+        op, dst = op_dst >> 24, op_dst & 0xFFFFFF
+        a, b = operand(a_w), operand(b_w)
+        if op == 2:
+            r = fe29_mul(a, b, p)
+        elif op == 0:
+            r = fe29_norm(fe29_add(a, b))
+        else:
+            r = fe29_norm(fe29_sub(a, b))
+        if dst != X_NO_STORE:
+            slots[dst] = r
+        if steps is not None:
+            steps.append((op, a, b, r, dst))
+    return fe29_to_api(r, p)

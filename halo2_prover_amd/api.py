@@ -238,6 +238,41 @@ def ntt_device(d_ptr, m, omega, log_n, curve="bn254", stream=0):
     _lib.check(st, "h2_ntt_device")
 
 
+def points_decompress_device(d_in, n, d_out, d_status, stream=0, curve="bn254"):
+    """n compressed G1 points (32 B each, the transcript's wire form) -> n affine points (64 B, Montgomery limbs) and n
+    status bytes; device pointers, asynchronous (h2_points_decompress_device)."""
+    _ensure_init()
+    st = _lib.load().h2_points_decompress_device(_curve_id(curve), ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out),
+                                                 ctypes.c_void_p(d_status), ctypes.c_void_p(stream))
+    _lib.check(st, "h2_points_decompress_device")
+
+
+def verify_proofs(params, proofs, jsons, circuit, rng=None):
+    """Batch verification (h2_verify_proofs): `proofs` and `jsons` of ONE circuit under ONE params blob -> list[bool],
+    entry i what verifying proof i alone gives.  rng: None (the OS) or a callable n -> n bytes for the batching weights."""
+    _ensure_init()
+    proofs = [bytes(p) for p in proofs]
+    texts = [j.encode() if isinstance(j, str) else bytes(j) for j in jsons]
+    count = len(proofs)
+    if len(texts) != count:
+        raise ValueError("verify_proofs: %d proofs but %d inputs" % (count, len(texts)))
+    params = bytes(params)
+    ptrs = (ctypes.c_char_p * count)(*proofs)
+    lens = (ctypes.c_size_t * count)(*[len(p) for p in proofs])
+    js = (ctypes.c_char_p * count)(*texts)
+    ok = (ctypes.c_int * count)()
+    all_ok = ctypes.c_int(0)
+    cb = None
+    if rng is not None:
+        def fill(_ctx, out, n):
+            ctypes.memmove(out, bytes(rng(n)), n)
+        cb = _lib.RNG_FILL(fill)
+    st = _lib.load().h2_verify_proofs(params, len(params), count, ptrs, lens, js, int(circuit), cb, None, ok,
+                                      ctypes.byref(all_ok))
+    _lib.check(st, "h2_verify_proofs")
+    return [bool(v) for v in ok]
+
+
 class ParamsKZG:
     """Mirror of halo2_proofs::poly::kzg::commitment::ParamsKZG<Bn256> for the prover side.
 

@@ -443,7 +443,7 @@ int init_devices(int n, const int* ids) {
 
 extern "C" {
 
-int h2_version(void) { return 1001; }
+int h2_version(void) { return 1002; }
 
 const char* h2_strerror(int s) {
   switch (s) {
@@ -624,6 +624,20 @@ int h2_points_sum_device(h2_curve_t curve, const void* d_in_jac, size_t groups, 
   if (count == 0) return H2_OK;
   hipError_t e = ops_of((int)curve)->points_sum(d_in_jac, d_out_jac, (uint32_t)groups, (uint32_t)count, k.stream);
   if (e != hipSuccess) return dev_fail(e, "points_sum_kernel");
+  return H2_OK;
+}
+
+int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine, void* d_status,
+                                void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !ops_of((int)curve)->points_decompress || n > (1u << 30)) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  // the kernel moves 16 bytes at a time
+  if (!d_compressed || !d_out_affine || !d_status || ((uintptr_t)d_compressed & 15) || ((uintptr_t)d_out_affine & 15))
+    return H2_EINVAL;
+  hipError_t e = ops_of((int)curve)->points_decompress(d_compressed, d_out_affine, d_status, (uint32_t)n, k.stream);
+  if (e != hipSuccess) return dev_fail(e, "points_decompress_kernel");
   return H2_OK;
 }
 

@@ -1,6 +1,7 @@
 // h2_curve_impl.hip -- kernels and launchers of ONE curve (selected by -DH2_CURVE_ID).
 #include "h2_curve_ops.hpp"
 #include "h2_msm.hpp"
+#include "h2_decompress.hpp"
 #include "h2_ntt.hpp"
 #include "h2_ntt29.hpp"
 #include "h2_tune.hpp"
@@ -83,6 +84,26 @@ hipError_t points_sum(const void* d_in_jac, void* d_out_jac, uint32_t groups, ui
                      (U128*)d_out_jac, groups, count);
   return hipGetLastError();
 }
+#if H2_CURVE_ID == 0
+hipError_t points_decompress(const void* d_compressed, void* d_out_affine, void* d_status, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(points_decompress_kernel<CV>, dim3((n + 63) / 64), dim3(64), 0, s, (const uint32_t*)d_compressed,
+                     (U128*)d_out_affine, (uint8_t*)d_status, n);
+  return hipGetLastError();
+}
+int selftest_decompress(const uint8_t in[32], uint64_t out_affine[8]) {
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++)
+    w[i] = (uint32_t)in[4 * i] | ((uint32_t)in[4 * i + 1] << 8) | ((uint32_t)in[4 * i + 2] << 16) | ((uint32_t)in[4 * i + 3] << 24);
+  Fe<FB> x, y;
+  const uint8_t st = g1_decompress<CV>(w, x, y);
+  memcpy(out_affine, x.v, 32);
+  memcpy(out_affine + 4, y.v, 32);
+  return st;
+}
+#else
+constexpr auto points_decompress = nullptr;      // 2-adicity 32: Tonelli-Shanks, not provided
+constexpr auto selftest_decompress = nullptr;
+#endif
 size_t ntt_table_bytes(uint32_t log_n) { return ntt29_tables(log_n).total; }
 bool ntt_scale_in_table(uint32_t log_n) { return ntt29_scale_in_table(log_n); }
 hipError_t ntt_twiddles(void* d_tw, const uint64_t omega[4], uint32_t log_n, hipStream_t s, const uint64_t* scale) {
@@ -367,7 +388,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 }
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_,    srs_powers, fixed_base_mul, msm_small,
-                      to_affine,   points_sum, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
+                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 

@@ -37,6 +37,11 @@ struct CurveOps {
   hipError_t (*to_affine)(const void* d_xyzz, void* d_out, uint32_t m, hipStream_t s);
   // d_out[j] = sum_g d_in[g * count + j], Jacobian points in the API form
   hipError_t (*points_sum)(const void* d_in_jac, void* d_out_jac, uint32_t groups, uint32_t count, hipStream_t s);
+  // n compressed points (32 bytes each, the transcript's wire form) -> n affine points in the API form and n status
+  // bytes (h2_decompress.hpp); NULL for curves whose base field has no square root by a single power (Pallas, Vesta)
+  hipError_t (*points_decompress)(const void* d_compressed, void* d_out_affine, void* d_status, uint32_t n, hipStream_t s);
+  // the same routine instantiated on the host, one point per call (CPU tests); NULL where points_decompress is
+  int (*selftest_decompress)(const uint8_t in[32], uint64_t out_affine[8]);
   // NTT over the scalar field
   // the tables of one (omega, log n [, constant]): inter-pass twiddles, unpacked radix twiddles per pass, the
   // canonicalisation table (h2_ntt29.hpp).  ntt_scale_in_table: a transform scaled by a constant takes that constant

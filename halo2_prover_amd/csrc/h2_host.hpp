@@ -353,6 +353,17 @@ class Transcript {
     return true;
   }
   bool read_point(G1* p);   // h2_prover.hip (needs the square root in Fq)
+  // Points of this proof that were decompressed before the replay (h2_verify_proofs: one kernel launch for a whole batch,
+  // h2_decompress.hpp): entry i belongs to the 32 bytes at offsets[i] (ascending) and is 64 bytes in the API form at
+  // points + 64 i with its status byte.  read_point takes a point it finds here instead of the square root; any other
+  // read goes the usual way.
+  struct PointTable {
+    const uint32_t* offsets = nullptr;
+    size_t count = 0;
+    const uint8_t* points = nullptr;
+    const uint8_t* status = nullptr;
+  };
+  void use_points(const PointTable& t) { pre_ = t; }
   const std::vector<uint8_t>& bytes() const { return out_; }
 
  private:
@@ -360,6 +371,7 @@ class Transcript {
   std::vector<uint8_t> out_;
   const uint8_t* in_ = nullptr;
   size_t in_len_ = 0, in_pos_ = 0;
+  PointTable pre_;
 
  public:
   const uint8_t* take32() {

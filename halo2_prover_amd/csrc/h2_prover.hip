@@ -703,13 +703,16 @@ struct DomainKit {
   std::unique_ptr<Dev> dev;
   Col omega_col = nullptr, xcol_ext = nullptr, basis_ext = nullptr, tinv = nullptr;
 };
-std::vector<std::unique_ptr<DomainKit>> g_kits;
+// shared with the keys built on a kit: the list below forgets its oldest entry, a key that still points into that kit's
+// device buffers must keep them alive
+std::vector<std::shared_ptr<DomainKit>> g_kits;
 
 struct ProvingKey {
   std::unique_ptr<Circuit> circuit;
   std::unique_ptr<Domain> dom;
   const Params* params = nullptr;
   std::unique_ptr<Dev> dev;                 // owns the key's device buffers
+  std::shared_ptr<const DomainKit> kit;     // owns omega_col, xcol_ext, basis_ext and tinv below
   int bf = 0;
   std::vector<std::vector<int>> sets;       // permutation columns, d - 2 per grand product
   Col fixed_values = nullptr, sigma_values = nullptr, fixed_polys = nullptr, sigma_polys = nullptr;
@@ -722,6 +725,7 @@ struct ProvingKey {
   int c_beta = -1, c_gamma = -1, c_y = -1;
   std::vector<int> c_beta_delta;            // beta * delta^j, one per permutation column
   const pk::XInstr* d_code = nullptr;
+  std::vector<uint32_t> point_offsets;      // where a proof's compressed points sit (h2_verify_proofs), filled on first use
   size_t nf() const { return (size_t)circuit->num_fixed; }
   size_t np() const { return circuit->permutation_columns.size(); }
   // the key's transforms may still be running on the second stream when a key that is not kept dies (verify with
@@ -897,10 +901,10 @@ void coeff_to_extended(Dev& d, const Domain& D, Col in, size_t m, Col out, hipSt
   d.ntt(out, m, D.ext_omega, D.ext_k, nullptr, on);
 }
 
-const DomainKit& domain_kit(const Domain& D, int bf, DevCtx* ctx) {
+std::shared_ptr<const DomainKit> domain_kit(const Domain& D, int bf, DevCtx* ctx) {
   for (auto& kp : g_kits)
-    if (kp->device == ctx->device && kp->k == D.k && kp->ext_k == D.ext_k && kp->bf == bf) return *kp;
-  auto kit = std::make_unique<DomainKit>();
+    if (kp->device == ctx->device && kp->k == D.k && kp->ext_k == D.ext_k && kp->bf == bf) return kp;
+  auto kit = std::make_shared<DomainKit>();
   kit->device = ctx->device;
   kit->k = D.k;
   kit->ext_k = D.ext_k;
@@ -949,7 +953,7 @@ const DomainKit& domain_kit(const Domain& D, int bf, DevCtx* ctx) {
   d.sync();
   if (g_kits.size() >= 8) g_kits.erase(g_kits.begin());
   g_kits.push_back(std::move(kit));
-  return *g_kits.back();
+  return g_kits.back();
 }
 
 // the permutation columns, d - 2 per grand product (halo2's chunking), and the blinding rows: host data of a key
@@ -1052,11 +1056,11 @@ std::unique_ptr<ProvingKey> keygen(const Params& P, std::unique_ptr<Circuit> cir
   K.sigma_values = lag + 2 * nf * (size_t)n;
   d.fill_sparse(K.fixed_values, n, fixed);
   // omega_col[i] = w^i (domain kit); sigma_j[i] = delta^j w^i except on the cells the copy constraints permute
-  const DomainKit& kit = domain_kit(D, K.bf, ctx);
-  K.omega_col = kit.omega_col;
-  K.basis_ext = kit.basis_ext;
-  K.xcol_ext = kit.xcol_ext;
-  K.tinv = kit.tinv;
+  K.kit = domain_kit(D, K.bf, ctx);
+  K.omega_col = K.kit->omega_col;
+  K.basis_ext = K.kit->basis_ext;
+  K.xcol_ext = K.kit->xcol_ext;
+  K.tinv = K.kit->tinv;
   const Fr delta = fr_delta();
   std::vector<std::pair<std::pair<int, uint32_t>, Fr>> moved;     // (permutation column, row) -> its sigma value
   {
@@ -1603,45 +1607,33 @@ void shplonk_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const std
 }
 
 // ---- verify_proof --------------------------------------------------------------------------------------------------------------
+// `tag` names the point within one proof's replay (the same point always under the same tag): the batch verifier adds up
+// scalars by tag instead of comparing points
+struct MsmTerm {
+  Fr first;
+  G1 second;
+  int tag;
+};
 struct MsmTerms {
-  std::vector<std::pair<Fr, G1>> t;
-  void append(const Fr& s, const G1& p) { t.push_back({s, p}); }
+  std::vector<MsmTerm> t;
+  void append(const Fr& s, const G1& p, int tag = -1) { t.push_back({s, p, tag}); }
   void scale(const Fr& f) {
     for (auto& x : t) x.first *= f;
   }
   void add(const MsmTerms& o) { t.insert(t.end(), o.t.begin(), o.t.end()); }
 };
 
-// the group elements of up to four MsmTerms, on the GPU side by side: equal points merged, the rest through the table-free
-// small MSM (msm_small_kernel: one quad per term)
-std::vector<G1> msm_eval(Dev& d, const std::vector<const MsmTerms*>& jobs) {
-  const size_t count = jobs.size();
+// up to four lists of terms (64-byte points and 32-byte scalars in the API form; no identities, no zero scalars) -> their
+// sums, in ONE launch of the table-free small MSM (msm_small_kernel: one quad per term); an empty list gives the identity
+std::vector<G1> msm_small_run(Dev& d, const std::vector<std::vector<uint8_t>>& pts, const std::vector<std::vector<uint8_t>>& sc) {
+  const size_t count = pts.size();
   std::vector<G1> out(count);
-  std::vector<std::vector<uint8_t>> pts(count), sc(count);
   std::vector<const void*> d_pts, d_sc;
   std::vector<uint32_t> ms, live;
   size_t mmax = 0;
   for (size_t j = 0; j < count; j++) {
-    std::vector<std::pair<G1, Fr>> merged;
-    for (auto& st : jobs[j]->t) {
-      if (st.second.inf || st.first.is_zero()) continue;
-      bool found = false;
-      for (auto& mg : merged)
-        if (mg.first == st.second) {
-          mg.second += st.first;
-          found = true;
-        }
-      if (!found) merged.push_back({st.second, st.first});
-    }
-    if (merged.empty()) continue;
-    const size_t m = merged.size();
-    pts[j].resize(m * 64);
-    sc[j].resize(m * 32);
-    for (size_t i = 0; i < m; i++) {
-      memcpy(pts[j].data() + 64 * i, merged[i].first.x.v.v, 32);
-      memcpy(pts[j].data() + 64 * i + 32, merged[i].first.y.v.v, 32);
-      memcpy(sc[j].data() + 32 * i, merged[i].second.v.v, 32);
-    }
+    const size_t m = pts[j].size() / 64;
+    if (m == 0) continue;
     d_pts.push_back(d.upload(pts[j].data(), pts[j].size()));
     d_sc.push_back(d.upload(sc[j].data(), sc[j].size()));
     ms.push_back((uint32_t)m);
@@ -1657,6 +1649,8 @@ std::vector<G1> msm_eval(Dev& d, const std::vector<const MsmTerms*>& jobs) {
   d.sync();
   d.release(work);
   d.release(d_out);
+  for (const void* p : d_pts) d.release(const_cast<void*>(p));
+  for (const void* p : d_sc) d.release(const_cast<void*>(p));
   for (size_t q = 0; q < nl; q++) {
     const uint64_t* J = jac.data() + 12 * q;
     const Fq X = Fq::from_mont_limbs(J), Y = Fq::from_mont_limbs(J + 4), Z = Fq::from_mont_limbs(J + 8);
@@ -1670,7 +1664,47 @@ std::vector<G1> msm_eval(Dev& d, const std::vector<const MsmTerms*>& jobs) {
   return out;
 }
 
-bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const std::vector<Fr>& instance, bool shplonk) {
+// the group elements of up to four MsmTerms, on the GPU side by side: equal points merged, the rest through msm_small_run
+std::vector<G1> msm_eval(Dev& d, const std::vector<const MsmTerms*>& jobs) {
+  const size_t count = jobs.size();
+  std::vector<std::vector<uint8_t>> pts(count), sc(count);
+  for (size_t j = 0; j < count; j++) {
+    std::vector<std::pair<G1, Fr>> merged;
+    for (auto& st : jobs[j]->t) {
+      if (st.second.inf || st.first.is_zero()) continue;
+      bool found = false;
+      for (auto& mg : merged)
+        if (mg.first == st.second) {
+          mg.second += st.first;
+          found = true;
+        }
+      if (!found) merged.push_back({st.second, st.first});
+    }
+    const size_t m = merged.size();
+    pts[j].resize(m * 64);
+    sc[j].resize(m * 32);
+    for (size_t i = 0; i < m; i++) {
+      memcpy(pts[j].data() + 64 * i, merged[i].first.x.v.v, 32);
+      memcpy(pts[j].data() + 64 * i + 32, merged[i].first.y.v.v, 32);
+      memcpy(sc[j].data() + 32 * i, merged[i].second.v.v, 32);
+    }
+  }
+  return msm_small_run(d, pts, sc);
+}
+
+// verify_proof in two halves.  replay_proof hashes the transcript and arrives at the two combinations whose pairing
+// decides the proof -- e(left, [s]G2) e(right, -G2) = 1 -- or returns false where the proof is malformed; the finish is
+// msm_eval (the two combinations on the GPU) and pairing_of.  verify_proof runs one after the other; h2_verify_proofs
+// replays every proof of a batch and finishes a random combination of all of them at once (BatchCheck).
+// Tags of the terms: the proof's commitments in the order they are registered below -- advice, permutation products,
+// the key's fixed and sigma commitments [shared0, shared0 + shared_count), the random polynomial -- then the quotient
+// pieces, the opening points and the SRS generator (tag_g0).
+struct Replay {
+  MsmTerms left, right;
+  int shared0 = 0, shared_count = 0, tag_g0 = 0, tags = 0;
+};
+bool replay_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const std::vector<Fr>& instance, bool shplonk,
+                  const Transcript::PointTable* pre, Replay& out) {
   const Circuit& C = *K.circuit;
   const Domain& D = *K.dom;
   const Params& P = *K.params;
@@ -1678,8 +1712,8 @@ bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const s
   const int bf = K.bf, deg = C.degree;
   if (instance.size() > n - (uint32_t)(bf + 1)) return false;
   if (!C.num_instance && !instance.empty()) return false;
-  Trace trace("verify");
   Transcript tr(proof, proof_len);
+  if (pre) tr.use_points(*pre);
   tr.common_scalar(K.transcript_repr);
   for (auto& v : instance) tr.common_scalar(v);
   std::vector<G1> advice_c(C.num_advice), z_c(K.sets.size()), h_c(deg - 1);
@@ -1754,10 +1788,12 @@ bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const s
   Fr folded = Fr::zero();
   for (auto& e : exprs) folded = folded * y + e;
   const Fr expected_h = folded * (xn - Fr::one()).inv();
+  const int tag_h0 = C.num_advice + (int)K.sets.size() + (int)K.fixed_commitments.size() + (int)K.sigma_commitments.size() + 1;
+  const int tag_open0 = tag_h0 + (int)h_c.size();
   MsmTerms h_msm;
   for (size_t i = h_c.size(); i-- > 0;) {
     h_msm.scale(xn);
-    h_msm.append(Fr::one(), h_c[i]);
+    h_msm.append(Fr::one(), h_c[i], tag_h0 + (int)i);
   }
   // the opening queries, in the prover's batching order; commitment -1 = the h combination
   struct VQ { Fr point; int id; Fr eval; };
@@ -1790,11 +1826,15 @@ bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const s
       m = h_msm;
       m.scale(factor);
     } else {
-      m.append(factor, commitments[id]);
+      m.append(factor, commitments[id], id);
     }
     return m;
   };
-  MsmTerms left, right;
+  MsmTerms& left = out.left;
+  MsmTerms& right = out.right;
+  out.shared0 = id_fix.empty() ? (id_sig.empty() ? 0 : id_sig[0]) : id_fix[0];
+  out.shared_count = (int)(id_fix.size() + id_sig.size());
+  int opening_points = 2;
   if (!shplonk) {
     // VerifierGWC (halo2_proofs src/poly/kzg/multiopen/gwc/verifier.rs)
     const Fr v = tr.squeeze_challenge();
@@ -1818,11 +1858,12 @@ bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const s
       batch.scale(up);
       right.add(batch);
       eval_multi += up * ev;
-      right.append(up * points[pi], ws[pi]);
-      left.append(up, ws[pi]);
+      right.append(up * points[pi], ws[pi], tag_open0 + (int)pi);
+      left.append(up, ws[pi], tag_open0 + (int)pi);
       up *= u;
     }
-    right.append(-eval_multi, P.g0);
+    opening_points = (int)points.size();
+    right.append(-eval_multi, P.g0, tag_open0 + opening_points);
   } else {
     // VerifierSHPLONK (src/poly/kzg/multiopen/shplonk/verifier.rs)
     std::vector<Fr> pts, evs;
@@ -1867,22 +1908,38 @@ bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const s
       r_outer += vp * r_inner * z_diff;
       vp *= v;
     }
-    outer.append(-r_outer, P.g0);
-    outer.append(-z_0, h1);
-    outer.append(u, h2);
-    left.append(Fr::one(), h2);
+    outer.append(-r_outer, P.g0, tag_open0 + 2);
+    outer.append(-z_0, h1, tag_open0);
+    outer.append(u, h2, tag_open0 + 1);
+    left.append(Fr::one(), h2, tag_open0 + 1);
     right.add(outer);
   }
+  out.tag_g0 = tag_open0 + opening_points;
+  out.tags = out.tag_g0 + 1;
+  return true;
+}
+
+uint64_t g_pairing_checks = 0;       // pairing checks made by the two verify entry points (h2_selftest_pairing_checks)
+
+// e(L, [s]G2) e(R, -G2) == 1
+bool pairing_of(const Params& P, const G1& L, const G1& Rr) {
+  bn::G2 neg_g2 = P.g2;
+  neg_g2.y = -neg_g2.y;
+  g_pairing_checks++;
+  return bn::pairing_check({{L, P.s_g2}, {Rr, neg_g2}});
+}
+
+bool verify_proof(ProvingKey& K, const uint8_t* proof, size_t proof_len, const std::vector<Fr>& instance, bool shplonk) {
+  const Params& P = *K.params;
+  Trace trace("verify");
+  Replay r;
+  if (!replay_proof(K, proof, proof_len, instance, shplonk, nullptr, r)) return false;
   if (!bn::g2_on_curve(P.g2) || !bn::g2_on_curve(P.s_g2)) return false;
   trace.mark("transcript replayed");
   Dev d(K.dev->c);
-  const std::vector<G1> lr = msm_eval(d, {&left, &right});
-  const G1& L = lr[0];
-  const G1& Rr = lr[1];
+  const std::vector<G1> lr = msm_eval(d, {&r.left, &r.right});
   trace.mark("two MSMs");
-  bn::G2 neg_g2 = P.g2;
-  neg_g2.y = -neg_g2.y;
-  const bool ok = bn::pairing_check({{L, P.s_g2}, {Rr, neg_g2}});
+  const bool ok = pairing_of(P, lr[0], lr[1]);
   trace.mark("pairing check");
   return ok;
 }
@@ -2035,12 +2092,198 @@ int emit(const std::vector<uint8_t>& data, uint8_t* out, size_t cap, size_t* out
   return H2_OK;
 }
 
+
+// ---- h2_verify_proofs: many proofs of one circuit behind one pairing check --------------------------------------------------------
+// Where the compressed points of a proof sit: fixed by the circuit, not by the challenges.  Commitments first (advice,
+// permutation products, the random polynomial, the quotient pieces), then every evaluation, then the opening points --
+// one per distinct rotation for GWC, h1 and h2 for SHPLONK.  Should a replay read a point anywhere else it takes the
+// square root itself (Transcript::read_point), so a miscount here costs time, never a decision.
+std::vector<uint32_t> proof_point_offsets(const ProvingKey& K, bool shplonk) {
+  const Circuit& C = *K.circuit;
+  const size_t ns = K.sets.size();
+  const size_t front = (size_t)C.num_advice + ns + 1 + (size_t)(C.degree - 1);
+  const size_t evals = C.advice_queries.size() + C.fixed_queries.size() + 1 + K.np() + (ns ? 3 * ns - 1 : 0);
+  size_t openings = 2;
+  if (!shplonk) {
+    const int64_t n = (int64_t)K.dom->n;
+    std::set<int64_t> rot{0};                                // sigma, h and the random polynomial are opened at x
+    for (auto& q : C.advice_queries) rot.insert(((q.second % n) + n) % n);
+    for (auto& q : C.fixed_queries) rot.insert(((q.second % n) + n) % n);
+    if (ns) rot.insert(1 % n);
+    if (ns >= 2) rot.insert(((-(int64_t)(K.bf + 1) % n) + n) % n);
+    openings = rot.size();
+  }
+  std::vector<uint32_t> off;
+  for (size_t i = 0; i < front; i++) off.push_back((uint32_t)(32 * i));
+  for (size_t i = 0; i < openings; i++) off.push_back((uint32_t)(32 * (front + evals + i)));
+  return off;
+}
+
+// one proof's two combinations with equal points added up (by tag): the key's commitments and the SRS generator, which
+// every proof of the batch shares, as scalars by index; the proof's own points as terms
+struct BatchItem {
+  bool replayed = false;
+  Fr weight;
+  std::vector<std::pair<Fr, G1>> own[2];
+  std::vector<Fr> shared[2];           // fixed commitments, sigma commitments, g0
+};
+void fold_replay(const Replay& r, BatchItem& it) {
+  const MsmTerms* side[2] = {&r.left, &r.right};
+  for (int s = 0; s < 2; s++) {
+    std::vector<Fr> acc((size_t)r.tags, Fr::zero());
+    std::vector<const G1*> pt((size_t)r.tags, nullptr);
+    for (auto& t : side[s]->t) {
+      if (t.tag < 0 || t.tag >= r.tags) fail(H2_EINVAL, "verify: a term without a tag");
+      acc[(size_t)t.tag] += t.first;
+      pt[(size_t)t.tag] = &t.second;
+    }
+    it.shared[s].assign((size_t)r.shared_count + 1, Fr::zero());
+    for (int tag = 0; tag < r.tags; tag++) {
+      if (tag >= r.shared0 && tag < r.shared0 + r.shared_count) it.shared[s][(size_t)(tag - r.shared0)] = acc[(size_t)tag];
+      else if (tag == r.tag_g0) it.shared[s][(size_t)r.shared_count] = acc[(size_t)tag];
+      else if (pt[(size_t)tag] && !pt[(size_t)tag]->inf && !acc[(size_t)tag].is_zero()) it.own[s].push_back({acc[(size_t)tag], *pt[(size_t)tag]});
+    }
+  }
+}
+
+struct BatchCheck {
+  ProvingKey& K;
+  Dev d;
+  Trace& trace;
+  std::vector<const G1*> shared_points;
+  uint64_t checks = 0;
+  BatchCheck(ProvingKey& key, Trace& tr) : K(key), d(key.dev->c), trace(tr) {
+    for (auto& c : K.fixed_commitments) shared_points.push_back(&c);
+    for (auto& c : K.sigma_commitments) shared_points.push_back(&c);
+    shared_points.push_back(&K.params->g0);
+  }
+  // sum_i w_i (left_i, right_i) over items[lo, hi) of `who`: one small-MSM launch with the two jobs side by side, one pairing
+  bool run(const std::vector<BatchItem>& items, const std::vector<size_t>& who, size_t lo, size_t hi) {
+    std::vector<std::vector<uint8_t>> pts(2), sc(2);
+    for (int s = 0; s < 2; s++) {
+      std::vector<Fr> acc(shared_points.size(), Fr::zero());
+      auto put = [&](const Fr& k, const G1& g) {
+        const size_t at = pts[s].size(), as = sc[s].size();
+        pts[s].resize(at + 64);
+        sc[s].resize(as + 32);
+        memcpy(pts[s].data() + at, g.x.v.v, 32);
+        memcpy(pts[s].data() + at + 32, g.y.v.v, 32);
+        memcpy(sc[s].data() + as, k.v.v, 32);
+      };
+      for (size_t q = lo; q < hi; q++) {
+        const BatchItem& it = items[who[q]];
+        for (auto& t : it.own[s]) put(t.first * it.weight, t.second);
+        for (size_t j = 0; j < acc.size(); j++) acc[j] += it.shared[s][j] * it.weight;
+      }
+      for (size_t j = 0; j < acc.size(); j++)
+        if (!acc[j].is_zero() && !shared_points[j]->inf) put(acc[j], *shared_points[j]);
+    }
+    const std::vector<G1> lr = msm_small_run(d, pts, sc);
+    trace.mark("combined msm");
+    const bool ok = pairing_of(*K.params, lr[0], lr[1]);
+    trace.mark("pairing");
+    checks++;
+    return ok;
+  }
+  // items[lo, hi) of `who` failed together (known_bad) or have not been checked: find the bad ones by halving.  A half
+  // whose sibling passed after the parent failed is bad without a check of its own.
+  void bisect(const std::vector<BatchItem>& items, const std::vector<size_t>& who, size_t lo, size_t hi, bool known_bad, int* ok) {
+    if (!known_bad && run(items, who, lo, hi)) {
+      for (size_t q = lo; q < hi; q++) ok[who[q]] = 1;
+      return;
+    }
+    if (hi - lo == 1) return;                               // ok stays 0
+    const size_t mid = lo + (hi - lo) / 2;
+    if (run(items, who, lo, mid)) {
+      for (size_t q = lo; q < mid; q++) ok[who[q]] = 1;
+      bisect(items, who, mid, hi, true, ok);
+    } else {
+      bisect(items, who, lo, mid, true, ok);
+      bisect(items, who, mid, hi, false, ok);
+    }
+  }
+};
+
+constexpr size_t VERIFY_GROUP = 1024;     // proofs behind one combined check
+
+// proofs [0, count) of one group; ok[] is zero on entry
+void verify_group(ProvingKey& K, bool shplonk, size_t count, const uint8_t* const* proofs, const size_t* lens,
+                  const Job* jobs, Rng& rng, int* ok, Trace& trace) {
+  if (K.point_offsets.empty()) K.point_offsets = proof_point_offsets(K, shplonk);
+  const std::vector<uint32_t>& off = K.point_offsets;
+  // the compressed points of every proof that lie inside it, proof by proof: one upload, one launch, one download
+  std::vector<size_t> first(count + 1, 0);
+  std::vector<uint8_t> words;
+  for (size_t i = 0; i < count; i++) {
+    size_t inside = 0;
+    while (inside < off.size() && (size_t)off[inside] + 32 <= lens[i]) inside++;
+    first[i + 1] = first[i] + inside;
+    for (size_t j = 0; j < inside; j++) words.insert(words.end(), proofs[i] + off[j], proofs[i] + off[j] + 32);
+  }
+  const size_t total = first[count];
+  std::vector<uint8_t> points(64 * total), status(total);
+  BatchCheck bc(K, trace);
+  if (total) {
+    Dev& d = bc.d;
+    void* d_in = d.upload(words.data(), words.size());
+    void* d_out = d.alloc(64 * total);
+    void* d_st = d.alloc(total);
+    hip_ok(d.ops->points_decompress(d_in, d_out, d_st, (uint32_t)total, d.s), "points_decompress");
+    hip_ok(hipMemcpyAsync(points.data(), d_out, 64 * total, hipMemcpyDeviceToHost, d.s), "hipMemcpyAsync(D2H)");
+    hip_ok(hipMemcpyAsync(status.data(), d_st, total, hipMemcpyDeviceToHost, d.s), "hipMemcpyAsync(D2H)");
+    d.sync();
+    d.release(d_in);
+    d.release(d_out);
+    d.release(d_st);
+  }
+  trace.mark("decompress");
+  // the weights: 16 bytes per proof, read little-endian; a zero draw becomes 1 (a weight must not cancel its proof)
+  std::vector<uint8_t> draw(16 * count);
+  rng.fill(draw.data(), draw.size());
+  std::vector<BatchItem> items(count);
+  std::vector<size_t> who;
+  for (size_t i = 0; i < count; i++) {
+    uint8_t w[32] = {0};
+    memcpy(w, draw.data() + 16 * i, 16);
+    items[i].weight = Fr::from_le_bytes_reduce(w);
+    if (items[i].weight.is_zero()) items[i].weight = Fr::one();
+    Transcript::PointTable pre;
+    pre.offsets = off.data();
+    pre.count = first[i + 1] - first[i];
+    pre.points = points.data() + 64 * first[i];
+    pre.status = status.data() + first[i];
+    Replay r;
+    if (!replay_proof(K, proofs[i], lens[i], jobs[i].public_input, shplonk, &pre, r)) continue;
+    fold_replay(r, items[i]);
+    items[i].replayed = true;
+    who.push_back(i);
+  }
+  trace.mark("replay");
+  if (!who.empty()) bc.bisect(items, who, 0, who.size(), false, ok);
+  if (trace.on) fprintf(stderr, "[h2 %s] checks %llu of %zu proofs (%zu replayed, %zu points)\n", trace.what,
+                        (unsigned long long)bc.checks, count, who.size(), total);
+}
+
 }  // namespace
 
 // Blake2bRead::read_point: 32 bytes, x little-endian with the parity of y in bit 6 and the identity flag in bit 7
 bool h2::Transcript::read_point(G1* p) {
   const uint8_t* src = take32();
   if (!src) return false;
+  if (pre_.count) {                          // decompressed ahead of the replay: the same decision, the same point
+    const size_t at = (size_t)(src - in_);
+    const uint32_t* hit = std::lower_bound(pre_.offsets, pre_.offsets + pre_.count, at,
+                                           [](uint32_t o, size_t v) { return (size_t)o < v; });
+    if (hit != pre_.offsets + pre_.count && (size_t)*hit == at) {
+      const size_t i = (size_t)(hit - pre_.offsets);
+      if (pre_.status[i] != 0) return false;
+      G1 g = affine_from_raw(pre_.points + 64 * i);
+      g.inf = false;
+      common_point(g);
+      *p = g;
+      return true;
+    }
+  }
   uint8_t b[32];
   memcpy(b, src, 32);
   const int sign = (b[31] >> 6) & 1, inf = (b[31] >> 7) & 1;
@@ -2207,6 +2450,47 @@ int h2_verify_proof(const uint8_t* params, size_t params_len, const uint8_t* pro
   });
 }
 
+int h2_verify_proofs(const uint8_t* params, size_t params_len, size_t count, const uint8_t* const* proofs,
+                     const size_t* proof_lens, const char* const* jsons, int circuit, h2_rng_fill_t rng_fn, void* rng_ctx,
+                     int* ok, int* all_ok) {
+  if (all_ok) *all_ok = 0;
+  if (ok)
+    for (size_t i = 0; i < count; i++) ok[i] = 0;
+  return guarded([&]() -> int {
+    if (count && (!ok || !proofs || !proof_lens || !jsons)) return H2_EINVAL;
+    for (size_t i = 0; i < count; i++)
+      if (!proofs[i] && proof_lens[i]) return H2_EINVAL;
+    Trace trace("verify_proofs");
+    DevCtx* ctx = the_ctx();
+    if (count == 0) {
+      if (all_ok) *all_ok = 1;
+      return H2_OK;
+    }
+    const Params& P = params_get(params, params_len);
+    std::vector<Job> jobs;
+    for (size_t i = 0; i < count; i++) jobs.push_back(job_for_verify(Json(jsons[i]), circuit));
+    std::unique_ptr<ProvingKey> owner;
+    ProvingKey& K = key_for(P, circuit, ctx, owner);
+    trace.mark("params, jobs, key");
+    if (bn::g2_on_curve(P.g2) && bn::g2_on_curve(P.s_g2)) {        // otherwise no proof verifies under these params
+      Rng rng{rng_fn, rng_ctx};
+      for (size_t g0 = 0; g0 < count; g0 += VERIFY_GROUP) {
+        const size_t cnt = std::min(VERIFY_GROUP, count - g0);
+        verify_group(K, jobs[g0].shplonk, cnt, proofs + g0, proof_lens + g0, jobs.data() + g0, rng, ok + g0, trace);
+      }
+    }
+    int all = 1;
+    for (size_t i = 0; i < count; i++) all &= ok[i];
+    if (all_ok) *all_ok = all;
+    return H2_OK;
+  });
+}
+
+uint64_t h2_selftest_pairing_checks(void) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  return g_pairing_checks;
+}
+
 // forget the resident SRS tables (the next call with any params blob parses and registers it again)
 int h2_params_cache_clear(void) {
   return guarded([&]() -> int {
@@ -2325,6 +2609,18 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
         uint8_t b[32];
         c.to_le_bytes(b);
         r.insert(r.end(), b, b + 32);
+      }
+    } else if (what == 8) {                // the decompression routine's host instantiation: n x 32 bytes -> n x (64 canonical
+      if (in_len % 32) return H2_EINVAL;   // LE bytes x || y, one status byte)
+      const CurveOps* ops = ops_of(H2_BN254);
+      for (size_t i = 0; i < in_len / 32; i++) {
+        uint64_t aff[8];
+        const int st = ops->selftest_decompress(in + 32 * i, aff);
+        uint8_t b[65];
+        Fq::from_mont_limbs(aff).to_le_bytes(b);
+        Fq::from_mont_limbs(aff + 4).to_le_bytes(b + 32);
+        b[64] = (uint8_t)st;
+        r.insert(r.end(), b, b + 65);
       }
     } else if (what == 5) {                // pairing check on two (G1, G2) pairs: 2 x (64 + 128) canonical bytes -> 1 byte
       if (in_len != 2 * 192) return H2_EINVAL;

@@ -45,6 +45,7 @@ SYMBOLS = {
     "h2_msm_device": (_I, [_I, _U64, _P, _Z, _Z, _P, _P]),
     "h2_msm_device_range": (_I, [_I, _U64, _P, _Z, _Z, _Z, _Z, _P, _P]),
     "h2_points_sum_device": (_I, [_I, _P, _Z, _Z, _P, _P]),
+    "h2_points_decompress_device": (_I, [_I, _P, _Z, _P, _P, _P]),
     "h2_stream_wait_msm_tail": (_I, [_P]),
     "h2_msm_device_multi": (_I, [_I, _P, _P, _Z, _Z, _Z, _Z, _P, _P]),
     "h2_ntt": (_I, [_I, _P, _P, _U32]),
@@ -67,6 +68,7 @@ SYMBOLS = {
     "h2_setup": (_I, [_U32, _P, _P, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_generate_proof": (_I, [_P, _Z, ctypes.c_char_p, _I, _P, _P, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_verify_proof": (_I, [_P, _Z, _P, _Z, ctypes.c_char_p, _I, ctypes.POINTER(_I)]),
+    "h2_verify_proofs": (_I, [_P, _Z, _Z, _P, _P, _P, _I, _P, _P, _P, ctypes.POINTER(_I)]),
     "h2_simulate": (_I, [ctypes.c_char_p, _I, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_circuit_count": (_I, []),
     "h2_params_cache_clear": (_I, []),
@@ -93,6 +95,7 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_arena_stats": (_I, [_P]),
     "h2_selftest_fe29_op": (_I, [_I, _I, _P, _P]),
     "h2_selftest_fe29_op_device": (_I, [_I, _I, _P, _P, _Z]),
+    "h2_selftest_pairing_checks": (_U64, []),
     "h2_selftest_expr_run": (_I, [_P, _Z, _P, _P, _U32, _U32, _U32, _P, _P]),
 }
 

@@ -144,6 +144,15 @@ int h2_msm_device_range(h2_curve_t curve, uint64_t bases_handle, const void* d_s
 int h2_points_sum_device(h2_curve_t curve, const void* d_in_jac, size_t groups, size_t count, void* d_out_jac,
                          void* stream);
 
+/* n compressed G1 points (32 bytes each: x little-endian, bit 6 of the last byte = parity of y, bit 7 = identity flag --
+ * the wire form of Blake2bRead / Blake2bWrite) -> n affine points in the API form (64 bytes,
+ * Montgomery limbs) and n status bytes: 0 = a point on the curve, 1 = x not canonical (>= q), 2 = the identity
+ * (flag set, or x = 0 with parity 0), 3 = x^3 + 3 is not a square.  For status != 0 the 64 output bytes are zero.
+ * One lane per point takes y = (x^3 + 3)^((q + 1) / 4), which needs q = 3 mod 4: H2_BN254 only, other curves H2_EINVAL.
+ * Device pointers; d_compressed and d_out_affine 16-byte aligned (H2_EINVAL otherwise); asynchronous on `stream`. */
+int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine,
+                                void* d_status, void* stream);
+
 /* ---- NTT == best_fft(a, omega, log_n) ---------------------------------------------------
  * In place, natural order in and out, A[i] = sum_j a[j] * omega^(i*j), unscaled, over the
  * SCALAR field of `curve` (bn256::Fr for H2_BN254).  a must hold exactly 1 << log_n elements. */
@@ -251,6 +260,19 @@ int h2_generate_proof(const uint8_t* params, size_t params_len, const char* json
                       void* rng_ctx, uint8_t* out, size_t cap, size_t* out_len);
 int h2_verify_proof(const uint8_t* params, size_t params_len, const uint8_t* proof, size_t proof_len,
                     const char* json, int circuit, int* ok);
+/* `count` proofs of ONE circuit under ONE params blob, each with its own JSON input (upstream halo2's
+ * plonk::BatchVerifier).  ok[i] (count ints, required) receives exactly what h2_verify_proof would have written for
+ * proof i; *all_ok (optional) = 1 iff every ok[i] is 1 (count = 0: H2_OK, *all_ok = 1).  The transcripts are replayed on
+ * the host one by one -- their compressed points decompressed beforehand by one kernel launch for the whole batch -- and
+ * the N final checks e(L_i, [s]G2) e(R_i, -G2) = 1 collapse into e(sum r_i L_i, [s]G2) e(sum r_i R_i, -G2) = 1: one small
+ * MSM launch and one pairing for up to 1024 proofs, which a batch holding a bad proof passes with probability at most
+ * 2^-128.  When it fails the batch is halved until the culprits are found (about 2 log2 N further checks per bad proof).
+ * rng supplies the weights r_i (16 bytes per proof, read little-endian; NULL = the OS); a zero weight is never used.
+ * The weights must be unpredictable to whoever made the proofs.  H2_EPROOF / H2_EINVAL under the same conditions as
+ * h2_verify_proof, for any item (a NULL ok, proofs, proof_lens or jsons with count > 0: H2_EINVAL). */
+int h2_verify_proofs(const uint8_t* params, size_t params_len, size_t count, const uint8_t* const* proofs,
+                     const size_t* proof_lens, const char* const* jsons, int circuit, h2_rng_fill_t rng, void* rng_ctx,
+                     int* ok, int* all_ok);
 /* the NUL-terminated result string of wasm_simulate_circuit ("N/A" for Collatz) */
 int h2_simulate(const char* json, int circuit, char* out, size_t cap, size_t* out_len);
 int h2_circuit_count(void);

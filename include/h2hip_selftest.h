@@ -72,7 +72,9 @@ int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* mo
  *    u32 nodes, u32 constants, then per node four i32 {op, a, b, x} -- op 0: constant x; 1: column a at rotation x;
  *    2 / 3 / 4: add / sub / mul of the EARLIER nodes a and b -- then the constants (32-byte canonical LE, bn256::Fr).
  *    The last node is the root.  H2_EINVAL for a later or unknown node, a rotation outside [-128, 127], a column
- *    index of 2^22 or more, or a root that is a bare constant or column. */
+ *    index of 2^22 or more, or a root that is a bare constant or column;
+ * 8: the host instantiation of the G1 decompression routine (csrc/h2_decompress.hpp): n x 32 bytes in the wire form ->
+ *    n x (64 canonical LE bytes x || y, then the status byte of the public decompression entry point in h2hip.h). */
 /* commit phases of the C++ prover / keygen that were spread over more than one context (h2_init_devices) so far */
 uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */
@@ -95,6 +97,8 @@ int h2_selftest_expr_run(const uint8_t* dag, size_t dag_len, const uint64_t* col
 /* scratch arenas of the current context: out = {allocations, cross-stream hand-overs (event waits), MSM slots taken
  * over by a further stream, NTT slots taken over} since h2_init */
 int h2_selftest_arena_stats(uint64_t out[4]);
+/* pairing checks the two verify entry points of the product surface have made since the library was loaded */
+uint64_t h2_selftest_pairing_checks(void);
 
 #ifdef __cplusplus
 }

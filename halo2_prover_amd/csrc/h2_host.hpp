@@ -352,7 +352,7 @@ class Transcript {
     common_scalar(*s);
     return true;
   }
-  bool read_point(G1* p);   // h2_prover.hip (needs the square root in Fq)
+  bool read_point(G1* p);   // h2_verify.hpp (needs the square root in Fq)
   // Points of this proof that were decompressed before the replay (h2_verify_proofs: one kernel launch for a whole batch,
   // h2_decompress.hpp): entry i belongs to the 32 bytes at offsets[i] (ascending) and is 64 bytes in the API form at
   // points + 64 i with its status byte.  read_point takes a point it finds here instead of the square root; any other

@@ -74,7 +74,15 @@ int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* mo
  *    The last node is the root.  H2_EINVAL for a later or unknown node, a rotation outside [-128, 127], a column
  *    index of 2^22 or more, or a root that is a bare constant or column;
  * 8: the host instantiation of the G1 decompression routine (csrc/h2_decompress.hpp): n x 32 bytes in the wire form ->
- *    n x (64 canonical LE bytes x || y, then the status byte of the public decompression entry point in h2hip.h). */
+ *    n x (64 canonical LE bytes x || y, then the status byte of the public decompression entry point in h2hip.h).;
+ * 9: the opening plan of circuit in[0] for k = in[1], as keygen builds it (csrc/h2_opening.hpp): which polynomial is
+ *    evaluated and opened at which rotation of x, and where a proof's compressed points sit.  Little-endian: five u32
+ *    {1 if the circuit opens with SHPLONK, leading commitments, evaluations E, opening points, opening queries Q}; the
+ *    byte offsets of the proof's compressed points (u32 each: leading commitments + opening points of them, ascending);
+ *    E records of three i32 {kind, index, rotation} in the order the evaluations go onto the transcript; Q records of
+ *    four i32 {kind, index, rotation, index of the query's evaluation among the E, -1 for h} in the batching order of
+ *    the multi-open.  kind: 0 advice, 1 fixed, 2 sigma, 3 permutation product, 4 random polynomial, 5 h; index: the
+ *    column, the permutation column or the product's set; rotation in rows (signed). */
 /* commit phases of the C++ prover / keygen that were spread over more than one context (h2_init_devices) so far */
 uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */

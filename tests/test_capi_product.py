@@ -157,7 +157,7 @@ def test_pairing_check_in_c_agrees_with_the_python_pairing(lib):
 
 
 def test_quotient_programs_are_well_formed_and_need_few_live_values(lib):
-    """ExprProgram::compile (h2_prover.hip): the straight-line program expr_kernel interprets.  Structure only here (the
+    """ExprProgram::compile (h2_expr_program.hpp): the straight-line program expr_kernel interprets.  Structure only here (the
     GPU tests below check its results through byte-identical proofs): operands refer to values that exist, a result
     without a slot is read by the very next instruction, and the live values stay few -- they are 36 bytes of LDS or
     nine registers per row each, which is what decides the kernel's occupancy."""
@@ -195,6 +195,63 @@ def test_quotient_programs_are_well_formed_and_need_few_live_values(lib):
                 written.add(dst)
         assert (muls, cols) == (n_mul, n_col)
         assert code[-1][0] >> 24 == 2          # the root: numerator times 1 / (X^n - 1)
+
+
+def test_opening_plan_matches_the_oracles_evaluation_and_query_order(lib):
+    """The opening plan a key is built with (h2_selftest_host what = 9), against the order oracle/halo2_ref.create_proof
+    writes its evaluations (step 7) and batches its opening queries (step 8), built here from the oracle's circuit
+    objects; and the plan's counts and point offsets against the recorded proofs: 32 bytes per point and per evaluation,
+    the offsets exactly the leading commitments and the trailing opening points."""
+    import struct
+    import halo2_ref as H
+    ADVICE, FIXED, SIGMA, Z, RANDOM, HPOLY = range(6)
+    for idx, circ, k, proof, n_points in ((0, H.CollatzCircuit([]), 10, golden("proof_collatz_k10.bin"), 10),
+                                          (1, H.ArithmeticCircuit(1, 2, 3), 4, golden("proof_arithmetic_k4.bin"), 13),
+                                          (2, H.PoseidonCircuit([1, 2]), 6, golden("proof_poseidon_k6.bin"), 16)):
+        assert len(proof) == {0: 640, 1: 1184, 2: 1536}[idx]
+        raw = host(lib, 9, bytes([idx, k]))
+        shplonk, leading, n_evals, n_open, n_queries = struct.unpack("<5I", raw[:20])
+        at = 20
+        offsets = list(struct.unpack("<%dI" % (leading + n_open), raw[at:at + 4 * (leading + n_open)]))
+        at += 4 * (leading + n_open)
+        evals = [struct.unpack("<3i", raw[at + 12 * i:at + 12 * i + 12]) for i in range(n_evals)]
+        at += 12 * n_evals
+        queries = [struct.unpack("<4i", raw[at + 16 * i:at + 16 * i + 16]) for i in range(n_queries)]
+        assert at + 16 * n_queries == len(raw)
+        # the oracle's order (halo2_ref.create_proof steps 7 and 8)
+        chunk = circ.degree - 2
+        n_sets = len(range(0, len(circ.perm_columns), chunk))
+        n_sigma = len(circ.perm_columns)
+        back = -(circ.blinding_factors() + 1)
+        want_evals = [(ADVICE, col, rot) for col, rot in circ.advice_queries]
+        want_evals += [(FIXED, col, rot) for col, rot in circ.fixed_queries]
+        want_evals += [(RANDOM, 0, 0)] + [(SIGMA, j, 0) for j in range(n_sigma)]
+        for i in range(n_sets):
+            want_evals += [(Z, i, 0), (Z, i, 1)] + ([(Z, i, back)] if i + 1 < n_sets else [])
+        want_queries = [(ADVICE, col, rot) for col, rot in circ.advice_queries]
+        for i in range(n_sets):
+            want_queries += [(Z, i, 0), (Z, i, 1)]
+        want_queries += [(Z, i, back) for i in reversed(range(n_sets - 1))]
+        want_queries += [(FIXED, col, rot) for col, rot in circ.fixed_queries]
+        want_queries += [(SIGMA, j, 0) for j in range(n_sigma)] + [(HPOLY, 0, 0), (RANDOM, 0, 0)]
+        assert evals == want_evals
+        assert [q[:3] for q in queries] == want_queries
+        for kind, index, rot, e in queries:                           # every query names its own evaluation; h has none
+            assert (e == -1) if kind == HPOLY else (evals[e] == (kind, index, rot))
+        assert shplonk == (1 if idx == 0 else 0)
+        # counts and offsets against the recorded proof
+        assert leading == circ.num_advice + n_sets + 1 + (circ.degree - 1)
+        distinct = []
+        for _, _, rot in want_queries:
+            if rot % (1 << k) not in distinct:
+                distinct.append(rot % (1 << k))
+        assert n_open == (2 if shplonk else len(distinct))
+        assert 32 * (leading + n_open + n_evals) == len(proof)
+        assert leading + n_open == n_points
+        assert offsets == [32 * i for i in range(leading)] + [len(proof) - 32 * (n_open - i) for i in range(n_open)]
+        assert not set(offsets) & {32 * (leading + i) for i in range(n_evals)}
+        words = b"".join(proof[o:o + 32] for o in offsets)            # and each of them holds a point of the curve
+        assert [host(lib, 8, words)[65 * i + 64] for i in range(n_points)] == [0] * n_points
 
 
 def test_simulate_and_count(lib):

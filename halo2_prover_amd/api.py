@@ -273,6 +273,39 @@ def verify_proofs(params, proofs, jsons, circuit, rng=None):
     return [bool(v) for v in ok]
 
 
+def generate_proofs(params, jsons, circuit, rngs=None):
+    """Batch proving (h2_generate_proofs): one proof per JSON input of ONE circuit under ONE params blob -> list[bytes],
+    entry i what proving input i alone gives under the same randomness.  rngs: None (the OS) or one callable
+    n -> n bytes per proof; proof i draws only from rngs[i]."""
+    _ensure_init()
+    texts = [j.encode() if isinstance(j, str) else bytes(j) for j in jsons]
+    count = len(texts)
+    if rngs is not None and len(rngs) != count:
+        raise ValueError("generate_proofs: %d inputs but %d rngs" % (count, len(rngs)))
+    if count == 0:
+        return []
+    params = bytes(params)
+    js = (ctypes.c_char_p * count)(*texts)
+    cb, ctxs = None, None
+    if rngs is not None:
+        def fill(ctx, out, n):
+            ctypes.memmove(out, bytes(rngs[ctx - 1](n)), n)
+        cb = _lib.RNG_FILL(fill)
+        ctxs = (ctypes.c_void_p * count)(*range(1, count + 1))         # proof i's context: i + 1 (0 would arrive as None)
+    lens = (ctypes.c_size_t * count)()
+    total = ctypes.c_size_t(0)
+    cap = count << 16
+    out = ctypes.create_string_buffer(cap)
+    st = _lib.load().h2_generate_proofs(params, len(params), count, js, int(circuit), cb, ctxs, out, cap, lens,
+                                        ctypes.byref(total))
+    _lib.check(st, "h2_generate_proofs")
+    proofs, at = [], 0
+    for n in lens:
+        proofs.append(out.raw[at:at + n])
+        at += n
+    return proofs
+
+
 class ParamsKZG:
     """Mirror of halo2_proofs::poly::kzg::commitment::ParamsKZG<Bn256> for the prover side.
 

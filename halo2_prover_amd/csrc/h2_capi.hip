@@ -227,7 +227,7 @@ static uint64_t g_msm_max_entries = (1ull << 31) - 1;   // lowered only by h2_se
 static bool g_msm_guard = false, g_msm_guard_poke = false, g_sort2_pack = true;
 static uint64_t g_guard_launches = 0, g_guard_violations = 0;
 static std::string g_guard_first;
-static size_t msm_cols_per_launch(const MsmGeom& geom, size_t n) {
+size_t msm_cols_per_launch(const MsmGeom& geom, size_t n) {
   const uint64_t per_col = (uint64_t)geom.W * n;
   const uint64_t by_entries = g_msm_max_entries / per_col;
   uint64_t by_keys = ((1ull << 31) - 1) / geom.B;

@@ -165,6 +165,9 @@ struct ArenaLease {
 int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_scalars, size_t first_base, size_t n,
                    size_t col_stride, size_t m, void* d_out, bool affine_out, hipStream_t stream,
                    const BasesEntry* const* per_column = nullptr);
+// columns of n scalars one MSM launch sequence takes under this geometry (0: a single column is already too long); a wider
+// call runs in groups of that many, and columns with their own bases (per_column) must fit one group
+size_t msm_cols_per_launch(const MsmGeom& geom, size_t n);
 int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, hipStream_t stream,
                 const uint64_t* scale = nullptr);
 int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t m, const BasesEntry** be);

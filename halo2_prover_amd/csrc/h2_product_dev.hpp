@@ -362,12 +362,14 @@ struct PendingCommit {
 // elements as the one-device commitment, hence the same proof bytes.  Transforms are NOT spread: a column would cross
 // xGMI twice (2 x 16 MiB for an extended column at k = 16, ~0.5 ms) for ~60 us of butterflies.
 inline uint64_t g_sharded_commits = 0;
+inline uint64_t g_commit_launches = 0;            // commit_begin calls since the library was loaded (tests)
 inline size_t g_shard_min_rows = 1024;            // per context; below this the copies and the extra launches cost more than they save
 // `split` < m: columns [0, split) commit against g_lagrange and [split, m) against g IN THE SAME LAUNCH (commitments
 // that do not wait for each other: the permutation products and the RNG-drawn random polynomial)
 inline PendingCommit commit_begin(Dev& d, const Params& P, Col cols, uint32_t n, size_t m, bool lagrange, size_t split = ~(size_t)0) {
   auto it = g_h2.bases.find(lagrange ? P.h_gl : P.h_g);
   if (it == g_h2.bases.end()) fail(H2_EHANDLE, "params bases released");
+  g_commit_launches++;
   PendingCommit pc;
   pc.m = m;
   pc.out = d.alloc(m * 96);

@@ -13,79 +13,111 @@ struct Query {
   Fr eval;
 };
 
-// ProverSHPLONK::create_proof (prover.py _shplonk_open)
-inline void shplonk_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const std::vector<Query>& queries) {
-  const Fr y = tr.squeeze_challenge(), v = tr.squeeze_challenge();
-  std::vector<Fr> pts, evs;
-  std::vector<uintptr_t> ids;
-  for (auto& q : queries) {
-    pts.push_back(q.point);
-    evs.push_back(q.eval);
-    ids.push_back((uintptr_t)q.poly);
-  }
-  const ShplonkSets S = shplonk_sets(pts, evs, ids);
-  Col h = d.col(n), acc = d.col(n), quo = d.col(n);
-  std::vector<std::vector<std::vector<Fr>>> rems(S.groups.size());
-  Fr vp = Fr::one();
-  for (size_t gi = 0; gi < S.groups.size(); gi++) {
-    const auto& G = S.groups[gi];
-    std::vector<std::pair<Col, Fr>> t;
-    std::vector<Fr> rsum(G.points.size(), Fr::zero());
-    Fr yp = Fr::one();
-    for (auto& m : G.members) {
-      std::vector<Fr> vals;
-      for (auto& pt : G.points) vals.push_back(m.evals.at(fr_key(pt)));
-      const std::vector<Fr> r = interpolate(G.points, vals);
-      rems[gi].push_back(r);
-      t.push_back({m.poly, yp});
-      for (size_t i = 0; i < r.size(); i++) rsum[i] += yp * r[i];
-      yp *= y;
+// The host side of ProverSHPLONK::create_proof (prover.py _shplonk_open), shared by the single and
+// the lockstep prover: the rotation sets, then per set the y-power combination of its members with the low coefficients
+// to subtract from it (the combined remainders) and the set's power of v; after u, the terms of L(X).
+struct ShplonkOpening {
+  Fr y, v;
+  ShplonkSets S;
+  std::vector<std::vector<std::vector<Fr>>> rems;      // [set][member]: the remainder through the member's evaluations
+  struct GroupWork {
+    std::vector<std::pair<Col, Fr>> terms;             // sum_j y^j f_j
+    std::vector<Fr> rsum;                              // sum_j y^j r_j
+    Fr vp;                                             // v^set
+  };
+  std::vector<GroupWork> groups;
+  ShplonkOpening(Transcript& tr, const std::vector<Query>& queries) {
+    y = tr.squeeze_challenge();
+    v = tr.squeeze_challenge();
+    std::vector<Fr> pts, evs;
+    std::vector<uintptr_t> ids;
+    for (auto& q : queries) {
+      pts.push_back(q.point);
+      evs.push_back(q.eval);
+      ids.push_back((uintptr_t)q.poly);
     }
-    d.lincomb(acc, n, t);
-    Col d_r = d.upload_frs(rsum);
-    launch("sub_prefix_kernel", pk::sub_prefix_kernel, dim3(1), dim3(64), d.s, acc, d_r, (uint32_t)rsum.size());
+    S = shplonk_sets(pts, evs, ids);
+    rems.resize(S.groups.size());
+    Fr vp = Fr::one();
+    for (size_t gi = 0; gi < S.groups.size(); gi++) {
+      const auto& G = S.groups[gi];
+      GroupWork w;
+      w.rsum.assign(G.points.size(), Fr::zero());
+      w.vp = vp;
+      Fr yp = Fr::one();
+      for (auto& m : G.members) {
+        std::vector<Fr> vals;
+        for (auto& pt : G.points) vals.push_back(m.evals.at(fr_key(pt)));
+        const std::vector<Fr> r = interpolate(G.points, vals);
+        rems[gi].push_back(r);
+        w.terms.push_back({m.poly, yp});
+        for (size_t i = 0; i < r.size(); i++) w.rsum[i] += yp * r[i];
+        yp *= y;
+      }
+      groups.push_back(std::move(w));
+      vp *= v;
+    }
+  }
+  // L(X) = sum_i v^i z_i (sum_j y^j (f_ij(X) - r_ij(u))) - Z_T(u) h(X): its terms, the constant to subtract and 1 / z_0
+  struct Final {
+    std::vector<std::pair<Col, Fr>> terms;
+    Fr lconst, z0_inv;
+  };
+  Final finish(const Fr& u, Col h) const {
+    Final f;
+    Fr zt = Fr::one();
+    for (auto& pt : S.super) zt *= u - pt;
+    f.lconst = Fr::zero();
+    Fr z0 = Fr::zero(), vp = Fr::one();
+    for (size_t gi = 0; gi < S.groups.size(); gi++) {
+      const auto& G = S.groups[gi];
+      Fr z_i = Fr::one();
+      for (auto& pt : S.super)
+        if (std::find(G.points.begin(), G.points.end(), pt) == G.points.end()) z_i *= u - pt;
+      if (gi == 0) z0 = z_i;
+      Fr yp = Fr::one();
+      for (size_t mi = 0; mi < G.members.size(); mi++) {
+        f.terms.push_back({G.members[mi].poly, vp * z_i * yp});
+        f.lconst += vp * z_i * yp * horner(rems[gi][mi], u);
+        yp *= y;
+      }
+      vp *= v;
+    }
+    f.terms.push_back({h, -zt});
+    f.z0_inv = z0.inv();
+    return f;
+  }
+};
+
+inline void shplonk_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const std::vector<Query>& queries) {
+  const ShplonkOpening O(tr, queries);
+  Col h = d.col(n), acc = d.col(n), quo = d.col(n);
+  for (size_t gi = 0; gi < O.groups.size(); gi++) {
+    const auto& w = O.groups[gi];
+    d.lincomb(acc, n, w.terms);
+    Col d_r = d.upload_frs(w.rsum);
+    launch("sub_prefix_kernel", pk::sub_prefix_kernel, dim3(1), dim3(64), d.s, acc, d_r, (uint32_t)w.rsum.size());
     // divide by prod (X - p): one synthetic division per point, ping-ponging two buffers (the quotient keeps the
     // column's length, its top coefficients are zero)
     Col src = acc, dst = quo;
-    for (auto& pt : G.points) {
+    for (auto& pt : O.S.groups[gi].points) {
       d.scan_batch(0, n, {src}, {dst}, {pt});
       std::swap(src, dst);
     }
-    d.lincomb(h, n, gi == 0 ? std::vector<std::pair<Col, Fr>>{{src, vp}}
-                            : std::vector<std::pair<Col, Fr>>{{h, Fr::one()}, {src, vp}});
-    vp *= v;
+    d.lincomb(h, n, gi == 0 ? std::vector<std::pair<Col, Fr>>{{src, w.vp}}
+                            : std::vector<std::pair<Col, Fr>>{{h, Fr::one()}, {src, w.vp}});
   }
   tr.write_point(commit(d, P, h, n, 1, false)[0]);
   const Fr u = tr.squeeze_challenge();
-  Fr zt = Fr::one();
-  for (auto& pt : S.super) zt *= u - pt;
-  // L(X) = sum_i v^i z_i (sum_j y^j (f_ij(X) - r_ij(u))) - Z_T(u) h(X), then / (X - u) / z_0
-  std::vector<std::pair<Col, Fr>> lt;
-  Fr lconst = Fr::zero(), z0 = Fr::zero();
-  vp = Fr::one();
-  for (size_t gi = 0; gi < S.groups.size(); gi++) {
-    const auto& G = S.groups[gi];
-    Fr z_i = Fr::one();
-    for (auto& pt : S.super)
-      if (std::find(G.points.begin(), G.points.end(), pt) == G.points.end()) z_i *= u - pt;
-    if (gi == 0) z0 = z_i;
-    Fr yp = Fr::one();
-    for (size_t mi = 0; mi < G.members.size(); mi++) {
-      lt.push_back({G.members[mi].poly, vp * z_i * yp});
-      lconst += vp * z_i * yp * horner(rems[gi][mi], u);
-      yp *= y;
-    }
-    vp *= v;
-  }
-  lt.push_back({h, -zt});
-  d.lincomb(acc, n, lt);
+  const ShplonkOpening::Final L = O.finish(u, h);    // then / (X - u) / z_0
+  d.lincomb(acc, n, L.terms);
   {
-    std::vector<Fr> c0(1, lconst);
+    std::vector<Fr> c0(1, L.lconst);
     Col d_c = d.upload_frs(c0);
     launch("sub_prefix_kernel", pk::sub_prefix_kernel, dim3(1), dim3(64), d.s, acc, d_c, 1u);
   }
   d.scan_batch(0, n, {acc}, {quo}, {u});
-  launch("scale_range_kernel", pk::scale_range_kernel, dim3((n + 255) / 256), dim3(256), d.s, quo, 0u, n, z0.inv().v);
+  launch("scale_range_kernel", pk::scale_range_kernel, dim3((n + 255) / 256), dim3(256), d.s, quo, 0u, n, L.z0_inv.v);
   tr.write_point(commit(d, P, quo, n, 1, false)[0]);
 }
 
@@ -114,6 +146,16 @@ inline void gwc_open(Transcript& tr, Dev& d, const Params& P, uint32_t n, const 
     d.scan_batch(0, n, in, out, points);          // the four synthetic divisions side by side
   }
   for (auto& pt : commit(d, P, witnesses, n, points.size(), false)) tr.write_point(pt);
+}
+
+// a witness's advice columns (not yet blinded) behind the checks a prover makes before it draws or enqueues anything
+inline std::vector<SparseCol> synthesize_checked(const Circuit& C, const std::vector<Fr>& public_input, uint32_t n, int bf) {
+  if (public_input.size() > n - (uint32_t)(bf + 1)) fail(H2_EINVAL, "instance too long");
+  if (!C.num_instance && !public_input.empty()) fail(H2_EINVAL, "circuit has no instance column");
+  std::vector<SparseCol> adv = C.synthesize_advice();
+  for (auto& col : adv)
+    if (!col.empty() && col.rbegin()->first >= n - (uint32_t)(bf + 1)) fail(H2_EINVAL, "k too small for this circuit");
+  return adv;
 }
 
 // One proof: its state, and its phases in the order create_proof calls them.  Every phase enqueues on the main stream
@@ -150,9 +192,8 @@ struct Proving {
         nf(key.nf()), np(key.np()) {}
 
   void upload_instance_and_advice() {
+    std::vector<SparseCol> adv = synthesize_checked(C, public_input, n, bf);
     tr.common_scalar(K.transcript_repr);
-    if (public_input.size() > n - (uint32_t)(bf + 1)) fail(H2_EINVAL, "instance too long");
-    if (!ni && !public_input.empty()) fail(H2_EINVAL, "circuit has no instance column");
     lag = d.col((na + ni + nz + 1) * (size_t)n);
     advice_values = lag;
     instance_values = lag + 2 * na * (size_t)n;
@@ -164,12 +205,9 @@ struct Proving {
       d.fill_sparse(instance_values, n, inst);
       for (auto& v : public_input) tr.common_scalar(v);
     }
-    // advice: synthesize, blind the last bf + 1 rows
-    std::vector<SparseCol> adv = C.synthesize_advice();
-    for (auto& col : adv) {
-      if (!col.empty() && col.rbegin()->first >= n - (uint32_t)(bf + 1)) fail(H2_EINVAL, "k too small for this circuit");
+    // advice: blind the last bf + 1 rows
+    for (auto& col : adv)
       for (uint32_t row = n - (bf + 1); row < n; row++) col[row] = rng.fr_random();
-    }
     for (size_t j = 0; j < adv.size(); j++) (void)rng.fr_random();       // the Blind of each commitment (unused by KZG)
     d.fill_sparse(advice_values, n, adv);
     trace.mark("witness uploaded");

@@ -1,5 +1,5 @@
 // h2_prover.hip -- the reference crate's product surface behind the C ABI (include/h2hip.h, "product surface"):
-//   h2_setup / h2_generate_proof / h2_verify_proof / h2_simulate / h2_circuit_count
+//   h2_setup / h2_generate_proof[s] / h2_verify_proof[s] / h2_simulate / h2_circuit_count
 // = setup / wasm_generate_proof / wasm_verify_proof / wasm_simulate_circuit / get_circuit_count of
 // /root/reference/circuits/src/wasm.rs:49,68,77,125,182, which call utils.rs:59-158 (generate_params, generate_keys,
 // generate_proof[_with_instance], verify[_with_instance]) over halo2_proofs @6b43b6b's keygen_vk / keygen_pk /
@@ -15,6 +15,7 @@
 // scalars from the caller's RNG in the reference's order, so that under the same RNG stream the proof bytes are the
 // reference's.
 #include "h2_prove.hpp"
+#include "h2_prove_batch.hpp"
 #include "h2_verify.hpp"
 
 using namespace h2;
@@ -216,6 +217,47 @@ int h2_generate_proof(const uint8_t* params, size_t params_len, const char* json
   });
 }
 
+int h2_generate_proofs(const uint8_t* params, size_t params_len, size_t count, const char* const* jsons, int circuit,
+                       h2_rng_fill_t rng_fn, void* const* rng_ctxs, uint8_t* out, size_t cap, size_t* proof_lens,
+                       size_t* out_len) {
+  return guarded([&]() -> int {
+    Trace trace("generate_proofs");
+    DevCtx* ctx = the_ctx();
+    if (count && (!jsons || !out_len || !proof_lens)) return H2_EINVAL;
+    if (count == 0) {
+      if (out_len) *out_len = 0;
+      return H2_OK;
+    }
+    const Params& P = params_get(params, params_len);
+    // every JSON parsed and every witness synthesised before anything is enqueued: a bad item ends the call here
+    std::vector<Job> jobs;
+    for (size_t i = 0; i < count; i++) jobs.push_back(job_for_proof(Json(jsons[i]), circuit));
+    std::unique_ptr<ProvingKey> owner;
+    ProvingKey& K = key_for(P, jobs[0].index, ctx, owner);
+    std::vector<Witness> items;
+    for (size_t i = 0; i < count; i++)
+      items.push_back({&jobs[i].public_input, synthesize_checked(*jobs[i].circuit, jobs[i].public_input, K.dom->n, K.bf),
+                       Rng{rng_fn, rng_ctxs ? rng_ctxs[i] : nullptr}});
+    trace.mark("params, jobs, key, witnesses");
+    // every proof of a circuit has the plan's length: the room is checked before a random byte is drawn
+    const size_t each = 32 * ((size_t)K.plan.leading + K.plan.evals.size() + K.plan.opening_points);
+    *out_len = each * count;
+    if (!out || cap < each * count) return H2_EINVAL;
+    const std::vector<std::vector<uint8_t>> proofs = create_proofs(K, items, trace);
+    trace.mark("create_proofs");
+    size_t total = 0;
+    for (auto& pr : proofs) total += pr.size();
+    if (total != each * count) fail(H2_EDEVICE, "a proof's length is not its plan's");
+    uint8_t* at = out;
+    for (size_t i = 0; i < count; i++) {
+      proof_lens[i] = proofs[i].size();
+      memcpy(at, proofs[i].data(), proofs[i].size());
+      at += proofs[i].size();
+    }
+    return H2_OK;
+  });
+}
+
 int h2_verify_proof(const uint8_t* params, size_t params_len, const uint8_t* proof, size_t proof_len, const char* json,
                     int circuit, int* ok) {
   if (ok) *ok = 0;
@@ -306,6 +348,19 @@ void h2_prover_shutdown(void) {
 uint64_t h2_selftest_sharded_commits(void) {
   std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   return g_sharded_commits;
+}
+
+// commit_begin calls since the library was loaded: a lockstep batch makes as many as one proof, a loop N times as many
+uint64_t h2_selftest_commit_launches(void) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  return g_commit_launches;
+}
+
+// test hook: proofs per lockstep group of h2_generate_proofs (0 restores the default)
+int h2_selftest_set_prove_group(size_t proofs) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  g_prove_group = proofs ? proofs : PROVE_GROUP;
+  return H2_OK;
 }
 
 // test hook: rows per context from which a commit phase is spread over the contexts (0 restores the default)

@@ -13,6 +13,7 @@
 //   * lincomb_kernel         sum_j c_j a_j, up to 24 columns per launch
 //   * coset_extend / coset_shrink   the zero-extension and the zeta^i scaling around the extended-domain NTTs
 // All HBM-bound elementwise work except expr_kernel (a few hundred field products per row).
+// The *_batch_kernel forms serve N proofs in lockstep (h2_prove_batch.hpp): grid.y = job or proof, arguments in HBM.
 #pragma once
 #include "h2_field.hpp"
 #include "h2_field29.hpp"
@@ -106,11 +107,9 @@ constexpr int PERM_MAX_SETS = 4;
 struct PermBatch {
   PermArgs set[PERM_MAX_SETS];
 };
-// grid.y = permutation set (the sets only share beta and gamma: all of them in one launch); ratio: one column per set
-static __global__ void __launch_bounds__(256)
-perm_ratio_kernel(PermBatch B, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base, uint32_t n) {
-  const PermArgs& A = B.set[blockIdx.y];
-  U128* ratio = ratio_base + 2 * (size_t)n * blockIdx.y;
+// one ratio column: PERM_RUN rows per thread
+__device__ __forceinline__ void perm_ratio_rows(const PermArgs& A, const U128* __restrict__ omega_col, U128* __restrict__ ratio,
+                                                uint32_t n) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lo = t * PERM_RUN;
   if (lo >= n) return;
@@ -118,7 +117,6 @@ perm_ratio_kernel(PermBatch B, const U128* __restrict__ omega_col, U128* __restr
   W num[PERM_RUN], den[PERM_RUN], pre[PERM_RUN];
   const W one = fe29_from_api(F::one());
   W acc = one;
-#pragma unroll
   for (int k = 0; k < PERM_RUN; k++) {
     const uint32_t i = lo + k;
     W nu = one, de = one;
@@ -137,12 +135,22 @@ perm_ratio_kernel(PermBatch B, const U128* __restrict__ omega_col, U128* __restr
     acc = fe29_mul(acc, de);
   }
   W inv = w_inv(acc);         // a zero denominator (probability 2^-250 per row) would zero the run, as 1/0 := 0 does
-#pragma unroll
   for (int k = PERM_RUN - 1; k >= 0; k--) {
     const uint32_t i = lo + k;
     if (i < n) w_store(ratio + 2 * (size_t)i, fe29_mul(num[k], fe29_mul(pre[k], inv)));
     inv = fe29_mul(inv, den[k]);
   }
+}
+// grid.y = permutation set (the sets only share beta and gamma: all of them in one launch); ratio: one column per set
+static __global__ void __launch_bounds__(256)
+perm_ratio_kernel(PermBatch B, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base, uint32_t n) {
+  perm_ratio_rows(B.set[blockIdx.y], omega_col, ratio_base + 2 * (size_t)n * blockIdx.y, n);
+}
+// the batch form (h2_prove_batch.hpp): grid.y = (proof, set), one PermArgs per ratio column in HBM
+static __global__ void __launch_bounds__(256)
+perm_ratio_batch_kernel(const PermArgs* __restrict__ args, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base,
+                        uint32_t n) {
+  perm_ratio_rows(args[blockIdx.y], omega_col, ratio_base + 2 * (size_t)n * blockIdx.y, n);
 }
 
 // a[i] = a[i] * c for rows [lo, hi)
@@ -176,6 +184,74 @@ lincomb_kernel(LincombArgs A, U128* __restrict__ out, uint32_t n, int accumulate
     acc = fe_add(acc, (j == 0 && A.unit_first) ? v : fe_mul(v, A.c[j]));
   }
   fe_store<FR>(out + 2 * (size_t)i, acc);
+}
+
+// ---- the batch forms (h2_prove_batch.hpp: N proofs of one circuit in lockstep) -------------------------------------------
+// They compute what their single forms above compute, element for element (field results are canonical, so the bytes
+// are the same); what the single forms take by value -- a handful of pointers and constants -- comes from a table in
+// HBM here, and grid.y picks the job or the proof.
+
+// grid.y = proof: out[p][i] = in[p][i] * zinv^i for i < count -- the kept coefficients of every proof's quotient, written
+// compactly (out_stride = count) from the extended columns (in_stride = en)
+static __global__ void __launch_bounds__(256)
+coset_shrink_batch_kernel(const U128* __restrict__ in, size_t in_stride, U128* __restrict__ out, size_t out_stride,
+                          uint32_t count, F zi1, F zi2) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const U128* src = in + 2 * (in_stride * blockIdx.y + i);
+  U128* dst = out + 2 * (out_stride * blockIdx.y + i);
+  F v = fe_load<FR>(src);
+  const uint32_t r = i % 3;
+  if (r != 0) v = fe_mul(v, r == 1 ? zi1 : zi2);
+  fe_store<FR>(dst, v);
+}
+
+// grid.y = job: a[i] *= c for i < n
+struct ScaleJob {
+  U128* a;
+  F c;
+};
+static __global__ void __launch_bounds__(256) scale_batch_kernel(const ScaleJob* __restrict__ jobs, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ScaleJob job = jobs[blockIdx.y];
+  fe_store<FR>(job.a + 2 * (size_t)i, fe_mul(fe_load<FR>(job.a + 2 * (size_t)i), job.c));
+}
+
+// grid.y = job: a[i] -= v[offset + i] for i < count (the low coefficients of a remainder; `v` is one table for the batch)
+struct SubPrefixJob {
+  U128* a;
+  uint32_t offset, count;
+};
+static __global__ void __launch_bounds__(64)
+sub_prefix_batch_kernel(const SubPrefixJob* __restrict__ jobs, const U128* __restrict__ v) {
+  const SubPrefixJob job = jobs[blockIdx.y];
+  for (uint32_t i = threadIdx.x; i < job.count; i += blockDim.x)
+    fe_store<FR>(job.a + 2 * (size_t)i,
+                 fe_sub(fe_load<FR>(job.a + 2 * (size_t)i), fe_load<FR>(v + 2 * ((size_t)job.offset + i))));
+}
+
+// grid.y = job: out[i] = sum_t c_t a_t[i] over the job's `count` terms, which start at terms[first].  `out` may be one
+// of the job's own operands (the sum is elementwise)
+struct LincombTerm {
+  const U128* a;
+  F c;
+};
+struct LincombJob {
+  U128* out;
+  uint32_t first, count;
+};
+static __global__ void __launch_bounds__(256)
+lincomb_batch_kernel(const LincombJob* __restrict__ jobs, const LincombTerm* __restrict__ terms, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LincombJob job = jobs[blockIdx.y];
+  F acc = F::zero();
+  for (uint32_t t = 0; t < job.count; t++) {
+    const LincombTerm term = terms[job.first + t];
+    acc = fe_add(acc, fe_mul(fe_load<FR>(term.a + 2 * (size_t)i), term.c));
+  }
+  fe_store<FR>(job.out + 2 * (size_t)i, acc);
 }
 
 // ---- evaluations: job q = (polynomial pointer, point); partial[q][block] then out[q] ------------------------------
@@ -249,10 +325,9 @@ constexpr int EXPR_COLUMN_BOUND = 16, EXPR_VALUE_BOUND = 32;
 //   * the last result goes back to the API form (one product) on its way out.
 // Operands that do not depend on the program's own results -- columns and constants -- are fetched TWO instructions
 // ahead (a global load is 0.5-2 us, an instruction 0.1-0.5).  LDS: 36 bytes per slot beyond the register slots and row.
-static __global__ void __launch_bounds__(EXPR_BLOCK)
-expr_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols,
-            const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts, U128* __restrict__ out, uint32_t step,
-            uint32_t en) {
+__device__ __forceinline__ void expr_rows(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols,
+                                          const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts,
+                                          U128* __restrict__ out, uint32_t step, uint32_t en) {
   using W = Fe29<FR>;
   extern __shared__ int32_t slots[];      // [slot][limb][thread]
   const uint32_t tid = threadIdx.x;
@@ -320,6 +395,22 @@ expr_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const*
     if (k + 1 < ninstr) run(k + 1, i1, pa1, pb1);
   }
   if (i < en) fe_store<FR>(out + 2 * (size_t)i, fe29_to_api(r));     // a domain smaller than one block: the spare lanes computed on wrapped rows
+}
+static __global__ void __launch_bounds__(EXPR_BLOCK)
+expr_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols,
+            const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts, U128* __restrict__ out, uint32_t step,
+            uint32_t en) {
+  expr_rows(prog, ninstr, cols, col_mask, consts, out, step, en);
+}
+// the batch form (h2_prove_batch.hpp): grid.y = proof.  One program and one set of row masks; proof p reads its column
+// pointers at cols + p ncols, its constants (y, beta, gamma, beta delta^j differ) at consts + p nconsts and writes the
+// extended column out + p en
+static __global__ void __launch_bounds__(EXPR_BLOCK)
+expr_batch_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols, uint32_t ncols,
+                  const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts, uint32_t nconsts,
+                  U128* __restrict__ out, uint32_t step, uint32_t en) {
+  const size_t p = blockIdx.y;
+  expr_rows(prog, ninstr, cols + p * ncols, col_mask, consts + 2 * p * nconsts, out + 2 * p * en, step, en);
 }
 
 }  // namespace pk

@@ -2,6 +2,8 @@
 // build made with -DH2_TUNING (H2_BUILD_TUNING=1 python -m halo2_prover_amd.build --force): the product library never
 // reads its configuration from the environment.
 #pragma once
+#include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 
 namespace h2 {
@@ -13,4 +15,14 @@ inline int tune_int(const char* name, int fallback) {
 #endif
   return fallback;
 }
+
+// Proofs that h2_generate_proofs runs in lockstep (h2_prove_batch.hpp); a larger batch is cut into groups of this many.
+// Budget: 4 GiB of device memory for a group's columns at k = 16.  The widest circuit of the product surface (Poseidon:
+// 4 advice, 1 instance and 2 product columns, extended domain 2^19 = 16 MiB a column) holds per proof 112 MiB of
+// extended columns, 16 MiB of quotient and 28 MiB of Lagrange and coefficient columns; the extended transforms' second
+// buffer adds up to 5 x 16 MiB per proof: 16 proofs come to 3.7 GiB.
+// The budget is k = 16's: a group's columns double with every step of k, so above PROVE_GROUP_K the prover halves the group
+// per step (create_proofs: 8 proofs at k = 17, 4 at 18, one from k = 20), and the 4 GiB hold at every k.
+constexpr size_t PROVE_GROUP = 16;
+constexpr uint32_t PROVE_GROUP_K = 16;
 }  // namespace h2

@@ -67,6 +67,7 @@ SYMBOLS = {
     "h2_fixed_base_mul": (_I, [_I, _P, _Z, _P, _P]),
     "h2_setup": (_I, [_U32, _P, _P, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_generate_proof": (_I, [_P, _Z, ctypes.c_char_p, _I, _P, _P, _P, _Z, ctypes.POINTER(_Z)]),
+    "h2_generate_proofs": (_I, [_P, _Z, _Z, _P, _I, _P, _P, _P, _Z, _P, ctypes.POINTER(_Z)]),
     "h2_verify_proof": (_I, [_P, _Z, _P, _Z, ctypes.c_char_p, _I, ctypes.POINTER(_I)]),
     "h2_verify_proofs": (_I, [_P, _Z, _Z, _P, _P, _P, _I, _P, _P, _P, ctypes.POINTER(_I)]),
     "h2_simulate": (_I, [ctypes.c_char_p, _I, _P, _Z, ctypes.POINTER(_Z)]),
@@ -75,6 +76,9 @@ SYMBOLS = {
     "h2_key_cache": (_I, [_I]),
     "h2_profile_enable": (_I, [_I]),
     "h2_profile_read": (_I, [ctypes.POINTER(Profile)]),
+    # the two hooks of include/h2hip_selftest.h that go with h2_generate_proofs: a host detects the batch prover by these names
+    "h2_selftest_commit_launches": (_U64, []),
+    "h2_selftest_set_prove_group": (_I, [_Z]),
 }
 # include/h2hip_selftest.h (host instantiation of the device templates; not a compute path)
 SELFTEST_SYMBOLS = {

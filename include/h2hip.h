@@ -258,6 +258,20 @@ typedef void (*h2_rng_fill_t)(void* ctx, uint8_t* out, size_t n);
 int h2_setup(uint32_t k, h2_rng_fill_t rng, void* rng_ctx, uint8_t* out, size_t cap, size_t* out_len);
 int h2_generate_proof(const uint8_t* params, size_t params_len, const char* json, int circuit, h2_rng_fill_t rng,
                       void* rng_ctx, uint8_t* out, size_t cap, size_t* out_len);
+/* `count` proofs of ONE circuit under ONE params blob, each from its own JSON input, made in lockstep: every commit
+ * phase, transform and read-back is issued once for the batch (in groups of 16 proofs up to k = 16, half as many with every step of k above
+ * that), not once per proof.  Proof i is
+ * byte for byte what h2_generate_proof(params, jsons[i], circuit, rng, rng_ctxs[i]) returns: proof i draws only through
+ * rng(rng_ctxs[i], ...), in h2_generate_proof's order.  rng = NULL: the OS.  rng_ctxs = NULL: every proof passes a NULL
+ * context (the order of draws BETWEEN proofs is then unspecified; within a proof it is h2_generate_proof's).
+ * The proofs are written back to back into `out`; proof_lens[i] (count entries, required when count > 0) receives each
+ * length, *out_len the total (also when the call returns H2_EINVAL because cap is too small).  All or nothing: every
+ * JSON is parsed and every witness synthesised before anything is enqueued; a bad item gives the status h2_generate_proof
+ * gives for it and `out` is not written.  count = 0: H2_OK, *out_len = 0.  h2_version() is unchanged by this entry
+ * point: a caller detects it by the symbol. */
+int h2_generate_proofs(const uint8_t* params, size_t params_len, size_t count, const char* const* jsons, int circuit,
+                       h2_rng_fill_t rng, void* const* rng_ctxs, uint8_t* out, size_t cap, size_t* proof_lens,
+                       size_t* out_len);
 int h2_verify_proof(const uint8_t* params, size_t params_len, const uint8_t* proof, size_t proof_len,
                     const char* json, int circuit, int* ok);
 /* `count` proofs of ONE circuit under ONE params blob, each with its own JSON input (upstream halo2's

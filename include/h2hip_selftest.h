@@ -87,6 +87,11 @@ int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* mo
 uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */
 int h2_selftest_set_shard_min_rows(size_t rows);
+/* commit phases (MSM launch sequences with their read-back) the C++ prover and keygen have started since the library was
+ * loaded: h2_generate_proofs makes as many for a group of proofs as h2_generate_proof makes for one */
+uint64_t h2_selftest_commit_launches(void);
+/* proofs that h2_generate_proofs runs in lockstep; a larger batch is cut into groups of this many (0 restores the default) */
+int h2_selftest_set_prove_group(size_t proofs);
 int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, size_t cap, size_t* out_len);
 /* the 29-bit working-form product (h2_field29.hpp) instantiated on the host, no GPU: field 0 bn254 Fq, 1 bn254 Fr,
  * 2 pasta Fp, 3 pasta Fq; in = four operands a, b, c, d of 9 signed 29-bit-radix limbs; op 0: fe29_mul(a, b),

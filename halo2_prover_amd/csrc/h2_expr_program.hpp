@@ -168,10 +168,11 @@ struct ExprProgram {
   }
 };
 
-// expr_kernel over en rows: the column pointers and row masks, the constant table (c, patched for the proof) in the
-// kernel's working form c 2^261, and the LDS of the slots beyond the registers -- checked against what one workgroup
-// may hold before anything is uploaded or launched.  create_proof and the test hook h2_selftest_expr_run both launch
-// the quotient program through here.
+// expr_kernel over en rows of `count` proofs (grid.y = proof): one program and one set of row masks; proof p's column
+// pointers at ptrs[p masks.size() ...], its constants (c, patched for the proof) at consts[p nconsts ...], uploaded in the
+// kernel's working form c 2^261, its result at out + p en; the LDS of the slots beyond the registers is checked against
+// what one workgroup may hold before anything is uploaded or launched.  create_proofs and the test hook
+// h2_selftest_expr_run (count = 1) both launch the quotient program through here.
 inline size_t expr_lds_bytes(const ExprProgram& X) {
   const size_t lds_slots = X.nslots > (uint32_t)pk::EXPR_REG_SLOTS ? X.nslots - pk::EXPR_REG_SLOTS : 1;
   const size_t lds = lds_slots * 9 * pk::EXPR_BLOCK * 4;
@@ -179,8 +180,10 @@ inline size_t expr_lds_bytes(const ExprProgram& X) {
   return lds;
 }
 inline void expr_launch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, const std::vector<const U128*>& ptrs,
-                 const std::vector<uint32_t>& masks, std::vector<Fr> consts, Col out, uint32_t step, uint32_t en) {
+                        const std::vector<uint32_t>& masks, std::vector<Fr> consts, size_t nconsts, Col out, uint32_t step,
+                        uint32_t en, size_t count) {
   const size_t lds = expr_lds_bytes(X);
+  if (ptrs.size() != count * masks.size() || consts.size() != count * nconsts) fail(H2_EINVAL, "expr_launch: table sizes");
   const U128* const* d_ptrs = (const U128* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
   const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
   for (auto& c : consts)
@@ -189,30 +192,10 @@ inline void expr_launch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, 
   if (lds > 64 * 1024)                                // past 64 KiB: raised, as the MSM and NTT kernels raise theirs
     hip_ok(hipFuncSetAttribute((const void*)pk::expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
            "hipFuncSetAttribute(expr_kernel)");
-  hipLaunchKernelGGL(pk::expr_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK), dim3(pk::EXPR_BLOCK), lds, d.s, d_code,
-                     (uint32_t)X.code.size(), d_ptrs, d_masks, d_consts, out, step, en);
+  hipLaunchKernelGGL(pk::expr_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK, (unsigned)count), dim3(pk::EXPR_BLOCK), lds,
+                     d.s, d_code, (uint32_t)X.code.size(), d_ptrs, (uint32_t)masks.size(), d_masks, d_consts, (uint32_t)nconsts, out,
+                     step, en);
   hip_ok(hipGetLastError(), "expr_kernel");
-}
-
-// expr_batch_kernel over en rows of `count` proofs (grid.y = proof): proof p's column pointers at ptrs[p masks.size() ...],
-// its constants at consts[p nconsts ...], its result at out + p en; the row masks are the program's, shared
-inline void expr_launch_batch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, const std::vector<const U128*>& ptrs,
-                              const std::vector<uint32_t>& masks, std::vector<Fr> consts, size_t nconsts, Col out, uint32_t step,
-                              uint32_t en, size_t count) {
-  const size_t lds = expr_lds_bytes(X);
-  if (ptrs.size() != count * masks.size() || consts.size() != count * nconsts) fail(H2_EINVAL, "expr_launch_batch: table sizes");
-  const U128* const* d_ptrs = (const U128* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
-  const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
-  for (auto& c : consts)
-    for (int t = 0; t < 5; t++) c = c + c;            // c 2^256 -> c 2^261, as expr_launch uploads them
-  Col d_consts = d.upload_frs(consts);
-  if (lds > 64 * 1024)
-    hip_ok(hipFuncSetAttribute((const void*)pk::expr_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-           "hipFuncSetAttribute(expr_batch_kernel)");
-  hipLaunchKernelGGL(pk::expr_batch_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK, (unsigned)count), dim3(pk::EXPR_BLOCK),
-                     lds, d.s, d_code, (uint32_t)X.code.size(), d_ptrs, (uint32_t)masks.size(), d_masks, d_consts, (uint32_t)nconsts,
-                     out, step, en);
-  hip_ok(hipGetLastError(), "expr_batch_kernel");
 }
 
 // a caller's expression DAG (the test hooks h2_selftest_host what = 7 and h2_selftest_expr_run): u32 node count, u32

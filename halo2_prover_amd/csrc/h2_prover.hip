@@ -15,7 +15,6 @@
 // scalars from the caller's RNG in the reference's order, so that under the same RNG stream the proof bytes are the
 // reference's.
 #include "h2_prove.hpp"
-#include "h2_prove_batch.hpp"
 #include "h2_verify.hpp"
 
 using namespace h2;
@@ -210,10 +209,12 @@ int h2_generate_proof(const uint8_t* params, size_t params_len, const char* json
     std::unique_ptr<ProvingKey> owner;
     ProvingKey& K = key_for(P, job.index, ctx, owner);
     trace.mark("key");
-    Rng rng{rng_fn, rng_ctx};
-    const std::vector<uint8_t> proof = create_proof(K, *job.circuit, job.public_input, rng);
+    // a batch of one: the witness is synthesised and checked before a random byte is drawn or anything is enqueued
+    std::vector<Witness> items;
+    items.push_back({&job.public_input, synthesize_checked(*job.circuit, job.public_input, K.dom->n, K.bf), Rng{rng_fn, rng_ctx}});
+    const std::vector<std::vector<uint8_t>> proofs = create_proofs(K, items, trace);
     trace.mark("create_proof");
-    return emit(proof, out, cap, out_len);
+    return emit(proofs[0], out, cap, out_len);
   });
 }
 
@@ -350,7 +351,7 @@ uint64_t h2_selftest_sharded_commits(void) {
   return g_sharded_commits;
 }
 
-// commit_begin calls since the library was loaded: a lockstep batch makes as many as one proof, a loop N times as many
+// commit_begin calls since the library was loaded: a lockstep batch makes as many as one proof, N calls N times as many
 uint64_t h2_selftest_commit_launches(void) {
   std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   return g_commit_launches;
@@ -517,7 +518,7 @@ int h2_selftest_expr_run(const uint8_t* dag, size_t dag_len, const uint64_t* col
       off += (size_t)1 << log_len[c];
     }
     Col d_out = d.col(en);
-    expr_launch(d, X, d_code, ptrs, masks, X.consts, d_out, step, en);
+    expr_launch(d, X, d_code, ptrs, masks, X.consts, X.consts.size(), d_out, step, en, 1);
     hip_ok(hipMemcpyAsync(out, d_out, (size_t)en * 32, hipMemcpyDeviceToHost, d.s), "hipMemcpyAsync(D2H)");
     d.sync();
     return H2_OK;

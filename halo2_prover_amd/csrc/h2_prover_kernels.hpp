@@ -3,17 +3,22 @@
 // These are the pieces of halo2_proofs::plonk::create_proof that sit BETWEEN the MSM / NTT calls (SURVEY.md App. A.4,
 // A.7; reached from /root/reference/circuits/src/utils.rs:83-91,105-120): witness columns, the permutation grand
 // product, the quotient numerator, evaluations at the challenge point, the opening combinations.  prover.py runs
-// them as ~600 generic pointwise launches; here each is ONE launch:
+// them as ~600 generic pointwise launches; here each is ONE launch for every proof of a lockstep group (h2_prove.hpp):
 //   * expr_kernel            the whole quotient numerator -- every gate, the permutation argument, the y-fold and the
 //                            division by the vanishing polynomial -- as a straight-line program interpreted per row
 //                            of the extended coset (operands: extended columns with rotations, constants, LDS slots)
 //   * perm_ratio_kernel      prod (v + beta delta^j w^i + gamma) / prod (v + beta sigma_j + gamma) with one inversion
 //                            per 4 rows (Montgomery's trick)
-//   * poly_eval_kernels      all evaluations of a proof (different polynomials at different points) in two launches
-//   * lincomb_kernel         sum_j c_j a_j, up to 24 columns per launch
+//   * poly_eval_kernels      all evaluations of the group (different polynomials at different points) in two launches
+//   * lincomb_batch_kernel   out_j = sum_t c_t a_t for a list of jobs (lincomb_kernel, up to 24 columns of one sum by
+//                            value, serves setup, keygen and the verifiers)
 //   * coset_extend / coset_shrink   the zero-extension and the zeta^i scaling around the extended-domain NTTs
+//   * scale_kernel, sub_prefix_kernel   a column times a constant; a remainder's low coefficients subtracted
 // All HBM-bound elementwise work except expr_kernel (a few hundred field products per row).
-// The *_batch_kernel forms serve N proofs in lockstep (h2_prove_batch.hpp): grid.y = job or proof, arguments in HBM.
+// The prover's kernels take grid.y = job or proof and read what differs between jobs -- a handful of pointers and
+// constants -- from a table in HBM: the prover uploads a phase's tables once (Proving::Steps), which makes one proof cost
+// what arguments passed by value would, and N proofs one launch.  Field results are canonical, so a proof's bytes do
+// not depend on how many jobs share its launches.
 #pragma once
 #include "h2_field.hpp"
 #include "h2_field29.hpp"
@@ -83,14 +88,19 @@ coset_extend_kernel(const U128* __restrict__ in, size_t in_stride, U128* __restr
   }
   fe_store<FR>(dst + 2 * (size_t)i, v);
 }
-// a[i] *= zinv^i in place for i < count (after the inverse extended NTT; only the n (d-1) kept coefficients)
-static __global__ void __launch_bounds__(256) coset_shrink_kernel(U128* __restrict__ a, uint32_t count, F zi1, F zi2) {
+// grid.y = proof: out[p][i] = in[p][i] * zinv^i for i < count (after the inverse extended NTT) -- the n (d-1) kept
+// coefficients of every proof's quotient, written compactly (out_stride = count) from the extended columns (in_stride = en)
+static __global__ void __launch_bounds__(256)
+coset_shrink_kernel(const U128* __restrict__ in, size_t in_stride, U128* __restrict__ out, size_t out_stride, uint32_t count,
+                    F zi1, F zi2) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
+  const U128* src = in + 2 * (in_stride * blockIdx.y + i);
+  U128* dst = out + 2 * (out_stride * blockIdx.y + i);
+  F v = fe_load<FR>(src);
   const uint32_t r = i % 3;
-  if (r == 0) return;
-  F v = fe_load<FR>(a + 2 * (size_t)i);
-  fe_store<FR>(a + 2 * (size_t)i, fe_mul(v, r == 1 ? zi1 : zi2));
+  if (r != 0) v = fe_mul(v, r == 1 ? zi1 : zi2);
+  fe_store<FR>(dst, v);
 }
 
 // ---- permutation grand product: ratio[i] = prod_j (v_j + beta delta^j w^i + gamma) / prod_j (v_j + beta sigma_j + gamma)
@@ -103,13 +113,12 @@ struct PermArgs {
   F beta, gamma;
   int ncols;
 };
-constexpr int PERM_MAX_SETS = 4;
-struct PermBatch {
-  PermArgs set[PERM_MAX_SETS];
-};
-// one ratio column: PERM_RUN rows per thread
-__device__ __forceinline__ void perm_ratio_rows(const PermArgs& A, const U128* __restrict__ omega_col, U128* __restrict__ ratio,
-                                                uint32_t n) {
+// grid.y = (proof, set), one PermArgs per ratio column in HBM (the columns of a proof only share beta and gamma); ratio:
+// one column per PermArgs; PERM_RUN rows per thread
+static __global__ void __launch_bounds__(256)
+perm_ratio_kernel(const PermArgs* __restrict__ args, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base, uint32_t n) {
+  const PermArgs& A = args[blockIdx.y];
+  U128* __restrict__ ratio = ratio_base + 2 * (size_t)n * blockIdx.y;
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lo = t * PERM_RUN;
   if (lo >= n) return;
@@ -141,29 +150,28 @@ __device__ __forceinline__ void perm_ratio_rows(const PermArgs& A, const U128* _
     inv = fe29_mul(inv, den[k]);
   }
 }
-// grid.y = permutation set (the sets only share beta and gamma: all of them in one launch); ratio: one column per set
-static __global__ void __launch_bounds__(256)
-perm_ratio_kernel(PermBatch B, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base, uint32_t n) {
-  perm_ratio_rows(B.set[blockIdx.y], omega_col, ratio_base + 2 * (size_t)n * blockIdx.y, n);
-}
-// the batch form (h2_prove_batch.hpp): grid.y = (proof, set), one PermArgs per ratio column in HBM
-static __global__ void __launch_bounds__(256)
-perm_ratio_batch_kernel(const PermArgs* __restrict__ args, const U128* __restrict__ omega_col, U128* __restrict__ ratio_base,
-                        uint32_t n) {
-  perm_ratio_rows(args[blockIdx.y], omega_col, ratio_base + 2 * (size_t)n * blockIdx.y, n);
+// grid.y = job: a[i] *= c for i < n
+struct ScaleJob {
+  U128* a;
+  F c;
+};
+static __global__ void __launch_bounds__(256) scale_kernel(const ScaleJob* __restrict__ jobs, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ScaleJob job = jobs[blockIdx.y];
+  fe_store<FR>(job.a + 2 * (size_t)i, fe_mul(fe_load<FR>(job.a + 2 * (size_t)i), job.c));
 }
 
-// a[i] = a[i] * c for rows [lo, hi)
-static __global__ void __launch_bounds__(256) scale_range_kernel(U128* __restrict__ a, uint32_t lo, uint32_t hi, F c) {
-  const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= hi) return;
-  fe_store<FR>(a + 2 * (size_t)i, fe_mul(fe_load<FR>(a + 2 * (size_t)i), c));
-}
-// a[i] -= v[i] for i < count
-static __global__ void sub_prefix_kernel(U128* __restrict__ a, const U128* __restrict__ v, uint32_t count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  fe_store<FR>(a + 2 * (size_t)i, fe_sub(fe_load<FR>(a + 2 * (size_t)i), fe_load<FR>(v + 2 * (size_t)i)));
+// grid.y = job: a[i] -= v[offset + i] for i < count (the low coefficients of a remainder; `v` is one table for the launch)
+struct SubPrefixJob {
+  U128* a;
+  uint32_t offset, count;
+};
+static __global__ void __launch_bounds__(64) sub_prefix_kernel(const SubPrefixJob* __restrict__ jobs, const U128* __restrict__ v) {
+  const SubPrefixJob job = jobs[blockIdx.y];
+  for (uint32_t i = threadIdx.x; i < job.count; i += blockDim.x)
+    fe_store<FR>(job.a + 2 * (size_t)i,
+                 fe_sub(fe_load<FR>(job.a + 2 * (size_t)i), fe_load<FR>(v + 2 * ((size_t)job.offset + i))));
 }
 
 // ---- out[i] = sum_j c_j a_j[i] ---------------------------------------------------------------------------------
@@ -184,51 +192,6 @@ lincomb_kernel(LincombArgs A, U128* __restrict__ out, uint32_t n, int accumulate
     acc = fe_add(acc, (j == 0 && A.unit_first) ? v : fe_mul(v, A.c[j]));
   }
   fe_store<FR>(out + 2 * (size_t)i, acc);
-}
-
-// ---- the batch forms (h2_prove_batch.hpp: N proofs of one circuit in lockstep) -------------------------------------------
-// They compute what their single forms above compute, element for element (field results are canonical, so the bytes
-// are the same); what the single forms take by value -- a handful of pointers and constants -- comes from a table in
-// HBM here, and grid.y picks the job or the proof.
-
-// grid.y = proof: out[p][i] = in[p][i] * zinv^i for i < count -- the kept coefficients of every proof's quotient, written
-// compactly (out_stride = count) from the extended columns (in_stride = en)
-static __global__ void __launch_bounds__(256)
-coset_shrink_batch_kernel(const U128* __restrict__ in, size_t in_stride, U128* __restrict__ out, size_t out_stride,
-                          uint32_t count, F zi1, F zi2) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const U128* src = in + 2 * (in_stride * blockIdx.y + i);
-  U128* dst = out + 2 * (out_stride * blockIdx.y + i);
-  F v = fe_load<FR>(src);
-  const uint32_t r = i % 3;
-  if (r != 0) v = fe_mul(v, r == 1 ? zi1 : zi2);
-  fe_store<FR>(dst, v);
-}
-
-// grid.y = job: a[i] *= c for i < n
-struct ScaleJob {
-  U128* a;
-  F c;
-};
-static __global__ void __launch_bounds__(256) scale_batch_kernel(const ScaleJob* __restrict__ jobs, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ScaleJob job = jobs[blockIdx.y];
-  fe_store<FR>(job.a + 2 * (size_t)i, fe_mul(fe_load<FR>(job.a + 2 * (size_t)i), job.c));
-}
-
-// grid.y = job: a[i] -= v[offset + i] for i < count (the low coefficients of a remainder; `v` is one table for the batch)
-struct SubPrefixJob {
-  U128* a;
-  uint32_t offset, count;
-};
-static __global__ void __launch_bounds__(64)
-sub_prefix_batch_kernel(const SubPrefixJob* __restrict__ jobs, const U128* __restrict__ v) {
-  const SubPrefixJob job = jobs[blockIdx.y];
-  for (uint32_t i = threadIdx.x; i < job.count; i += blockDim.x)
-    fe_store<FR>(job.a + 2 * (size_t)i,
-                 fe_sub(fe_load<FR>(job.a + 2 * (size_t)i), fe_load<FR>(v + 2 * ((size_t)job.offset + i))));
 }
 
 // grid.y = job: out[i] = sum_t c_t a_t[i] over the job's `count` terms, which start at terms[first].  `out` may be one
@@ -325,9 +288,15 @@ constexpr int EXPR_COLUMN_BOUND = 16, EXPR_VALUE_BOUND = 32;
 //   * the last result goes back to the API form (one product) on its way out.
 // Operands that do not depend on the program's own results -- columns and constants -- are fetched TWO instructions
 // ahead (a global load is 0.5-2 us, an instruction 0.1-0.5).  LDS: 36 bytes per slot beyond the register slots and row.
-__device__ __forceinline__ void expr_rows(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols,
-                                          const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts,
-                                          U128* __restrict__ out, uint32_t step, uint32_t en) {
+// grid.y = proof.  One program and one set of row masks; proof p reads its column pointers at cols + p ncols, its
+// constants (y, beta, gamma, beta delta^j differ) at consts + p nconsts and writes the extended column out + p en
+static __global__ void __launch_bounds__(EXPR_BLOCK)
+expr_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ all_cols, uint32_t ncols,
+            const uint32_t* __restrict__ col_mask, const U128* __restrict__ all_consts, uint32_t nconsts,
+            U128* __restrict__ all_out, uint32_t step, uint32_t en) {
+  const U128* const* __restrict__ cols = all_cols + (size_t)blockIdx.y * ncols;
+  const U128* __restrict__ consts = all_consts + 2 * (size_t)blockIdx.y * nconsts;
+  U128* __restrict__ out = all_out + 2 * (size_t)blockIdx.y * en;
   using W = Fe29<FR>;
   extern __shared__ int32_t slots[];      // [slot][limb][thread]
   const uint32_t tid = threadIdx.x;
@@ -395,22 +364,6 @@ __device__ __forceinline__ void expr_rows(const XInstr* __restrict__ prog, uint3
     if (k + 1 < ninstr) run(k + 1, i1, pa1, pb1);
   }
   if (i < en) fe_store<FR>(out + 2 * (size_t)i, fe29_to_api(r));     // a domain smaller than one block: the spare lanes computed on wrapped rows
-}
-static __global__ void __launch_bounds__(EXPR_BLOCK)
-expr_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols,
-            const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts, U128* __restrict__ out, uint32_t step,
-            uint32_t en) {
-  expr_rows(prog, ninstr, cols, col_mask, consts, out, step, en);
-}
-// the batch form (h2_prove_batch.hpp): grid.y = proof.  One program and one set of row masks; proof p reads its column
-// pointers at cols + p ncols, its constants (y, beta, gamma, beta delta^j differ) at consts + p nconsts and writes the
-// extended column out + p en
-static __global__ void __launch_bounds__(EXPR_BLOCK)
-expr_batch_kernel(const XInstr* __restrict__ prog, uint32_t ninstr, const U128* const* __restrict__ cols, uint32_t ncols,
-                  const uint32_t* __restrict__ col_mask, const U128* __restrict__ consts, uint32_t nconsts,
-                  U128* __restrict__ out, uint32_t step, uint32_t en) {
-  const size_t p = blockIdx.y;
-  expr_rows(prog, ninstr, cols + p * ncols, col_mask, consts + 2 * p * nconsts, out + 2 * p * en, step, en);
 }
 
 }  // namespace pk

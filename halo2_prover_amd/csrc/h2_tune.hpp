@@ -16,7 +16,7 @@ inline int tune_int(const char* name, int fallback) {
   return fallback;
 }
 
-// Proofs that h2_generate_proofs runs in lockstep (h2_prove_batch.hpp); a larger batch is cut into groups of this many.
+// Proofs that h2_generate_proofs runs in lockstep (h2_prove.hpp); a larger batch is cut into groups of this many.
 // Budget: 4 GiB of device memory for a group's columns at k = 16.  The widest circuit of the product surface (Poseidon:
 // 4 advice, 1 instance and 2 product columns, extended domain 2^19 = 16 MiB a column) holds per proof 112 MiB of
 // extended columns, 16 MiB of quotient and 28 MiB of Lagrange and coefficient columns; the extended transforms' second

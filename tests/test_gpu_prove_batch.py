@@ -1,25 +1,29 @@
 """h2_generate_proofs on the GPU, through ctypes as a Rust or JS host would call it.
 
-The judge of every batch is the single prover, itself pinned to the reference's recorded proofs: under the same RNG
-stream proof i of a batch must be, byte for byte, what h2_generate_proof returns for input i.  Exact comparison
-throughout.  The commit-phase counter tells a lockstep batch from a loop over the single prover, which would pass every
-byte comparison.
+The judge of every batch is the CPU oracle (oracle/halo2_ref.py create_proof, itself pinned to the reference's recorded
+proofs by test_proof_pins.py): tests/golden/prove_batch_pins.json, written by tests/golden/make_prove_batch_pins.py
+without the GPU library, holds the inputs and the sha256 of the oracle's proof of each under its RNG stream, and proof i
+of a batch must hash to pin i.  h2_generate_proof is the same prover with a batch of one, so the second comparison --
+proof i of a batch is, byte for byte, what the one-witness call returns for input i -- shows that a proof does not
+depend on its neighbours or its group.  Exact comparison throughout.  The commit-phase counter tells a lockstep batch
+from N one-witness calls, which would pass every byte comparison.
 """
 import ctypes
 import hashlib
-import random
+import json
+import os
 import subprocess
 import sys
 
 import pytest
 
 import pyref as R
-from test_capi_product import (ARITH_INPUT, COLLATZ_INPUT, POSEIDON_INPUT, PROOF_SHA256, ROOT, Stream, c_prove, c_setup, c_verify,
-                               golden)
-from test_gpu_verify_batch import c_verify_batch, orbit, simulate
+from test_capi_product import (ARITH_INPUT, COLLATZ_INPUT, GOLDEN, POSEIDON_INPUT, PROOF_SHA256, ROOT, Stream, c_prove, c_setup,
+                               c_verify, golden)
+from test_gpu_verify_batch import c_verify_batch, simulate
 
 pytestmark = pytest.mark.gpu
-SIZES = [1, 2, 3, 9, 17]          # 9 passes SCAN_MAX_JOBS = 8 and PERM_MAX_SETS = 4, 17 passes MSM_MAX_MULTI = 16
+SIZES = [1, 2, 3, 9, 17]          # 9 passes SCAN_MAX_JOBS = 8, 17 passes MSM_MAX_MULTI = 16
 
 
 @pytest.fixture(scope="module")
@@ -63,8 +67,12 @@ def c_prove_batch(L, params, jsons, idx, rng=None, ctxs=None, cap=None, fill=0xA
     return rc, proofs, list(lens)[:n], total.value, False
 
 
+def sha(proofs):
+    return [hashlib.sha256(p).hexdigest() for p in proofs]
+
+
 def prove_both_ways(L, params, jsons, idx, first=8):
-    """the batch under per-proof streams, and the single prover on every item under the same streams"""
+    """the batch under per-proof streams, and the one-witness call on every item under the same streams"""
     cb, ctxs = streams_rng(len(jsons), first)
     rc, proofs, lens, total, _ = c_prove_batch(L, params, jsons, idx, cb, ctxs)
     assert rc == 0, (rc, L.h2_last_device_error())
@@ -75,27 +83,22 @@ def prove_both_ways(L, params, jsons, idx, first=8):
 
 @pytest.fixture(scope="module")
 def inputs(h2, lib):
-    """per circuit: (params, circuit index, 17 distinct inputs, the recorded one first), generated as
-    test_gpu_verify_batch.pools generates its own"""
-    rnd = random.Random(64)
-    out = {}
-    items = [ARITH_INPUT]
-    while len(items) < 17:
-        x, y, c = rnd.randrange(1 << 12), rnd.randrange(1 << 12), rnd.randrange(1 << 30)
-        items.append('{"x":%d,"y":%d,"constant":%d,"z":%d}' % (x, y, c, x * x * y * y + c))
-    out["arithmetic"] = (golden("params_k4.bin"), 1, items)
-    items = [POSEIDON_INPUT]
-    while len(items) < 17:
-        msg = (rnd.randrange(1 << 64), rnd.randrange(1 << 64))
-        items.append('{"x":[%d,%d],"output":"%s"}' % (msg[0], msg[1], simulate(lib, '{"x":[%d,%d]}' % msg, 2)))
-    out["poseidon"] = (golden("params_k6.bin"), 2, items)
-    items, start = [COLLATZ_INPUT], 2
-    while len(items) < 17:
-        start += 1
-        seq = orbit(start)
-        if len(seq) <= 32:
-            items.append('{"x":%s}' % str(seq).replace(" ", ""))
-    out["collatz"] = (c_setup(lib, 10, Stream(0)), 0, items)          # the recorded Collatz proof was made under this SRS
+    """per circuit: (params, circuit index, 17 inputs -- the recorded one first --, the oracle's proof hashes), from
+    tests/golden/prove_batch_pins.json; "poseidon_k11": the hashes of the first three Poseidon inputs at k = 11.
+    Collatz items 0 and 7 are both the orbit of 9 (the recorded input, and again among the orbits of 3, 4, ...): one
+    witness under two RNG streams, so 17 different proofs all the same."""
+    pins = json.load(open(os.path.join(GOLDEN, "prove_batch_pins.json")))
+    first = {"arithmetic": ARITH_INPUT, "poseidon": POSEIDON_INPUT, "collatz": COLLATZ_INPUT}
+    for name, js in first.items():
+        assert pins[name]["inputs"][0] == js and len(pins[name]["inputs"]) == 17 == len(set(pins[name]["proof_sha256"]))
+    for js in pins["poseidon"]["inputs"]:                             # the stored outputs are what the library computes
+        item = json.loads(js)
+        assert simulate(lib, '{"x":[%d,%d]}' % tuple(item["x"]), 2) == item["output"]
+    p10 = c_setup(lib, 10, Stream(0))                                 # the recorded Collatz proof was made under this SRS
+    out = {name: (params, idx, pins[name]["inputs"], pins[name]["proof_sha256"])
+           for name, params, idx in (("arithmetic", golden("params_k4.bin"), 1), ("poseidon", golden("params_k6.bin"), 2),
+                                     ("collatz", p10, 0))}
+    out["poseidon_k11"] = pins["poseidon_k11"]["proof_sha256"]
     return out
 
 
@@ -105,9 +108,10 @@ RECORDED = {"arithmetic": "proof_arithmetic_k4.bin", "poseidon": "proof_poseidon
 @pytest.mark.parametrize("name", ["arithmetic", "poseidon", "collatz"])
 @pytest.mark.parametrize("n", SIZES)
 def test_batch_bytes_equal_the_single_prover(h2, lib, inputs, name, n):
-    params, idx, items = inputs[name]
+    params, idx, items, pins = inputs[name]
     proofs, singles = prove_both_ways(lib, params, items[:n], idx)
     for i in range(n):
+        assert hashlib.sha256(proofs[i]).hexdigest() == pins[i], (name, n, i)        # the oracle's proof of item i
         assert proofs[i] == singles[i], (name, n, i)
     assert proofs[0] == golden(RECORDED[name])                       # item 0 draws from start 8: the reference's own bytes
 
@@ -118,17 +122,19 @@ def test_one_larger_size(h2, lib, inputs):
     params = c_setup(lib, 11, rng)
     first = rng.s.counter                                             # the stream continues behind the setup
     proofs, singles = prove_both_ways(lib, params, inputs["poseidon"][2][:3], 2, first)
+    assert sha(proofs) == inputs["poseidon_k11"]
     assert proofs == singles
     assert hashlib.sha256(proofs[0]).hexdigest() == PROOF_SHA256[("poseidon", 11)]
 
 
 def test_groups(h2, lib, inputs):
-    params, idx, items = inputs["arithmetic"]
+    params, idx, items, pins = inputs["arithmetic"]
     lib.h2_selftest_set_prove_group(4)
     try:
         proofs, singles = prove_both_ways(lib, params, items[:9], idx)
     finally:
         lib.h2_selftest_set_prove_group(0)
+    assert sha(proofs) == pins[:9]
     assert proofs == singles
 
 
@@ -136,7 +142,7 @@ def test_split_launch_respects_the_msm_column_limit(h2, lib, inputs):
     """Columns that bring their own bases cannot be cut into groups, so the products / random-polynomial split launch
     must fit one MSM launch sequence.  From k = 18 a sequence holds 8 columns; here the entries cap holds it to 4, so a
     Poseidon batch of 2 or 3 (6 or 9 such columns) has to take one launch per base, while the single proof (3) splits."""
-    params, idx, items = inputs["poseidon"]
+    params, idx, items, pins = inputs["poseidon"]
     geom = (ctypes.c_uint64 * 8)()
     assert lib.h2_selftest_msm_check(0, 64, 64, 1, 64, 0, geom) == 0
     windows = geom[1]
@@ -144,6 +150,7 @@ def test_split_launch_respects_the_msm_column_limit(h2, lib, inputs):
     try:
         for n in (2, 3):
             proofs, singles = prove_both_ways(lib, params, items[:n], idx)
+            assert sha(proofs) == pins[:n], n
             assert proofs == singles, n
         assert proofs[0] == golden("proof_poseidon_k6.bin")
     finally:
@@ -152,7 +159,7 @@ def test_split_launch_respects_the_msm_column_limit(h2, lib, inputs):
 
 @pytest.mark.parametrize("name", ["poseidon", "collatz"])
 def test_lockstep_not_a_loop(h2, lib, inputs, name):
-    params, idx, items = inputs[name]
+    params, idx, items, _ = inputs[name]
     c_prove(lib, params, items[0], idx, None)                         # the key is built and cached
     before = lib.h2_selftest_commit_launches()
     c_prove(lib, params, items[0], idx, None)
@@ -173,18 +180,19 @@ def test_lockstep_not_a_loop(h2, lib, inputs, name):
 
 
 def test_a_bad_witness_among_good_ones(h2, lib, inputs):
-    params, idx, items = inputs["arithmetic"]
+    params, idx, items, pins = inputs["arithmetic"]
     jsons = list(items[:5])
     x, y, c, z = [int(v.split(":")[1]) for v in jsons[2].strip("{}").split(",")]
     jsons[2] = '{"x":%d,"y":%d,"constant":%d,"z":%d}' % (x, y, c, z + 1)          # well-formed, false
     proofs, singles = prove_both_ways(lib, params, jsons, idx)
     assert proofs == singles
+    assert [h == w for h, w in zip(sha(proofs), pins)] == [True, True, False, True, True]     # the good ones are the oracle's
     assert c_verify_batch(lib, params, list(zip(proofs, jsons)), idx) == (0, [1, 1, 0, 1, 1], 0)
 
 
 @pytest.mark.parametrize("name", ["arithmetic", "poseidon", "collatz"])
 def test_os_randomness(h2, lib, inputs, name):
-    params, idx, items = inputs[name]
+    params, idx, items, _ = inputs[name]
     rc, proofs, lens, total, _ = c_prove_batch(lib, params, items[:16], idx)
     assert rc == 0 and total == sum(lens)
     assert len(set(lens)) == 1 and len(set(proofs)) == 16
@@ -192,7 +200,7 @@ def test_os_randomness(h2, lib, inputs, name):
 
 
 def test_statuses(h2, lib, inputs):
-    params, idx, items = inputs["arithmetic"]
+    params, idx, items, _ = inputs["arithmetic"]
     total = ctypes.c_size_t(77)
     assert lib.h2_generate_proofs(params, len(params), 0, None, idx, None, None, None, 0, None, ctypes.byref(total)) == 0
     assert total.value == 0
@@ -210,7 +218,7 @@ def test_statuses(h2, lib, inputs):
     assert lib.h2_generate_proofs(*args, js, idx, None, None, out, 1 << 14, lens2, None) == -1
     assert lib.h2_generate_proofs(*args, js, idx, None, None, out, 1 << 14, None, ctypes.byref(total)) == -1
     # circuit 7 is Poseidon, as for h2_generate_proof
-    p6, _, pos = inputs["poseidon"]
+    p6, _, pos, _ = inputs["poseidon"]
     cb, ctxs = streams_rng(1)
     rc, proofs, _, _, _ = c_prove_batch(lib, p6, pos[:1], 7, cb, ctxs)
     assert rc == 0 and proofs[0] == golden("proof_poseidon_k6.bin")
@@ -224,7 +232,7 @@ def c_prove_status(L, params, js, idx):
 
 
 _TWO_CONTEXTS = r'''
-import ctypes, os, sys
+import ctypes, json, os, sys
 ROOT = %r
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
@@ -232,15 +240,12 @@ import halo2_prover_amd as h2
 from halo2_prover_amd import api
 import test_capi_product as T
 import test_gpu_prove_batch as B
-import test_gpu_verify_batch as V
 api.init_devices([0, 0])                      # two contexts on the one GPU
 L = h2.load()
 assert L.h2_device_count() == 2
 L.h2_selftest_set_shard_min_rows(16)          # spread the k = 6 commitments (64 rows) over the contexts
 params = T.golden("params_k6.bin")
-jsons = [T.POSEIDON_INPUT]
-for msg in ((3, 4), (5, 6)):
-    jsons.append('{"x":[%%d,%%d],"output":"%%s"}' %% (msg[0], msg[1], V.simulate(L, '{"x":[%%d,%%d]}' %% msg, 2)))
+jsons = json.load(open(os.path.join(T.GOLDEN, "prove_batch_pins.json")))["poseidon"]["inputs"][:3]
 before = L.h2_selftest_sharded_commits()
 cb, ctxs = B.streams_rng(3)
 rc, proofs, lens, total, _ = B.c_prove_batch(L, params, jsons, 2, cb, ctxs)
@@ -252,23 +257,21 @@ print("two contexts ok " + " ".join(p.hex() for p in proofs))
 
 
 def test_two_contexts(h2, lib, inputs):
-    """the batch's commit phases spread over two contexts by point range: the bytes of the one-context single proofs"""
+    """the batch's commit phases spread over two contexts by point range: the bytes of the one-context one-witness calls"""
     r = subprocess.run([sys.executable, "-c", _TWO_CONTEXTS % ROOT], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "two contexts ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
     got = [bytes.fromhex(h) for h in r.stdout.split("two contexts ok ")[1].split()]
-    params = golden("params_k6.bin")
-    jsons = [POSEIDON_INPUT]
-    for msg in ((3, 4), (5, 6)):
-        jsons.append('{"x":[%d,%d],"output":"%s"}' % (msg[0], msg[1], simulate(lib, '{"x":[%d,%d]}' % msg, 2)))
-    singles = [c_prove(lib, params, js, 2, Stream(start_of(i))) for i, js in enumerate(jsons)]
+    params, idx, items, pins = inputs["poseidon"]
+    singles = [c_prove(lib, params, js, idx, Stream(start_of(i))) for i, js in enumerate(items[:3])]
+    assert sha(got) == pins[:3]
     assert got == singles
 
 
 def test_python_wrapper(h2, lib, inputs):
-    params, idx, items = inputs["poseidon"]
+    params, idx, items, pins = inputs["poseidon"]
     cb, ctxs = streams_rng(3)
     rc, proofs, _, _, _ = c_prove_batch(lib, params, items[:3], idx, cb, ctxs)
-    assert rc == 0
+    assert rc == 0 and sha(proofs) == pins[:3]
     rngs = [R.SurveyStream(start=start_of(i)).fill for i in range(3)]
     assert h2.generate_proofs(params, items[:3], idx, rngs) == proofs
     assert h2.generate_proofs(params, [], idx) == []

@@ -1,15 +1,15 @@
-"""h2_generate_proofs against a loop of h2_generate_proof calls: arithmetic at k = 4, Poseidon at k = 6, 11 and 16, Collatz
+"""h2_generate_proofs against N one-witness calls of h2_generate_proof: arithmetic at k = 4, Poseidon at k = 6, 11 and 16, Collatz
 (SHPLONK) at k = 10, N = 1 .. 32 proofs.  Writes profiles/prove_batch_times.json (or --out FILE) and prints the table of
 DESIGN.md section 7.3.
 
-One process, key cached.  Per (circuit, N): milliseconds for the loop of N single calls (that code is unchanged by the
-batch prover, so it is the baseline) and for one batch call, each the best of five with the spread (max - min) of the
-five; the proofs of every timed call of either route are compared byte for byte -- proof i draws from its own recorded
-stream in both -- and item 0 with the recorded proof's hash.  The streams reach the library through a Python callback,
+One process, key cached.  Per (circuit, N): milliseconds for the loop of N one-witness calls (the same prover with a
+batch of one: what a host that does not batch pays) and for one batch call, each the best of five with the spread
+(max - min) of the five; the proofs of every timed call of either route are compared byte for byte -- proof i draws from
+its own recorded stream in both -- and item 0 with the recorded proof's hash.  The streams reach the library through a Python callback,
 which costs both routes the same per proof; the `os` columns repeat the timing with OS randomness (no callback, no
 byte comparison), and one more batch call per row runs under H2_TRACE for its phase marks.
 
-Exits non-zero when a comparison fails, when a batch of one is slower than the single call by more than the loop's
+Exits non-zero when a comparison fails, when a batch of one is slower than the one-witness call by more than the loop's
 spread, or when at N = 16 the batch is not below the loop by more than that spread.  No ratio is fixed in advance.
 """
 import argparse

@@ -1101,7 +1101,8 @@ extern "C" int h2_selftest_msm_guard(int on) {
   std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   h2::g_msm_guard = on != 0;
   h2::g_msm_guard_poke = on == 2;
-  h2::g_sort2_pack = on != 3;            // guard(3): the two-level sort keeps the low key bits in the side array
+  h2::g_sort2_pack = on != 3;            // guard(3): the unpacked forms -- the two-level sort keeps the low key bits in the
+                                         // side array, the staged scatter a reference and a 16-bit bucket per entry
   h2::g_guard_launches = h2::g_guard_violations = 0;
   h2::g_guard_first.clear();
   return H2_OK;
@@ -1140,6 +1141,22 @@ extern "C" int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t
     g_h2.last_error = std::string("msm launch geometry: ") + broken;
     return H2_EINVAL;
   }
+  return H2_OK;
+}
+// host only: the sort front of a launch of m columns of n scalars against n_bases bases, laid out as msm_device_run
+// lays it out (`pack` = 0: with the unpacked forms, as under h2_selftest_msm_guard(3)); out: include/h2hip_selftest.h
+extern "C" int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !out || n == 0 || m == 0 || n > n_bases || n_bases >= (1ull << 31)) return H2_EINVAL;
+  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
+  if (m > msm_cols_per_launch(g, n)) return H2_EINVAL;
+  const MsmWorkspace ws = msm_workspace(n, m, g, 0, n_bases, pack != 0);
+  const char* broken = msm_check(ws, g, n, m, n, (uint32_t)n_bases, ws.total);
+  if (broken) g_h2.last_error = std::string("msm launch geometry: ") + broken;
+  out[0] = ws.sort2 ? ws.s2.tile : ws.tile; out[1] = ws.staged; out[2] = ws.stage_lds; out[3] = ws.pack.on;
+  out[4] = ws.pack.bbits; out[5] = ws.pack.ibits; out[6] = ws.pack.wbits; out[7] = broken ? 0 : 1;
+  out[8] = msm_effective_t((uint32_t)ws.E, ws.T); out[9] = MSM_HOT_SPAN; out[10] = MSM_HOT_SEG; out[11] = ws.max_tasks;
   return H2_OK;
 }
 // scratch arenas of the current context: out = {allocations (first use or growth), cross-stream hand-overs (event waits),

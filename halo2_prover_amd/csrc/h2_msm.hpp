@@ -55,7 +55,7 @@ __device__ unsigned long long* h2_stamps;
 constexpr uint32_t MSM_SIGN = 0x80000000u;
 constexpr uint32_t MSM_MAX_WINDOWS = 48;
 constexpr uint32_t MSM_HOT_SPAN = 256;    // keys cut into more pieces than this take the hierarchical path
-constexpr uint32_t MSM_HOT_SEG = 128;     // pieces summed by one wave of msm_hot_reduce_kernel
+constexpr uint32_t MSM_HOT_SEG = 128;     // pieces summed by one task wave of msm_fixup_kernel
 constexpr uint32_t MSM_NOT_HOT = 0xFFFFFFFFu;
 constexpr uint32_t MSM_SORT_THREADS = 1024;   // block size of the digits / scatter kernels
 constexpr uint32_t MSM_CHUNK_WAVES = 3;   // resident waves per SIMD of the accumulate kernel (159 VGPRs)
@@ -464,7 +464,7 @@ scan_apply_kernel(const uint32_t* in, const uint32_t* block_sums, uint32_t* offs
 // sparse launch put 64 dependent additions on each of a few hundred threads of an idle GPU (1.9 ms for keygen's 16
 // sparse columns).  Every kernel that cuts the sorted list into chunks calls this with the same arguments.  Never
 // above the host's T, so the chunk count stays within the arrays sized for it.
-__device__ __forceinline__ uint32_t msm_effective_t(uint32_t E, uint32_t t_host) {
+__host__ __device__ __forceinline__ uint32_t msm_effective_t(uint32_t E, uint32_t t_host) {
   uint32_t t = (E + MSM_CHUNK_WAVES * 65536u - 1) / (MSM_CHUNK_WAVES * 65536u);
   if (t < 8) t = 8;
   return t < t_host ? t : t_host;
@@ -491,6 +491,7 @@ struct MsmKeysArgs {
   uint32_t* chunk_first;
   uint32_t* hot_slot;
   uint32_t* tasks;          // 2 words each: key, segment
+  uint32_t* hot_arrive;     // per hot key, at its first slot: the segments summed so far (msm_fixup_kernel's hand-off)
   uint32_t* task_count;
   uint32_t max_tasks, T_host;
   uint32_t keys_per_block;  // staged scatter: every block runs the keys pass for this many keys first (0: it does not)
@@ -534,6 +535,7 @@ __device__ __forceinline__ void msm_keys_block(const uint32_t* __restrict__ offs
       const uint32_t first = atomicAdd(A.task_count, nseg);
       if (first + nseg <= A.max_tasks) {     // cannot fail by construction (see msm_workspace); stay in bounds anyway
         slot = first;
+        A.hot_arrive[first] = 0;
         for (uint32_t q = 0; q < nseg; q++) {
           A.tasks[2 * (first + q)] = (uint32_t)key;
           A.tasks[2 * (first + q) + 1] = q;
@@ -595,15 +597,42 @@ msm_scatter_kernel(const U128* __restrict__ scalars, const uint32_t* __restrict_
 // store instruction holds staged entry j, so the ~4 entries of one (tile, bucket) run -- consecutive in the bucket's
 // list -- sit in neighbouring lanes and leave as one request instead of four.  (A scattered 4-byte store is one 32-byte
 // fabric write on this chip whatever the L2 holds: 152 MB of WRITE_SIZE for 21 MB of entries with the direct kernel.)
-// LDS: cursors and (global - local) offsets per bucket, 4 + 2 bytes per staged entry; the host picks this kernel when
-// a tile with a few entries per bucket fits (msm_workspace) and the direct one otherwise (wide windows, long columns).
-template <class CV>
+// LDS: cursors and (global - local) offsets per bucket, and the staged entries.  Inside a tile an entry is known by its
+// window, the scalar's index WITHIN THE TILE, its sign and its bucket: where those fit 32 bits (MsmStagePack: 5 + 11 + 1
+// + 11 bits at 2^16) the staged entry is that one word, and the global reference w * n_bases + i | sign is rebuilt in
+// the store loop, which reads the bucket anyway.  At 4 bytes per entry instead of 4 + 2 (the reference and a 16-bit
+// bucket, kept for the geometries whose fields do not fit: PACKED = false) a launch of up to 6 columns of 2^16 is one
+// round of <= 256 blocks.  The host picks this kernel when a tile with a few entries per bucket fits (msm_workspace)
+// and the direct one otherwise (wide windows, long columns).
+constexpr size_t MSM_STAGE_LDS_CAP = 160 * 1024 - 512;
+struct MsmStagePack {
+  uint32_t on;                     // 1: one packed word per staged entry; 0: reference + 16-bit bucket
+  uint32_t bbits, ibits, wbits;    // bucket in bits [0, bbits), index in tile above it, window above that, sign in bit 31
+};
+inline uint32_t msm_bits_for(uint64_t count) {   // bits that hold 0 .. count - 1
+  uint32_t b = 0;
+  while (((uint64_t)1 << b) < count) b++;
+  return b;
+}
+inline MsmStagePack msm_stage_pack(const MsmGeom& g, size_t tile) {
+  MsmStagePack p{};
+  p.bbits = msm_bits_for(g.B);
+  p.ibits = msm_bits_for(tile);
+  p.wbits = msm_bits_for(g.W);
+  p.on = p.bbits + p.ibits + p.wbits <= 31 ? 1u : 0u;
+  return p;
+}
+inline size_t msm_stage_need(const MsmGeom& g, size_t tile, bool packed) {
+  return (size_t)8 * g.B + (size_t)(packed ? 4 : 6) * tile * g.W + 64;
+}
+template <class CV, bool PACKED>
 __global__ void __launch_bounds__(1024)
 msm_scatter_staged_kernel(const U128* __restrict__ scalars, const uint32_t* __restrict__ offsets,
                           const uint32_t* __restrict__ gcounts, const uint32_t* __restrict__ tile_base,
                           const uint32_t* __restrict__ tile_hist, uint32_t* __restrict__ sorted_ref, uint32_t n,
                           size_t col_stride /* elements */, uint32_t n_bases, uint32_t tile, uint32_t tiles, uint32_t m,
-                          MsmGeom g, uint32_t stage_cap /* entries the staging area holds = tile * W */, MsmKeysArgs keys) {
+                          MsmGeom g, uint32_t stage_cap /* entries the staging area holds = tile * W */, MsmStagePack pk,
+                          MsmKeysArgs keys) {
   using S = typename CV::Scalar;
   extern __shared__ uint32_t hist[];
   __shared__ uint32_t wave_sum[16];
@@ -611,7 +640,7 @@ msm_scatter_staged_kernel(const U128* __restrict__ scalars, const uint32_t* __re
   uint32_t* cur = hist;                                   // B cursors into the staging area
   uint32_t* delta = hist + g.B;                           // B: (position in sorted_ref) - (position in the staging area)
   uint32_t* sref = hist + 2 * (size_t)g.B;                // stage_cap entries
-  uint16_t* sbkt = reinterpret_cast<uint16_t*>(sref + stage_cap);   // their buckets
+  uint16_t* sbkt = reinterpret_cast<uint16_t*>(sref + stage_cap);   // their buckets (!PACKED)
   const MsmTileId id = msm_tile_id(tiles, m);
   if (!id.live) return;
   const uint32_t col = id.col;
@@ -657,15 +686,28 @@ msm_scatter_staged_kernel(const U128* __restrict__ scalars, const uint32_t* __re
         const uint32_t b = (enc & ~MSM_SIGN) - 1;
         const uint32_t pos = atomicAdd(&cur[b], 1u);
         if (pos < stage_cap) {             // always: the counts come from the same digits (msm_digits_kernel)
-          sref[pos] = (w * n_bases + i) | (enc & MSM_SIGN);
-          sbkt[pos] = (uint16_t)b;
+          if (PACKED) {
+            sref[pos] = b | ((i - lo) << pk.bbits) | (w << (pk.bbits + pk.ibits)) | (enc & MSM_SIGN);
+          } else {
+            sref[pos] = (w * n_bases + i) | (enc & MSM_SIGN);
+            sbkt[pos] = (uint16_t)b;
+          }
         }
       }
     }
   }
   __syncthreads();
   const uint32_t total = min(total_s, stage_cap);
-  for (uint32_t j = threadIdx.x; j < total; j += blockDim.x) sorted_ref[delta[sbkt[j]] + j] = sref[j];
+  if (PACKED) {
+    const uint32_t bmask = (1u << pk.bbits) - 1, imask = (1u << pk.ibits) - 1;
+    for (uint32_t j = threadIdx.x; j < total; j += blockDim.x) {
+      const uint32_t e = sref[j];
+      const uint32_t w = (e & ~MSM_SIGN) >> (pk.bbits + pk.ibits), i = lo + ((e >> pk.bbits) & imask);
+      sorted_ref[delta[e & bmask] + j] = (w * n_bases + i) | (e & MSM_SIGN);
+    }
+  } else {
+    for (uint32_t j = threadIdx.x; j < total; j += blockDim.x) sorted_ref[delta[sbkt[j]] + j] = sref[j];
+  }
 }
 
 // ---- accumulate: every thread adds T consecutive sorted entries ---------------------------------
@@ -773,47 +815,65 @@ __device__ __forceinline__ Xyzz29<CV> msm_piece(const uint32_t* __restrict__ hea
   return xyzz29_load<CV>(src + XYZZ29_WORDS * (size_t)j);
 }
 
-// one wave per task = 16 quads (4 lanes per point, h2_curve_quad.hpp): quad g folds pieces g, g+16, ... of the
-// task's MSM_HOT_SEG pieces, then a 4-level shuffle tree across the quads
-template <class CV>
-__global__ void __launch_bounds__(64)
-msm_hot_reduce_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host, const uint32_t* __restrict__ hot_slot,
-                      const uint32_t* __restrict__ tasks, const uint32_t* __restrict__ task_count, uint32_t max_tasks,
-                      const uint32_t* __restrict__ head, const uint32_t* __restrict__ tail, uint32_t* __restrict__ hot_part) {
-  __builtin_amdgcn_s_setprio(3);   // a dependent chain on a mostly idle SIMD: issue ahead of co-resident throughput kernels
-  const uint32_t ntask = min(*task_count, max_tasks);
-  const uint32_t T = msm_effective_t(offsets[K], T_host);
-  const uint32_t quad = threadIdx.x >> 2;
-  for (uint32_t t = blockIdx.x; t < ntask; t += gridDim.x) {
-    const uint32_t key = tasks[2 * t], q = tasks[2 * t + 1];
-    const uint32_t s = offsets[key], e = offsets[key + 1];
-    const uint32_t j0 = s / T, span = (e - 1) / T - j0 + 1;
-    const uint32_t lo = q * MSM_HOT_SEG, hi = min(span, lo + MSM_HOT_SEG);
-    Xyzz29<CV> a = Xyzz29<CV>::identity();
-    for (uint32_t p = lo + quad; p < hi; p += 16) a = xyzz29_add_quad(a, msm_piece<CV>(head, tail, s, j0, T, p));
-    for (uint32_t d = 32; d >= 4; d >>= 1) a = xyzz_fold_down(a, d, threadIdx.x);
-    if (threadIdx.x == 0) xyzz29_store<CV>(hot_part + XYZZ29_WORDS * (size_t)(hot_slot[key] + q), a);
-  }
-}
-
-// Fix-up: G lanes = G/4 quads per key (G = 2^log_g, 4 <= G <= 64; 4 lanes per point, h2_curve_quad.hpp).  The
-// quads of a key share out its pieces (or its hot partials), then a shuffle tree across the quads; lane 0 writes
-// xsum[key], the bucket's point sum.
+// Fix-up, one launch for both kinds of bucket.
+//
+// Blocks [0, task_blocks): the hot tasks, if the keys pass emitted any (a column of a real proof has none: these blocks
+// read the task count and leave -- as a kernel of its own this was 4.8-5.4 us of stream time between the accumulate kernel
+// and the fix-up in every launch sequence).  One wave per task = 16 quads (4 lanes per point, h2_curve_quad.hpp): quad g
+// folds pieces g, g + 16, ... of the task's MSM_HOT_SEG pieces, then a 4-level shuffle tree across the quads.  The wave
+// publishes its partial and counts itself in at the key's counter (hot_arrive, zeroed by the keys pass); the wave that
+// arrives LAST for a key adds the key's partials and writes xsum[key].  Last-arrival hand-off only (the form of
+// msm_final_kernel): no wave ever waits for another, so nothing can hang beside another stream's kernels.
+//
+// The blocks behind them: G lanes = G/4 quads per key (G = 2^log_g, 4 <= G <= 64).  The quads of a key share out its
+// pieces, then a shuffle tree across the quads; lane 0 writes xsum[key], the bucket's point sum.  The lanes of hot keys
+// skip: their sum comes from the task waves, which run beside these blocks rather than in front of them.
+inline uint32_t msm_fixup_task_blocks(uint32_t max_tasks) { return std::min<uint32_t>(256u, (max_tasks + 3) / 4); }
 template <class CV>
 __global__ void __launch_bounds__(256)
 msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host, uint32_t log_g,
                  const uint32_t* __restrict__ bucket_sum, const uint32_t* __restrict__ head,
                  const uint32_t* __restrict__ tail, const uint32_t* __restrict__ hot_slot,
-                 const uint32_t* __restrict__ hot_part, uint32_t* __restrict__ xsum) {
+                 const uint32_t* __restrict__ tasks, const uint32_t* __restrict__ task_count, uint32_t max_tasks,
+                 uint32_t task_blocks, uint32_t* hot_part, uint32_t* hot_arrive, uint32_t* __restrict__ xsum) {
   __builtin_amdgcn_s_setprio(3);   // a dependent chain on a mostly idle SIMD: issue ahead of co-resident throughput kernels
-  const uint32_t G = 1u << log_g;
   const uint32_t T = msm_effective_t(offsets[K], T_host);
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.x < task_blocks) {
+    const uint32_t ntask = min(*task_count, max_tasks);
+    const uint32_t lane = threadIdx.x & 63u, quad = lane >> 2;
+    for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < ntask; t += task_blocks * 4) {
+      const uint32_t key = tasks[2 * t], q = tasks[2 * t + 1];
+      const uint32_t s = offsets[key], e = offsets[key + 1];
+      const uint32_t j0 = s / T, span = (e - 1) / T - j0 + 1;
+      const uint32_t lo = q * MSM_HOT_SEG, hi = min(span, lo + MSM_HOT_SEG);
+      const uint32_t nseg = (span + MSM_HOT_SEG - 1) / MSM_HOT_SEG, slot = hot_slot[key];
+      uint32_t* part = hot_part + XYZZ29_WORDS * (size_t)slot;
+      Xyzz29<CV> a = Xyzz29<CV>::identity();
+      for (uint32_t p = lo + quad; p < hi; p += 16) a = xyzz29_add_quad(a, msm_piece<CV>(head, tail, s, j0, T, p));
+      for (uint32_t d = 32; d >= 4; d >>= 1) a = xyzz_fold_down(a, d, lane);
+      uint32_t arrived = 0;
+      if (lane == 0) {
+        xyzz29_store<CV>(part + XYZZ29_WORDS * (size_t)q, a);
+        h2_publish_release();                              // the partial is visible device-wide before the count
+        arrived = atomicAdd(hot_arrive + slot, 1u);
+      }
+      arrived = __shfl(arrived, 0, 64);
+      if (arrived != nseg - 1) continue;
+      h2_consume_acquire();
+      a = Xyzz29<CV>::identity();
+      for (uint32_t r = quad; r < nseg; r += 16) a = xyzz29_add_quad(a, xyzz29_load<CV>(part + XYZZ29_WORDS * (size_t)r));
+      for (uint32_t d = 32; d >= 4; d >>= 1) a = xyzz_fold_down(a, d, lane);
+      if (lane == 0) xyzz29_store<CV>(xsum + XYZZ29_WORDS * (size_t)key, a);
+    }
+    return;
+  }
+  const uint32_t G = 1u << log_g;
+  const size_t gt = (size_t)(blockIdx.x - task_blocks) * blockDim.x + threadIdx.x;
   const size_t key = gt >> log_g;
   const uint32_t lane = (uint32_t)gt & (G - 1);
   const uint32_t quad = lane >> 2, nquad = G >> 2;
   // all lanes of a wave stay in the shuffle tree together; out-of-range keys work on identities
-  const bool live = key < K;
+  bool live = key < K;
   Xyzz29<CV> x = Xyzz29<CV>::identity();
   if (live) {
     const uint32_t s = offsets[key], e = offsets[key + 1];
@@ -822,9 +882,7 @@ msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host
       if (j0 == j1) {
         if (quad == 0) x = xyzz29_load<CV>(bucket_sum + XYZZ29_WORDS * key);
       } else if (hot_slot[key] != MSM_NOT_HOT) {
-        const uint32_t nseg = (j1 - j0 + 1 + MSM_HOT_SEG - 1) / MSM_HOT_SEG;
-        const uint32_t* part = hot_part + XYZZ29_WORDS * (size_t)hot_slot[key];
-        for (uint32_t q = quad; q < nseg; q += nquad) x = xyzz29_add_quad(x, xyzz29_load<CV>(part + XYZZ29_WORDS * (size_t)q));
+        live = false;                                      // summed by the task waves
       } else if (quad <= j1 - j0) {
         // the next piece is on its way while the current one is added (a piece is 144 bytes from HBM: ~1.5 us exposed
         // per addition otherwise, the chain has nothing else to do)
@@ -1238,12 +1296,13 @@ struct MsmWorkspace {
   uint32_t tile;        // scalars per block in the digits / scatter kernels
   uint32_t staged;      // the scatter stages its tile in LDS (msm_scatter_staged_kernel); stage_lds bytes of dynamic LDS
   size_t stage_lds;
+  MsmStagePack pack;    // the staged entry's form (one packed word, or reference + 16-bit bucket)
   uint32_t sort2;       // the two-level sort (h2_msm_sort2.hpp) instead of digits / scan / scatter
   Sort2Geom s2;
   uint32_t lb;          // low bits of a bucket index in the row / column split of the weights (msm_rowcol_kernel)
   uint32_t rc;          // row + column sums per column = 2^(log_b - lb) + 2^lb
   size_t off_counts, off_gcounts, off_offsets, off_tile_base, off_tile_hist, off_blocksums, off_ref, off_key, off_misc, off_bsum,
-      off_head, off_tail, off_xsum, off_rc, off_part, off_done, off_tree2, off_hot_slot, off_hot_tasks, off_hot_part, total;
+      off_head, off_tail, off_xsum, off_rc, off_part, off_done, off_tree2, off_hot_slot, off_hot_tasks, off_hot_part, off_hot_arrive, total;
   size_t off_cstart, off_group_base, off_mid_ref, off_mid_lo;   // two-level sort only
   size_t zero_bytes;    // misc + the counters behind it: cleared by one memset per launch
   uint32_t max_tasks;
@@ -1318,25 +1377,43 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
   tile *= (size_t)tune_int("H2_TUNE_TILE_MUL", 2);   // measured with 1024-thread blocks (MSM_SORT_THREADS): longer runs per (tile, bucket), fewer sector writes
   if (tile > n) tile = n;
   // the staged scatter: buckets fit 16 bits, and a tile with >= 2 entries per bucket fits the CU's LDS next to the two
-  // per-bucket arrays.  One block per CU then, so the tile is sized for a whole number of rounds of 256 blocks, as
-  // few as fit, two at most (m = 4 at 2^16: 256 blocks of 1024 scalars, 152 KB; m = 5: 512 blocks of 640).
+  // per-bucket arrays.  One block per CU then, so the launch is sized for a whole number of rounds of 256 blocks, as
+  // few as fit, two at most.  The TILES PER COLUMN are chosen first, tpc = floor(256 * rounds / m), and the tile from
+  // them, so that ceil(n / tile) * m <= 256 * rounds: a tile of ceil(n * m / 256) scalars left m = 3 at 2^16 with 258
+  // blocks and m = 5 with 515, a few stragglers with a round of their own.  A staged entry is one packed word where its
+  // fields fit (MsmStagePack), else 4 + 2 bytes; at 2^16 with 4 bytes per entry m = 3: 255 blocks of 772 scalars, 83 KB;
+  // m = 4: 256 of 1024, 104 KB; m = 5: 255 of 1286, 127 KB; m = 6: 252 of 1561, 150 KB -- all one round.
   ws.staged = 0;
   ws.stage_lds = 0;
+  ws.pack = MsmStagePack{};
   if (!ws.sort2) {
-    const size_t cap = 160 * 1024 - 512;
-    auto need = [&](size_t t) { return (size_t)8 * g.B + (size_t)6 * t * g.W + 64; };
-    if (g.B <= 65536 && n * m >= 8192 && need(dense) <= cap) {
+    const size_t cap = MSM_STAGE_LDS_CAP;
+    // (`allow_pack` = false, a test hook: the 4 + 2 byte entry even where the packed word fits.  At every geometry this
+    // branch accepts today the fields fit -- B <= 8192 and tile * W <= ~40 K leave them within 30 bits -- so the hook is
+    // the only way into the unpacked form, which stays as the net under a future geometry)
+    auto pack_of = [&](size_t t) {
+      MsmStagePack pk = msm_stage_pack(g, t);
+      if (!allow_pack) pk.on = 0;
+      return pk;
+    };
+    if (g.B <= 65536 && n * m >= 8192 && msm_stage_need(g, dense, pack_of(dense).on != 0) <= cap) {
       // (more than two rounds of one-block-per-CU tiles cost more than the stores save: keygen's 16 sparse columns took
       // 214 us per launch staged in four rounds against 85 us direct)
       for (size_t rounds = 1; rounds <= 2; rounds++) {
-        size_t t = (n * m + 256 * rounds - 1) / (256 * rounds);
+        const size_t tpc = 256 * rounds / m;
+        // (tpc = 0, more columns than blocks of the round: no whole tile count per column exists and the tile is sized
+        // by scalars as before.  From 257 to 512 columns that is the first round only; the second has tpc = 1, one tile
+        // of n scalars per column and m <= 512 blocks, which the LDS bound below then accepts or not like any other)
+        size_t t = tpc ? (n + tpc - 1) / tpc : (n * m + 256 * rounds - 1) / (256 * rounds);
         if (t < dense) t = dense;
         if (t < 256) t = 256;
         if (t > n) t = n;
-        if (need(t) <= cap) {
+        const MsmStagePack pk = pack_of(t);
+        if (msm_stage_need(g, t, pk.on != 0) <= cap) {
           tile = t;
           ws.staged = 1;
-          ws.stage_lds = need(t);
+          ws.stage_lds = msm_stage_need(g, t, pk.on != 0);
+          ws.pack = pk;
           break;
         }
       }
@@ -1395,6 +1472,7 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
   ws.off_hot_slot = region("hot slots", ws.K * 4);
   ws.off_hot_tasks = region("hot tasks", (size_t)ws.max_tasks * 8);
   ws.off_hot_part = region("hot partials", (size_t)ws.max_tasks * (XYZZ29_WORDS * 4));
+  ws.off_hot_arrive = region("hot arrivals", (size_t)ws.max_tasks * 4);
   ws.total = o;
   return ws;
 }
@@ -1457,7 +1535,11 @@ inline const char* msm_check(const MsmWorkspace& ws, const MsmGeom& g, size_t n,
     if (ws.staged) {
       MSM_REQUIRE(bytes_at(ws.off_tile_hist) >= tiles * ws.K * 4);
       MSM_REQUIRE(g.B <= 65536);                                         // staged buckets are 16-bit
-      MSM_REQUIRE(ws.stage_lds >= (size_t)8 * g.B + (size_t)6 * ws.tile * g.W && ws.stage_lds <= 160 * 1024 - 512);
+      MSM_REQUIRE(ws.stage_lds >= (size_t)8 * g.B + (size_t)(ws.pack.on ? 4 : 6) * ws.tile * g.W && ws.stage_lds <= MSM_STAGE_LDS_CAP);
+      // a packed entry: bucket | index in tile | window below the sign bit
+      MSM_REQUIRE(!ws.pack.on || (g.B <= (1ull << ws.pack.bbits) && ws.tile <= (1ull << ws.pack.ibits) && g.W <= (1ull << ws.pack.wbits) &&
+                                  ws.pack.bbits + ws.pack.ibits + ws.pack.wbits <= 31));
+      MSM_REQUIRE(m > 256 || tiles * m <= 512);                          // one block per CU: two rounds at most
     }
     if (ws.K > SCAN_LDS_MAX) {
       MSM_REQUIRE(ws.nblk * SCAN_BLOCK >= ws.K && ws.nblk < (1ull << 31));
@@ -1481,6 +1563,9 @@ inline const char* msm_check(const MsmWorkspace& ws, const MsmGeom& g, size_t n,
   MSM_REQUIRE(bytes_at(ws.off_hot_slot) >= ws.K * 4);
   MSM_REQUIRE(bytes_at(ws.off_hot_tasks) >= (size_t)ws.max_tasks * 8);
   MSM_REQUIRE(bytes_at(ws.off_hot_part) >= (size_t)ws.max_tasks * (XYZZ29_WORDS * 4));
+  MSM_REQUIRE(bytes_at(ws.off_hot_arrive) >= (size_t)ws.max_tasks * 4);                  // a hot key's counter sits at its first slot
+  MSM_REQUIRE(ws.max_tasks >= 1 && msm_fixup_task_blocks(ws.max_tasks) >= 1);
+  MSM_REQUIRE(((ws.K << ws.log_g) + 255) / 256 + msm_fixup_task_blocks(ws.max_tasks) < (1ull << 31));
   MSM_REQUIRE(m <= 65535);                                               // grid.y of the row / column and final kernels
   return nullptr;
 }
@@ -1504,7 +1589,8 @@ inline hipError_t msm_kernel_setup() {
   const int lds = (int)((1u << (MSM_MAX_C_ONE_LEVEL - 1)) * 4);
   if ((e = hipFuncSetAttribute((const void*)msm_digits_kernel<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)msm_scatter_kernel<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute((const void*)msm_scatter_staged_kernel<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)msm_scatter_staged_kernel<CV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_STAGE_LDS_CAP)) != hipSuccess) return e;
+  if ((e = hipFuncSetAttribute((const void*)msm_scatter_staged_kernel<CV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_STAGE_LDS_CAP)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)msm2_scatter_kernel<CV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512)) != hipSuccess) return e;
   if ((e = hipFuncSetAttribute((const void*)msm2_fine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)msm_sort2_lds_fine())) != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)scan_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SCAN_LDS_MAX * 4));
@@ -1539,6 +1625,7 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
   uint32_t* hot_slot = (uint32_t*)(ws_base + ws.off_hot_slot);
   uint32_t* hot_tasks = (uint32_t*)(ws_base + ws.off_hot_tasks);
   uint32_t* hot_part = (uint32_t*)(ws_base + ws.off_hot_part);
+  uint32_t* hot_arrive = (uint32_t*)(ws_base + ws.off_hot_arrive);
   hipError_t e;
   if (per_column && m > MSM_MAX_MULTI) return hipErrorInvalidValue;
   // one memset: misc (256 B) and the sort's counters behind it.  Nothing else needs clearing: every slot of bucket_sum /
@@ -1553,6 +1640,7 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
   keys_args.chunk_first = chunk_first;
   keys_args.hot_slot = hot_slot;
   keys_args.tasks = hot_tasks;
+  keys_args.hot_arrive = hot_arrive;
   keys_args.task_count = misc;
   keys_args.max_tasks = ws.max_tasks;
   keys_args.T_host = ws.T;
@@ -1603,9 +1691,13 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
       MsmKeysArgs ka = keys_args;
       const uint32_t grid = sort_grid;
       if (keys_merged) ka.keys_per_block = (uint32_t)per;
-      hipLaunchKernelGGL(msm_scatter_staged_kernel<CV>, dim3(grid), dim3(MSM_SORT_THREADS), ws.stage_lds, stream, d_scalars,
-                         offsets, gcounts, tile_base, tile_hist, sref, (uint32_t)n, col_stride, n_bases, ws.tile, tiles,
-                         (uint32_t)m, g, (uint32_t)(ws.tile * g.W), ka);
+      auto scatter = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MSM_SORT_THREADS), ws.stage_lds, stream, d_scalars, (const uint32_t*)offsets,
+                           (const uint32_t*)gcounts, (const uint32_t*)tile_base, (const uint32_t*)tile_hist, sref, (uint32_t)n,
+                           col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g, (uint32_t)(ws.tile * g.W), ws.pack, ka);
+      };
+      if (ws.pack.on) scatter(msm_scatter_staged_kernel<CV, true>);
+      else scatter(msm_scatter_staged_kernel<CV, false>);
     } else
       hipLaunchKernelGGL(msm_scatter_kernel<CV>, dim3(sort_grid), dim3(MSM_SORT_THREADS), lds, stream, d_scalars, offsets,
                          gcounts, tile_base, sref, (uint32_t)n, col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g);
@@ -1626,11 +1718,12 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
     hipLaunchKernelGGL(msm_chunk_kernel<CV>, dim3((unsigned)((ws.nchunks + 255) / 256)), dim3(256), 0, stream, table,
                        (const U128* const*)d_tables, log_b, sref, chunk_first, offsets, ws.K, ws.T, bsum, head, tail);
   if (ev_stop && ev_tail) (void)hipEventRecord(ev_tail, stream);
-  hipLaunchKernelGGL(msm_hot_reduce_kernel<CV>, dim3(1024), dim3(64), 0, stream, offsets, ws.K, ws.T, hot_slot, hot_tasks,
-                     misc, ws.max_tasks, head, tail, hot_part);
+  // hot tasks and the buckets' pieces in one launch: the task blocks come first in the grid
   const size_t fix_threads = ws.K << ws.log_g;
-  hipLaunchKernelGGL(msm_fixup_kernel<CV>, dim3((unsigned)((fix_threads + 255) / 256)), dim3(256), 0, stream, offsets,
-                     ws.K, ws.T, ws.log_g, bsum, head, tail, hot_slot, hot_part, xsum);
+  const uint32_t task_blocks = msm_fixup_task_blocks(ws.max_tasks);
+  hipLaunchKernelGGL(msm_fixup_kernel<CV>, dim3((unsigned)((fix_threads + 255) / 256) + task_blocks), dim3(256), 0, stream, offsets,
+                     ws.K, ws.T, ws.log_g, bsum, head, tail, hot_slot, hot_tasks, misc, ws.max_tasks, task_blocks, hot_part,
+                     hot_arrive, xsum);
   uint32_t* part = (uint32_t*)(ws_base + ws.off_part);
   uint32_t* done = (uint32_t*)(ws_base + ws.off_done);
   hipLaunchKernelGGL(msm_rowcol_kernel<CV>, dim3(ws.rc, (unsigned)m), dim3(64 * msm_rowcol_waves(g.c - 1, ws.lb, m)), 0, stream,

@@ -43,15 +43,23 @@ int h2_selftest_set_msm_max_entries(uint64_t limit);
  *   (col_stride elements apart) against n_bases registered bases and runs the bounds proof msm_device_run runs before
  *   every launch (each kernel's largest index against the region it indexes).  out[0..7] = window bits, windows,
  *   buckets, scalars per sort tile, staged scatter?, two-level sort?, entries per accumulate thread, regions.
+ * h2_selftest_msm_front: host only -- the same layout and proof for the sort front of that launch (`pack` = 0: with the
+ *   unpacked forms of h2_selftest_msm_guard(3)).  out[0..7] = scalars per sort tile, staged scatter?, its dynamic LDS in
+ *   bytes, packed staged entries?, bits of a packed entry's bucket, index-in-tile and window fields, 1 if the bounds
+ *   proof held; out[8..11] = entries per accumulate thread when every digit of the launch is non-zero (fewer entries
+ *   never give more), the pieces above which a bucket takes the hot-task path, the pieces per hot task, the task slots.
  * h2_selftest_msm_tiles: host only -- the one-level sort's block -> (column, tile) mapping is a bijection onto the
  *   live pairs and every surplus block of the rounded-up grid is dead.
  * h2_selftest_msm_guard(1): from now on every MSM launch lays its arena out with a 256-byte red zone behind every
  *   region, fills the arena with a pattern first and counts the red-zone bytes that changed afterwards (synchronous;
  *   tests only; guard(2) also writes one byte behind the second region itself, to test the checker; guard(3) also makes
- *   the two-level sort carry the key's low bits in its side array, the layout of SRS sizes whose entries have no spare bits).
+ *   the two-level sort carry the key's low bits in its side array, the layout of SRS sizes whose entries have no spare bits,
+ *   and the staged scatter keep a reference and a 16-bit bucket per entry, the layout of geometries whose fields do not
+ *   fit one word).
  *   h2_selftest_msm_guard_report: out[0] = launches checked, out[1] = regions overrun since guard(1);
  *   `first` = a description of the first one. */
 int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]);
+int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]);
 int h2_selftest_msm_tiles(uint32_t tiles, uint32_t m);
 int h2_selftest_msm_guard(int on);
 int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap);

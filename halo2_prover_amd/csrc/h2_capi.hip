@@ -387,6 +387,24 @@ int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[
   return A ? A->release() : H2_OK;
 }
 
+int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
+                              const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n, void* d_out,
+                              hipStream_t stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops) return H2_EINVAL;
+  const void* tw = nullptr;
+  int rc = get_twiddles(c, ops, ext_omega, ext_log_n, nullptr, &tw);
+  if (rc != H2_OK) return rc;
+  std::optional<ArenaLease> A;     // pass 0 writes it; the padded source column never exists
+  if (ntt_make_plan(ext_log_n).npass > 1) {
+    A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << ext_log_n), stream);
+    if (A->rc != H2_OK) return A->rc;
+  }
+  hipError_t e = ops->ntt_extend_launch(d_coeff, col_stride, log_n, zeta, d_out, A ? A->a.p : nullptr, tw, ext_log_n, m, stream);
+  if (e != hipSuccess) return dev_fail(e, "ntt_extend_launch");
+  return A ? A->release() : H2_OK;
+}
+
 }  // namespace h2
 
 namespace {
@@ -811,6 +829,27 @@ int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t o
     return H2_OK;
   }
   return ntt_enqueue(*k.c, (int)curve, d_a, m, omega, log_n, k.stream, scale);
+}
+
+int h2_coeff_to_extended_device(h2_curve_t curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
+                                const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n, void* d_out,
+                                void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !zeta || !ext_omega || ext_log_n > 30 || ext_log_n < log_n) return H2_EINVAL;
+  const size_t n = (size_t)1 << log_n, en = (size_t)1 << ext_log_n;
+  if (col_stride < n) return H2_EINVAL;
+  if (m == 0) return H2_OK;
+  if (!d_coeff || !d_out || m > 65535) return H2_EINVAL;             // grid.y = column
+  // [first byte, last byte) of what is read and of what is written
+  const uintptr_t s0 = (uintptr_t)d_coeff, s1 = s0 + ((m - 1) * col_stride + n) * 32;
+  const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + m * en * 32;
+  if (s0 < o1 && o0 < s1) return H2_EINVAL;
+  if (ext_log_n == 0) {            // one coefficient, one point: out[c][0] = in[c][0]
+    H2_TRY(hipMemcpy2DAsync(d_out, 32, d_coeff, col_stride * 32, 32, m, hipMemcpyDeviceToDevice, k.stream));
+    return H2_OK;
+  }
+  return coeff_to_extended_enqueue(*k.c, (int)curve, d_coeff, col_stride, log_n, m, zeta, ext_omega, ext_log_n, d_out, k.stream);
 }
 
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream_) {

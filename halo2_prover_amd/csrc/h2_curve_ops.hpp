@@ -51,6 +51,11 @@ struct CurveOps {
   hipError_t (*ntt_twiddles)(void* d_tables, const uint64_t omega[4], uint32_t log_n, hipStream_t s, const uint64_t* scale /* or null */);
   hipError_t (*ntt_launch)(void* d_data, void* d_scratch, const void* d_tw, uint32_t log_n, size_t m,
                            hipStream_t s, const uint64_t* scale /* 4 limbs or null */);
+  // coeff_to_extended: m columns of 2^log_src coefficients (src_stride elements apart, read only) -> m columns of
+  // 2^log_n values in d_out: the transform of the zero-extended column times zeta^i, the padding never materialised
+  // (pass 0 of h2_ntt29.hpp's extending kernel).  Tables of (omega, log_n) unscaled; log_n >= 1; d_scratch as ntt_launch
+  hipError_t (*ntt_extend_launch)(const void* d_src, size_t src_stride, uint32_t log_src, const uint64_t zeta[4], void* d_out,
+                                  void* d_scratch, const void* d_tw, uint32_t log_n, size_t m, hipStream_t s);
   // best_fft over group elements (FftGroup for the curve: g_to_lagrange): n = 2^log_n Jacobian points (API form) in,
   // the transform out (may alias), natural order, unscaled; d_scratch: group_fft_scratch(log_n) bytes
   size_t (*group_fft_scratch)(uint32_t log_n);

@@ -170,6 +170,11 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
 size_t msm_cols_per_launch(const MsmGeom& geom, size_t n);
 int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, hipStream_t stream,
                 const uint64_t* scale = nullptr);
+// EvaluationDomain::coeff_to_extended (h2_coeff_to_extended_device; arguments checked by the caller, ext_log_n >= 1):
+// the tables of (ext_omega, ext_log_n) unscaled -- ntt_enqueue's entry -- and its second buffer on `stream`
+int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
+                              const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n, void* d_out,
+                              hipStream_t stream);
 int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t m, const BasesEntry** be);
 
 #define H2_TRY(call)                                        \

@@ -134,9 +134,7 @@ inline HX hx_mul(const Fr& k, const HX& p) {
 
 // coeff (m columns of n, stride n) -> extended-coset evaluations (m columns of en)
 inline void coeff_to_extended(Dev& d, const Domain& D, Col in, size_t m, Col out, hipStream_t on = nullptr) {
-  launch("coset_extend_kernel", pk::coset_extend_kernel, dim3((D.en + 255) / 256, (unsigned)m), dim3(256), on ? on : d.s, in,
-         (size_t)D.n, out, D.n, D.en, D.zeta.v, D.zeta.sqr().v);
-  d.ntt(out, m, D.ext_omega, D.ext_k, nullptr, on);
+  d.extend(in, D.n, D.k, m, D.zeta, D.ext_omega, D.ext_k, out, on);
 }
 
 inline std::shared_ptr<const DomainKit> domain_kit(const Domain& D, int bf, DevCtx* ctx) {
@@ -171,9 +169,7 @@ inline std::shared_ptr<const DomainKit> domain_kit(const Domain& D, int bf, DevC
     d.fill_sparse(basis, n, b);
     d.ntt(basis, 3, D.omega_inv, D.k, &D.n_inv);
     kit->basis_ext = d.col(3 * (size_t)D.en);
-    launch("coset_extend_kernel", pk::coset_extend_kernel, dim3((D.en + 255) / 256, 3u), dim3(256), d.s, basis, (size_t)n,
-           kit->basis_ext, n, D.en, D.zeta.v, D.zeta.sqr().v);
-    d.ntt(kit->basis_ext, 3, D.ext_omega, D.ext_k);
+    d.extend(basis, n, D.k, 3, D.zeta, D.ext_omega, D.ext_k, kit->basis_ext);
     d.release(basis);
   }
   // the polynomial X on the coset: zeta w_ext^i

@@ -8,10 +8,20 @@
 //   * a product costs 81 + 9k multiply-adds without carry counters or a conditional subtraction, additions and
 //     subtractions are nine limb operations without carries; every value written back to LDS is carry-normalised
 //     (limbs in [0, 2^29), the top limb takes the sign);
-//   * magnitudes: a tile's inputs are below 3p/2 (canonical API data, or what a non-final pass stored: see below); a
-//     radix-4 double stage adds at most two products (each in (-3p/2, p/2)) to an element, the very first one (all
-//     twiddles 1) at most quadruples it: <= 4 * 1.5p + 3p * 4 = 18p after the five double stages of a 1024-row tile,
-//     well inside fe29_mul's |a| |b| <= 64 p^2 with a canonical twiddle as b.
+//   * magnitudes: a tile's inputs are below 3p/2 IN MAGNITUDE.  The plain pass reads values in [0, 3p/2): canonical
+//     API data, or what a non-final pass stored (see below).  The EXTENDING pass 0 (EvaluationDomain::coeff_to_extended,
+//     at the end of this comment) reads canonical data in [0, p) and multiplies two of every three elements by zeta or
+//     zeta^2 on the way in: fe29_mul of two canonical operands (|a| |b| < p^2, far inside 64 p^2) is in
+//     (a b / R' - p, a b / R'], i.e. in (-p, p/128] -- inside the product's general (-3p/2, p/2], normalised, the top
+//     limb signed like every value the stages keep in LDS; an element beyond the source's length is exact zero.  So
+//     there a tile input lies in (-3p/2, p/2) or [0, p), not in [0, 3p/2): the sign differs, the magnitude does not,
+//     and nothing below uses the sign.  A radix-4 double stage adds at most two products (each in (-3p/2, p/2)) to an
+//     element, the very first one (all twiddles 1) at most quadruples it: |x| <= 4 * 1.5p + 3p * 4 = 18p after the
+//     five double stages of a 1024-row tile, well inside fe29_mul's |a| |b| <= 64 p^2 with a canonical twiddle as b.
+//     The first stage's operands are sums and differences of two inputs: normalised limbs 0..7 in [0, 2^29) and a
+//     top limb of magnitude below 2^24 whatever the sign, so their limbs stay within +-2^29 as fe29_mul asks.  The
+//     exits take either sign: a non-final pass adds 32p first, the final one indexes the canonicalisation table by
+//     the SIGNED top limb (|t| <= 144 < NTT_CANON_OFF).
 // Round 3: what the pass did besides products:
 //   * leaving a NON-FINAL pass an element x is multiplied by the inter-pass twiddle anyway.  It is first moved to
 //     32p + x (or 32p - x where the exponent asks for -w: the negation costs nothing) -- positive, limbs below 2^30 --
@@ -25,6 +35,17 @@
 //     the constant (table built once per (omega, log n, constant)): no product in its final pass either;
 //   * the radix twiddles are kept UNPACKED (36 bytes in three planes, in LDS or -- 1024-row tiles -- global memory):
 //     three loads per use instead of two loads and a 27-instruction unpack, three times per radix-4 group.
+// The extending pass 0 (ntt29_extend_pass_kernel, the template flag EXT of the pass body; h2_coeff_to_extended_device):
+//   coeff_to_extended is "pad the n coefficients with zeros to 2^ext_k, multiply element i by zeta^i, transform".  As
+//   two launches that writes a column that is mostly zeros and reads it back.  Pass 0 loads its tile straight from HBM
+//   into registers, so the padding and the factor ride on that load: the source is a separate, read-only buffer of
+//   columns of n elements (any stride >= n); a tile element whose SOURCE INDEX -- i_first + cc + (j << log_inner) in a
+//   non-final pass 0 (log_outer = 0: the tile's in_base is i_first), j in a one-pass plan -- is >= n is zero and is not
+//   loaded; a loaded one with index = 1, 2 mod 3 is multiplied by zeta, zeta^2 (zeta^3 = 1: at most 2n/3 products per
+//   column, the only extra arithmetic).  Everything behind the load is the plain pass; later passes ARE the plain
+//   kernel.  The plain kernel is its own instantiation (EXT = false): same registers and occupancy as before the flag
+//   existed (profiles/coeff_to_extended_resources.txt).  The butterflies on known zeros are NOT skipped (with 2^e-fold
+//   padding the first e stages are copies times twiddles): not built, not measured.
 // LDS: 36 bytes per element in three planes (two of 16 bytes, one of 4: ds_read_b128 x 2 + ds_read_b32).
 #pragma once
 #include "h2_field29.hpp"
@@ -137,12 +158,23 @@ __global__ void __launch_bounds__(64) ntt_canon29_kernel(int32_t* canon) {
   }
 }
 
+// What the EXTENDING pass 0 takes besides the plain pass's arguments (EvaluationDomain::coeff_to_extended in one call,
+// ntt29_extend_launch): the source is another buffer of shorter columns, zero beyond them, times zeta^i on the way in.
 template <class FP>
-__global__ void __launch_bounds__(1024)
-ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
-                  const uint32_t* __restrict__ radix /* this pass's unpacked radix twiddles */,
-                  const int32_t* __restrict__ canon, NttPass P, size_t col_stride /* elements */,
-                  Fe<FP> scale29 /* R' form, canonical; used when P.has_scale */) {
+struct NttExtend {
+  size_t src_stride;   // elements between the source's columns
+  uint32_t n;          // the source's length: a tile element whose source index is >= n is zero and is not loaded
+  Fe<FP> z1, z2;       // zeta and zeta^2 (zeta^3 = 1), R' form, canonical
+};
+
+// The pass.  EXT = false is the transform as it always was (ntt29_pass_kernel: its code does not depend on anything
+// below that is `if constexpr (EXT)`); EXT = true is pass 0 of an extending transform (ntt29_extend_pass_kernel).
+template <class FP, bool EXT>
+__device__ __forceinline__ void
+ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
+                const uint32_t* __restrict__ radix /* this pass's unpacked radix twiddles */,
+                const int32_t* __restrict__ canon, const NttPass& P, size_t col_stride /* elements */,
+                const Fe<FP>& scale29 /* R' form, canonical; used when P.has_scale */, const NttExtend<FP>* X) {
   extern __shared__ U128 lds[];
   const uint32_t R = 1u << P.log_r, C = 1u << P.log_c;
   const uint32_t RC = R * C;
@@ -184,6 +216,8 @@ ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U12
   }
   src += 2 * in_base;
   dst += 2 * out_base;
+  [[maybe_unused]] const U128* xsrc = nullptr;          // EXT: this block's source column (read only through load_el)
+  if constexpr (EXT) xsrc = in + 2 * X->src_stride * blockIdx.y;
 
   auto lds_put = [&](uint32_t i, const Fe29<FP>& u) {
     tile0[i] = U128{(uint32_t)u.v[0], (uint32_t)u.v[1], (uint32_t)u.v[2], (uint32_t)u.v[3]};
@@ -274,8 +308,21 @@ ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U12
     g[1] = U128{r.v[4], r.v[5], r.v[6], r.v[7]};
   };
   // element j of column cc of the tile, as the API's bytes (x 2^256 = the R' form of x / 32): one of the two shifts is 0
+  // EXT: pass 0 reads the SOURCE (log_outer = 0, so in_base = i_first; a one-pass plan has one tile and one column):
+  // element `si` of the source column, nothing where si >= n, times zeta^(si mod 3) -- the one extra product, on at
+  // most 2n/3 elements of a column.  x is canonical API data (an operand like any unpacked value), zeta's limbs are
+  // canonical: the product is in (-p, p/128], normalised (fe29_mul's contract; the header's magnitude paragraph)
   auto load_el = [&](uint32_t j, uint32_t cc) {
-    return fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
+    if constexpr (EXT) {
+      const uint32_t si = P.is_final ? j : i_first + cc + (j << P.log_inner);
+      if (si >= X->n) return Fe29<FP>::zero();
+      const Fe29<FP> x = fe29_unpack(fe_load<FP>(xsrc + 2 * (size_t)si));
+      const uint32_t r = si % 3;
+      if (r == 0) return x;
+      return fe29_mul(x, fe29_unpack(r == 1 ? X->z1 : X->z2));
+    } else {
+      return fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
+    }
   };
   // one radix-4 group (two fused radix-2 stages s, s + 1) of elements e0..e3 at LDS distance `step`
   auto radix4 = [&](Fe29<FP>& e0, Fe29<FP>& e1, Fe29<FP>& e2, Fe29<FP>& e3, uint32_t s, uint32_t pos) {
@@ -387,6 +434,22 @@ ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U12
   }
 }
 
+template <class FP>
+__global__ void __launch_bounds__(1024)
+ntt29_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
+                  const uint32_t* __restrict__ radix, const int32_t* __restrict__ canon, NttPass P,
+                  size_t col_stride /* elements */, Fe<FP> scale29) {
+  ntt29_pass_body<FP, false>(in, out, tw, radix, canon, P, col_stride, scale29, nullptr);
+}
+// pass 0 of an extending transform: `in` is the source (X.src_stride, X.n), `out` has columns of col_stride = 2^P.log_n
+template <class FP>
+__global__ void __launch_bounds__(1024)
+ntt29_extend_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
+                         const uint32_t* __restrict__ radix, const int32_t* __restrict__ canon, NttPass P,
+                         size_t col_stride /* elements */, NttExtend<FP> X) {
+  ntt29_pass_body<FP, true>(in, out, tw, radix, canon, P, col_stride, Fe<FP>::zero(), &X);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 inline size_t ntt29_lds_bytes(const NttPass& P) {
   const size_t rc = (size_t)1 << (P.log_r + P.log_c), r = (size_t)1 << P.log_r;
@@ -406,13 +469,12 @@ inline bool ntt29_tw_global(const NttPass& P) {
 // with that constant (ntt29_build_tables(..., scale))
 inline bool ntt29_scale_in_table(uint32_t log_n) { return ntt_make_plan(log_n).npass == 2; }
 
-// Enqueue the transform of m columns (column stride = n elements) on `stream`; data in place, scratch m*n elements
-// when the plan has more than one pass; `tables` from ntt29_build_tables; scale (optional) in the API's Montgomery
-// form -- with ntt29_scale_in_table(log_n) the tables must carry it.
+// The passes of one transform of m columns: `in` -> (scratch ->) `out`, columns of n elements in scratch and out.
+// ext = null: the plain transform, in's columns are n apart too (ntt29_launch passes in = out).  ext: pass 0 is the
+// extending kernel and reads ext->n elements per column, ext->src_stride apart; the later passes are the plain ones.
 template <class FP>
-inline hipError_t ntt29_launch(U128* data, U128* scratch, const void* tables, uint32_t log_n, size_t m,
-                               hipStream_t stream, const Fe<FP>* scale = nullptr) {
-  if (log_n == 0 || m == 0) return hipSuccess;
+inline hipError_t ntt29_launch_passes(const U128* in, U128* out, U128* scratch, const void* tables, uint32_t log_n, size_t m,
+                                      hipStream_t stream, const Fe<FP>* scale, const NttExtend<FP>* ext) {
   NttPlan pl = ntt_make_plan(log_n);
   const NttTables tb = ntt29_tables(log_n);
   const U128* tw = (const U128*)tables;
@@ -424,9 +486,9 @@ inline hipError_t ntt29_launch(U128* data, U128* scratch, const void* tables, ui
   for (int p = 0; p < pl.npass; p++) {
     const U128* src;
     U128* dst;
-    if (pl.npass == 1) { src = data; dst = data; }
-    else if (p == 0) { src = data; dst = scratch; }
-    else if (p == pl.npass - 1) { src = scratch; dst = data; }
+    if (pl.npass == 1) { src = in; dst = out; }
+    else if (p == 0) { src = in; dst = scratch; }
+    else if (p == pl.npass - 1) { src = scratch; dst = out; }
     else { src = scratch; dst = scratch; }
     dim3 grid(pl.tiles[p], (unsigned)m);
     NttPass P = pl.pass[p];
@@ -434,16 +496,51 @@ inline hipError_t ntt29_launch(U128* data, U128* scratch, const void* tables, ui
     P.tw_global = ntt29_tw_global(P) ? 1u : 0u;
     const uint32_t* radix = (const uint32_t*)((const char*)tables + tb.off_radix[p]);
     static const size_t lds_pad = (size_t)tune_int("H2_TUNE_NTT_LDS_PAD", 0);      // tuning builds: fewer blocks per CU
-    hipLaunchKernelGGL(ntt29_pass_kernel<FP>, grid, dim3(pl.threads[p]), std::min<size_t>(ntt29_lds_bytes(P) + lds_pad, 160 * 1024), stream, src, dst, tw, radix,
-                       canon, P, n, sc);
+    const size_t lds = std::min<size_t>(ntt29_lds_bytes(P) + lds_pad, 160 * 1024);
+    if (ext && p == 0)
+      hipLaunchKernelGGL(ntt29_extend_pass_kernel<FP>, grid, dim3(pl.threads[p]), lds, stream, src, dst, tw, radix, canon, P, n,
+                         *ext);
+    else
+      hipLaunchKernelGGL(ntt29_pass_kernel<FP>, grid, dim3(pl.threads[p]), lds, stream, src, dst, tw, radix, canon, P, n, sc);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
+// Enqueue the transform of m columns (column stride = n elements) on `stream`; data in place, scratch m*n elements
+// when the plan has more than one pass; `tables` from ntt29_build_tables; scale (optional) in the API's Montgomery
+// form -- with ntt29_scale_in_table(log_n) the tables must carry it.
+template <class FP>
+inline hipError_t ntt29_launch(U128* data, U128* scratch, const void* tables, uint32_t log_n, size_t m,
+                               hipStream_t stream, const Fe<FP>* scale = nullptr) {
+  if (log_n == 0 || m == 0) return hipSuccess;
+  return ntt29_launch_passes<FP>(data, data, scratch, tables, log_n, m, stream, scale, nullptr);
+}
+// EvaluationDomain::coeff_to_extended: m source columns of 2^log_src coefficients, src_stride elements apart ->
+// out[c][i] = sum_j src[c][j] zeta^j w^(ij) over 2^log_n >= 2^log_src points (zeta^3 = 1, API Montgomery form; tables
+// of (w, log_n), unscaled).  Out of place: src is only read; scratch m * 2^log_n elements when the plan has more
+// than one pass.  No padded column exists anywhere: pass 0 does not load what would be its zeros.  log_n >= 1.
+template <class FP>
+inline hipError_t ntt29_extend_launch(const U128* src, size_t src_stride, uint32_t log_src, const Fe<FP>& zeta, U128* out,
+                                      U128* scratch, const void* tables, uint32_t log_n, size_t m, hipStream_t stream) {
+  if (m == 0) return hipSuccess;
+  if (log_n == 0 || log_src > log_n) return hipErrorInvalidValue;
+  NttExtend<FP> X;
+  X.src_stride = src_stride;
+  X.n = 1u << log_src;
+  X.z1 = zeta;
+  X.z2 = fe_mul(zeta, zeta);
+  for (int d = 0; d < 5; d++) {                         // x 2^256 -> x 2^261
+    X.z1 = fe_dbl(X.z1);
+    X.z2 = fe_dbl(X.z2);
+  }
+  return ntt29_launch_passes<FP>(src, out, scratch, tables, log_n, m, stream, nullptr, &X);
+}
 template <class FP>
 inline hipError_t ntt29_kernel_setup() {
-  return hipFuncSetAttribute((const void*)ntt29_pass_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t e = hipFuncSetAttribute((const void*)ntt29_pass_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)ntt29_extend_pass_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 // `tables`: ntt29_tables(log_n).total bytes.  scale (API Montgomery form) or null.
 template <class FP>

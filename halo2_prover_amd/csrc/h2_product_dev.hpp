@@ -109,6 +109,16 @@ struct Dev {
     if (scale) limbs(*scale, sc);
     st_ok(ntt_enqueue(*c, H2_BN254, a, m, w, log_n, on ? on : s, scale ? sc : nullptr), "ntt_enqueue");
   }
+  // m columns of 2^log_n coefficients (stride `stride` elements) -> their 2^ext_log_n values on the coset zeta <ext_omega>
+  // in `out` (another buffer): one call, the zero padding never written or read (h2_ntt29.hpp's extending pass 0)
+  void extend(Col in, size_t stride, uint32_t log_n, size_t m, const Fr& zeta, const Fr& ext_omega, uint32_t ext_log_n, Col out,
+              hipStream_t on = nullptr) {
+    uint64_t z[4], w[4];
+    limbs(zeta, z);
+    limbs(ext_omega, w);
+    st_ok(coeff_to_extended_enqueue(*c, H2_BN254, in, stride, log_n, m, z, w, ext_log_n, out, on ? on : s),
+          "coeff_to_extended_enqueue");
+  }
   // `on` waits for the accumulate kernel of the MSM enqueued last on this context (commit_begin)
   void wait_msm_tail(hipStream_t on) {
     if (c->tail_recorded && c->tail_wait) hip_ok(hipStreamWaitEvent(on, c->tail_wait, 0), "hipStreamWaitEvent(tail)");

@@ -12,7 +12,8 @@
 //   * poly_eval_kernels      all evaluations of the group (different polynomials at different points) in two launches
 //   * lincomb_batch_kernel   out_j = sum_t c_t a_t for a list of jobs (lincomb_kernel, up to 24 columns of one sum by
 //                            value, serves setup, keygen and the verifiers)
-//   * coset_extend / coset_shrink   the zero-extension and the zeta^i scaling around the extended-domain NTTs
+//   * coset_shrink           the zeta^-i scaling of the kept prefix after the inverse extended-domain NTT (the way in,
+//                            zero-extension and zeta^i, is pass 0 of the extending NTT: h2_ntt29.hpp)
 //   * scale_kernel, sub_prefix_kernel   a column times a constant; a remainder's low coefficients subtracted
 // All HBM-bound elementwise work except expr_kernel (a few hundred field products per row).
 // The prover's kernels take grid.y = job or proof and read what differs between jobs -- a handful of pointers and
@@ -71,23 +72,6 @@ scatter_cells_kernel(U128* __restrict__ base, size_t col_stride /* elements */, 
   dst[1] = vals[2 * i + 1];
 }
 
-// out[c][i] = i < n ? in[c][i] * zeta^i : 0 for i < en   (zeta^3 = 1: the factor is one of three constants)
-static __global__ void __launch_bounds__(256)
-coset_extend_kernel(const U128* __restrict__ in, size_t in_stride, U128* __restrict__ out, uint32_t n, uint32_t en, F z1,
-                    F z2) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= en) return;
-  const U128* src = in + 2 * in_stride * blockIdx.y;
-  U128* dst = out + 2 * (size_t)en * blockIdx.y;
-  F v = F::zero();
-  if (i < n) {
-    v = fe_load<FR>(src + 2 * (size_t)i);
-    const uint32_t r = i % 3;
-    if (r == 1) v = fe_mul(v, z1);
-    else if (r == 2) v = fe_mul(v, z2);
-  }
-  fe_store<FR>(dst + 2 * (size_t)i, v);
-}
 // grid.y = proof: out[p][i] = in[p][i] * zinv^i for i < count (after the inverse extended NTT) -- the n (d-1) kept
 // coefficients of every proof's quotient, written compactly (out_stride = count) from the extended columns (in_stride = en)
 static __global__ void __launch_bounds__(256)

@@ -7,6 +7,7 @@ constructed inside keygen / create_proof reached from /root/reference/circuits/s
                                 omega / extended_omega from ROOT_OF_UNITY, g_coset = ZETA (a cube root of unity)
     lagrange_to_coeff(a)        ifft: best_fft(a, omega^-1, k) then * n^-1
     coeff_to_extended(a)        zero-extend to 2^extended_k, a[i] *= g_coset^i, best_fft(a, extended_omega)
+                                (h2_coeff_to_extended_device: one call, the padded column is never built)
     extended_to_coeff(a)        ifft on the extended domain, a[i] *= g_coset^-i, truncate to n (j-1)
     divide_by_vanishing_poly(a) a[i] *= t_evaluations[i mod 2^(extended_k-k)],  t_i = 1 / ((zeta w_ext^i)^n - 1)
 
@@ -111,17 +112,16 @@ class EvaluationDomain:
         return a
 
     def coeff_to_extended(self, a):
-        """returns a new (..., 2^extended_k, 4) tensor: evaluations of a on the coset g * <extended_omega>"""
+        """returns a new (..., 2^extended_k, 4) tensor: evaluations of a on the coset g * <extended_omega> (one call:
+        the zero padding and the g^i factor ride on the first NTT pass's load, no padded column is built)"""
         import torch
         m = self._shape(a, self.n)
         en = 1 << self.extended_k
-        out = torch.zeros(a.shape[:-2] + (en, 4), dtype=torch.int64, device=a.device)
-        out[..., : self.n, :] = a
-        ptr = ctypes.c_void_p(out.data_ptr())
-        _lib.check(self._L.h2_poly_coset_device(self.curve, ptr, en, m, self._m["g_coset"].ctypes.data, self._stream()),
-                   "h2_poly_coset_device")
-        _lib.check(self._L.h2_ntt_device(self.curve, ptr, m, self._m["extended_omega"].ctypes.data, self.extended_k,
-                                         self._stream()), "h2_ntt_device")
+        out = torch.empty(a.shape[:-2] + (en, 4), dtype=torch.int64, device=a.device)
+        st = self._L.h2_coeff_to_extended_device(self.curve, ctypes.c_void_p(a.data_ptr()), self.n, self.k, m,
+                                                 self._m["g_coset"].ctypes.data, self._m["extended_omega"].ctypes.data,
+                                                 self.extended_k, ctypes.c_void_p(out.data_ptr()), self._stream())
+        _lib.check(st, "h2_coeff_to_extended_device")
         return out
 
     def extended_to_coeff(self, a):

@@ -170,6 +170,23 @@ int h2_ntt_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t omega[4]
 /* best_fft followed by a[i] *= scale, fused into the last pass: EvaluationDomain::ifft(a, omega_inv, k, n^-1) */
 int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n,
                          const uint64_t scale[4], void* stream);
+/* EvaluationDomain::coeff_to_extended.  m columns of n = 2^log_n coefficients, column stride col_stride elements
+ * (col_stride >= n), over the SCALAR field of `curve`  ->  m columns of 2^ext_log_n values, column stride 2^ext_log_n:
+ *   out[c][i] = sum_{j < n} in[c][j] * z[j mod 3] * ext_omega^(i*j),   z = {1, zeta, zeta^2}
+ * i.e. halo2's distribute_powers_zeta (for zeta^3 = 1 this is zeta^j) then best_fft on the zero-extended column.
+ * Out of place: the source is read only, d_out must not overlap it.  Canonical output, natural order.
+ * Asynchronous on `stream`.
+ * The zero-extended column is never written or read: the first NTT pass loads the n coefficients from the source,
+ * multiplies by zeta^j on the way in and treats the rest of its tile as zero -- no pad, copy or coset launch.  Stream
+ * and scratch rules are h2_ntt_device's (the same twiddle tables, keyed by (ext_omega, ext_log_n); a multi-pass plan
+ * uses the stream's second buffer of m * 2^ext_log_n elements); no other device memory is allocated.
+ * H2_EINVAL -- checked on the host before anything is enqueued -- for: a null pointer with m > 0, ext_log_n < log_n,
+ * ext_log_n > 30 (h2_ntt_device's limit), col_stride < n, m > 65535, byte ranges of source and destination that
+ * overlap.  m = 0 is H2_OK and enqueues nothing; ext_log_n == log_n is legal (a coset shift plus an out-of-place NTT).
+ * h2_version() did not change for this entry point: a host detects it by its symbol, as with h2_generate_proofs. */
+int h2_coeff_to_extended_device(h2_curve_t curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
+                                const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n,
+                                void* d_out, void* stream);
 /* a[i] *= c */
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream);
 /* a[i] *= g^i : distribute_powers_zeta / the coset shift before an extended-domain NTT (and its inverse) */

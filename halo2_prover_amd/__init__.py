@@ -5,5 +5,5 @@ package does not touch the GPU; the first compute call (or `init()`) binds the p
 one device.  There is no CPU fallback.
 """
 from .api import (Bases, ParamsKZG, best_fft, best_fft_batch, best_fft_group, best_multiexp, generate_proofs, init,  # noqa: F401
-                  ntt_device, points_decompress_device, verify_proofs)
+                  msm_points, msm_points_device, msm_points_plan, ntt_device, points_decompress_device, verify_proofs)
 from .lib import CURVES, H2Error, LIB_PATH, SYMBOLS, load  # noqa: F401

@@ -168,7 +168,8 @@ def init_devices(device_ids):
 
 def best_multiexp(coeffs, bases, curve="bn254"):
     """best_multiexp(coeffs, bases) -> Jacobian point (12 limbs).  One-shot form: registers the
-    bases, runs the MSM and releases them (use `Bases` / `ParamsKZG` to keep an SRS resident)."""
+    bases, runs the MSM and releases them (use `Bases` / `ParamsKZG` to keep an SRS resident).  `msm_points` computes
+    the same sum without building a table, for bases that are used once."""
     coeffs = _as_u64(coeffs, 4, "coeffs")
     bases = _as_u64(bases, 8, "bases")
     if coeffs.shape[0] != bases.shape[0]:
@@ -180,6 +181,40 @@ def best_multiexp(coeffs, bases, curve="bn254"):
         return b.msm(coeffs)
     finally:
         b.release()
+
+
+def msm_points(coeffs, bases, curve="bn254"):
+    """sum_i coeffs[i] * bases[i] -> Jacobian point (12 limbs) for bases that are NOT registered (h2_msm_points): a
+    table-free bucket MSM, nothing is kept.  The points are not checked to be on the curve."""
+    _ensure_init()
+    coeffs = _as_u64(coeffs, 4, "coeffs")
+    bases = _as_u64(bases, 8, "bases")
+    if coeffs.shape[0] != bases.shape[0]:
+        raise ValueError("msm_points: coeffs.len() != bases.len() (%d vs %d)" % (coeffs.shape[0], bases.shape[0]))
+    n = coeffs.shape[0]
+    out = np.zeros(12, dtype=np.uint64)
+    st = _lib.load().h2_msm_points(_curve_id(curve), bases.ctypes.data if n else None, coeffs.ctypes.data if n else None,
+                                   n, out.ctypes.data)
+    _lib.check(st, "h2_msm_points")
+    return out
+
+
+def msm_points_device(d_points, d_scalars, n, col_stride, m, d_out_jac, stream=0, curve="bn254"):
+    """Device-resident form (h2_msm_points_device): n affine points, m scalar columns col_stride elements apart -> m
+    Jacobian points; asynchronous on `stream`."""
+    _ensure_init()
+    st = _lib.load().h2_msm_points_device(_curve_id(curve), ctypes.c_void_p(d_points), ctypes.c_void_p(d_scalars), n,
+                                          col_stride, m, ctypes.c_void_p(d_out_jac), ctypes.c_void_p(stream))
+    _lib.check(st, "h2_msm_points_device")
+
+
+def msm_points_plan(n, curve="bn254"):
+    """Geometry h2_msm_points* would use for n terms (host only)."""
+    p = _lib.MsmPointsPlan()
+    _lib.check(_lib.load().h2_msm_points_plan(_curve_id(curve), n, ctypes.byref(p)), "h2_msm_points_plan")
+    return {"window_bits": p.window_bits, "windows": p.windows, "buckets": p.buckets, "route": p.route,
+            "scalar_bits": p.scalar_bits, "lds_bytes": p.lds_bytes, "lds_limit": p.lds_limit, "crossover": p.crossover,
+            "max_n": p.max_n, "width": list(p.width[:p.windows]), "offset": list(p.offset[:p.windows])}
 
 
 def best_fft(a, omega, log_n, curve="bn254"):

@@ -330,6 +330,86 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
   return H2_OK;
 }
 
+// ---- table-free MSM over the caller's points (h2_msm_points.hpp) ---------------------------------------------------
+// terms below which a call takes msm_small_kernel's double-and-add route; moved only by
+// h2_selftest_set_msm_points_small_max (tests, tools/msm_points_bench.py)
+static size_t g_points_small_max = MSM_POINTS_SMALL_MAX;
+
+static void guard_inspect_note(const MsmWorkspace& ws, const std::vector<uint32_t>& bad, size_t n, size_t m, const char* what) {
+  g_guard_launches++;
+  for (uint32_t r = 0; r < ws.n_regions; r++)
+    if (bad[r]) {
+      if (!g_guard_violations)
+        g_guard_first = std::string(ws.regions[r].name) + ": " + std::to_string(bad[r]) + " byte(s) behind the region, n=" +
+                        std::to_string(n) + " m=" + std::to_string(m) + what;
+      g_guard_violations++;
+    }
+}
+
+// arguments checked by the caller; n >= 1, m >= 1
+static int msm_points_run(DevCtx& c, int curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride,
+                          size_t m, void* d_out, hipStream_t stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (n < g_points_small_max) {
+    // short inputs: one quad per term, m jobs side by side in groups of MSM_SMALL_MAX; the partials live in the MSM workspace
+    const size_t blocks = (n + 15) / 16, work = MSM_SMALL_MAX * (blocks * (XYZZ29_WORDS * 4) + 4);
+    for (size_t j0 = 0; j0 < m; j0 += MSM_SMALL_MAX) {
+      const uint32_t count = (uint32_t)std::min<size_t>(MSM_SMALL_MAX, m - j0);
+      ArenaLease lease(c.msm_ws.of(stream), work, stream);
+      if (lease.rc != H2_OK) return lease.rc;
+      const void* pts[MSM_SMALL_MAX];
+      const void* sc[MSM_SMALL_MAX];
+      uint32_t len[MSM_SMALL_MAX];
+      for (uint32_t j = 0; j < count; j++) {
+        pts[j] = d_points;
+        sc[j] = (const char*)d_scalars + (j0 + j) * col_stride * 32;
+        len[j] = (uint32_t)n;
+      }
+      hipError_t e = ops->msm_small(pts, sc, len, count, lease.a.p, (char*)d_out + j0 * 96, stream);
+      if (e != hipSuccess) return dev_fail(e, "msm_small_kernel");
+      if (int rc = lease.release(); rc != H2_OK) return rc;
+    }
+    return H2_OK;
+  }
+  const MsmGeom g = msm_points_geometry(n, ops->scalar_bits);
+  const size_t group = msm_points_cols_per_launch(g, n);
+  if (group == 0) return H2_EINVAL;
+  for (size_t j0 = 0; j0 < m; j0 += group) {
+    const size_t mm = std::min(group, m - j0);
+    const MsmWorkspace ws = msm_points_workspace(n, mm, g, g_msm_guard ? 256u : 0u);
+    ArenaLease lease(c.msm_ws.of(stream), ws.total, stream);
+    if (lease.rc != H2_OK) return lease.rc;
+    Arena& A = lease.a;
+    // every kernel's index range against the region it indexes, before anything is enqueued
+    if (const char* broken = msm_points_check(ws, g, n, mm, col_stride, A.bytes)) {
+      g_h2.last_error = std::string("msm points launch geometry: ") + broken;
+      return H2_EDEVICE;
+    }
+    if (g_msm_guard) H2_TRY(hipMemsetAsync(A.p, MSM_GUARD_BYTE, ws.total, stream));
+    // the previous launch sequence on this workspace (of either kind) left its counter region zero
+    const bool zeroed = !g_msm_guard && lease.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
+    hipError_t e = ops->msm_points_launch(d_points, (const char*)d_scalars + j0 * col_stride * 32, n, col_stride, mm, g, (char*)A.p, ws,
+                                          stream, (char*)d_out + j0 * 96, zeroed);
+    if (e != hipSuccess) return dev_fail(e, "msm_points_launch");
+    if (!g_msm_guard) {
+      A.clean_off = ws.off_misc;
+      A.clean_bytes = ws.zero_bytes;
+    } else {
+      void* d_bad = nullptr;
+      if (int rc = device_alloc(&d_bad, ws.n_regions * 4, "guard"); rc != H2_OK) return rc;
+      DeviceBuffer owner(d_bad);
+      std::vector<uint32_t> bad(ws.n_regions, 0);
+      H2_TRY(hipMemsetAsync(d_bad, 0, ws.n_regions * 4, stream));
+      hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)A.p, ws, (uint32_t*)d_bad);
+      H2_TRY(hipMemcpyAsync(bad.data(), d_bad, ws.n_regions * 4, hipMemcpyDeviceToHost, stream));
+      H2_TRY(hipStreamSynchronize(stream));
+      guard_inspect_note(ws, bad, n, mm, " points front");
+    }
+    if (int rc = lease.release(); rc != H2_OK) return rc;
+  }
+  return H2_OK;
+}
+
 // ---- NTT -----------------------------------------------------------------------------------
 static int get_twiddles(DevCtx& c, const CurveOps* ops, const uint64_t omega[4], uint32_t log_n, const uint64_t* scale,
                         const void** out) {
@@ -756,6 +836,64 @@ int h2_msm_batch(h2_curve_t curve, uint64_t handle, const uint64_t* const* scala
   return msm_host(curve, handle, scalars, n, m, out_affine, true);
 }
 
+int h2_msm_points_plan(h2_curve_t curve, size_t n, h2_msm_points_plan_t* out) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!curve_ok((int)curve) || !out || n > MSM_POINTS_MAX_N) return H2_EINVAL;
+  const MsmGeom g = msm_points_geometry(n ? n : 1, ops_of((int)curve)->scalar_bits);
+  memset(out, 0, sizeof *out);
+  out->window_bits = g.c;
+  out->windows = g.W;
+  out->buckets = g.B;
+  out->route = n < g_points_small_max ? 0u : 1u;
+  out->scalar_bits = g.nbits;
+  out->lds_bytes = (uint32_t)((size_t)g.W * g.B * 4);
+  out->lds_limit = (uint32_t)MSM_POINTS_LDS_CAP;
+  out->crossover = (uint64_t)g_points_small_max;
+  out->max_n = (uint64_t)MSM_POINTS_MAX_N;
+  for (uint32_t w = 0; w < g.W; w++) {
+    out->width[w] = g.width[w];
+    out->offset[w] = g.off[w];
+  }
+  return H2_OK;
+}
+
+int h2_msm_points_device(h2_curve_t curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride, size_t m,
+                         void* d_out_jac, void* stream_) {
+  Call k(stream_);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!curve_ok((int)curve) || col_stride < n || n > MSM_POINTS_MAX_N) return H2_EINVAL;
+  if (((uintptr_t)d_points & 15) || ((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_jac & 15)) return H2_EINVAL;
+  if (m > 0 && (!d_out_jac || (n > 0 && (!d_points || !d_scalars)))) return H2_EINVAL;
+  if (k.rc != H2_OK) return k.rc;
+  if (m == 0) return H2_OK;
+  if (n == 0) {
+    H2_TRY(hipMemsetAsync(d_out_jac, 0, m * 96, k.stream));
+    return H2_OK;
+  }
+  return msm_points_run(*k.c, (int)curve, d_points, d_scalars, n, col_stride, m, d_out_jac, k.stream);
+}
+
+int h2_msm_points(h2_curve_t curve, const uint64_t* points, const uint64_t* scalars, size_t n, uint64_t out_jac[12]) {
+  Call k(nullptr);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!curve_ok((int)curve) || n > MSM_POINTS_MAX_N || !out_jac || (n > 0 && (!points || !scalars))) return H2_EINVAL;
+  if (k.rc != H2_OK) return k.rc;
+  if (n == 0) {
+    memset(out_jac, 0, 96);
+    return H2_OK;
+  }
+  DevCtx& c = *k.c;
+  const size_t off_sc = h2_align256(n * 64), off_res = off_sc + h2_align256(n * 32);
+  ArenaLease stage(c.stage, off_res + 96, c.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  char* base = (char*)c.stage.p;
+  H2_TRY(hipMemcpyAsync(base, points, n * 64, hipMemcpyHostToDevice, c.stream));
+  H2_TRY(hipMemcpyAsync(base + off_sc, scalars, n * 32, hipMemcpyHostToDevice, c.stream));
+  if (int rc = msm_points_run(c, (int)curve, base, base + off_sc, n, n, 1, base + off_res, c.stream); rc != H2_OK) return rc;
+  H2_TRY(hipMemcpyAsync(out_jac, base + off_res, 96, hipMemcpyDeviceToHost, c.stream));
+  return stage.wait();
+}
+
 int h2_srs_generate(h2_curve_t curve, const uint64_t s[4], size_t n, void* d_out_affine, void* stream_) {
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
@@ -1180,6 +1318,31 @@ extern "C" int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t
     g_h2.last_error = std::string("msm launch geometry: ") + broken;
     return H2_EINVAL;
   }
+  return H2_OK;
+}
+// host only: the layout and the bounds proof of a table-free launch (h2_msm_points*) of m columns of n scalars, as
+// msm_points_run makes them; out: include/h2hip_selftest.h
+extern "C" int h2_selftest_msm_points_check(int curve, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!curve_ok(curve) || !out || n == 0 || m == 0 || n > MSM_POINTS_MAX_N) return H2_EINVAL;
+  if (col_stride < n) { g_h2.last_error = "msm points launch geometry: col_stride >= n"; return H2_EINVAL; }
+  const MsmGeom g = msm_points_geometry(n, ops_of(curve)->scalar_bits);
+  // as msm_points_run: a batch wider than one launch runs in column groups; the first (widest) group is checked
+  const size_t group = msm_points_cols_per_launch(g, n);
+  if (group == 0) return H2_EINVAL;
+  if (m > group) m = group;
+  const MsmWorkspace ws = msm_points_workspace(n, m, g, guard ? 256u : 0u);
+  out[0] = g.c; out[1] = g.W; out[2] = g.B; out[3] = ws.tile; out[4] = (uint64_t)g.W * g.B * 4; out[5] = m;
+  out[6] = ws.T; out[7] = ws.n_regions;
+  if (const char* broken = msm_points_check(ws, g, n, m, col_stride, ws.total)) {
+    g_h2.last_error = std::string("msm points launch geometry: ") + broken;
+    return H2_EDEVICE;
+  }
+  return H2_OK;
+}
+extern "C" int h2_selftest_set_msm_points_small_max(size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  h2::g_points_small_max = n == SIZE_MAX ? MSM_POINTS_SMALL_MAX : n;
   return H2_OK;
 }
 // host only: the sort front of a launch of m columns of n scalars against n_bases bases, laid out as msm_device_run

@@ -30,6 +30,7 @@ using FB = typename CV::Base;
 hipError_t kernel_setup() {
   hipError_t e = msm_kernel_setup<CV>();
   if (e != hipSuccess) return e;
+  if ((e = msm_points_kernel_setup<CV>()) != hipSuccess) return e;
   return ntt29_kernel_setup<FS>();
 }
 hipError_t table_build(const void* d_bases, void* d_table, void* d_scratch, uint32_t n, const MsmGeom& g, uint32_t* d_bad, hipStream_t s) {
@@ -42,6 +43,10 @@ hipError_t msm_launch_(const void* d_table, const void* const* per_column, uint3
                        hipEvent_t ev_stop, hipEvent_t ev_tail, void* d_out_jac, bool zeroed) {
   return msm_launch<CV>((const U128*)d_table, (const U128* const*)per_column, n_bases, (const U128*)d_scalars, n, col_stride, m, g, ws_base, ws, s, ev_start,
                         ev_stop, ev_tail, (U128*)d_out_jac, zeroed);
+}
+hipError_t msm_points_launch_(const void* d_points, const void* d_scalars, size_t n, size_t col_stride, size_t m, const MsmGeom& g,
+                              char* ws_base, const MsmWorkspace& ws, hipStream_t s, void* d_out_jac, bool zeroed) {
+  return msm_points_launch<CV>((const U128*)d_points, (const U128*)d_scalars, n, col_stride, m, g, ws_base, ws, s, (U128*)d_out_jac, zeroed);
 }
 hipError_t srs_powers(void* d_out_affine, const uint64_t s_mont[4], uint32_t n, hipStream_t s) {
   Fe<FS> sv;
@@ -393,7 +398,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
   return carry ? -2 : 0;  // a carry out of the top window would lose value
 }
 
-const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_,    srs_powers, fixed_base_mul, msm_small,
+const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};

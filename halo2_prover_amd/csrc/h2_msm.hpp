@@ -1304,6 +1304,7 @@ struct MsmWorkspace {
   size_t off_counts, off_gcounts, off_offsets, off_tile_base, off_tile_hist, off_blocksums, off_ref, off_key, off_misc, off_bsum,
       off_head, off_tail, off_xsum, off_rc, off_part, off_done, off_tree2, off_hot_slot, off_hot_tasks, off_hot_part, off_hot_arrive, total;
   size_t off_cstart, off_group_base, off_mid_ref, off_mid_lo;   // two-level sort only
+  size_t off_points;    // table-free MSM only (h2_msm_points.hpp): the caller's points in the table's form
   size_t zero_bytes;    // misc + the counters behind it: cleared by one memset per launch
   uint32_t max_tasks;
   uint32_t guard;       // bytes of red zone behind every region (0 in the product path)
@@ -1322,8 +1323,16 @@ inline bool msm_use_sort2(size_t n, size_t m, const MsmGeom& g) {
   return fits && g.B > 4096;
 }
 
+// `pts` (the table-free MSM, h2_msm_points.hpp): the m columns are the VIRTUAL columns of pts->m real columns of
+// pts->W windows each (m = pts->m * pts->W, g the one-window geometry of a virtual column).  The sort front then tiles
+// the real columns -- a block decomposes each scalar once, for all its windows -- and scatters directly, and the arena
+// also holds the n points in the table's form.
+struct MsmPointsShape {
+  size_t m;      // real scalar columns
+  uint32_t W;    // windows of a scalar = virtual columns per real column
+};
 inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t guard = 0, size_t n_bases = 0,
-                                  bool allow_pack = true) {
+                                  bool allow_pack = true, const MsmPointsShape* pts = nullptr) {
   if (!n_bases) n_bases = n;
   MsmWorkspace ws{};
   ws.n = n;
@@ -1369,7 +1378,7 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
   ws.sort2 = msm_use_sort2(n, m, g) ? 1u : 0u;
   ws.s2 = msm_sort2_geom(n, g, allow_pack ? n_bases : 0);
   // digits / scatter tiling: about 1024 blocks over the launch, at least one wave of scalars per block
-  size_t tile = (n * m + 1023) / 1024;
+  size_t tile = (n * (pts ? pts->m : m) + 1023) / 1024;
   // a tile should carry a few entries per bucket, or zeroing / flushing the LDS histogram dominates
   const size_t dense = (size_t)2 * g.B / g.W;
   if (tile < dense) tile = dense;
@@ -1386,7 +1395,7 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
   ws.staged = 0;
   ws.stage_lds = 0;
   ws.pack = MsmStagePack{};
-  if (!ws.sort2) {
+  if (!ws.sort2 && !pts) {
     const size_t cap = MSM_STAGE_LDS_CAP;
     // (`allow_pack` = false, a test hook: the 4 + 2 byte entry even where the packed word fits.  At every geometry this
     // branch accepts today the fields fit -- B <= 8192 and tile * W <= ~40 K leave them within 30 bits -- so the hook is
@@ -1473,6 +1482,7 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
   ws.off_hot_tasks = region("hot tasks", (size_t)ws.max_tasks * 8);
   ws.off_hot_part = region("hot partials", (size_t)ws.max_tasks * (XYZZ29_WORDS * 4));
   ws.off_hot_arrive = region("hot arrivals", (size_t)ws.max_tasks * 4);
+  ws.off_points = pts ? region("packed points", n * 64) : 0;
   ws.total = o;
   return ws;
 }
@@ -1596,23 +1606,51 @@ inline hipError_t msm_kernel_setup() {
   return hipFuncSetAttribute((const void*)scan_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SCAN_LDS_MAX * 4));
 }
 
-// Enqueue m MSMs of n terms against `table` (built for n_bases points with geometry g); column j's scalars start
-// col_stride elements after column j-1's.
-// Result: m XYZZ points at ws_base + off_tree2.  ev_start / ev_stop (optional) bracket the
-// accumulate (chunk) kernel for the roofline measurement.
-template <class CV>
-inline hipError_t msm_launch(const U128* table, const U128* const* per_column /* host array of m tables, or null */,
-                             uint32_t n_bases, const U128* d_scalars, size_t n, size_t col_stride,
-                             size_t m, const MsmGeom& g, char* ws_base, const MsmWorkspace& ws, hipStream_t stream,
-                             hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, hipEvent_t ev_tail = nullptr,
-                             U128* d_out_jac = nullptr /* m Jacobian points in the API's form, written by the last kernel */,
-                             bool zeroed = false /* [off_misc, + zero_bytes) is zero already: the previous launch sequence on
-                                                    this workspace left it so (same off_misc, at least as many bytes) */) {
+// The launch sequence in steps: a sort front (msm_launch below: digits, scan, scatter; h2_msm_points.hpp has its own
+// digits and scatter), the scan between the front's two kernels, and the back -- everything behind the sorted entries --
+// which both fronts share.
+// Exclusive scan of the K per-key counts the digits kernel left in `gcounts` (one-level sort)
+inline void msm_launch_scan(char* ws_base, const MsmWorkspace& ws, hipStream_t stream) {
   uint32_t* counts = (uint32_t*)(ws_base + ws.off_counts);
   uint32_t* gcounts = (uint32_t*)(ws_base + ws.off_gcounts);
   uint32_t* offsets = (uint32_t*)(ws_base + ws.off_offsets);
-  uint32_t* tile_base = (uint32_t*)(ws_base + ws.off_tile_base);
   uint32_t* blocksums = (uint32_t*)(ws_base + ws.off_blocksums);
+  uint32_t* misc = (uint32_t*)(ws_base + ws.off_misc);
+  if (ws.K <= SCAN_LDS_MAX) {
+    uint32_t per = (uint32_t)((ws.K + 1023) / 1024);
+    per |= 1u;                                 // odd stride: the per-thread LDS walks do not collide on banks
+    hipLaunchKernelGGL(scan_lds_kernel, dim3(1), dim3(1024), ws.K * 4, stream, gcounts, offsets, (uint32_t)ws.K, per);
+  } else {
+    hipLaunchKernelGGL(msm_group_fold_kernel, dim3((unsigned)((ws.K + 255) / 256)), dim3(256), 0, stream, gcounts, counts, ws.K);
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)ws.nblk), dim3(256), 0, stream, counts, blocksums, ws.K);
+    hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(1024), 0, stream, blocksums, (uint32_t)ws.nblk, misc + 1);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)ws.nblk), dim3(256), 0, stream, counts, blocksums, offsets,
+                       ws.K);
+  }
+}
+
+// the keys pass's arguments (msm_keys_block): the pass runs after the scan, beside or behind the scatter
+inline MsmKeysArgs msm_keys_args(char* ws_base, const MsmWorkspace& ws) {
+  MsmKeysArgs a{};
+  a.chunk_first = (uint32_t*)(ws_base + ws.off_key);
+  a.hot_slot = (uint32_t*)(ws_base + ws.off_hot_slot);
+  a.tasks = (uint32_t*)(ws_base + ws.off_hot_tasks);
+  a.hot_arrive = (uint32_t*)(ws_base + ws.off_hot_arrive);
+  a.task_count = (uint32_t*)(ws_base + ws.off_misc);
+  a.max_tasks = ws.max_tasks;
+  a.T_host = ws.T;
+  return a;
+}
+
+// The back: the keys pass (unless the front's scatter ran it), accumulate, fix-up, bucket weights, final -- on the m
+// columns of the workspace, whose `offsets` and sorted entries the front has written.  An entry indexes `table` (or the
+// column's own table, `d_tables`).  Result: m XYZZ points at ws_base + off_tree2, and m Jacobian points at d_out_jac if
+// given.
+template <class CV>
+inline hipError_t msm_launch_back(const U128* table, const U128** d_tables, uint32_t log_b, size_t m, const MsmGeom& g,
+                                  char* ws_base, const MsmWorkspace& ws, const MsmKeysArgs& keys_args, bool keys_merged,
+                                  hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, hipEvent_t ev_tail, U128* d_out_jac) {
+  uint32_t* offsets = (uint32_t*)(ws_base + ws.off_offsets);
   uint32_t* sref = (uint32_t*)(ws_base + ws.off_ref);
   uint32_t* chunk_first = (uint32_t*)(ws_base + ws.off_key);
   uint32_t* misc = (uint32_t*)(ws_base + ws.off_misc);
@@ -1626,82 +1664,6 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
   uint32_t* hot_tasks = (uint32_t*)(ws_base + ws.off_hot_tasks);
   uint32_t* hot_part = (uint32_t*)(ws_base + ws.off_hot_part);
   uint32_t* hot_arrive = (uint32_t*)(ws_base + ws.off_hot_arrive);
-  hipError_t e;
-  if (per_column && m > MSM_MAX_MULTI) return hipErrorInvalidValue;
-  // one memset: misc (256 B) and the sort's counters behind it.  Nothing else needs clearing: every slot of bucket_sum /
-  // head / tail that a later kernel reads has been written by the accumulate kernel (the fix-up decides from
-  // `offsets` which slots exist).
-  if (!zeroed && (e = hipMemsetAsync(misc, 0, ws.zero_bytes, stream)) != hipSuccess) return e;
-  uint32_t* tile_hist = (ws.staged || ws.sort2) ? (uint32_t*)(ws_base + ws.off_tile_hist) : nullptr;
-  // the keys pass (msm_keys_block): after the scan, beside or behind the scatter
-  const U128** d_tables = nullptr;
-  uint32_t log_b = 0;
-  MsmKeysArgs keys_args{};
-  keys_args.chunk_first = chunk_first;
-  keys_args.hot_slot = hot_slot;
-  keys_args.tasks = hot_tasks;
-  keys_args.hot_arrive = hot_arrive;
-  keys_args.task_count = misc;
-  keys_args.max_tasks = ws.max_tasks;
-  keys_args.T_host = ws.T;
-  if (per_column) {
-    d_tables = (const U128**)(misc + 16);                          // 128 bytes of the 256-byte misc block
-    keys_args.n_tables = (uint32_t)m;
-    keys_args.tables_dst = d_tables;
-    for (size_t j = 0; j < m; j++) keys_args.tables.t[j] = per_column[j];
-    while ((1u << log_b) < g.B) log_b++;
-  }
-  bool keys_merged = false;
-  if (ws.sort2) {
-    const Sort2Geom& s2 = ws.s2;
-    const uint32_t H = s2.Hc * (uint32_t)m;
-    uint32_t* cstart = (uint32_t*)(ws_base + ws.off_cstart);
-    uint32_t* mid_ref = (uint32_t*)(ws_base + ws.off_mid_ref);
-    uint8_t* mid_lo = (uint8_t*)(ws_base + ws.off_mid_lo);
-    uint32_t* group_base = (uint32_t*)(ws_base + ws.off_group_base);
-    hipLaunchKernelGGL(msm2_count_kernel<CV>, dim3(s2.groups, (unsigned)m), dim3(S2_THREADS), (size_t)s2.Hc * 8, stream, d_scalars,
-                       gcounts, tile_base, tile_hist, group_base, (uint32_t)n, col_stride, s2, g);
-    hipLaunchKernelGGL(msm2_coarse_scan_kernel, dim3(1), dim3(1024), 0, stream, gcounts, cstart, H, offsets + ws.K);
-    hipLaunchKernelGGL(msm2_scatter_kernel<CV>, dim3(s2.tiles, (unsigned)m), dim3(S2_THREADS), msm_sort2_lds_scatter(s2, g), stream,
-                       d_scalars, cstart, tile_base, tile_hist, group_base, mid_ref, mid_lo, (uint32_t)n, col_stride, n_bases, s2, g);
-    hipLaunchKernelGGL(msm2_fine_kernel, dim3(H), dim3(S2_THREADS), msm_sort2_lds_fine(), stream, cstart, mid_ref, mid_lo, sref,
-                       offsets, s2.F, s2.lo_bits, s2.pack_shift);
-  } else {
-    const size_t lds = (size_t)g.B * 4;     // dynamic LDS limits were raised once per device by msm_kernel_setup
-    const uint32_t tiles = (uint32_t)((n + ws.tile - 1) / ws.tile);
-    const uint32_t sort_grid = msm_tile_grid(tiles, (uint32_t)m);
-    hipLaunchKernelGGL(msm_digits_kernel<CV>, dim3(sort_grid), dim3(MSM_SORT_THREADS), lds, stream, d_scalars, gcounts,
-                       tile_base, tile_hist, (uint32_t)n, col_stride, ws.tile, tiles, (uint32_t)m, g);
-    if (ws.K <= SCAN_LDS_MAX) {
-      uint32_t per = (uint32_t)((ws.K + 1023) / 1024);
-      per |= 1u;                                 // odd stride: the per-thread LDS walks do not collide on banks
-      hipLaunchKernelGGL(scan_lds_kernel, dim3(1), dim3(1024), ws.K * 4, stream, gcounts, offsets, (uint32_t)ws.K, per);
-    } else {
-      hipLaunchKernelGGL(msm_group_fold_kernel, dim3((unsigned)((ws.K + 255) / 256)), dim3(256), 0, stream, gcounts, counts, ws.K);
-      hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)ws.nblk), dim3(256), 0, stream, counts, blocksums, ws.K);
-      hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(1024), 0, stream, blocksums, (uint32_t)ws.nblk, misc + 1);
-      hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)ws.nblk), dim3(256), 0, stream, counts, blocksums, offsets,
-                         ws.K);
-    }
-    if (ws.staged) {
-      // the keys pass shared out over the scatter's blocks (at most one key per thread; the staging area holds its LDS
-      // at every bucket count this sort is chosen for -- the checks keep small geometries honest)
-      const size_t per = (ws.K + (size_t)tiles * m - 1) / ((size_t)tiles * m);
-      keys_merged = per <= MSM_SORT_THREADS && ws.stage_lds >= (size_t)4 * (MSM_SORT_THREADS + 1);
-      MsmKeysArgs ka = keys_args;
-      const uint32_t grid = sort_grid;
-      if (keys_merged) ka.keys_per_block = (uint32_t)per;
-      auto scatter = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MSM_SORT_THREADS), ws.stage_lds, stream, d_scalars, (const uint32_t*)offsets,
-                           (const uint32_t*)gcounts, (const uint32_t*)tile_base, (const uint32_t*)tile_hist, sref, (uint32_t)n,
-                           col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g, (uint32_t)(ws.tile * g.W), ws.pack, ka);
-      };
-      if (ws.pack.on) scatter(msm_scatter_staged_kernel<CV, true>);
-      else scatter(msm_scatter_staged_kernel<CV, false>);
-    } else
-      hipLaunchKernelGGL(msm_scatter_kernel<CV>, dim3(sort_grid), dim3(MSM_SORT_THREADS), lds, stream, d_scalars, offsets,
-                         gcounts, tile_base, sref, (uint32_t)n, col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g);
-  }
   if (!keys_merged)
     hipLaunchKernelGGL(msm_keys_kernel, dim3((unsigned)((ws.K + MSM_KEYS_THREADS - 1) / MSM_KEYS_THREADS)), dim3(MSM_KEYS_THREADS), 0,
                        stream, (const uint32_t*)offsets, ws.K, keys_args);
@@ -1733,4 +1695,85 @@ inline hipError_t msm_launch(const U128* table, const U128* const* per_column /*
   return hipGetLastError();
 }
 
+// Enqueue m MSMs of n terms against `table` (built for n_bases points with geometry g); column j's scalars start
+// col_stride elements after column j-1's.
+// Result: m XYZZ points at ws_base + off_tree2.  ev_start / ev_stop (optional) bracket the
+// accumulate (chunk) kernel for the roofline measurement.
+template <class CV>
+inline hipError_t msm_launch(const U128* table, const U128* const* per_column /* host array of m tables, or null */,
+                             uint32_t n_bases, const U128* d_scalars, size_t n, size_t col_stride,
+                             size_t m, const MsmGeom& g, char* ws_base, const MsmWorkspace& ws, hipStream_t stream,
+                             hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, hipEvent_t ev_tail = nullptr,
+                             U128* d_out_jac = nullptr /* m Jacobian points in the API's form, written by the last kernel */,
+                             bool zeroed = false /* [off_misc, + zero_bytes) is zero already: the previous launch sequence on
+                                                    this workspace left it so (same off_misc, at least as many bytes) */) {
+  uint32_t* gcounts = (uint32_t*)(ws_base + ws.off_gcounts);
+  uint32_t* offsets = (uint32_t*)(ws_base + ws.off_offsets);
+  uint32_t* tile_base = (uint32_t*)(ws_base + ws.off_tile_base);
+  uint32_t* sref = (uint32_t*)(ws_base + ws.off_ref);
+  uint32_t* misc = (uint32_t*)(ws_base + ws.off_misc);
+  hipError_t e;
+  if (per_column && m > MSM_MAX_MULTI) return hipErrorInvalidValue;
+  // one memset: misc (256 B) and the sort's counters behind it.  Nothing else needs clearing: every slot of bucket_sum /
+  // head / tail that a later kernel reads has been written by the accumulate kernel (the fix-up decides from
+  // `offsets` which slots exist).
+  if (!zeroed && (e = hipMemsetAsync(misc, 0, ws.zero_bytes, stream)) != hipSuccess) return e;
+  uint32_t* tile_hist = (ws.staged || ws.sort2) ? (uint32_t*)(ws_base + ws.off_tile_hist) : nullptr;
+  // the keys pass (msm_keys_block): after the scan, beside or behind the scatter
+  const U128** d_tables = nullptr;
+  uint32_t log_b = 0;
+  MsmKeysArgs keys_args = msm_keys_args(ws_base, ws);
+  if (per_column) {
+    d_tables = (const U128**)(misc + 16);                          // 128 bytes of the 256-byte misc block
+    keys_args.n_tables = (uint32_t)m;
+    keys_args.tables_dst = d_tables;
+    for (size_t j = 0; j < m; j++) keys_args.tables.t[j] = per_column[j];
+    while ((1u << log_b) < g.B) log_b++;
+  }
+  bool keys_merged = false;
+  if (ws.sort2) {
+    const Sort2Geom& s2 = ws.s2;
+    const uint32_t H = s2.Hc * (uint32_t)m;
+    uint32_t* cstart = (uint32_t*)(ws_base + ws.off_cstart);
+    uint32_t* mid_ref = (uint32_t*)(ws_base + ws.off_mid_ref);
+    uint8_t* mid_lo = (uint8_t*)(ws_base + ws.off_mid_lo);
+    uint32_t* group_base = (uint32_t*)(ws_base + ws.off_group_base);
+    hipLaunchKernelGGL(msm2_count_kernel<CV>, dim3(s2.groups, (unsigned)m), dim3(S2_THREADS), (size_t)s2.Hc * 8, stream, d_scalars,
+                       gcounts, tile_base, tile_hist, group_base, (uint32_t)n, col_stride, s2, g);
+    hipLaunchKernelGGL(msm2_coarse_scan_kernel, dim3(1), dim3(1024), 0, stream, gcounts, cstart, H, offsets + ws.K);
+    hipLaunchKernelGGL(msm2_scatter_kernel<CV>, dim3(s2.tiles, (unsigned)m), dim3(S2_THREADS), msm_sort2_lds_scatter(s2, g), stream,
+                       d_scalars, cstart, tile_base, tile_hist, group_base, mid_ref, mid_lo, (uint32_t)n, col_stride, n_bases, s2, g);
+    hipLaunchKernelGGL(msm2_fine_kernel, dim3(H), dim3(S2_THREADS), msm_sort2_lds_fine(), stream, cstart, mid_ref, mid_lo, sref,
+                       offsets, s2.F, s2.lo_bits, s2.pack_shift);
+  } else {
+    const size_t lds = (size_t)g.B * 4;     // dynamic LDS limits were raised once per device by msm_kernel_setup
+    const uint32_t tiles = (uint32_t)((n + ws.tile - 1) / ws.tile);
+    const uint32_t sort_grid = msm_tile_grid(tiles, (uint32_t)m);
+    hipLaunchKernelGGL(msm_digits_kernel<CV>, dim3(sort_grid), dim3(MSM_SORT_THREADS), lds, stream, d_scalars, gcounts,
+                       tile_base, tile_hist, (uint32_t)n, col_stride, ws.tile, tiles, (uint32_t)m, g);
+    msm_launch_scan(ws_base, ws, stream);
+    if (ws.staged) {
+      // the keys pass shared out over the scatter's blocks (at most one key per thread; the staging area holds its LDS
+      // at every bucket count this sort is chosen for -- the checks keep small geometries honest)
+      const size_t per = (ws.K + (size_t)tiles * m - 1) / ((size_t)tiles * m);
+      keys_merged = per <= MSM_SORT_THREADS && ws.stage_lds >= (size_t)4 * (MSM_SORT_THREADS + 1);
+      MsmKeysArgs ka = keys_args;
+      const uint32_t grid = sort_grid;
+      if (keys_merged) ka.keys_per_block = (uint32_t)per;
+      auto scatter = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MSM_SORT_THREADS), ws.stage_lds, stream, d_scalars, (const uint32_t*)offsets,
+                           (const uint32_t*)gcounts, (const uint32_t*)tile_base, (const uint32_t*)tile_hist, sref, (uint32_t)n,
+                           col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g, (uint32_t)(ws.tile * g.W), ws.pack, ka);
+      };
+      if (ws.pack.on) scatter(msm_scatter_staged_kernel<CV, true>);
+      else scatter(msm_scatter_staged_kernel<CV, false>);
+    } else
+      hipLaunchKernelGGL(msm_scatter_kernel<CV>, dim3(sort_grid), dim3(MSM_SORT_THREADS), lds, stream, d_scalars, offsets,
+                         gcounts, tile_base, sref, (uint32_t)n, col_stride, n_bases, ws.tile, tiles, (uint32_t)m, g);
+  }
+  return msm_launch_back<CV>(table, d_tables, log_b, m, g, ws_base, ws, keys_args, keys_merged, stream, ev_start, ev_stop, ev_tail,
+                             d_out_jac);
+}
+
 }  // namespace h2
+#include "h2_msm_points.hpp"

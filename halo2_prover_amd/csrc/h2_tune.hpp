@@ -24,5 +24,12 @@ inline int tune_int(const char* name, int fallback) {
 // The budget is k = 16's: a group's columns double with every step of k, so above PROVE_GROUP_K the prover halves the group
 // per step (create_proofs: 8 proofs at k = 17, 4 at 18, one from k = 20), and the 4 GiB hold at every k.
 constexpr size_t PROVE_GROUP = 16;
+
+// Terms below which the table-free MSM (h2_msm_points*, h2_msm_points.hpp) takes msm_small_kernel's double-and-add route
+// instead of buckets: the smallest n of the sweep n = 8 ... 8192 from which the bucket route's median is lower
+// (profiles/msm_points_crossover.txt, tools/msm_points_bench.py --crossover).  The bucket route is lower at EVERY swept
+// n, 8 included (~0.9 ms against 1.3 - 1.6: both are one chain of ~255 doublings, and the double-and-add route also
+// carries its additions on that chain), so the constant is the sweep's first size and only n < 8 is left to that route.
+constexpr size_t MSM_POINTS_SMALL_MAX = 8;
 constexpr uint32_t PROVE_GROUP_K = 16;
 }  // namespace h2

@@ -28,6 +28,12 @@ class MsmPlan(ctypes.Structure):
     _fields_ = [("window_bits", _U32), ("windows", _U32), ("buckets", _U32), ("table_bytes", _U64)]
 
 
+class MsmPointsPlan(ctypes.Structure):
+    _fields_ = [("window_bits", _U32), ("windows", _U32), ("buckets", _U32), ("route", _U32), ("scalar_bits", _U32),
+                ("lds_bytes", _U32), ("lds_limit", _U32), ("reserved", _U32), ("crossover", _U64), ("max_n", _U64),
+                ("width", ctypes.c_uint8 * 48), ("offset", ctypes.c_uint8 * 48)]
+
+
 SYMBOLS = {
     "h2_init": (_I, [_I]),
     "h2_init_devices": (_I, [_I, _P]),
@@ -48,6 +54,9 @@ SYMBOLS = {
     "h2_points_decompress_device": (_I, [_I, _P, _Z, _P, _P, _P]),
     "h2_stream_wait_msm_tail": (_I, [_P]),
     "h2_msm_device_multi": (_I, [_I, _P, _P, _Z, _Z, _Z, _Z, _P, _P]),
+    "h2_msm_points_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P]),
+    "h2_msm_points": (_I, [_I, _P, _P, _Z, _P]),
+    "h2_msm_points_plan": (_I, [_I, _Z, ctypes.POINTER(MsmPointsPlan)]),
     "h2_ntt": (_I, [_I, _P, _P, _U32]),
     "h2_ntt_batch": (_I, [_I, _P, _Z, _P, _U32]),
     "h2_ntt_device": (_I, [_I, _P, _Z, _P, _U32, _P]),
@@ -80,6 +89,9 @@ SYMBOLS = {
     # the two hooks of include/h2hip_selftest.h that go with h2_generate_proofs: a host detects the batch prover by these names
     "h2_selftest_commit_launches": (_U64, []),
     "h2_selftest_set_prove_group": (_I, [_Z]),
+    # the two hooks that go with h2_msm_points*
+    "h2_selftest_msm_points_check": (_I, [_I, _Z, _Z, _Z, _I, _P]),
+    "h2_selftest_set_msm_points_small_max": (_I, [_Z]),
 }
 # include/h2hip_selftest.h (host instantiation of the device templates; not a compute path)
 SELFTEST_SYMBOLS = {

@@ -144,6 +144,54 @@ int h2_msm_device_range(h2_curve_t curve, uint64_t bases_handle, const void* d_s
 int h2_points_sum_device(h2_curve_t curve, const void* d_in_jac, size_t groups, size_t count, void* d_out_jac,
                          void* stream);
 
+/* ---- MSM over points passed WITH the call: best_multiexp(coeffs, bases) for bases that are NOT registered ----------
+ * out_j = sum_{i<n} scalars_j[i] * points[i].  points: n affine points (64 bytes, API form, identity = (0,0));
+ * m scalar columns col_stride elements apart (col_stride >= n); d_out_jac: m Jacobian points (identity: z = 0; any
+ * representative of the group element, compare after normalisation).  No table is built or kept: a bucket MSM with a
+ * bucket set per window, the window results combined by doublings at the end.  This is the call for a slice used once -- a
+ * sub-slice, a one-off vector, a verifier's terms, an SRS read for a single proof; bases that many MSMs share belong in
+ * h2_bases_register, whose table makes each of those MSMs cheaper.
+ *
+ * Streams and scratch.  h2_msm_points_device is asynchronous on `stream` under h2_msm_device's rules: it uses the
+ * stream's MSM workspace slot, the points in their working form live in that scratch too, and nothing outlives the call
+ * (no handle, no table, no entry in any map).  h2_msm_points takes host pointers, runs on the library's stream of the
+ * current context and returns with the result in host memory.
+ * Contexts.  With several contexts (h2_init_devices) both forms act on ONE context -- that of the calling thread's
+ * current HIP device -- and do not shard; a caller splits by point range and adds with h2_points_sum_device, as for
+ * h2_msm_device_range.
+ * Point validity.  The points are NOT checked to be on the curve (best_multiexp does not check either).  Every index
+ * the kernels form depends on the scalars and on n only, so a bad point gives a wrong sum and never an out-of-range
+ * access.  h2_bases_register stays the checked route.
+ * Sizes.  Every n from 0 up to 2^26 (h2_msm_points_plan_t.max_n: a column's sorted entries are indexed with 31 bits);
+ * below h2_msm_points_plan_t.crossover terms the call takes a double-and-add route (one quad of lanes per term),
+ * from there on buckets.  m is not limited: wide batches run in groups of columns on the same stream.
+ * Returns.  H2_ENOTINIT before h2_init.  H2_EINVAL, checked on the host before anything is enqueued: a null pointer
+ * with n > 0 && m > 0 (d_out_jac: with m > 0), col_stride < n, an unknown curve, a device pointer that is not 16-byte
+ * aligned, n > 2^26.  m == 0: H2_OK, nothing enqueued.  n == 0: H2_OK, m identities are written.  H2_EDEVICE with the
+ * violated condition in h2_last_device_error if the host-side bounds proof of the launch sequence fails (nothing is
+ * enqueued then). */
+int h2_msm_points_device(h2_curve_t curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride,
+                         size_t m, void* d_out_jac, void* stream);
+int h2_msm_points(h2_curve_t curve, const uint64_t* points /* n*8 */, const uint64_t* scalars /* n*4 */, size_t n,
+                  uint64_t out_jac[12]);
+/* Geometry the calls above would use for n terms.  Host only: no GPU, no h2_init needed.  H2_EINVAL: unknown curve, null
+ * `out`, n > 2^26. */
+typedef struct {
+  uint32_t window_bits;   /* widest window c */
+  uint32_t windows;       /* W: windows of a scalar = bucket sets per column */
+  uint32_t buckets;       /* per window: 2^(c-1) */
+  uint32_t route;         /* 0 = the double-and-add route for short inputs (n < crossover), 1 = buckets */
+  uint32_t scalar_bits;   /* the windows cover scalar_bits + 1 bits */
+  uint32_t lds_bytes;     /* W * buckets * 4: the sort front's histogram per workgroup ... */
+  uint32_t lds_limit;     /* ... and what it may use */
+  uint32_t reserved;
+  uint64_t crossover;     /* terms from which the bucket route is taken */
+  uint64_t max_n;         /* the largest n a call takes */
+  uint8_t width[48];      /* bits of window w, w < windows */
+  uint8_t offset[48];     /* first bit of window w */
+} h2_msm_points_plan_t;
+int h2_msm_points_plan(h2_curve_t curve, size_t n, h2_msm_points_plan_t* out);
+
 /* n compressed G1 points (32 bytes each: x little-endian, bit 6 of the last byte = parity of y, bit 7 = identity flag --
  * the wire form of Blake2bRead / Blake2bWrite) -> n affine points in the API form (64 bytes,
  * Montgomery limbs) and n status bytes: 0 = a point on the curve, 1 = x not canonical (>= q), 2 = the identity

@@ -63,6 +63,18 @@ int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pac
 int h2_selftest_msm_tiles(uint32_t tiles, uint32_t m);
 int h2_selftest_msm_guard(int on);
 int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap);
+/* The table-free MSM (h2_msm_points*).
+ * h2_selftest_msm_points_check: host only, no GPU -- lays out the scratch arena of the bucket route for m columns of n
+ *   scalars col_stride elements apart (the first column group, if m takes several) and runs the bounds proof that runs
+ *   before every such launch sequence: msm_check's conditions for the m * W virtual columns behind the sort front, and the
+ *   front's own (packed points, tile bases and group counters for m * W columns, the W * B histogram against the LDS, the
+ *   31-bit entry).  out[0..7] = window bits, windows, buckets, scalars per sort tile, histogram bytes, columns in the
+ *   group, entries per accumulate thread, regions.  H2_EINVAL for col_stride < n; H2_EDEVICE if a condition fails.
+ *   h2_selftest_msm_guard(1) lays out and inspects these launch sequences' arenas as well.
+ * h2_selftest_set_msm_points_small_max: tests only -- inputs of fewer than n terms take the double-and-add route; 0: every
+ *   input takes buckets; SIZE_MAX restores the default (h2_msm_points_plan_t.crossover shows the value in force). */
+int h2_selftest_msm_points_check(int curve, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]);
+int h2_selftest_set_msm_points_small_max(size_t n);
 /* the integer ceiling the MSM kernels are priced against: dependent products of the MSM's working field form
  * (9 x 29-bit limbs) over `curve`'s base field, every CU busy with `waves_per_simd` waves per SIMD; measured
  * chip-wide modmul/s (best of three launches).  bench.py reports it as `modmul_ceiling`. */

@@ -7,6 +7,7 @@
 // best_multiexp's assert_eq!(coeffs.len(), bases.len()) -- become H2_EINVAL here).
 #include "h2_internal.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <optional>
@@ -483,6 +484,33 @@ int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t 
   hipError_t e = ops->ntt_extend_launch(d_coeff, col_stride, log_n, zeta, d_out, A ? A->a.p : nullptr, tw, ext_log_n, m, stream);
   if (e != hipSuccess) return dev_fail(e, "ntt_extend_launch");
   return A ? A->release() : H2_OK;
+}
+
+int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
+                      hipStream_t stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || n == 0 || n > POLY_EVAL_MAX_N || q == 0) return H2_EINVAL;
+  // jobs per launch sequence: grid.y, and what keeps the group's tile values under POLY_EVAL_WS_CAP
+  const size_t per_job = poly_eval_ws_bytes(1, n);
+  const size_t group = std::min<size_t>({q, (size_t)65535, std::max<size_t>(1, POLY_EVAL_WS_CAP / per_job)});
+  const size_t table_bytes = h2_align256(q * sizeof(PolyEvalJob));
+  ArenaLease A(c.div_ws, table_bytes + poly_eval_ws_bytes(group, n), stream);
+  if (A.rc != H2_OK) return A.rc;
+  std::vector<PolyEvalJob> table(q);
+  for (size_t t = 0; t < q; t++) {
+    table[t].poly = d_polys[t];
+    memcpy(table[t].point, points + 4 * t, 32);
+  }
+  // a pageable source: the runtime has read `table` when the call returns (it stages the bytes or waits for the copy)
+  H2_TRY(hipMemcpyAsync(A.a.p, table.data(), q * sizeof(PolyEvalJob), hipMemcpyHostToDevice, stream));
+  const PolyEvalJob* d_jobs = (const PolyEvalJob*)A.a.p;
+  void* ws = (char*)A.a.p + table_bytes;
+  for (size_t t0 = 0; t0 < q; t0 += group) {             // the groups share `ws`: the stream runs them in order
+    const size_t cnt = std::min(group, q - t0);
+    hipError_t e = ops->poly_eval(d_jobs + t0, (uint32_t)cnt, n, ws, (char*)d_out + 32 * t0, stream);
+    if (e != hipSuccess) return dev_fail(e, "poly_eval kernels");
+  }
+  return A.release();
 }
 
 }  // namespace h2
@@ -1054,6 +1082,44 @@ int h2_poly_prefix_product_device(h2_curve_t curve, const void* d_a, size_t n, v
   hipError_t e = ops_of((int)curve)->poly_scan(1, &d_a, &d_out, nullptr, 1, n, A.a.p, k.stream);
   if (e != hipSuccess) return dev_fail(e, "poly_scan kernels");
   return A.release();
+}
+
+int h2_poly_eval_tile(void) { return POLY_EVAL_TILE; }
+
+int h2_poly_eval_device(h2_curve_t curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
+                        void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || n > POLY_EVAL_MAX_N) return H2_EINVAL;
+  if (q == 0) return H2_OK;
+  if (!d_polys || !points || !d_out) return H2_EINVAL;
+  if (n == 0) {
+    H2_TRY(hipMemsetAsync(d_out, 0, q * 32, k.stream));
+    return H2_OK;
+  }
+  for (size_t t = 0; t < q; t++)
+    if (!d_polys[t] || ((uintptr_t)d_polys[t] & 15)) return H2_EINVAL;
+  return poly_eval_enqueue(*k.c, (int)curve, d_polys, n, points, q, d_out, k.stream);
+}
+
+int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs, size_t n, const uint64_t point[4], uint64_t out[4]) {
+  Call k(nullptr);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || n > POLY_EVAL_MAX_N || !point || !out || (n > 0 && !coeffs)) return H2_EINVAL;
+  if (n == 0) {
+    memset(out, 0, 32);
+    return H2_OK;
+  }
+  DevCtx& c = *k.c;
+  const size_t off_res = h2_align256(n * 32);
+  ArenaLease stage(c.stage, off_res + 32, c.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  char* base = (char*)c.stage.p;
+  H2_TRY(hipMemcpyAsync(base, coeffs, n * 32, hipMemcpyHostToDevice, c.stream));
+  const void* poly = base;
+  if (int rc = poly_eval_enqueue(c, (int)curve, &poly, n, point, 1, base + off_res, c.stream); rc != H2_OK) return rc;
+  H2_TRY(hipMemcpyAsync(out, base + off_res, 32, hipMemcpyDeviceToHost, c.stream));
+  return stage.wait();
 }
 
 int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_t first_block, size_t n, void* d_out,

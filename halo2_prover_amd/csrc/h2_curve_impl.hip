@@ -180,6 +180,18 @@ hipError_t poly_scan(int mode, const void* const* d_a, void* const* d_out, const
   hipLaunchKernelGGL(poly_scan_apply_kernel<FS>, dim3((C + 63) / 64, jobs), dim3(64), 0, s, B, mode, n, L, C, G);
   return hipGetLastError();
 }
+hipError_t poly_eval(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d_ws, void* d_out, hipStream_t s) {
+  if (jobs == 0 || jobs > 65535 || n == 0 || n > POLY_EVAL_MAX_N) return hipErrorInvalidValue;
+  const uint32_t tiles = (uint32_t)poly_eval_tiles(n);
+  U128* partial = (U128*)d_ws;
+  int32_t* powers = (int32_t*)((char*)d_ws + (size_t)jobs * tiles * 32);
+  hipLaunchKernelGGL(poly_eval_powers_kernel<FS>, dim3((jobs + 63) / 64), dim3(64), 0, s, d_jobs, jobs, powers);
+  hipLaunchKernelGGL(poly_eval_tile_kernel<FS>, dim3(tiles, jobs), dim3(POLY_EVAL_THREADS), 0, s, d_jobs, n,
+                     (const int32_t*)powers, partial, tiles);
+  hipLaunchKernelGGL(poly_eval_fold_kernel<FS>, dim3((jobs + 63) / 64), dim3(64), 0, s, jobs, (const int32_t*)powers,
+                     (const U128*)partial, tiles, (U128*)d_out);
+  return hipGetLastError();
+}
 hipError_t chacha20_scalars(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s) {
   ChaChaKey k;
   memcpy(k.w, key, 32);
@@ -400,7 +412,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_scan, chacha20_scalars, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, poly_eval, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 
 }  // namespace

@@ -12,6 +12,13 @@ struct U128;
 struct MsmGeom;
 struct MsmWorkspace;
 
+// one evaluation: the polynomial's coefficients in HBM (API form, 16-byte aligned) and the point's 8 x 32-bit
+// Montgomery limbs.  The poly_eval kernels read a table of these from HBM (h2_poly.hpp)
+struct PolyEvalJob {
+  const void* poly;
+  uint32_t point[8];
+};
+
 struct CurveOps {
   int curve_id;
   int scalar_field_id;
@@ -77,6 +84,9 @@ struct CurveOps {
   // mode 1: d_out[j][i] = prod_{t < i} d_a[j][t] (d_out[j][0] = 1; may alias d_a[j]), z unused
   hipError_t (*poly_scan)(int mode, const void* const* d_a, void* const* d_out, const uint64_t* z, uint32_t jobs, size_t n,
                           void* d_ws, hipStream_t s);
+  // d_out[t] = sum_{i < n} poly_t[i] point_t^i for the 1 <= jobs <= 65535 entries of the table d_jobs (grid.y = job),
+  // 1 <= n <= 2^30 coefficients each; d_ws: poly_eval_ws_bytes(jobs, n), 16-byte aligned (h2_poly.hpp); three launches
+  hipError_t (*poly_eval)(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d_ws, void* d_out, hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)

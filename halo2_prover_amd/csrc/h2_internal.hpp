@@ -175,6 +175,11 @@ int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[
 int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
                               const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n, void* d_out,
                               hipStream_t stream);
+// eval_polynomial (h2_poly_eval_device; arguments checked by the caller, n >= 1, q >= 1): q jobs in groups of at most
+// 65535, the job table and the groups' scratch (h2_poly.hpp) in c.div_ws for the length of the call.  d_polys and
+// points are host arrays, read before the call returns
+int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
+                      hipStream_t stream);
 int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t m, const BasesEntry** be);
 
 #define H2_TRY(call)                                        \

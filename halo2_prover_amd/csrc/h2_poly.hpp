@@ -6,6 +6,7 @@
 // All are one read + one write of the column: HBM-bound elementwise kernels (64 B per element), kept on
 // device so a column never leaves HBM between its NTTs and its MSM.
 #pragma once
+#include "h2_curve_ops.hpp"
 #include "h2_field.hpp"
 #include "h2_field29.hpp"
 
@@ -274,6 +275,178 @@ poly_scan_apply_kernel(ScanBatch<FP> B, int mode, size_t n, uint32_t L, uint32_t
       at += cnt;
     }
   }
+}
+
+// ---- eval_polynomial: out[job] = sum_{i < n} poly_job[i] x_job^i, many (polynomial, point) jobs per launch sequence -------
+// halo2_proofs @6b43b6b src/arithmetic.rs `eval_polynomial` (create_proof evaluates every advice, fixed, permutation and
+// quotient polynomial at x w^rot before it opens them).  Three launches, every one deterministic, grid.y = job:
+//   powers   one thread per job: x^R, x^2R, x^4R, ..., x^T by 4 + log2(threads) squarings -- the only powers the job needs,
+//            computed once, so no thread exponentiates for itself
+//   tile     a workgroup of POLY_EVAL_THREADS threads covers T = POLY_EVAL_TILE coefficients: each thread runs Horner over
+//            its own R = POLY_EVAL_RUN consecutive coefficients (R - 1 products), then the workgroup folds its threads'
+//            values pairwise, lo + x^(R 2^l) hi at level l, compacting through LDS so that level l keeps only
+//            threads / 2^(l+1) lanes busy (whole waves drop out); one value per (job, tile) goes to HBM
+//   fold     one thread per job: Horner over the job's tile values in x^T, the result in the API's form
+// Products per job: about n (1 - 1/R) in the runs, n / R in the trees, 4 + log2(threads) for the powers, n / T in the fold.
+// Scratch per job (POLY_EVAL_WS_BYTES): ceil(n / T) tile values of 32 bytes and POLY_EVAL_POWERS powers of 36 bytes.
+//
+// Magnitudes, in units of p, on the 9 x 29-bit lazy form (h2_field29.hpp; R' = 2^261 > 128 p for the three fields):
+//   * a coefficient or point in HBM is x 2^256, canonical; expr_column_operand (shifted unpack minus 16 p) makes it the
+//     working form of x in (-16 p, 16 p) with limbs below 2^29 in magnitude.  A slot past the end of the polynomial is
+//     loaded as 0 and becomes -16 p: zero mod p, inside the same bounds, so runs and tiles need no special last case.
+//   * a Horner step is acc' = acc x / R' + c.  fe29_mul asks for limbs below 2^30 on one side and below 2^29 on the other
+//     and nothing of the values; it returns normalised limbs and a value in (a b / R' - p, a b / R'].  With |x| < 16 p a
+//     product is below |acc| / 8 + p, so |acc| <= M + 16 p with M = (M + 16 p) / 8 + p, M = 24 p / 7: every acc stays below
+//     20 p.  acc' is a normalised product plus a fresh operand: limbs below 2^29 + 2^29 = 2^30, a valid FIRST operand of
+//     the next product as it is (no carry pass); the point, the second operand, keeps limbs below 2^29.
+//   * the powers are products of normalised values below 1.2 p (x 1 / R' first, then squares): |pw| < 1.2 p.
+//   * a tree level is lo + hi pw / R': below |lo| + |hi| / 100 + p, so each of the at most 10 levels adds less than
+//     1.3 p to the 20 p of a run: below 33 p.  A level's result is the sum of two normalised values, limbs below 2^30;
+//     it is carry-normalised before it goes to LDS, so both what a level reads are valid operands.
+//   * a tile value leaves through fe29_to_api (any |x| < 64 p) as canonical API limbs; the fold reads them back through
+//     expr_column_operand and is the same Horner step with x^T (|pw| < 1.2 p) for the point: below 20 p, out through
+//     fe29_to_api -- canonical Montgomery limbs, bit-exact whatever the grouping.
+constexpr int POLY_EVAL_RUN = 16;                                   // R: coefficients per thread
+constexpr int POLY_EVAL_AHEAD = 4;                                  // coefficients loaded ahead of a run's chain
+constexpr int POLY_EVAL_THREADS = 256;
+constexpr int POLY_EVAL_TILE = POLY_EVAL_RUN * POLY_EVAL_THREADS;   // T = 4096 coefficients per workgroup
+constexpr int POLY_EVAL_LEVELS = 8;                                 // log2(threads)
+constexpr int POLY_EVAL_POWERS = POLY_EVAL_LEVELS + 1;              // x^(R 2^l), l = 0 .. log2(threads): the last is x^T
+constexpr size_t POLY_EVAL_MAX_N = (size_t)1 << 30;
+constexpr size_t POLY_EVAL_WS_CAP = (size_t)64 << 20;                // scratch of the jobs that share a launch sequence
+static_assert((1 << POLY_EVAL_LEVELS) == POLY_EVAL_THREADS && (POLY_EVAL_RUN & (POLY_EVAL_RUN - 1)) == 0, "powers of two");
+inline size_t poly_eval_tiles(size_t n) { return (n + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE; }
+// scratch of `jobs` jobs: the tile values (32-byte elements first, for their alignment), then the powers
+inline size_t poly_eval_ws_bytes(size_t jobs, size_t n) { return jobs * (poly_eval_tiles(n) * 32 + POLY_EVAL_POWERS * 36); }
+
+template <class FP>
+__global__ void __launch_bounds__(64)
+poly_eval_powers_kernel(const PolyEvalJob* __restrict__ jobs, uint32_t njobs, int32_t* __restrict__ powers) {
+  using W = Fe29<FP>;
+  const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
+  if (job >= njobs) return;
+  Fe<FP> x;
+#pragma unroll
+  for (int i = 0; i < 8; i++) x.v[i] = jobs[job].point[i];
+  W p = fe29_mul(expr_column_operand(x), fe29_from_api(Fe<FP>::one()));    // |p| < 16 p p / R' + p < 1.2 p
+  for (int r = 1; r < POLY_EVAL_RUN; r <<= 1) p = fe29_sqr(p);              // x^R
+  int32_t* dst = powers + (size_t)job * POLY_EVAL_POWERS * 9;
+  for (int l = 0; l < POLY_EVAL_POWERS; l++) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) dst[l * 9 + i] = p.v[i];
+    p = fe29_sqr(p);
+  }
+}
+
+template <class FP>
+__global__ void __launch_bounds__(POLY_EVAL_THREADS)
+poly_eval_tile_kernel(const PolyEvalJob* __restrict__ jobs, size_t n, const int32_t* __restrict__ powers,
+                      U128* __restrict__ partial, uint32_t tiles) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  constexpr int R = POLY_EVAL_RUN, TH = POLY_EVAL_THREADS;
+  __shared__ int32_t lds[2][9 * TH];                    // [buffer][limb][entry]: a level reads one, writes the other
+  __shared__ int32_t pw[POLY_EVAL_LEVELS * 9];          // x^(R 2^l), l < log2(threads)
+  const uint32_t t = threadIdx.x, tile = blockIdx.x, job = blockIdx.y;
+  const PolyEvalJob& J = jobs[job];
+  const U128* __restrict__ a = (const U128*)J.poly;
+  const size_t base = (size_t)tile * POLY_EVAL_TILE;    // < n: the grid has ceil(n / T) tiles
+  const size_t left = n - base;
+  // entries of this tile that hold coefficients: the tree runs on these alone
+  uint32_t cnt = left >= (size_t)POLY_EVAL_TILE ? (uint32_t)TH : (uint32_t)((left + R - 1) / R);
+  int32_t my_pw = 0;
+  if (t < POLY_EVAL_LEVELS * 9) my_pw = powers[(size_t)job * POLY_EVAL_POWERS * 9 + t];    // in flight during the run
+  auto put = [&](int b, uint32_t i, const W& x) {
+#pragma unroll
+    for (int l = 0; l < 9; l++) lds[b][l * TH + i] = x.v[l];
+  };
+  auto get = [&](int b, uint32_t i) {
+    W x;
+#pragma unroll
+    for (int l = 0; l < 9; l++) x.v[l] = lds[b][l * TH + i];
+    return x;
+  };
+  W cur = W::zero();
+  if (t < cnt) {
+    const size_t lo = base + (size_t)t * R;
+    F x;
+#pragma unroll
+    for (int i = 0; i < 8; i++) x.v[i] = J.point[i];
+    const W xw = expr_column_operand(x);
+    // from the run's top coefficient down, POLY_EVAL_AHEAD at a time; the next batch is loaded before this one's products
+    // (the chain itself cannot hide a load).  The loop stays rolled: its body is four products, and a run unrolled whole
+    // keeps R coefficients live at once
+    constexpr int A = POLY_EVAL_AHEAD;
+    auto load = [&](F* v, int top) {                    // coefficients top - 1 .. top - A of the run; 0 past the end
+#pragma unroll
+      for (int j = 0; j < A; j++) {
+        const size_t i = lo + (size_t)(top - 1 - j);
+        v[j] = i < n ? fe_load<FP>(a + 2 * i) : F::zero();
+      }
+    };
+    F now[A], next[A];
+    load(now, R);
+    W acc = W::zero();
+#pragma nounroll
+    for (int top = R; top > 0; top -= A) {
+      if (top > A) load(next, top - A);
+#pragma unroll
+      for (int j = 0; j < A; j++) {
+        const W c = expr_column_operand(now[j]);
+        acc = (j == 0 && top == R) ? c : fe29_add(fe29_mul(acc, xw), c);
+      }
+#pragma unroll
+      for (int j = 0; j < A; j++) now[j] = next[j];
+    }
+    cur = fe29_norm(acc);
+    put(0, t, cur);
+  }
+  if (t < POLY_EVAL_LEVELS * 9) pw[t] = my_pw;
+  __syncthreads();
+  int b = 0;
+  for (int l = 0; cnt > 1; l++) {                       // cnt is the same for the whole workgroup
+    const uint32_t half = (cnt + 1) >> 1;
+    if (t < half) {
+      cur = get(b, 2 * t);
+      if (2 * t + 1 < cnt) {
+        W p;
+#pragma unroll
+        for (int i = 0; i < 9; i++) p.v[i] = pw[l * 9 + i];
+        cur = fe29_norm(fe29_add(cur, fe29_mul(get(b, 2 * t + 1), p)));
+      }
+      put(b ^ 1, t, cur);
+    }
+    __syncthreads();
+    b ^= 1;
+    cnt = half;
+  }
+  if (t == 0) fe_store<FP>(partial + 2 * ((size_t)job * tiles + tile), fe29_to_api(cur));
+}
+
+template <class FP>
+__global__ void __launch_bounds__(64)
+poly_eval_fold_kernel(uint32_t njobs, const int32_t* __restrict__ powers, const U128* __restrict__ partial, uint32_t tiles,
+                      U128* __restrict__ out) {
+  using W = Fe29<FP>;
+  const uint32_t job = blockIdx.x * blockDim.x + threadIdx.x;
+  if (job >= njobs) return;
+  W y;                                                  // x^T
+#pragma unroll
+  for (int i = 0; i < 9; i++) y.v[i] = powers[((size_t)job * POLY_EVAL_POWERS + POLY_EVAL_LEVELS) * 9 + i];
+  const U128* v = partial + 2 * (size_t)job * tiles;
+  W acc = expr_column_operand(fe_load<FP>(v + 2 * (size_t)(tiles - 1)));
+  for (uint32_t top = tiles - 1; top > 0;) {            // values loaded ahead of the chain, as in the scan kernels
+    const uint32_t cnt = min((uint32_t)SCAN_AHEAD, top);
+    Fe<FP> c[SCAN_AHEAD];
+#pragma unroll
+    for (int k = 0; k < SCAN_AHEAD; k++)
+      if ((uint32_t)k < cnt) c[k] = fe_load<FP>(v + 2 * (size_t)(top - 1 - k));
+#pragma unroll
+    for (int k = 0; k < SCAN_AHEAD; k++)
+      if ((uint32_t)k < cnt) acc = fe29_add(fe29_mul(acc, y), expr_column_operand(c[k]));
+    top -= cnt;
+  }
+  fe_store<FP>(out + 2 * (size_t)job, fe29_to_api(acc));
 }
 
 // ---- the blinding polynomial's coefficients ------------------------------------------------------------------

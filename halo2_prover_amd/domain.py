@@ -145,6 +145,31 @@ class EvaluationDomain:
         _lib.check(st, "h2_poly_mul_periodic_device")
         return a
 
+    def eval_polynomial(self, cols, points):
+        """arithmetic.rs eval_polynomial on resident columns: `cols` is an (m, n, 4) tensor of coefficients, `points` one
+        point or m points (canonical ints); returns the m values cols[j](points[j]) as canonical ints after ONE
+        h2_poly_eval_device call and one read-back of m * 32 bytes"""
+        import torch
+        if cols.dim() != 3:
+            raise ValueError("expected shape (m, n, 4), got %r" % (tuple(cols.shape),))
+        n = cols.shape[1]
+        m = self._shape(cols, n) if n else cols.shape[0]
+        pts = [points] * m if isinstance(points, int) else list(points)
+        if len(pts) != m:
+            raise ValueError("expected one point or %d points, got %d" % (m, len(pts)))
+        if m == 0:
+            return []
+        base = cols.data_ptr()
+        ptrs = (ctypes.c_void_p * m)(*[base + 32 * n * j for j in range(m)])
+        pm = np.concatenate([self.mont(x) for x in pts])
+        out = torch.empty((m, 4), dtype=torch.int64, device=cols.device)
+        st = self._L.h2_poly_eval_device(self.curve, ptrs, n, pm.ctypes.data, m, ctypes.c_void_p(out.data_ptr()),
+                                         self._stream())
+        _lib.check(st, "h2_poly_eval_device")
+        raw = out.cpu().numpy().tobytes()
+        rinv = pow(self.R, -1, self.p)
+        return [int.from_bytes(raw[32 * j:32 * j + 32], "little") * rinv % self.p for j in range(m)]
+
     def pointwise(self, op, a, b):
         """a = a (op) b elementwise, op in {'add', 'sub', 'mul'}"""
         if a.shape != b.shape:

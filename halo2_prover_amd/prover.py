@@ -706,21 +706,9 @@ class _Dev:
         return t
 
     def evals(self, cols, point):
-        """f_j(point) for the m coefficient-form columns of `cols` (m, n, 4): multiply by the powers of the point
-        and fold the halves together (log2 n pointwise additions over all columns at once)"""
-        m, n = cols.shape[0], cols.shape[1]
-        # (n, m, 4) so that halves are contiguous; always a fresh copy: the fold below works in place
-        a = cols.permute(1, 0, 2).clone(memory_format=self.torch.contiguous_format)
-        pw = self.powers(point, n).unsqueeze(1).expand(n, m, 4).contiguous()
-        self.mul_(a, pw)
-        length = n
-        while length > 1:
-            half = length // 2
-            lo, hi = a[:half], a[half:length]
-            _lib.check(self.L.h2_poly_pointwise_device(self.curve, 0, self._p(lo), self._p(hi), half * m,
-                                                       self.dom._stream()), "h2_poly_pointwise_device")
-            length = half
-        return self.to_ints(a[0])
+        """f_j(point) for the m coefficient-form columns of `cols` (m, n, 4): one h2_poly_eval_device call, one
+        read-back"""
+        return self.dom.eval_polynomial(cols.contiguous(), point)
 
     def commit(self, cols, lagrange):
         """m device columns (m, n, 4) -> m affine points (canonical ints); the MSM result never leaves the device

@@ -254,6 +254,28 @@ int h2_poly_divide_linear_device(h2_curve_t curve, const void* d_a, size_t n, co
  * argument, z[i+1] = z[i] * ratio[i] (halo2_proofs src/plonk/permutation/prover.rs `Argument::commit`; SURVEY.md
  * App. A.4) -- the caller multiplies by last_z and writes the blinding rows. */
 int h2_poly_prefix_product_device(h2_curve_t curve, const void* d_a, size_t n, void* d_out, void* stream);
+/* arithmetic.rs eval_polynomial on resident columns: out[t] = sum_{i<n} d_polys[t][i] * points[t]^i for t < q.
+ * d_polys: HOST array of q device pointers (n coefficients each, API form, 16-byte aligned; pointers may repeat);
+ * points: HOST array of q * 4 limbs; both are read before the call returns.  d_out: q * 32 bytes of device memory,
+ * must not overlap any polynomial.  Asynchronous on `stream` under h2_ntt_device's rules.
+ * Results are canonical Montgomery limbs, the same bits whatever q and however the jobs are grouped.  0^0 = 1: a zero
+ * point returns coefficient 0; n = 0 writes q zeros; q = 0 is H2_OK and enqueues nothing.
+ * Three launches per group of jobs (the powers x^16 .. x^T of every point once; one workgroup per T = h2_poly_eval_tile()
+ * coefficients: a run of 16 per thread by Horner, the threads' values folded pairwise in LDS; one thread per job folds
+ * the tile values by Horner in x^T), job in grid.y.  A group is at most 65535 jobs and at most what keeps its scratch
+ * -- (ceil(n / T) * 32 + 324) bytes per job -- under 64 MiB (always at least one job); a larger q runs group after
+ * group on `stream`.  That scratch and the job table (40 bytes per job) live in the context's scan arena for the
+ * length of the call; nothing is cached.  With several contexts (h2_init_devices) the call acts on the context of the
+ * calling thread's current HIP device, as h2_msm_points_device does.
+ * H2_EINVAL -- checked on the host before anything is enqueued -- for: an unknown curve, n > 2^30, and with q > 0 a
+ * null d_polys, points or d_out, or (n > 0) a d_polys[t] that is null or not 16-byte aligned.
+ * h2_version() did not change for these entry points: a host detects them by their symbols. */
+int h2_poly_eval_device(h2_curve_t curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q,
+                        void* d_out, void* stream);
+/* one host polynomial at one point, synchronous: the drop-in for eval_polynomial(poly, point) */
+int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs /* n*4 */, size_t n, const uint64_t point[4], uint64_t out[4]);
+/* coefficients one workgroup covers (T above).  Host only, no h2_init needed: tests size their shapes by it. */
+int h2_poly_eval_tile(void);
 /* out[i] = Scalar::random(rng) number first_block + i of rng = ChaCha20Rng::from_seed(seed), Montgomery limbs:
  * the coefficients of the vanishing argument's random_poly (halo2_proofs src/plonk/vanishing/prover.rs
  * `Argument::commit`).  Each draw consumes one 64-byte ChaCha20 block. */

@@ -486,6 +486,28 @@ int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t 
   return A ? A->release() : H2_OK;
 }
 
+int extended_to_coeff_enqueue(DevCtx& c, int curve, const void* d_ext, uint32_t ext_log_n, size_t m,
+                              const uint64_t ext_omega_inv[4], const uint64_t scale[4], const uint64_t zeta_inv[4], const void* d_t,
+                              size_t t_period, void* d_out, size_t out_len, size_t out_stride, hipStream_t stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops) return H2_EINVAL;
+  if (m == 0 || out_len == 0) return H2_OK;
+  const void* tw = nullptr;      // ntt_enqueue's entry for the same (omega, log n, scale); one element needs none
+  if (ext_log_n > 0) {
+    int rc = get_twiddles(c, ops, ext_omega_inv, ext_log_n, ops->ntt_scale_in_table(ext_log_n) ? scale : nullptr, &tw);
+    if (rc != H2_OK) return rc;
+  }
+  std::optional<ArenaLease> A;     // pass 0 writes it: the source is only read
+  if (ntt_make_plan(ext_log_n).npass > 1) {
+    A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << ext_log_n), stream);
+    if (A->rc != H2_OK) return A->rc;
+  }
+  hipError_t e = ops->ntt_coeff_launch(d_ext, d_t, t_period, scale, zeta_inv, d_out, out_len, out_stride, A ? A->a.p : nullptr, tw,
+                                       ext_log_n, m, stream);
+  if (e != hipSuccess) return dev_fail(e, "ntt_coeff_launch");
+  return A ? A->release() : H2_OK;
+}
+
 int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
                       hipStream_t stream) {
   const CurveOps* ops = ops_of(curve);
@@ -1016,6 +1038,26 @@ int h2_coeff_to_extended_device(h2_curve_t curve, const void* d_coeff, size_t co
     return H2_OK;
   }
   return coeff_to_extended_enqueue(*k.c, (int)curve, d_coeff, col_stride, log_n, m, zeta, ext_omega, ext_log_n, d_out, k.stream);
+}
+
+int h2_extended_to_coeff_device(h2_curve_t curve, const void* d_ext, uint32_t ext_log_n, size_t m, const uint64_t ext_omega_inv[4],
+                                const uint64_t scale[4], const uint64_t zeta_inv[4], const void* d_t, size_t t_period, void* d_out,
+                                size_t out_len, size_t out_stride, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || ext_log_n > 30 || m > 65535) return H2_EINVAL;                  // grid.y = column
+  const size_t en = (size_t)1 << ext_log_n;
+  if (out_len > en || out_stride < out_len || out_stride > ((size_t)1 << 40)) return H2_EINVAL;
+  if (d_t && (t_period == 0 || (t_period & (t_period - 1)) || t_period > en)) return H2_EINVAL;
+  if ((((uintptr_t)d_ext | (uintptr_t)d_out | (uintptr_t)d_t) & 15) != 0) return H2_EINVAL;
+  if (m == 0 || out_len == 0) return H2_OK;
+  if (!d_ext || !d_out || !ext_omega_inv || !scale || !zeta_inv) return H2_EINVAL;
+  // [first byte, last byte) of what is read and of what is written
+  const uintptr_t s0 = (uintptr_t)d_ext, s1 = s0 + m * en * 32;
+  const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((m - 1) * out_stride + out_len) * 32;
+  if (s0 < o1 && o0 < s1) return H2_EINVAL;
+  return extended_to_coeff_enqueue(*k.c, (int)curve, d_ext, ext_log_n, m, ext_omega_inv, scale, zeta_inv, d_t, t_period, d_out,
+                                   out_len, out_stride, k.stream);
 }
 
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream_) {

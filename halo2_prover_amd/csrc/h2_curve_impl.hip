@@ -129,6 +129,15 @@ hipError_t ntt_extend_launch_(const void* d_src, size_t src_stride, uint32_t log
   memcpy(z.v, zeta, 32);
   return ntt29_extend_launch<FS>((const U128*)d_src, src_stride, log_src, z, (U128*)d_out, (U128*)d_scratch, d_tw, log_n, m, s);
 }
+hipError_t ntt_coeff_launch_(const void* d_src, const void* d_t, size_t t_period, const uint64_t scale[4], const uint64_t zeta_inv[4],
+                             void* d_out, size_t out_len, size_t out_stride, void* d_scratch, const void* d_tw, uint32_t log_n,
+                             size_t m, hipStream_t s) {
+  Fe<FS> sc, zi;
+  memcpy(sc.v, scale, 32);
+  memcpy(zi.v, zeta_inv, 32);
+  return ntt29_coeff_launch<FS>((const U128*)d_src, (const U128*)d_t, t_period, sc, zi, (U128*)d_out, out_len, out_stride,
+                                (U128*)d_scratch, d_tw, log_n, m, s);
+}
 size_t group_fft_scratch(uint32_t log_n) { return gfft_scratch_bytes(log_n); }
 hipError_t group_fft(const void* d_in_jac, void* d_out_jac, void* d_scratch, const uint64_t omega[4], uint32_t log_n, hipStream_t s) {
   Fe<FS> w;
@@ -411,7 +420,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 }
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
-                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
+                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 

@@ -68,6 +68,13 @@ struct CurveOps {
   // (pass 0 of h2_ntt29.hpp's extending kernel).  Tables of (omega, log_n) unscaled; log_n >= 1; d_scratch as ntt_launch
   hipError_t (*ntt_extend_launch)(const void* d_src, size_t src_stride, uint32_t log_src, const uint64_t zeta[4], void* d_out,
                                   void* d_scratch, const void* d_tw, uint32_t log_n, size_t m, hipStream_t s);
+  // extended_to_coeff (with divide_by_vanishing_poly when d_t is set): m columns of 2^log_n values (read only) ->
+  // out[c][j] = zi[j mod 3] scale sum_i src[c][i] t[i mod t_period] w^(ij) for j < out_len, columns out_stride apart,
+  // nothing written beyond out_len (the dividing pass 0 and the shrinking final pass of h2_ntt29.hpp).  Tables of
+  // (w, log_n), built with `scale` when ntt_scale_in_table(log_n); none needed for log_n = 0; d_scratch as ntt_launch
+  hipError_t (*ntt_coeff_launch)(const void* d_src, const void* d_t, size_t t_period, const uint64_t scale[4],
+                                 const uint64_t zeta_inv[4], void* d_out, size_t out_len, size_t out_stride, void* d_scratch,
+                                 const void* d_tw, uint32_t log_n, size_t m, hipStream_t s);
   // best_fft over group elements (FftGroup for the curve: g_to_lagrange): n = 2^log_n Jacobian points (API form) in,
   // the transform out (may alias), natural order, unscaled; d_scratch: group_fft_scratch(log_n) bytes
   size_t (*group_fft_scratch)(uint32_t log_n);

@@ -180,6 +180,11 @@ int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t 
 // points are host arrays, read before the call returns
 int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
                       hipStream_t stream);
+// EvaluationDomain::extended_to_coeff, with divide_by_vanishing_poly when d_t is set (h2_extended_to_coeff_device;
+// arguments checked by the caller): ntt_enqueue's table for (ext_omega_inv, ext_log_n, scale) and its second buffer
+int extended_to_coeff_enqueue(DevCtx& c, int curve, const void* d_ext, uint32_t ext_log_n, size_t m,
+                              const uint64_t ext_omega_inv[4], const uint64_t scale[4], const uint64_t zeta_inv[4], const void* d_t,
+                              size_t t_period, void* d_out, size_t out_len, size_t out_stride, hipStream_t stream);
 int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t m, const BasesEntry** be);
 
 #define H2_TRY(call)                                        \

@@ -13,7 +13,10 @@
 //     at the end of this comment) reads canonical data in [0, p) and multiplies two of every three elements by zeta or
 //     zeta^2 on the way in: fe29_mul of two canonical operands (|a| |b| < p^2, far inside 64 p^2) is in
 //     (a b / R' - p, a b / R'], i.e. in (-p, p/128] -- inside the product's general (-3p/2, p/2], normalised, the top
-//     limb signed like every value the stages keep in LDS; an element beyond the source's length is exact zero.  So
+//     limb signed like every value the stages keep in LDS; an element beyond the source's length is exact zero.  The
+//     DIVIDING pass 0 (EvaluationDomain::divide_by_vanishing_poly on the way into extended_to_coeff, at the end of
+//     this comment) is the same case with another constant: canonical data times a canonical t[i mod period], in
+//     (-p, p/128], on EVERY element.  So
 //     there a tile input lies in (-3p/2, p/2) or [0, p), not in [0, 3p/2): the sign differs, the magnitude does not,
 //     and nothing below uses the sign.  A radix-4 double stage adds at most two products (each in (-3p/2, p/2)) to an
 //     element, the very first one (all twiddles 1) at most quadruples it: |x| <= 4 * 1.5p + 3p * 4 = 18p after the
@@ -46,6 +49,28 @@
 //   kernel.  The plain kernel is its own instantiation (EXT = false): same registers and occupancy as before the flag
 //   existed (profiles/coeff_to_extended_resources.txt).  The butterflies on known zeros are NOT skipped (with 2^e-fold
 //   padding the first e stages are copies times twiddles): not built, not measured.
+// The dividing pass 0 and the shrinking final pass (the template flags DIV and SHR; h2_extended_to_coeff_device):
+//   extended_to_coeff is "transform with ext_omega^-1, times 1 / 2^ext_k, times zeta^-j, keep the first n (d - 1)
+//   coefficients", and the prover divides by the vanishing polynomial (element i times t[i mod period]) just before.
+//   Composed, that is two more passes over the whole extended column and a copy of its kept prefix.  Here:
+//   * DIV, pass 0: load_el multiplies element i -- the same index as EXT's -- by t[i mod period].  t comes in the API
+//     form and the product needs the R' form: five doublings per table ENTRY, done once per block into LDS behind the
+//     tile where the block needs at most NTT_DIV_LDS_MAX entries (any period up to 2^log_inner: one entry per tile
+//     column), at the element's load otherwise (then an entry serves fewer than RC / NTT_DIV_LDS_MAX elements of the
+//     block; with period = 2^log_n, exactly one).  The staging is followed by a barrier of its own: the fused first
+//     stage loads before the block's first barrier;
+//   * SHR, the final pass: emit knows its output index out_base + (k << out_k_shift) + cc.  At or beyond out_len it
+//     returns before any arithmetic -- k holds the index's top bits, so with out_len <= 3/4 2^log_n a quarter of the
+//     last radix-4 stage's register outputs leave without a product, a canonicalisation or a store.  Otherwise the
+//     index mod 3 picks the exit: with has_scale (one and three passes) the scale's product takes scale, scale zeta^-1
+//     or scale zeta^-2 -- the un-shift costs nothing; in a two-pass plan (the scale rides in the inter-pass twiddles,
+//     the table h2_ntt_scaled_device uses) index = 0 mod 3 takes the product-free canonicalisation and the other two
+//     one product by zeta^-1 or zeta^-2 through the same positive-operand path (32p + x times a canonical constant,
+//     rounded up, minus p: in [-p, 50p/128), canonical after at most one addition).  The destination's columns are
+//     out_stride apart and nothing is written at or beyond out_len;
+//   * a one-pass plan (log n <= 10) is both at once; without a t table pass 0 of a longer plan is the plain kernel.
+//   The plain and the extending instantiations do not depend on anything that is `if constexpr (DIV)` or `(SHR)`: same
+//   registers and occupancy as before the flags existed (profiles/extended_to_coeff_resources.txt).
 // LDS: 36 bytes per element in three planes (two of 16 bytes, one of 4: ds_read_b128 x 2 + ds_read_b32).
 #pragma once
 #include "h2_field29.hpp"
@@ -167,14 +192,34 @@ struct NttExtend {
   Fe<FP> z1, z2;       // zeta and zeta^2 (zeta^3 = 1), R' form, canonical
 };
 
-// The pass.  EXT = false is the transform as it always was (ntt29_pass_kernel: its code does not depend on anything
-// below that is `if constexpr (EXT)`); EXT = true is pass 0 of an extending transform (ntt29_extend_pass_kernel).
-template <class FP, bool EXT>
+// What the DIVIDING pass 0 and the SHRINKING final pass take besides the plain pass's arguments
+// (EvaluationDomain::extended_to_coeff in one call, ntt29_coeff_launch; a one-pass plan uses both halves).
+constexpr uint32_t NTT_DIV_LDS_MAX = 128;   // converted t entries a block keeps in LDS (32 B each: 4 KB at most)
+template <class FP>
+struct NttCoeff {
+  // DIV: element i of a column is multiplied by t[i & t_mask] on its way into pass 0
+  const U128* t;        // t_mask + 1 canonical elements, API form
+  uint32_t t_mask;
+  uint32_t t_jbits;     // how many low bits of the tile row j reach the index's bits below the period (0: only cc does)
+  uint32_t t_staged;    // the block's (C << t_jbits) entries are converted once, into LDS at t_lds_off
+  uint32_t t_lds_off;   // in 16-byte units from the start of dynamic LDS (behind everything the plain pass uses)
+  // SHR: the final pass stores out[c][j] for j < out_len only, columns out_stride apart, times c[j mod 3]
+  uint32_t out_len;
+  size_t out_stride;
+  Fe<FP> c0, c1, c2;    // R' form, canonical.  has_scale: scale, scale zeta^-1, scale zeta^-2; else c0 unused, zeta^-1, zeta^-2
+};
+
+// The pass.  EXT = DIV = SHR = false is the transform as it always was (ntt29_pass_kernel: its code does not depend on
+// anything below that is `if constexpr` of a flag); EXT is pass 0 of an extending transform
+// (ntt29_extend_pass_kernel); DIV is pass 0 and SHR the final pass of extended_to_coeff (ntt29_coeff_pass_kernel).
+template <class FP, bool EXT, bool DIV = false, bool SHR = false>
 __device__ __forceinline__ void
 ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
                 const uint32_t* __restrict__ radix /* this pass's unpacked radix twiddles */,
                 const int32_t* __restrict__ canon, const NttPass& P, size_t col_stride /* elements */,
-                const Fe<FP>& scale29 /* R' form, canonical; used when P.has_scale */, const NttExtend<FP>* X) {
+                const Fe<FP>& scale29 /* R' form, canonical; used when P.has_scale */, const NttExtend<FP>* X,
+                const NttCoeff<FP>* Y = nullptr) {
+  static_assert(!(EXT && (DIV || SHR)), "the extending pass 0 neither divides nor shrinks");
   extern __shared__ U128 lds[];
   const uint32_t R = 1u << P.log_r, C = 1u << P.log_c;
   const uint32_t RC = R * C;
@@ -215,9 +260,26 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
     out_k_shift = P.log_r1 + P.log_r2;
   }
   src += 2 * in_base;
+  if constexpr (SHR) dst = out + 2 * Y->out_stride * blockIdx.y;        // the kept prefixes, out_stride apart
   dst += 2 * out_base;
   [[maybe_unused]] const U128* xsrc = nullptr;          // EXT: this block's source column (read only through load_el)
   if constexpr (EXT) xsrc = in + 2 * X->src_stride * blockIdx.y;
+  // DIV: entry ((jl << log_c) + cc) of the block's table is t[(i_first + cc + (jl << log_inner)) & t_mask] in R' form,
+  // jl = the low t_jbits bits of the tile row (pass 0: log_outer = 0; a one-pass plan: log_inner = log_c = 0, i = j)
+  [[maybe_unused]] U128* tlds = nullptr;
+  if constexpr (DIV) {
+    if (Y->t_staged) {
+      tlds = lds + Y->t_lds_off;
+      for (uint32_t li = tid; li < (C << Y->t_jbits); li += nthr) {
+        const uint32_t ti = (i_first + (li & (C - 1)) + ((li >> P.log_c) << P.log_inner)) & Y->t_mask;
+        Fe<FP> t = fe_load<FP>(Y->t + 2 * (size_t)ti);
+#pragma unroll
+        for (int d = 0; d < 5; d++) t = fe_dbl(t);       // x 2^256 -> x 2^261
+        fe_store<FP>(tlds + 2 * li, t);
+      }
+      __syncthreads();                                   // (uniform: a kernel argument) the fused first stage loads next
+    }
+  }
 
   auto lds_put = [&](uint32_t i, const Fe29<FP>& u) {
     tile0[i] = U128{(uint32_t)u.v[0], (uint32_t)u.v[1], (uint32_t)u.v[2], (uint32_t)u.v[3]};
@@ -272,7 +334,17 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
   }
   auto emit = [&](uint32_t k, uint32_t cc, Fe29<FP> x) {
     Fe<FP> r;
-    if (!P.is_final || P.has_scale) {
+    // SHR (always the final pass): nothing at all for an output at or beyond out_len; the others leave times
+    // c[index mod 3] -- folded into the scale's product, or (no has_scale) a product only where index mod 3 != 0
+    [[maybe_unused]] uint32_t r3 = 0;
+    bool product = !P.is_final || P.has_scale;
+    if constexpr (SHR) {
+      const uint32_t oi = (uint32_t)out_base + (k << out_k_shift) + cc;      // < 2^log_n <= 2^30
+      if (oi >= Y->out_len) return;
+      r3 = oi % 3;
+      product = P.has_scale || r3 != 0;
+    }
+    if (product) {
       // one product: the inter-pass twiddle w^(outer * i * k) (the table's entry 0 is 1, or the constant of a scaled
       // transform) or the final pass's scale.  32p +- x is positive (|x| <= 18p) with limbs below 2^30, so the product
       // rounded up (fe29_mul_up) is in [0, 50 p / 128 + p) and its limbs are those of a non-negative integer below
@@ -285,7 +357,8 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
         negate = ex >= half_n;
         t = fe29_unpack(fe_load<FP>(tw + 2 * (size_t)(negate ? ex - half_n : ex)));
       } else {
-        t = fe29_unpack(scale29);
+        if constexpr (SHR) t = fe29_unpack(r3 == 0 ? Y->c0 : (r3 == 1 ? Y->c1 : Y->c2));
+        else t = fe29_unpack(scale29);
       }
       x = negate ? fe29_sub(p32, x) : fe29_add(p32, x);
       x = fe29_mul_up(x, t);
@@ -320,6 +393,20 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
       const uint32_t r = si % 3;
       if (r == 0) return x;
       return fe29_mul(x, fe29_unpack(r == 1 ? X->z1 : X->z2));
+    } else if constexpr (DIV) {
+      // the plain load times t[i & t_mask]: canonical data, a canonical constant -- EXT's product, on every element
+      Fe<FP> t;
+      if (Y->t_staged) {
+        t = fe_load<FP>(tlds + 2 * (((j & ((1u << Y->t_jbits) - 1)) << P.log_c) + cc));
+      } else {
+        const uint32_t si = P.is_final ? j : i_first + cc + (j << P.log_inner);
+        t = fe_load<FP>(Y->t + 2 * (size_t)(si & Y->t_mask));
+#pragma unroll
+        for (int d = 0; d < 5; d++) t = fe_dbl(t);
+      }
+      const Fe29<FP> tv = fe29_unpack(t);
+      const Fe29<FP> x = fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
+      return fe29_mul(x, tv);
     } else {
       return fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
     }
@@ -449,6 +536,15 @@ ntt29_extend_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, co
                          size_t col_stride /* elements */, NttExtend<FP> X) {
   ntt29_pass_body<FP, true>(in, out, tw, radix, canon, P, col_stride, Fe<FP>::zero(), &X);
 }
+// extended_to_coeff: DIV = pass 0 multiplies by the t table on the way in, SHR = the final pass keeps Y.out_len outputs
+// per column, times zeta^-j (and the scale), in columns Y.out_stride apart.  Both in a one-pass plan
+template <class FP, bool DIV, bool SHR>
+__global__ void __launch_bounds__(1024)
+ntt29_coeff_pass_kernel(const U128* __restrict__ in, U128* __restrict__ out, const U128* __restrict__ tw,
+                        const uint32_t* __restrict__ radix, const int32_t* __restrict__ canon, NttPass P,
+                        size_t col_stride /* elements */, NttCoeff<FP> Y) {
+  ntt29_pass_body<FP, false, DIV, SHR>(in, out, tw, radix, canon, P, col_stride, Fe<FP>::zero(), nullptr, &Y);
+}
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 inline size_t ntt29_lds_bytes(const NttPass& P) {
@@ -469,12 +565,55 @@ inline bool ntt29_tw_global(const NttPass& P) {
 // with that constant (ntt29_build_tables(..., scale))
 inline bool ntt29_scale_in_table(uint32_t log_n) { return ntt_make_plan(log_n).npass == 2; }
 
+// The dividing pass 0's view of the t table (P = pass 0 with tw_global set; t_mask = period - 1): which row bits reach
+// the index's bits below the period, whether the block's C << jbits entries are staged in LDS, where, and the dynamic
+// LDS the launch asks for.  Element i = i_first + cc + (j << log_inner) (a one-pass plan: log_inner = log_c = 0).
+inline size_t ntt29_div_geometry(const NttPass& P, uint32_t t_mask, uint32_t* jbits, uint32_t* staged, uint32_t* lds_off) {
+  uint32_t log_period = 0;
+  while ((1u << log_period) <= t_mask && log_period < 31) log_period++;          // period = 2^log_period
+  *jbits = log_period > P.log_inner ? std::min(log_period - P.log_inner, P.log_r) : 0;
+  const size_t entries = (size_t)1 << (P.log_c + *jbits);
+  *staged = entries <= NTT_DIV_LDS_MAX ? 1u : 0u;
+  const size_t base = (ntt29_lds_bytes(P) + 15) & ~(size_t)15;
+  *lds_off = (uint32_t)(base / 16);
+  return *staged ? base + entries * 32 : base;
+}
+// Every global and LDS index that DIV and SHR add to the plain pass, against its buffer, from the call's shape alone
+// (the plain pass's own indices are below 2^log_n in columns 2^log_n apart, as ever).  Null when all is in bounds, else
+// what is not.  The caller's buffers: t of t_period elements (has_t), out of (m - 1) * out_stride + out_len.
+inline const char* ntt29_coeff_check(uint32_t log_n, size_t out_len, size_t out_stride, bool has_t, size_t t_period, size_t m) {
+  if (log_n > 30) return "log_n > 30";
+  const size_t n = (size_t)1 << log_n;
+  if (m == 0 || m > 65535) return "grid.y = column: 1 <= m <= 65535";
+  // SHR stores out[c * out_stride + oi] for oi < out_len only (oi < n is a 32-bit value): the last element written is
+  // (m - 1) * out_stride + out_len - 1, and columns do not run into each other
+  if (out_len == 0 || out_len > n) return "out_len outside [1, 2^log_n]";
+  if (out_stride < out_len) return "out_stride < out_len";
+  if (out_stride > ((size_t)1 << 40)) return "out_stride > 2^40";
+  if (has_t) {
+    // DIV reads t[i & (t_period - 1)]: inside the table for a power of two
+    if (t_period == 0 || (t_period & (t_period - 1)) || t_period > n) return "t_period not a power of two in [1, 2^log_n]";
+    NttPass P = ntt_make_plan(log_n).pass[0];
+    P.tw_global = ntt29_tw_global(P) ? 1u : 0u;
+    uint32_t jbits, staged, off;
+    const size_t lds = ntt29_div_geometry(P, (uint32_t)(t_period - 1), &jbits, &staged, &off);
+    // the staged table: entry ((j & (2^jbits - 1)) << log_c) + cc < C << jbits, 32 bytes each from 16 * off
+    if (jbits > P.log_r) return "t_jbits > log_r";
+    if (staged && (size_t)16 * off + (((size_t)32 << P.log_c) << jbits) > lds) return "staged t entries beyond the LDS asked for";
+    if (lds > 160 * 1024) return "LDS > 160 KB";
+  }
+  return nullptr;
+}
+
 // The passes of one transform of m columns: `in` -> (scratch ->) `out`, columns of n elements in scratch and out.
 // ext = null: the plain transform, in's columns are n apart too (ntt29_launch passes in = out).  ext: pass 0 is the
 // extending kernel and reads ext->n elements per column, ext->src_stride apart; the later passes are the plain ones.
+// co: extended_to_coeff (ntt29_coeff_launch, which has checked the geometry): pass 0 divides when co->t is set, the final
+// pass shrinks into out's columns of co->out_stride; a pass that does neither is the plain kernel.
 template <class FP>
 inline hipError_t ntt29_launch_passes(const U128* in, U128* out, U128* scratch, const void* tables, uint32_t log_n, size_t m,
-                                      hipStream_t stream, const Fe<FP>* scale, const NttExtend<FP>* ext) {
+                                      hipStream_t stream, const Fe<FP>* scale, const NttExtend<FP>* ext,
+                                      const NttCoeff<FP>* co = nullptr) {
   NttPlan pl = ntt_make_plan(log_n);
   const NttTables tb = ntt29_tables(log_n);
   const U128* tw = (const U128*)tables;
@@ -497,7 +636,19 @@ inline hipError_t ntt29_launch_passes(const U128* in, U128* out, U128* scratch, 
     const uint32_t* radix = (const uint32_t*)((const char*)tables + tb.off_radix[p]);
     static const size_t lds_pad = (size_t)tune_int("H2_TUNE_NTT_LDS_PAD", 0);      // tuning builds: fewer blocks per CU
     const size_t lds = std::min<size_t>(ntt29_lds_bytes(P) + lds_pad, 160 * 1024);
-    if (ext && p == 0)
+    const bool div = co && co->t && p == 0, shr = co && P.is_final;
+    if (div || shr) {
+      NttCoeff<FP> Y = *co;
+      size_t lds_y = lds;
+      if (div) lds_y = ntt29_div_geometry(P, Y.t_mask, &Y.t_jbits, &Y.t_staged, &Y.t_lds_off);
+      const dim3 block(pl.threads[p]);
+      if (div && shr)
+        hipLaunchKernelGGL((ntt29_coeff_pass_kernel<FP, true, true>), grid, block, lds_y, stream, src, dst, tw, radix, canon, P, n, Y);
+      else if (div)
+        hipLaunchKernelGGL((ntt29_coeff_pass_kernel<FP, true, false>), grid, block, lds_y, stream, src, dst, tw, radix, canon, P, n, Y);
+      else
+        hipLaunchKernelGGL((ntt29_coeff_pass_kernel<FP, false, true>), grid, block, lds_y, stream, src, dst, tw, radix, canon, P, n, Y);
+    } else if (ext && p == 0)
       hipLaunchKernelGGL(ntt29_extend_pass_kernel<FP>, grid, dim3(pl.threads[p]), lds, stream, src, dst, tw, radix, canon, P, n,
                          *ext);
     else
@@ -536,11 +687,51 @@ inline hipError_t ntt29_extend_launch(const U128* src, size_t src_stride, uint32
   }
   return ntt29_launch_passes<FP>(src, out, scratch, tables, log_n, m, stream, nullptr, &X);
 }
+// EvaluationDomain::extended_to_coeff (after divide_by_vanishing_poly when t is given): m columns of 2^log_n values,
+// 2^log_n apart, read only ->
+//   out[c][j] = zi[j mod 3] * scale * sum_i src[c][i] * t[i mod t_period] * w^(ij)   for j < out_len, zi = {1, zeta_inv, zeta_inv^2}
+// in columns out_stride apart; nothing is written at or beyond out_len.  t: t_period canonical elements in the API form,
+// or null (no factor).  Tables of (w, log_n), built with `scale` when ntt29_scale_in_table(log_n); scratch m * 2^log_n
+// elements when the plan has more than one pass.  log_n = 0 needs no tables.  Every index is checked before the first
+// launch (ntt29_coeff_check): hipErrorInvalidValue and nothing enqueued when one is out of bounds.
+template <class FP>
+inline hipError_t ntt29_coeff_launch(const U128* src, const U128* t, size_t t_period, const Fe<FP>& scale, const Fe<FP>& zeta_inv,
+                                     U128* out, size_t out_len, size_t out_stride, U128* scratch, const void* tables,
+                                     uint32_t log_n, size_t m, hipStream_t stream) {
+  if (m == 0 || out_len == 0) return hipSuccess;
+  if (ntt29_coeff_check(log_n, out_len, out_stride, t != nullptr, t_period, m)) return hipErrorInvalidValue;
+  NttCoeff<FP> Y{};
+  Y.t = t;
+  Y.t_mask = t ? (uint32_t)(t_period - 1) : 0;
+  Y.out_len = (uint32_t)out_len;
+  Y.out_stride = out_stride;
+  const Fe<FP> z2 = fe_mul(zeta_inv, zeta_inv);
+  if (ntt29_scale_in_table(log_n)) {                    // the final pass has no scale product: 1 (no product), zeta^-1, zeta^-2
+    Y.c0 = Fe<FP>::zero();
+    Y.c1 = zeta_inv;
+    Y.c2 = z2;
+  } else {
+    Y.c0 = scale;
+    Y.c1 = fe_mul(scale, zeta_inv);
+    Y.c2 = fe_mul(scale, z2);
+  }
+  for (int d = 0; d < 5; d++) {                         // x 2^256 -> x 2^261
+    Y.c0 = fe_dbl(Y.c0);
+    Y.c1 = fe_dbl(Y.c1);
+    Y.c2 = fe_dbl(Y.c2);
+  }
+  return ntt29_launch_passes<FP>(src, out, scratch, tables, log_n, m, stream, &scale, nullptr, &Y);
+}
 template <class FP>
 inline hipError_t ntt29_kernel_setup() {
-  hipError_t e = hipFuncSetAttribute((const void*)ntt29_pass_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)ntt29_extend_pass_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  const void* kernels[] = {(const void*)ntt29_pass_kernel<FP>, (const void*)ntt29_extend_pass_kernel<FP>,
+                           (const void*)ntt29_coeff_pass_kernel<FP, true, false>, (const void*)ntt29_coeff_pass_kernel<FP, false, true>,
+                           (const void*)ntt29_coeff_pass_kernel<FP, true, true>};
+  for (const void* k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 // `tables`: ntt29_tables(log_n).total bytes.  scale (API Montgomery form) or null.
 template <class FP>

@@ -9,6 +9,7 @@ constructed inside keygen / create_proof reached from /root/reference/circuits/s
     coeff_to_extended(a)        zero-extend to 2^extended_k, a[i] *= g_coset^i, best_fft(a, extended_omega)
                                 (h2_coeff_to_extended_device: one call, the padded column is never built)
     extended_to_coeff(a)        ifft on the extended domain, a[i] *= g_coset^-i, truncate to n (j-1)
+                                (h2_extended_to_coeff_device: one call, out of place, optionally with the division below)
     divide_by_vanishing_poly(a) a[i] *= t_evaluations[i mod 2^(extended_k-k)],  t_i = 1 / ((zeta w_ext^i)^n - 1)
 
 Columns are torch int64 CUDA tensors of shape (..., n, 4) viewing halo2curves' 4 x u64 Montgomery limbs; they
@@ -124,17 +125,24 @@ class EvaluationDomain:
         _lib.check(st, "h2_coeff_to_extended_device")
         return out
 
-    def extended_to_coeff(self, a):
-        """extended-coset evaluations -> the n*(j-1) coefficients (new tensor); a is overwritten"""
+    def extended_to_coeff(self, a, divide_by_vanishing=False):
+        """extended-coset evaluations -> a new (..., n (j-1), 4) tensor of coefficients; a is only read.  One call
+        (h2_extended_to_coeff_device): the 1 / 2^extended_k scale, the g^-i factor and the truncation ride on the last
+        NTT pass's exit, and with divide_by_vanishing=True the t_evaluations factor of divide_by_vanishing_poly rides
+        on the first pass's load -- no full-length coefficient column is written, read back or copied"""
+        import torch
         en = 1 << self.extended_k
         m = self._shape(a, en)
-        ptr = ctypes.c_void_p(a.data_ptr())
-        _lib.check(self._L.h2_ntt_scaled_device(self.curve, ptr, m, self._m["extended_omega_inv"].ctypes.data,
-                                                self.extended_k, self._m["extended_ifft_divisor"].ctypes.data,
-                                                self._stream()), "h2_ntt_scaled_device")
-        _lib.check(self._L.h2_poly_coset_device(self.curve, ptr, en, m, self._m["g_coset_inv"].ctypes.data,
-                                                self._stream()), "h2_poly_coset_device")
-        return a[..., : self.n * self.quotient_poly_degree, :].contiguous()
+        hlen = self.n * self.quotient_poly_degree
+        out = torch.empty(a.shape[:-2] + (hlen, 4), dtype=torch.int64, device=a.device)
+        t = ctypes.c_void_p(self.t_evaluations.data_ptr()) if divide_by_vanishing else None
+        st = self._L.h2_extended_to_coeff_device(self.curve, ctypes.c_void_p(a.data_ptr()), self.extended_k, m,
+                                                 self._m["extended_omega_inv"].ctypes.data,
+                                                 self._m["extended_ifft_divisor"].ctypes.data,
+                                                 self._m["g_coset_inv"].ctypes.data, t, 1 << (self.extended_k - self.k),
+                                                 ctypes.c_void_p(out.data_ptr()), hlen, hlen, self._stream())
+        _lib.check(st, "h2_extended_to_coeff_device")
+        return out
 
     def divide_by_vanishing_poly(self, a):
         en = 1 << self.extended_k

@@ -64,6 +64,7 @@ SYMBOLS = {
     "h2_fft_group_device": (_I, [_I, _P, _P, _U32, _P]),
     "h2_ntt_scaled_device": (_I, [_I, _P, _Z, _P, _U32, _P, _P]),
     "h2_coeff_to_extended_device": (_I, [_I, _P, _Z, _U32, _Z, _P, _P, _U32, _P, _P]),
+    "h2_extended_to_coeff_device": (_I, [_I, _P, _U32, _Z, _P, _P, _P, _P, _Z, _P, _Z, _Z, _P]),
     "h2_poly_scale_device": (_I, [_I, _P, _Z, _Z, _P, _P]),
     "h2_poly_coset_device": (_I, [_I, _P, _Z, _Z, _P, _P]),
     "h2_poly_mul_periodic_device": (_I, [_I, _P, _Z, _Z, _P, _Z, _P]),

@@ -1096,7 +1096,7 @@ def _create_proof(params, pk, circuit, public_input, rng, trace, opening):
     numer = terms[0]
     for t in terms[1:]:
         numer = ops.add(ops.scale(numer, y), t)
-    h_pieces = dom.extended_to_coeff(dom.divide_by_vanishing_poly(numer)).view(d - 1, n, 4)
+    h_pieces = dom.extended_to_coeff(numer, divide_by_vanishing=True).view(d - 1, n, 4)
     del terms, numer, adv_e, fix_e, inst_e, sig_e, z_e, ext_of
     for pt in dev.commit(h_pieces, lagrange=False):
         tr.write_point(pt)

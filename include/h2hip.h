@@ -235,6 +235,31 @@ int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t o
 int h2_coeff_to_extended_device(h2_curve_t curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
                                 const uint64_t zeta[4], const uint64_t ext_omega[4], uint32_t ext_log_n,
                                 void* d_out, void* stream);
+/* EvaluationDomain::extended_to_coeff -- and divide_by_vanishing_poly before it when d_t is given -- in ONE call.
+ * m columns of 2^ext_log_n values over the SCALAR field of `curve`, column stride 2^ext_log_n  ->  m columns of out_len
+ * coefficients, column stride out_stride elements:
+ *   out[c][j] = zi[j mod 3] * scale * sum_{i < 2^ext_log_n} ext[c][i] * t[i mod t_period] * ext_omega_inv^(i*j)
+ *               for j < out_len,   zi = {1, zeta_inv, zeta_inv^2}
+ * d_t: a device table of t_period canonical Montgomery elements (h2_poly_mul_periodic_device's meaning), or NULL: no
+ * factor, t_period ignored.  With scale = 1 / 2^ext_log_n, zeta_inv = g_coset^-1 and out_len = n (j - 1) this is the
+ * ifft on the extended domain, the coset un-shift and the truncation.
+ * Out of place: the source is read only, d_out must not overlap it.  Canonical output, natural order.  Rows
+ * [out_len, out_stride) of every destination column are not touched.  Asynchronous on `stream`.
+ * No full-length coefficient column is written, read back or copied: the t factor rides on the first NTT pass's load;
+ * the last pass drops an output at or beyond out_len before any arithmetic and multiplies the others by zeta_inv^j
+ * (folded into the scale's product where the last pass has one) on their way out.  Stream, scratch and table rules
+ * are h2_ntt_scaled_device's: the same twiddle table for the same (ext_omega_inv, ext_log_n, scale), a multi-pass plan
+ * uses the stream's second buffer of m * 2^ext_log_n elements; nothing else is allocated, nothing else is cached.
+ * H2_EINVAL -- checked on the host before anything is enqueued -- for: a null d_ext, d_out, ext_omega_inv, scale or
+ * zeta_inv with m > 0 and out_len > 0; ext_log_n > 30; out_len > 2^ext_log_n; out_stride < out_len (or above 2^40);
+ * m > 65535; with d_t, a t_period that is zero, not a power of two or above 2^ext_log_n; a device pointer that is not
+ * 16-byte aligned; byte ranges of source and destination that overlap.  m = 0 or out_len = 0 is H2_OK and enqueues
+ * nothing; ext_log_n = 0 is legal (out[c][0] = ext[c][0] * t[0] * scale).
+ * h2_version() did not change for this entry point: a host detects it by its symbol. */
+int h2_extended_to_coeff_device(h2_curve_t curve, const void* d_ext, uint32_t ext_log_n, size_t m,
+                                const uint64_t ext_omega_inv[4], const uint64_t scale[4], const uint64_t zeta_inv[4],
+                                const void* d_t, size_t t_period,
+                                void* d_out, size_t out_len, size_t out_stride, void* stream);
 /* a[i] *= c */
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream);
 /* a[i] *= g^i : distribute_powers_zeta / the coset shift before an extended-domain NTT (and its inverse) */

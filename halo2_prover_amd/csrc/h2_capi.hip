@@ -18,44 +18,12 @@
 
 using namespace h2;
 
-namespace {
-// m Jacobian points (96 B, Montgomery limbs) -> m affine points (64 B, identity = (0, 0)) on the host, the m inversions
-// folded into one: the one-thread-per-point device kernel this replaces took 0.35 ms of pure latency per call
-template <class FP>
-void jac_to_affine_host(const uint8_t* jac, size_t m, uint8_t* out) {
-  using H = HF<FP>;
-  std::vector<H> z(m), pre(m);
-  H acc = H::one();
-  for (size_t j = 0; j < m; j++) {
-    z[j] = H::from_mont_limbs(jac + 96 * j + 64);
-    pre[j] = acc;
-    if (!z[j].is_zero()) acc *= z[j];
-  }
-  H inv = acc.inv();
-  for (size_t j = m; j-- > 0;) {
-    uint8_t* o = out + 64 * j;
-    if (z[j].is_zero()) {
-      memset(o, 0, 64);
-      continue;
-    }
-    const H zi = inv * pre[j], zi2 = zi.sqr();
-    inv *= z[j];
-    const H x = H::from_mont_limbs(jac + 96 * j) * zi2, y = H::from_mont_limbs(jac + 96 * j + 32) * zi2 * zi;
-    memcpy(o, x.v.v, 32);
-    memcpy(o + 32, y.v.v, 32);
-  }
-}
-void jac_to_affine_host(int curve, const uint8_t* jac, size_t m, uint8_t* out) {
-  if (curve == H2_BN254) jac_to_affine_host<BN254_FQ>(jac, m, out);
-  else if (curve == H2_PALLAS) jac_to_affine_host<PASTA_FP>(jac, m, out);
-  else jac_to_affine_host<PASTA_FQ>(jac, m, out);
-}
-}  // namespace
-
 namespace h2 {
 
 Global g_h2;
 std::recursive_mutex g_h2_mu;
+TestKnobs g_knobs;
+TestCounters g_counts;
 
 int dev_fail(hipError_t e, const char* where) {
   char buf[256];
@@ -96,13 +64,12 @@ int device_alloc(void** p, size_t bytes, const char* what) {
 }
 
 // ---- arenas ----------------------------------------------------------------------------------
-static uint64_t g_arena_growths = 0, g_arena_waits = 0;
 ArenaLease::ArenaLease(Arena& arena, size_t want, hipStream_t stream) : a(arena), s(stream) { rc = acquire(want); }
 int ArenaLease::acquire(size_t want) {
   clean_bytes = a.bytes < want ? 0 : a.clean_bytes;   // this user takes over the region and may overwrite it
   a.clean_bytes = 0;
   if (a.bytes < want) {
-    g_arena_growths++;
+    g_counts.arena_growths++;
     if (a.p) {
       // rare: a larger call than any before.  Work enqueued on other streams may still use the arena.
       H2_TRY(hipDeviceSynchronize());
@@ -117,7 +84,7 @@ int ArenaLease::acquire(size_t want) {
   }
   if (!a.ev) H2_TRY(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
   if (a.used && a.last != s) {                                         // order behind the previous user
-    g_arena_waits++;
+    g_counts.arena_waits++;
     H2_TRY(hipStreamWaitEvent(s, a.ev, 0));
   }
   return H2_OK;
@@ -222,15 +189,9 @@ int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t
 
 // Columns per launch: the sort indexes its m * W * n entries with 32 bits, so a wide batch of long columns
 // (2^24 rows x 8 columns) goes through in groups of columns, one after the other on the same stream and workspace.
-static uint64_t g_msm_max_entries = (1ull << 31) - 1;   // lowered only by h2_selftest_set_msm_max_entries (tests)
-// guard mode (tests only, h2_selftest_msm_guard): the workspace is laid out with a red zone behind every region, filled
-// with a pattern before each launch sequence and inspected after it
-static bool g_msm_guard = false, g_msm_guard_poke = false, g_sort2_pack = true;
-static uint64_t g_guard_launches = 0, g_guard_violations = 0;
-static std::string g_guard_first;
 size_t msm_cols_per_launch(const MsmGeom& geom, size_t n) {
   const uint64_t per_col = (uint64_t)geom.W * n;
-  const uint64_t by_entries = g_msm_max_entries / per_col;
+  const uint64_t by_entries = g_knobs.msm_max_entries / per_col;
   uint64_t by_keys = ((1ull << 31) - 1) / geom.B;
   // wide windows go through the two-level sort, whose one-block scan of the coarse bins holds S2_MAX_H of them: rather
   // than fall back to the one-level sort's scattered stores (which windows beyond 16 bits cannot use at all), a wider
@@ -242,15 +203,82 @@ size_t msm_cols_per_launch(const MsmGeom& geom, size_t n) {
   return (size_t)(by_entries < by_keys ? by_entries : by_keys);   // 0: a single column is already too long
 }
 
+// guard mode (tests only, h2_selftest_msm_guard): count the red-zone bytes that the launch sequence just enqueued changed
+// (synchronous) and note the first overrun; `m` (the caller's columns) and `what` describe the launch in that note
+static int msm_guard_inspect(const MsmWorkspace& ws, char* ws_base, hipStream_t stream, size_t m, const char* what) {
+  void* d_bad = nullptr;
+  if (int rc = device_alloc(&d_bad, ws.n_regions * 4, "guard"); rc != H2_OK) return rc;
+  DeviceBuffer owner(d_bad);
+  std::vector<uint32_t> bad(ws.n_regions, 0);
+  H2_TRY(hipMemsetAsync(d_bad, 0, ws.n_regions * 4, stream));
+  if (g_knobs.msm_guard_poke)        // the checker's own test: one byte just behind the second region
+    H2_TRY(hipMemsetAsync(ws_base + ws.regions[1].off + ws.regions[1].bytes, 0, 1, stream));
+  hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)ws_base, ws, (uint32_t*)d_bad);
+  H2_TRY(hipMemcpyAsync(bad.data(), d_bad, ws.n_regions * 4, hipMemcpyDeviceToHost, stream));
+  H2_TRY(hipStreamSynchronize(stream));
+  g_counts.guard_launches++;
+  for (uint32_t r = 0; r < ws.n_regions; r++)
+    if (bad[r]) {
+      if (!g_counts.guard_violations)
+        g_counts.guard_first = std::string(ws.regions[r].name) + ": " + std::to_string(bad[r]) + " byte(s) behind the region, n=" +
+                               std::to_string(ws.n) + " m=" + std::to_string(m) + what;
+      g_counts.guard_violations++;
+    }
+  return H2_OK;
+}
+
+// One planned launch sequence on the MSM workspace of `stream`, leased from its first kernel to its last:
+// launch(ws_base, zeroed) -> hipError_t enqueues it (`label` names it in an error), then finish(ws_base) -> status what
+// still reads the workspace.  A plan whose bounds proof failed ("<route> launch geometry: ...") enqueues nothing.
+template <class Launch, class Finish>
+static int msm_run_group(DevCtx& c, hipStream_t stream, const MsmGroupPlan& plan, const char* route, const char* label, size_t m,
+                         const char* guard_what, Launch&& launch, Finish&& finish) {
+  const MsmWorkspace& ws = plan.ws;
+  ArenaLease lease(c.msm_ws.of(stream), ws.total, stream);
+  if (lease.rc != H2_OK) return lease.rc;
+  Arena& A = lease.a;
+  // the plan proved the layout against its own size; the arena the lease handed out must hold it
+  if (const char* broken = plan.broken ? plan.broken : ws.total <= A.bytes ? nullptr : "ws.total <= arena_bytes") {
+    g_h2.last_error = std::string(route) + " launch geometry: " + broken;
+    return H2_EDEVICE;
+  }
+  const bool guard = g_knobs.msm_guard;
+  if (guard) H2_TRY(hipMemsetAsync(A.p, MSM_GUARD_BYTE, ws.total, stream));
+  // the previous launch sequence on this workspace (of either route) left its counter region zero: no memset when this
+  // one's fits in it
+  const bool zeroed = !guard && lease.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
+  if (int rc = launched(launch((char*)A.p, zeroed), label); rc != H2_OK) return rc;
+  if (guard) {
+    if (int rc = msm_guard_inspect(ws, (char*)A.p, stream, m, guard_what); rc != H2_OK) return rc;
+  } else {
+    A.clean_off = ws.off_misc;
+    A.clean_bytes = ws.zero_bytes;
+  }
+  if (int rc = finish((char*)A.p); rc != H2_OK) return rc;
+  return lease.release();
+}
+
+// h2_profile_*: the event pair around the accumulate kernel of a launch of m columns of n scalars, or nulls (profiling
+// off, or no event to be had)
+static std::pair<hipEvent_t, hipEvent_t> msm_prof_events(DevCtx& c, size_t n, size_t m) {
+  if (!g_h2.profiling) return {nullptr, nullptr};
+  if (c.prof_used == c.prof_events.size()) {
+    hipEvent_t a, b;
+    if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) c.prof_events.push_back({a, b});
+  }
+  if (c.prof_used == c.prof_events.size()) return {nullptr, nullptr};
+  c.prof_alg_bytes += (double)m * (double)n * 96.0 + (double)m * 96.0;  // SURVEY.md 8(d) bytes_msm
+  return c.prof_events[c.prof_used++];
+}
+
 int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_scalars, size_t first_base, size_t n,
                    size_t col_stride, size_t m, void* d_out, bool affine_out, hipStream_t stream,
                    const BasesEntry* const* per_column) {
-  const size_t group = msm_cols_per_launch(be.geom, n);
-  if (group == 0) return H2_EINVAL;
+  if (msm_cols_per_launch(be.geom, n) == 0) return H2_EINVAL;   // a single column is already too long
   // columns with their own bases: one launch only (they must share the registered length, hence the geometry)
   const void* col_tables[MSM_MAX_MULTI];
   if (per_column) {
-    if (m > MSM_MAX_MULTI || m > group) return H2_EINVAL;
+    if (m > MSM_MAX_MULTI) return H2_EINVAL;
     for (size_t j = 0; j < m; j++) {
       if (per_column[j]->n != be.n || per_column[j]->curve != be.curve) return H2_EINVAL;
       col_tables[j] = (const char*)per_column[j]->table[ctx_index(&c)] + first_base * 64;
@@ -260,98 +288,40 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
   const CurveOps* ops = ops_of(curve);
   // the table rows of bases first_base ...: entries are w * n_bases + i relative to this pointer
   const char* table = (const char*)be.table[ctx_index(&c)] + first_base * 64;
-  for (size_t j0 = 0; j0 < m; j0 += group) {
-    const size_t mm = m - j0 < group ? m - j0 : group;
-    MsmWorkspace ws = msm_workspace(n, mm, be.geom, g_msm_guard ? 256u : 0u, be.n, g_sort2_pack);
+  for (size_t j0 = 0; j0 < m;) {
+    const MsmGroupPlan plan = msm_plan_group(be.geom, be.n, n, m - j0, col_stride, g_knobs.msm_guard, g_knobs.sort2_pack);
+    const MsmWorkspace& ws = plan.ws;
+    const size_t mm = plan.cols;
+    if (per_column && mm < m) return H2_EINVAL;
     if (ws.E >= (1ull << 31) || ws.K >= (1ull << 31)) return H2_EINVAL;
-    ArenaLease lease(c.msm_ws.of(stream), ws.total, stream);
-    if (lease.rc != H2_OK) return lease.rc;
-    Arena& A = lease.a;
-    // every kernel's index range against the region it indexes, before anything is enqueued.  (n_bases is the
-    // REGISTERED length whatever the range: a sorted entry is w * be.n + i relative to the table row of first_base)
-    if (const char* broken = msm_check(ws, be.geom, n, mm, col_stride, (uint32_t)be.n, A.bytes)) {
-      g_h2.last_error = std::string("msm launch geometry: ") + broken;
-      return H2_EDEVICE;
-    }
-    if (g_msm_guard) H2_TRY(hipMemsetAsync(A.p, MSM_GUARD_BYTE, ws.total, stream));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g_h2.profiling) {
-      if (c.prof_used == c.prof_events.size()) {
-        hipEvent_t a, b;
-        if (hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) c.prof_events.push_back({a, b});
-      }
-      if (c.prof_used < c.prof_events.size()) {
-        ev0 = c.prof_events[c.prof_used].first;
-        ev1 = c.prof_events[c.prof_used].second;
-        c.prof_used++;
-        c.prof_alg_bytes += (double)mm * (double)n * 96.0 + (double)mm * 96.0;  // SURVEY.md 8(d) bytes_msm
-      }
-    }
     if (c.tail_wanted && !c.tail_event) H2_TRY(hipEventCreateWithFlags(&c.tail_event, hipEventDisableTiming));
     void* dst = (char*)d_out + j0 * out_sz;
-    // the previous launch sequence on this workspace left its counter region zero: no memset when this one's fits in it
-    const bool zeroed = !g_msm_guard && lease.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
-    hipError_t e = ops->msm_launch(table, per_column ? col_tables : nullptr, (uint32_t)be.n,
-                                   (const char*)d_scalars + j0 * col_stride * 32, n, col_stride,
-                                   mm, be.geom, (char*)A.p, ws, stream, ev0, ev1, (c.tail_wanted && !ev1) ? c.tail_event : nullptr,
-                                   affine_out ? nullptr : dst, zeroed);
-    c.tail_recorded = c.tail_wanted;
-    c.tail_wait = ev1 ? ev1 : c.tail_event;
-    if (e != hipSuccess) return dev_fail(e, "msm_launch");
-    if (!g_msm_guard) {
-      A.clean_off = ws.off_misc;
-      A.clean_bytes = ws.zero_bytes;
-    }
-    if (g_msm_guard) {
-      void* d_bad = nullptr;
-      if (int rc = device_alloc(&d_bad, ws.n_regions * 4, "guard"); rc != H2_OK) return rc;
-      DeviceBuffer owner(d_bad);
-      std::vector<uint32_t> bad(ws.n_regions, 0);
-      H2_TRY(hipMemsetAsync(d_bad, 0, ws.n_regions * 4, stream));
-      if (g_msm_guard_poke)        // the checker's own test: one byte just behind the second region
-        H2_TRY(hipMemsetAsync((char*)A.p + ws.regions[1].off + ws.regions[1].bytes, 0, 1, stream));
-      hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)A.p, ws, (uint32_t*)d_bad);
-      H2_TRY(hipMemcpyAsync(bad.data(), d_bad, ws.n_regions * 4, hipMemcpyDeviceToHost, stream));
-      H2_TRY(hipStreamSynchronize(stream));
-      g_guard_launches++;
-      for (uint32_t r = 0; r < ws.n_regions; r++)
-        if (bad[r]) {
-          if (!g_guard_violations)
-            g_guard_first = std::string(ws.regions[r].name) + ": " + std::to_string(bad[r]) + " byte(s) behind the region, n=" +
-                            std::to_string(n) + " m=" + std::to_string(mm) + (ws.sort2 ? " two-level sort" : ws.staged ? " staged scatter" : " direct scatter");
-          g_guard_violations++;
-        }
-    }
-    if (affine_out) {
-      e = ops->to_affine((char*)A.p + ws.off_tree2, dst, (uint32_t)mm, stream);
-      if (e != hipSuccess) return dev_fail(e, "msm finish kernel");
-    }
-    if (int rc = lease.release(); rc != H2_OK) return rc;
+    int rc = msm_run_group(
+        c, stream, plan, "msm", "msm_launch", mm, ws.sort2 ? " two-level sort" : ws.staged ? " staged scatter" : " direct scatter",
+        [&](char* ws_base, bool zeroed) {
+          const auto [ev0, ev1] = msm_prof_events(c, n, mm);
+          hipError_t e = ops->msm_launch(table, per_column ? col_tables : nullptr, (uint32_t)be.n,
+                                         (const char*)d_scalars + j0 * col_stride * 32, n, col_stride, mm, be.geom, ws_base, ws, stream,
+                                         ev0, ev1, (c.tail_wanted && !ev1) ? c.tail_event : nullptr, affine_out ? nullptr : dst, zeroed);
+          c.tail_recorded = c.tail_wanted;
+          c.tail_wait = ev1 ? ev1 : c.tail_event;
+          return e;
+        },
+        [&](char* ws_base) {
+          return affine_out ? launched(ops->to_affine(ws_base + ws.off_tree2, dst, (uint32_t)mm, stream), "msm finish kernel") : H2_OK;
+        });
+    if (rc != H2_OK) return rc;
+    j0 += mm;
   }
   return H2_OK;
 }
 
 // ---- table-free MSM over the caller's points (h2_msm_points.hpp) ---------------------------------------------------
-// terms below which a call takes msm_small_kernel's double-and-add route; moved only by
-// h2_selftest_set_msm_points_small_max (tests, tools/msm_points_bench.py)
-static size_t g_points_small_max = MSM_POINTS_SMALL_MAX;
-
-static void guard_inspect_note(const MsmWorkspace& ws, const std::vector<uint32_t>& bad, size_t n, size_t m, const char* what) {
-  g_guard_launches++;
-  for (uint32_t r = 0; r < ws.n_regions; r++)
-    if (bad[r]) {
-      if (!g_guard_violations)
-        g_guard_first = std::string(ws.regions[r].name) + ": " + std::to_string(bad[r]) + " byte(s) behind the region, n=" +
-                        std::to_string(n) + " m=" + std::to_string(m) + what;
-      g_guard_violations++;
-    }
-}
-
 // arguments checked by the caller; n >= 1, m >= 1
 static int msm_points_run(DevCtx& c, int curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride,
                           size_t m, void* d_out, hipStream_t stream) {
   const CurveOps* ops = ops_of(curve);
-  if (n < g_points_small_max) {
+  if (n < g_knobs.points_small_max) {
     // short inputs: one quad per term, m jobs side by side in groups of MSM_SMALL_MAX; the partials live in the MSM workspace
     const size_t blocks = (n + 15) / 16, work = MSM_SMALL_MAX * (blocks * (XYZZ29_WORDS * 4) + 4);
     for (size_t j0 = 0; j0 < m; j0 += MSM_SMALL_MAX) {
@@ -366,47 +336,26 @@ static int msm_points_run(DevCtx& c, int curve, const void* d_points, const void
         sc[j] = (const char*)d_scalars + (j0 + j) * col_stride * 32;
         len[j] = (uint32_t)n;
       }
-      hipError_t e = ops->msm_small(pts, sc, len, count, lease.a.p, (char*)d_out + j0 * 96, stream);
-      if (e != hipSuccess) return dev_fail(e, "msm_small_kernel");
+      if (int rc = launched(ops->msm_small(pts, sc, len, count, lease.a.p, (char*)d_out + j0 * 96, stream), "msm_small_kernel"); rc != H2_OK)
+        return rc;
       if (int rc = lease.release(); rc != H2_OK) return rc;
     }
     return H2_OK;
   }
   const MsmGeom g = msm_points_geometry(n, ops->scalar_bits);
-  const size_t group = msm_points_cols_per_launch(g, n);
-  if (group == 0) return H2_EINVAL;
-  for (size_t j0 = 0; j0 < m; j0 += group) {
-    const size_t mm = std::min(group, m - j0);
-    const MsmWorkspace ws = msm_points_workspace(n, mm, g, g_msm_guard ? 256u : 0u);
-    ArenaLease lease(c.msm_ws.of(stream), ws.total, stream);
-    if (lease.rc != H2_OK) return lease.rc;
-    Arena& A = lease.a;
-    // every kernel's index range against the region it indexes, before anything is enqueued
-    if (const char* broken = msm_points_check(ws, g, n, mm, col_stride, A.bytes)) {
-      g_h2.last_error = std::string("msm points launch geometry: ") + broken;
-      return H2_EDEVICE;
-    }
-    if (g_msm_guard) H2_TRY(hipMemsetAsync(A.p, MSM_GUARD_BYTE, ws.total, stream));
-    // the previous launch sequence on this workspace (of either kind) left its counter region zero
-    const bool zeroed = !g_msm_guard && lease.clean_bytes >= ws.zero_bytes && A.clean_off == ws.off_misc;
-    hipError_t e = ops->msm_points_launch(d_points, (const char*)d_scalars + j0 * col_stride * 32, n, col_stride, mm, g, (char*)A.p, ws,
-                                          stream, (char*)d_out + j0 * 96, zeroed);
-    if (e != hipSuccess) return dev_fail(e, "msm_points_launch");
-    if (!g_msm_guard) {
-      A.clean_off = ws.off_misc;
-      A.clean_bytes = ws.zero_bytes;
-    } else {
-      void* d_bad = nullptr;
-      if (int rc = device_alloc(&d_bad, ws.n_regions * 4, "guard"); rc != H2_OK) return rc;
-      DeviceBuffer owner(d_bad);
-      std::vector<uint32_t> bad(ws.n_regions, 0);
-      H2_TRY(hipMemsetAsync(d_bad, 0, ws.n_regions * 4, stream));
-      hipLaunchKernelGGL(msm_guard_check_kernel, dim3(ws.n_regions), dim3(256), 0, stream, (const uint8_t*)A.p, ws, (uint32_t*)d_bad);
-      H2_TRY(hipMemcpyAsync(bad.data(), d_bad, ws.n_regions * 4, hipMemcpyDeviceToHost, stream));
-      H2_TRY(hipStreamSynchronize(stream));
-      guard_inspect_note(ws, bad, n, mm, " points front");
-    }
-    if (int rc = lease.release(); rc != H2_OK) return rc;
+  for (size_t j0 = 0; j0 < m;) {
+    const MsmGroupPlan plan = msm_points_plan_group(g, n, m - j0, col_stride, g_knobs.msm_guard);
+    const size_t mm = plan.cols;
+    if (mm == 0) return H2_EINVAL;
+    int rc = msm_run_group(
+        c, stream, plan, "msm points", "msm_points_launch", mm, " points front",
+        [&](char* ws_base, bool zeroed) {
+          return ops->msm_points_launch(d_points, (const char*)d_scalars + j0 * col_stride * 32, n, col_stride, mm, g, ws_base, plan.ws,
+                                        stream, (char*)d_out + j0 * 96, zeroed);
+        },
+        [](char*) { return (int)H2_OK; });
+    if (rc != H2_OK) return rc;
+    j0 += mm;
   }
   return H2_OK;
 }
@@ -450,22 +399,31 @@ static int get_twiddles(DevCtx& c, const CurveOps* ops, const uint64_t omega[4],
   return H2_OK;
 }
 
-int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, hipStream_t stream,
-                const uint64_t* scale) {
-  const CurveOps* ops = ops_of(curve);
-  if (!ops) return H2_EINVAL;
+// One transform launch sequence of m columns of 2^log_n: the tables of (omega, log_n[, table_scale]) -- none for one
+// element -- and, for a two-pass plan, the second buffer on `stream` for as long as launch(tables, scratch) -> hipError_t
+// uses it; `what` names the launch in an error
+template <class Launch>
+static int ntt_run(DevCtx& c, const CurveOps* ops, const uint64_t omega[4], uint32_t log_n, const uint64_t* table_scale, size_t m,
+                   hipStream_t stream, const char* what, Launch&& launch) {
   const void* tw = nullptr;
-  // a constant that rides in the inter-pass twiddles needs tables built with it
-  int rc = get_twiddles(c, ops, omega, log_n, (scale && ops->ntt_scale_in_table(log_n)) ? scale : nullptr, &tw);
-  if (rc != H2_OK) return rc;
-  std::optional<ArenaLease> A;     // the second buffer of a two-pass transform
+  if (log_n > 0)
+    if (int rc = get_twiddles(c, ops, omega, log_n, table_scale, &tw); rc != H2_OK) return rc;
+  std::optional<ArenaLease> A;
   if (ntt_make_plan(log_n).npass > 1) {
     A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << log_n), stream);
     if (A->rc != H2_OK) return A->rc;
   }
-  hipError_t e = ops->ntt_launch(d_a, A ? A->a.p : nullptr, tw, log_n, m, stream, scale);
-  if (e != hipSuccess) return dev_fail(e, "ntt_launch");
+  if (int rc = launched(launch(tw, A ? A->a.p : nullptr), what); rc != H2_OK) return rc;
   return A ? A->release() : H2_OK;
+}
+
+int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, hipStream_t stream,
+                const uint64_t* scale) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops) return H2_EINVAL;
+  // a constant that rides in the inter-pass twiddles needs tables built with it
+  return ntt_run(c, ops, omega, log_n, (scale && ops->ntt_scale_in_table(log_n)) ? scale : nullptr, m, stream, "ntt_launch",
+                 [&](const void* tw, void* scratch) { return ops->ntt_launch(d_a, scratch, tw, log_n, m, stream, scale); });
 }
 
 int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t col_stride, uint32_t log_n, size_t m,
@@ -473,17 +431,10 @@ int coeff_to_extended_enqueue(DevCtx& c, int curve, const void* d_coeff, size_t 
                               hipStream_t stream) {
   const CurveOps* ops = ops_of(curve);
   if (!ops) return H2_EINVAL;
-  const void* tw = nullptr;
-  int rc = get_twiddles(c, ops, ext_omega, ext_log_n, nullptr, &tw);
-  if (rc != H2_OK) return rc;
-  std::optional<ArenaLease> A;     // pass 0 writes it; the padded source column never exists
-  if (ntt_make_plan(ext_log_n).npass > 1) {
-    A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << ext_log_n), stream);
-    if (A->rc != H2_OK) return A->rc;
-  }
-  hipError_t e = ops->ntt_extend_launch(d_coeff, col_stride, log_n, zeta, d_out, A ? A->a.p : nullptr, tw, ext_log_n, m, stream);
-  if (e != hipSuccess) return dev_fail(e, "ntt_extend_launch");
-  return A ? A->release() : H2_OK;
+  // pass 0 writes the second buffer; the padded source column never exists
+  return ntt_run(c, ops, ext_omega, ext_log_n, nullptr, m, stream, "ntt_extend_launch", [&](const void* tw, void* scratch) {
+    return ops->ntt_extend_launch(d_coeff, col_stride, log_n, zeta, d_out, scratch, tw, ext_log_n, m, stream);
+  });
 }
 
 int extended_to_coeff_enqueue(DevCtx& c, int curve, const void* d_ext, uint32_t ext_log_n, size_t m,
@@ -492,20 +443,12 @@ int extended_to_coeff_enqueue(DevCtx& c, int curve, const void* d_ext, uint32_t 
   const CurveOps* ops = ops_of(curve);
   if (!ops) return H2_EINVAL;
   if (m == 0 || out_len == 0) return H2_OK;
-  const void* tw = nullptr;      // ntt_enqueue's entry for the same (omega, log n, scale); one element needs none
-  if (ext_log_n > 0) {
-    int rc = get_twiddles(c, ops, ext_omega_inv, ext_log_n, ops->ntt_scale_in_table(ext_log_n) ? scale : nullptr, &tw);
-    if (rc != H2_OK) return rc;
-  }
-  std::optional<ArenaLease> A;     // pass 0 writes it: the source is only read
-  if (ntt_make_plan(ext_log_n).npass > 1) {
-    A.emplace(c.ntt_ws.of(stream), m * ((size_t)32 << ext_log_n), stream);
-    if (A->rc != H2_OK) return A->rc;
-  }
-  hipError_t e = ops->ntt_coeff_launch(d_ext, d_t, t_period, scale, zeta_inv, d_out, out_len, out_stride, A ? A->a.p : nullptr, tw,
-                                       ext_log_n, m, stream);
-  if (e != hipSuccess) return dev_fail(e, "ntt_coeff_launch");
-  return A ? A->release() : H2_OK;
+  // ntt_enqueue's tables for the same (omega, log n, scale); pass 0 writes the second buffer: the source is only read
+  return ntt_run(c, ops, ext_omega_inv, ext_log_n, ops->ntt_scale_in_table(ext_log_n) ? scale : nullptr, m, stream, "ntt_coeff_launch",
+                 [&](const void* tw, void* scratch) {
+                   return ops->ntt_coeff_launch(d_ext, d_t, t_period, scale, zeta_inv, d_out, out_len, out_stride, scratch, tw, ext_log_n,
+                                                m, stream);
+                 });
 }
 
 int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n, const uint64_t* points, size_t q, void* d_out,
@@ -529,8 +472,8 @@ int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n
   void* ws = (char*)A.a.p + table_bytes;
   for (size_t t0 = 0; t0 < q; t0 += group) {             // the groups share `ws`: the stream runs them in order
     const size_t cnt = std::min(group, q - t0);
-    hipError_t e = ops->poly_eval(d_jobs + t0, (uint32_t)cnt, n, ws, (char*)d_out + 32 * t0, stream);
-    if (e != hipSuccess) return dev_fail(e, "poly_eval kernels");
+    if (int rc = launched(ops->poly_eval(d_jobs + t0, (uint32_t)cnt, n, ws, (char*)d_out + 32 * t0, stream), "poly_eval kernels"); rc != H2_OK)
+      return rc;
   }
   return A.release();
 }
@@ -584,6 +527,122 @@ int init_devices(int n, const int* ids) {
   // one context: stay on its device (h2_init(device) has always left the process there); several: back to where we were
   H2_TRY(hipSetDevice(n == 1 ? ids[0] : prev));
   g_h2.ready = true;
+  return H2_OK;
+}
+
+// m Jacobian points (96 B, Montgomery limbs) -> m affine points (64 B, identity = (0, 0)) on the host, the m inversions
+// folded into one: the one-thread-per-point device kernel this replaces took 0.35 ms of pure latency per call
+template <class FP>
+void jac_to_affine_host(const uint8_t* jac, size_t m, uint8_t* out) {
+  using H = HF<FP>;
+  std::vector<H> z(m), pre(m);
+  H acc = H::one();
+  for (size_t j = 0; j < m; j++) {
+    z[j] = H::from_mont_limbs(jac + 96 * j + 64);
+    pre[j] = acc;
+    if (!z[j].is_zero()) acc *= z[j];
+  }
+  H inv = acc.inv();
+  for (size_t j = m; j-- > 0;) {
+    uint8_t* o = out + 64 * j;
+    if (z[j].is_zero()) {
+      memset(o, 0, 64);
+      continue;
+    }
+    const H zi = inv * pre[j], zi2 = zi.sqr();
+    inv *= z[j];
+    const H x = H::from_mont_limbs(jac + 96 * j) * zi2, y = H::from_mont_limbs(jac + 96 * j + 32) * zi2 * zi;
+    memcpy(o, x.v.v, 32);
+    memcpy(o + 32, y.v.v, 32);
+  }
+}
+void jac_to_affine_host(int curve, const uint8_t* jac, size_t m, uint8_t* out) {
+  if (curve == H2_BN254) jac_to_affine_host<BN254_FQ>(jac, m, out);
+  else if (curve == H2_PALLAS) jac_to_affine_host<PASTA_FP>(jac, m, out);
+  else jac_to_affine_host<PASTA_FQ>(jac, m, out);
+}
+
+// Host-pointer MSMs.  With several contexts (h2_init_devices) a batch is sharded by column, column j -> context
+// j mod G, and a single long MSM by contiguous point range with the G partial sums added on context 0
+// (SURVEY.md section 8(e)); every context works on its own stream, the host waits once at the end.
+int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* cols, size_t n, size_t m, uint64_t* out,
+                    bool affine_out) {
+  const BasesEntry* be = nullptr;
+  int rc = msm_common_checks((int)curve, handle, 0, n, m, &be);
+  if (rc != H2_OK) return rc;
+  if (!out || !cols) return H2_EINVAL;
+  const size_t out_sz = affine_out ? 64 : 96;
+  if (n == 0) {
+    memset(out, 0, m * out_sz);
+    return H2_OK;
+  }
+  for (size_t j = 0; j < m; j++)
+    if (!cols[j]) return H2_EINVAL;
+  const size_t G = g_h2.ctx.size();
+  const size_t col_bytes = n * 32;
+  if (m == 1 && G > 1 && n >= 4096 * G) {
+    // point-range split of one MSM: context g takes bases [lo_g, hi_g)
+    std::vector<uint64_t> partial(G * 12);
+    std::vector<std::optional<ArenaLease>> stages(G);
+    for (size_t g = 0; g < G; g++) {
+      DevCtx& c = g_h2.ctx[g];
+      DeviceGuard dg(c.device);
+      const size_t lo = n * g / G, hi = n * (g + 1) / G, cnt = hi - lo;
+      const size_t res_off = h2_align256(cnt * 32);
+      if (int st = stages[g].emplace(c.stage, res_off + 96, c.stream).rc; st != H2_OK) return st;
+      H2_TRY(hipMemcpyAsync(c.stage.p, (const char*)cols[0] + lo * 32, cnt * 32, hipMemcpyHostToDevice, c.stream));
+      void* d_res = (char*)c.stage.p + res_off;
+      rc = msm_device_run(c, (int)curve, *be, c.stage.p, lo, cnt, cnt, 1, d_res, false, c.stream);
+      if (rc != H2_OK) return rc;
+      H2_TRY(hipMemcpyAsync(&partial[12 * g], d_res, 96, hipMemcpyDeviceToHost, c.stream));
+    }
+    for (size_t g = 0; g < G; g++) {
+      DeviceGuard dg(g_h2.ctx[g].device);
+      if (int st = stages[g]->wait(); st != H2_OK) return st;
+    }
+    // add the G partial sums on context 0 (they are 96 bytes each)
+    DevCtx& c = g_h2.ctx[0];
+    DeviceGuard dg(c.device);
+    const size_t res_off = h2_align256(G * 96);
+    ArenaLease stage(c.stage, res_off + 96, c.stream);
+    if (stage.rc != H2_OK) return stage.rc;
+    H2_TRY(hipMemcpyAsync(c.stage.p, partial.data(), G * 96, hipMemcpyHostToDevice, c.stream));
+    void* d_res = (char*)c.stage.p + res_off;
+    if (int st = launched(ops_of((int)curve)->points_sum(c.stage.p, d_res, (uint32_t)G, 1, c.stream), "points_sum_kernel"); st != H2_OK)
+      return st;
+    if (affine_out) return H2_EINVAL;   // not reached: h2_msm asks for Jacobian
+    H2_TRY(hipMemcpyAsync(out, d_res, 96, hipMemcpyDeviceToHost, c.stream));
+    return stage.wait();
+  }
+  // column sharding: context g takes columns g, g + G, ...; the results come back as Jacobian points and are
+  // normalised on the host when the caller wants affine ones
+  std::vector<uint8_t> jac(affine_out ? m * 96 : 0);
+  uint8_t* dst = affine_out ? jac.data() : (uint8_t*)out;
+  std::vector<std::optional<ArenaLease>> stages(G);
+  for (size_t g = 0; g < G && g < m; g++) {
+    DevCtx& c = g_h2.ctx[g];
+    DeviceGuard dg(c.device);
+    const size_t mine = (m - g + G - 1) / G;
+    const size_t res_off = h2_align256(mine * col_bytes);
+    if (int st = stages[g].emplace(c.stage, res_off + mine * 96, c.stream).rc; st != H2_OK) return st;
+    for (size_t i = 0; i < mine; i++)
+      H2_TRY(hipMemcpyAsync((char*)c.stage.p + i * col_bytes, cols[g + i * G], col_bytes, hipMemcpyHostToDevice,
+                            c.stream));
+    void* d_res = (char*)c.stage.p + res_off;
+    rc = msm_device_run(c, (int)curve, *be, c.stage.p, 0, n, n, mine, d_res, false, c.stream);
+    if (rc != H2_OK) return rc;
+    if (G == 1) {
+      H2_TRY(hipMemcpyAsync(dst, d_res, mine * 96, hipMemcpyDeviceToHost, c.stream));
+    } else {
+      for (size_t i = 0; i < mine; i++)
+        H2_TRY(hipMemcpyAsync(dst + (g + i * G) * 96, (char*)d_res + i * 96, 96, hipMemcpyDeviceToHost, c.stream));
+    }
+  }
+  for (size_t g = 0; g < G && g < m; g++) {
+    DeviceGuard dg(g_h2.ctx[g].device);
+    if (int st = stages[g]->wait(); st != H2_OK) return st;
+  }
+  if (affine_out) jac_to_affine_host((int)curve, jac.data(), m, (uint8_t*)out);
   return H2_OK;
 }
 
@@ -770,9 +829,7 @@ int h2_points_sum_device(h2_curve_t curve, const void* d_in_jac, size_t groups, 
   if (!curve_ok((int)curve) || !d_in_jac || !d_out_jac || groups == 0 || groups > (1u << 20) || count > (1u << 24))
     return H2_EINVAL;
   if (count == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->points_sum(d_in_jac, d_out_jac, (uint32_t)groups, (uint32_t)count, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "points_sum_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->points_sum(d_in_jac, d_out_jac, (uint32_t)groups, (uint32_t)count, k.stream), "points_sum_kernel");
 }
 
 int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine, void* d_status,
@@ -784,93 +841,7 @@ int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size
   // the kernel moves 16 bytes at a time
   if (!d_compressed || !d_out_affine || !d_status || ((uintptr_t)d_compressed & 15) || ((uintptr_t)d_out_affine & 15))
     return H2_EINVAL;
-  hipError_t e = ops_of((int)curve)->points_decompress(d_compressed, d_out_affine, d_status, (uint32_t)n, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "points_decompress_kernel");
-  return H2_OK;
-}
-
-// Host-pointer MSMs.  With several contexts (h2_init_devices) a batch is sharded by column, column j -> context
-// j mod G, and a single long MSM by contiguous point range with the G partial sums added on context 0
-// (SURVEY.md section 8(e)); every context works on its own stream, the host waits once at the end.
-static int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* cols, size_t n, size_t m, uint64_t* out,
-                    bool affine_out) {
-  const BasesEntry* be = nullptr;
-  int rc = msm_common_checks((int)curve, handle, 0, n, m, &be);
-  if (rc != H2_OK) return rc;
-  if (!out || !cols) return H2_EINVAL;
-  const size_t out_sz = affine_out ? 64 : 96;
-  if (n == 0) {
-    memset(out, 0, m * out_sz);
-    return H2_OK;
-  }
-  for (size_t j = 0; j < m; j++)
-    if (!cols[j]) return H2_EINVAL;
-  const size_t G = g_h2.ctx.size();
-  const size_t col_bytes = n * 32;
-  if (m == 1 && G > 1 && n >= 4096 * G) {
-    // point-range split of one MSM: context g takes bases [lo_g, hi_g)
-    std::vector<uint64_t> partial(G * 12);
-    std::vector<std::optional<ArenaLease>> stages(G);
-    for (size_t g = 0; g < G; g++) {
-      DevCtx& c = g_h2.ctx[g];
-      DeviceGuard dg(c.device);
-      const size_t lo = n * g / G, hi = n * (g + 1) / G, cnt = hi - lo;
-      const size_t res_off = h2_align256(cnt * 32);
-      if (int st = stages[g].emplace(c.stage, res_off + 96, c.stream).rc; st != H2_OK) return st;
-      H2_TRY(hipMemcpyAsync(c.stage.p, (const char*)cols[0] + lo * 32, cnt * 32, hipMemcpyHostToDevice, c.stream));
-      void* d_res = (char*)c.stage.p + res_off;
-      rc = msm_device_run(c, (int)curve, *be, c.stage.p, lo, cnt, cnt, 1, d_res, false, c.stream);
-      if (rc != H2_OK) return rc;
-      H2_TRY(hipMemcpyAsync(&partial[12 * g], d_res, 96, hipMemcpyDeviceToHost, c.stream));
-    }
-    for (size_t g = 0; g < G; g++) {
-      DeviceGuard dg(g_h2.ctx[g].device);
-      if (int st = stages[g]->wait(); st != H2_OK) return st;
-    }
-    // add the G partial sums on context 0 (they are 96 bytes each)
-    DevCtx& c = g_h2.ctx[0];
-    DeviceGuard dg(c.device);
-    const size_t res_off = h2_align256(G * 96);
-    ArenaLease stage(c.stage, res_off + 96, c.stream);
-    if (stage.rc != H2_OK) return stage.rc;
-    H2_TRY(hipMemcpyAsync(c.stage.p, partial.data(), G * 96, hipMemcpyHostToDevice, c.stream));
-    void* d_res = (char*)c.stage.p + res_off;
-    hipError_t e = ops_of((int)curve)->points_sum(c.stage.p, d_res, (uint32_t)G, 1, c.stream);
-    if (e != hipSuccess) return dev_fail(e, "points_sum_kernel");
-    if (affine_out) return H2_EINVAL;   // not reached: h2_msm asks for Jacobian
-    H2_TRY(hipMemcpyAsync(out, d_res, 96, hipMemcpyDeviceToHost, c.stream));
-    return stage.wait();
-  }
-  // column sharding: context g takes columns g, g + G, ...; the results come back as Jacobian points and are
-  // normalised on the host when the caller wants affine ones
-  std::vector<uint8_t> jac(affine_out ? m * 96 : 0);
-  uint8_t* dst = affine_out ? jac.data() : (uint8_t*)out;
-  std::vector<std::optional<ArenaLease>> stages(G);
-  for (size_t g = 0; g < G && g < m; g++) {
-    DevCtx& c = g_h2.ctx[g];
-    DeviceGuard dg(c.device);
-    const size_t mine = (m - g + G - 1) / G;
-    const size_t res_off = h2_align256(mine * col_bytes);
-    if (int st = stages[g].emplace(c.stage, res_off + mine * 96, c.stream).rc; st != H2_OK) return st;
-    for (size_t i = 0; i < mine; i++)
-      H2_TRY(hipMemcpyAsync((char*)c.stage.p + i * col_bytes, cols[g + i * G], col_bytes, hipMemcpyHostToDevice,
-                            c.stream));
-    void* d_res = (char*)c.stage.p + res_off;
-    rc = msm_device_run(c, (int)curve, *be, c.stage.p, 0, n, n, mine, d_res, false, c.stream);
-    if (rc != H2_OK) return rc;
-    if (G == 1) {
-      H2_TRY(hipMemcpyAsync(dst, d_res, mine * 96, hipMemcpyDeviceToHost, c.stream));
-    } else {
-      for (size_t i = 0; i < mine; i++)
-        H2_TRY(hipMemcpyAsync(dst + (g + i * G) * 96, (char*)d_res + i * 96, 96, hipMemcpyDeviceToHost, c.stream));
-    }
-  }
-  for (size_t g = 0; g < G && g < m; g++) {
-    DeviceGuard dg(g_h2.ctx[g].device);
-    if (int st = stages[g]->wait(); st != H2_OK) return st;
-  }
-  if (affine_out) jac_to_affine_host((int)curve, jac.data(), m, (uint8_t*)out);
-  return H2_OK;
+  return launched(ops_of((int)curve)->points_decompress(d_compressed, d_out_affine, d_status, (uint32_t)n, k.stream), "points_decompress_kernel");
 }
 
 int h2_msm(h2_curve_t curve, uint64_t handle, const uint64_t* scalars, size_t n, uint64_t out_jac[12]) {
@@ -894,11 +865,11 @@ int h2_msm_points_plan(h2_curve_t curve, size_t n, h2_msm_points_plan_t* out) {
   out->window_bits = g.c;
   out->windows = g.W;
   out->buckets = g.B;
-  out->route = n < g_points_small_max ? 0u : 1u;
+  out->route = n < g_knobs.points_small_max ? 0u : 1u;
   out->scalar_bits = g.nbits;
   out->lds_bytes = (uint32_t)((size_t)g.W * g.B * 4);
   out->lds_limit = (uint32_t)MSM_POINTS_LDS_CAP;
-  out->crossover = (uint64_t)g_points_small_max;
+  out->crossover = (uint64_t)g_knobs.points_small_max;
   out->max_n = (uint64_t)MSM_POINTS_MAX_N;
   for (uint32_t w = 0; w < g.W; w++) {
     out->width[w] = g.width[w];
@@ -910,11 +881,10 @@ int h2_msm_points_plan(h2_curve_t curve, size_t n, h2_msm_points_plan_t* out) {
 int h2_msm_points_device(h2_curve_t curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride, size_t m,
                          void* d_out_jac, void* stream_) {
   Call k(stream_);
-  if (!g_h2.ready) return H2_ENOTINIT;
+  if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || col_stride < n || n > MSM_POINTS_MAX_N) return H2_EINVAL;
   if (((uintptr_t)d_points & 15) || ((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_jac & 15)) return H2_EINVAL;
   if (m > 0 && (!d_out_jac || (n > 0 && (!d_points || !d_scalars)))) return H2_EINVAL;
-  if (k.rc != H2_OK) return k.rc;
   if (m == 0) return H2_OK;
   if (n == 0) {
     H2_TRY(hipMemsetAsync(d_out_jac, 0, m * 96, k.stream));
@@ -925,9 +895,8 @@ int h2_msm_points_device(h2_curve_t curve, const void* d_points, const void* d_s
 
 int h2_msm_points(h2_curve_t curve, const uint64_t* points, const uint64_t* scalars, size_t n, uint64_t out_jac[12]) {
   Call k(nullptr);
-  if (!g_h2.ready) return H2_ENOTINIT;
-  if (!curve_ok((int)curve) || n > MSM_POINTS_MAX_N || !out_jac || (n > 0 && (!points || !scalars))) return H2_EINVAL;
   if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || n > MSM_POINTS_MAX_N || !out_jac || (n > 0 && (!points || !scalars))) return H2_EINVAL;
   if (n == 0) {
     memset(out_jac, 0, 96);
     return H2_OK;
@@ -949,9 +918,7 @@ int h2_srs_generate(h2_curve_t curve, const uint64_t s[4], size_t n, void* d_out
   if (k.rc != H2_OK) return k.rc;
   const CurveOps* ops = ops_of((int)curve);
   if (!ops || !s || !d_out_affine || n == 0 || n >= (1ull << 32)) return H2_EINVAL;
-  hipError_t e = ops->srs_powers(d_out_affine, s, (uint32_t)n, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "srs_powers_kernel");
-  return H2_OK;
+  return launched(ops->srs_powers(d_out_affine, s, (uint32_t)n, k.stream), "srs_powers_kernel");
 }
 
 int h2_fixed_base_mul(h2_curve_t curve, const void* d_scalars, size_t n, void* d_out_affine, void* stream_) {
@@ -959,9 +926,7 @@ int h2_fixed_base_mul(h2_curve_t curve, const void* d_scalars, size_t n, void* d
   if (k.rc != H2_OK) return k.rc;
   const CurveOps* ops = ops_of((int)curve);
   if (!ops || !d_scalars || !d_out_affine || n == 0 || n >= (1ull << 32)) return H2_EINVAL;
-  hipError_t e = ops->fixed_base_mul(d_out_affine, d_scalars, (uint32_t)n, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "fixed_base_mul_kernel");
-  return H2_OK;
+  return launched(ops->fixed_base_mul(d_out_affine, d_scalars, (uint32_t)n, k.stream), "fixed_base_mul_kernel");
 }
 
 int h2_profile_enable(int on) {
@@ -1012,9 +977,7 @@ int h2_ntt_scaled_device(h2_curve_t curve, void* d_a, size_t m, const uint64_t o
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !omega || !scale || m == 0 || log_n > 30) return H2_EINVAL;
   if (log_n == 0) {
-    hipError_t e = ops_of((int)curve)->poly_scale(d_a, m, scale, k.stream);
-    if (e != hipSuccess) return dev_fail(e, "poly_scale_kernel");
-    return H2_OK;
+    return launched(ops_of((int)curve)->poly_scale(d_a, m, scale, k.stream), "poly_scale_kernel");
   }
   return ntt_enqueue(*k.c, (int)curve, d_a, m, omega, log_n, k.stream, scale);
 }
@@ -1065,9 +1028,7 @@ int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const 
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !c) return H2_EINVAL;
   if (n * m == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->poly_scale(d_a, n * m, c, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_scale_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->poly_scale(d_a, n * m, c, k.stream), "poly_scale_kernel");
 }
 
 int h2_poly_coset_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t g[4], void* stream_) {
@@ -1075,9 +1036,7 @@ int h2_poly_coset_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const 
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !g) return H2_EINVAL;
   if (n * m == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->poly_powers(d_a, n, m, g, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_powers_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->poly_powers(d_a, n, m, g, k.stream), "poly_powers_kernel");
 }
 
 int h2_poly_mul_periodic_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const void* d_t, size_t period,
@@ -1086,9 +1045,7 @@ int h2_poly_mul_periodic_device(h2_curve_t curve, void* d_a, size_t n, size_t m,
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_t || period == 0 || (period & (period - 1))) return H2_EINVAL;
   if (n * m == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->poly_mul_periodic(d_a, n * m, d_t, period, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_mul_periodic_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->poly_mul_periodic(d_a, n * m, d_t, period, k.stream), "poly_mul_periodic_kernel");
 }
 
 int h2_poly_inverse_device(h2_curve_t curve, void* d_a, size_t n, void* stream_) {
@@ -1096,9 +1053,7 @@ int h2_poly_inverse_device(h2_curve_t curve, void* d_a, size_t n, void* stream_)
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->poly_inverse(d_a, n, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_inverse_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->poly_inverse(d_a, n, k.stream), "poly_inverse_kernel");
 }
 
 int h2_poly_divide_linear_device(h2_curve_t curve, const void* d_a, size_t n, const uint64_t z[4], void* d_q,
@@ -1109,8 +1064,7 @@ int h2_poly_divide_linear_device(h2_curve_t curve, const void* d_a, size_t n, co
   if (n == 0) return H2_OK;
   ArenaLease A(k.c->div_ws, SCAN_WS_BYTES, k.stream);
   if (A.rc != H2_OK) return A.rc;
-  hipError_t e = ops_of((int)curve)->poly_scan(0, &d_a, &d_q, z, 1, n, A.a.p, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_scan kernels");
+  if (int rc = launched(ops_of((int)curve)->poly_scan(0, &d_a, &d_q, z, 1, n, A.a.p, k.stream), "poly_scan kernels"); rc != H2_OK) return rc;
   return A.release();
 }
 
@@ -1121,8 +1075,7 @@ int h2_poly_prefix_product_device(h2_curve_t curve, const void* d_a, size_t n, v
   if (n == 0) return H2_OK;
   ArenaLease A(k.c->div_ws, SCAN_WS_BYTES, k.stream);
   if (A.rc != H2_OK) return A.rc;
-  hipError_t e = ops_of((int)curve)->poly_scan(1, &d_a, &d_out, nullptr, 1, n, A.a.p, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_scan kernels");
+  if (int rc = launched(ops_of((int)curve)->poly_scan(1, &d_a, &d_out, nullptr, 1, n, A.a.p, k.stream), "poly_scan kernels"); rc != H2_OK) return rc;
   return A.release();
 }
 
@@ -1174,9 +1127,7 @@ int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_
   for (int i = 0; i < 8; i++)
     key[i] = (uint32_t)seed[4 * i] | ((uint32_t)seed[4 * i + 1] << 8) | ((uint32_t)seed[4 * i + 2] << 16) |
              ((uint32_t)seed[4 * i + 3] << 24);
-  hipError_t e = ops_of((int)curve)->chacha20_scalars(d_out, n, first_block, key, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "chacha20_scalars_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->chacha20_scalars(d_out, n, first_block, key, k.stream), "chacha20_scalars_kernel");
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {
@@ -1184,9 +1135,7 @@ int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || !d_a || !d_b || op < 0 || op > 2) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  hipError_t e = ops_of((int)curve)->poly_pointwise(d_a, d_b, n, op, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "poly_pointwise_kernel");
-  return H2_OK;
+  return launched(ops_of((int)curve)->poly_pointwise(d_a, d_b, n, op, k.stream), "poly_pointwise_kernel");
 }
 
 // host columns; with several contexts column j is transformed by context j mod G (a single NTT is not split:
@@ -1231,8 +1180,7 @@ int h2_fft_group_device(h2_curve_t curve, void* d_points_jac, const uint64_t ome
   const CurveOps* ops = ops_of((int)curve);
   ArenaLease A(k.c->msm_ws.of(k.stream), ops->group_fft_scratch(log_n), k.stream);      // the MSM workspace, idle here
   if (A.rc != H2_OK) return A.rc;
-  hipError_t e = ops->group_fft(d_points_jac, d_points_jac, A.a.p, omega, log_n, k.stream);
-  if (e != hipSuccess) return dev_fail(e, "group fft kernels");
+  if (int rc = launched(ops->group_fft(d_points_jac, d_points_jac, A.a.p, omega, log_n, k.stream), "group fft kernels"); rc != H2_OK) return rc;
   return A.release();
 }
 
@@ -1259,264 +1207,3 @@ int h2_ntt(h2_curve_t curve, uint64_t* a, const uint64_t omega[4], uint32_t log_
 }
 
 }  // extern "C"
-
-// ---- host self-test hooks (include/h2hip_selftest.h) ------------------------------------------
-#include "../../include/h2hip_selftest.h"
-extern "C" int h2_selftest_field_op(int field, int op, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) {
-  if (!a || !b || !out) return H2_EINVAL;
-  int rc = -1;
-  switch (field) {
-    case 0: rc = curve_ops_bn254()->selftest_field(0, op, a, b, out); break;   // bn254 Fq
-    case 1: rc = curve_ops_bn254()->selftest_field(1, op, a, b, out); break;   // bn254 Fr
-    case 2: rc = curve_ops_pallas()->selftest_field(0, op, a, b, out); break;  // pasta Fp
-    case 3: rc = curve_ops_pallas()->selftest_field(1, op, a, b, out); break;  // pasta Fq
-  }
-  return rc == 0 ? H2_OK : H2_EINVAL;
-}
-// one operand set (a, b, c, d: 9 limbs each) through op 0..3; the host hook and the device kernel run this same source
-template <class FP>
-H2_HD void selftest_fe29_run(int op, const int32_t* in, int32_t* out) {
-  Fe29<FP> a[4];
-  for (int k = 0; k < 4; k++)
-    for (int l = 0; l < 9; l++) a[k].v[l] = in[9 * k + l];
-  Fe29<FP> r;
-  switch (op) {
-    case 0: r = fe29_mul(a[0], a[1]); break;
-    case 1: r = fe29_sqr(a[0]); break;
-    case 2: r = fe29_mul_sub(a[0], a[1], a[2], a[3]); break;
-    default: r = fe29_mul_up(a[0], a[1]); break;
-  }
-  for (int l = 0; l < 9; l++) out[l] = r.v[l];
-}
-template <class FP>
-__global__ void __launch_bounds__(64) selftest_fe29_kernel(int op, const int32_t* __restrict__ in, int32_t* __restrict__ out,
-                                                           uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  selftest_fe29_run<FP>(op, in + 36 * (size_t)i, out + 9 * (size_t)i);
-}
-extern "C" int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]) {
-  if (!in || !out || op < 0 || op > 3) return H2_EINVAL;
-  switch (field) {
-    case 0: selftest_fe29_run<BN254_FQ>(op, in, out); return H2_OK;
-    case 1: selftest_fe29_run<BN254_FR>(op, in, out); return H2_OK;
-    case 2: selftest_fe29_run<PASTA_FP>(op, in, out); return H2_OK;
-    case 3: selftest_fe29_run<PASTA_FQ>(op, in, out); return H2_OK;
-  }
-  return H2_EINVAL;
-}
-// n operand sets through the DEVICE instantiation, one kernel launch; host pointers in (36 limbs per set) and out (9)
-extern "C" int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* out, size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!g_h2.ready) return H2_ENOTINIT;
-  if (!in || !out || n == 0 || n > (1u << 20) || field < 0 || field > 3 || op < 0 || op > 3) return H2_EINVAL;
-  DevCtx& g_ctx = g_h2.ctx[0];
-  DeviceGuard dg(g_ctx.device);
-  const size_t in_bytes = n * 36 * 4, out_bytes = n * 9 * 4;
-  ArenaLease stage(g_ctx.stage, in_bytes + out_bytes, g_ctx.stream);
-  if (stage.rc != H2_OK) return stage.rc;
-  int32_t* d_in = (int32_t*)g_ctx.stage.p;
-  int32_t* d_out = (int32_t*)((char*)g_ctx.stage.p + in_bytes);
-  H2_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, g_ctx.stream));
-  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-  switch (field) {
-    case 0: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
-    case 1: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FR>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
-    case 2: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FP>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
-    default: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dev_fail(e, "selftest_fe29_kernel");
-  H2_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
-  return stage.wait();
-}
-extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) {
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !p || !q || !out) return H2_EINVAL;
-  return ops->selftest_curve(op, p, q, out) == 0 ? H2_OK : H2_EINVAL;
-}
-extern "C" int h2_selftest_digits(int curve, const uint64_t scalar[4], size_t n_for_geometry, uint32_t* out,
-                                  uint32_t cap) {
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !scalar || !out) return H2_EINVAL;
-  return ops->selftest_digits(scalar, n_for_geometry, out, cap);
-}
-// n element pairs through the DEVICE instantiation (one kernel launch); host pointers in and out
-extern "C" int h2_selftest_curve_op_device(int curve, int op, const uint64_t* p, const uint64_t* q, uint64_t* out,
-                                           size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!g_h2.ready) return H2_ENOTINIT;
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !p || !q || !out || n == 0 || n > (1u << 20)) return H2_EINVAL;
-  DevCtx& g_ctx = g_h2.ctx[0];
-  DeviceGuard dg(g_ctx.device);
-  ArenaLease stage(g_ctx.stage, 3 * n * 64, g_ctx.stream);
-  if (stage.rc != H2_OK) return stage.rc;
-  char* d = (char*)g_ctx.stage.p;
-  H2_TRY(hipMemcpyAsync(d, p, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
-  H2_TRY(hipMemcpyAsync(d + n * 64, q, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
-  hipError_t e = ops->selftest_curve_device(op, d, d + n * 64, d + 2 * n * 64, (uint32_t)n, g_ctx.stream);
-  if (e != hipSuccess) return dev_fail(e, "selftest_curve_kernel");
-  H2_TRY(hipMemcpyAsync(out, d + 2 * n * 64, n * 64, hipMemcpyDeviceToHost, g_ctx.stream));
-  return stage.wait();
-}
-
-extern "C" int h2_selftest_field_op_device(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
-                                           size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!g_h2.ready) return H2_ENOTINIT;
-  if (!a || !b || !out || n == 0 || n > (1u << 24) || field < 0 || field > 3) return H2_EINVAL;
-  const CurveOps* ops = field < 2 ? curve_ops_bn254() : curve_ops_pallas();
-  const int which = field & 1;
-  DevCtx& g_ctx = g_h2.ctx[0];
-  DeviceGuard dg(g_ctx.device);
-  ArenaLease stage(g_ctx.stage, 3 * n * 32, g_ctx.stream);
-  if (stage.rc != H2_OK) return stage.rc;
-  char* d = (char*)g_ctx.stage.p;
-  H2_TRY(hipMemcpyAsync(d, a, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
-  H2_TRY(hipMemcpyAsync(d + n * 32, b, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
-  hipError_t e = ops->selftest_field_device(which, op, d, d + n * 32, d + 2 * n * 32, (uint32_t)n, g_ctx.stream);
-  if (e != hipSuccess) return dev_fail(e, "selftest_field_kernel");
-  H2_TRY(hipMemcpyAsync(out, d + 2 * n * 32, n * 32, hipMemcpyDeviceToHost, g_ctx.stream));
-  return stage.wait();
-}
-
-// test hooks around the MSM workspace (include/h2hip_selftest.h)
-extern "C" int h2_selftest_msm_guard(int on) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  h2::g_msm_guard = on != 0;
-  h2::g_msm_guard_poke = on == 2;
-  h2::g_sort2_pack = on != 3;            // guard(3): the unpacked forms -- the two-level sort keeps the low key bits in the
-                                         // side array, the staged scatter a reference and a 16-bit bucket per entry
-  h2::g_guard_launches = h2::g_guard_violations = 0;
-  h2::g_guard_first.clear();
-  return H2_OK;
-}
-extern "C" int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!out) return H2_EINVAL;
-  out[0] = h2::g_guard_launches;
-  out[1] = h2::g_guard_violations;
-  if (first && cap) {
-    snprintf(first, cap, "%s", h2::g_guard_first.c_str());
-  }
-  return H2_OK;
-}
-// host only: lay out the workspace of an (n_bases, n, m, col_stride) launch as msm_device_run would and run the bounds
-// proof on it; out[0..7] = window bits, windows, buckets, tile, staged, two-level sort, entries per thread, regions.
-// Returns H2_OK, or H2_EINVAL with the violated condition in h2_last_device_error().
-extern "C" int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || n == 0 || m == 0 || n > n_bases) return H2_EINVAL;
-  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
-  // as msm_device_run: a batch wider than one launch takes runs in column groups; the first (widest) group is checked
-  const size_t group = msm_cols_per_launch(g, n);
-  if (group == 0) return H2_EINVAL;
-  if (m > group) {
-    if (col_stride < n) { g_h2.last_error = "msm launch geometry: col_stride >= n"; return H2_EINVAL; }
-    m = group;
-  }
-  const MsmWorkspace ws = msm_workspace(n, m, g, guard ? 256u : 0u, n_bases);
-  if (out) {
-    out[0] = g.c; out[1] = g.W; out[2] = g.B; out[3] = ws.sort2 ? ws.s2.tile : ws.tile;
-    out[4] = ws.staged; out[5] = ws.sort2; out[6] = ws.T; out[7] = ws.n_regions;
-  }
-  if (const char* broken = msm_check(ws, g, n, m, col_stride, (uint32_t)n_bases, ws.total)) {
-    g_h2.last_error = std::string("msm launch geometry: ") + broken;
-    return H2_EINVAL;
-  }
-  return H2_OK;
-}
-// host only: the layout and the bounds proof of a table-free launch (h2_msm_points*) of m columns of n scalars, as
-// msm_points_run makes them; out: include/h2hip_selftest.h
-extern "C" int h2_selftest_msm_points_check(int curve, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!curve_ok(curve) || !out || n == 0 || m == 0 || n > MSM_POINTS_MAX_N) return H2_EINVAL;
-  if (col_stride < n) { g_h2.last_error = "msm points launch geometry: col_stride >= n"; return H2_EINVAL; }
-  const MsmGeom g = msm_points_geometry(n, ops_of(curve)->scalar_bits);
-  // as msm_points_run: a batch wider than one launch runs in column groups; the first (widest) group is checked
-  const size_t group = msm_points_cols_per_launch(g, n);
-  if (group == 0) return H2_EINVAL;
-  if (m > group) m = group;
-  const MsmWorkspace ws = msm_points_workspace(n, m, g, guard ? 256u : 0u);
-  out[0] = g.c; out[1] = g.W; out[2] = g.B; out[3] = ws.tile; out[4] = (uint64_t)g.W * g.B * 4; out[5] = m;
-  out[6] = ws.T; out[7] = ws.n_regions;
-  if (const char* broken = msm_points_check(ws, g, n, m, col_stride, ws.total)) {
-    g_h2.last_error = std::string("msm points launch geometry: ") + broken;
-    return H2_EDEVICE;
-  }
-  return H2_OK;
-}
-extern "C" int h2_selftest_set_msm_points_small_max(size_t n) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  h2::g_points_small_max = n == SIZE_MAX ? MSM_POINTS_SMALL_MAX : n;
-  return H2_OK;
-}
-// host only: the sort front of a launch of m columns of n scalars against n_bases bases, laid out as msm_device_run
-// lays it out (`pack` = 0: with the unpacked forms, as under h2_selftest_msm_guard(3)); out: include/h2hip_selftest.h
-extern "C" int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !out || n == 0 || m == 0 || n > n_bases || n_bases >= (1ull << 31)) return H2_EINVAL;
-  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
-  if (m > msm_cols_per_launch(g, n)) return H2_EINVAL;
-  const MsmWorkspace ws = msm_workspace(n, m, g, 0, n_bases, pack != 0);
-  const char* broken = msm_check(ws, g, n, m, n, (uint32_t)n_bases, ws.total);
-  if (broken) g_h2.last_error = std::string("msm launch geometry: ") + broken;
-  out[0] = ws.sort2 ? ws.s2.tile : ws.tile; out[1] = ws.staged; out[2] = ws.stage_lds; out[3] = ws.pack.on;
-  out[4] = ws.pack.bbits; out[5] = ws.pack.ibits; out[6] = ws.pack.wbits; out[7] = broken ? 0 : 1;
-  out[8] = msm_effective_t((uint32_t)ws.E, ws.T); out[9] = MSM_HOT_SPAN; out[10] = MSM_HOT_SEG; out[11] = ws.max_tasks;
-  return H2_OK;
-}
-// scratch arenas of the current context: out = {allocations (first use or growth), cross-stream hand-overs (event waits),
-// MSM slots taken over, NTT slots taken over}
-extern "C" int h2_selftest_arena_stats(uint64_t out[4]) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  DevCtx* c = g_h2.ready ? ctx_current() : nullptr;
-  if (!c || !out) return H2_EINVAL;
-  out[0] = g_arena_growths;
-  out[1] = g_arena_waits;
-  out[2] = c->msm_ws.takeovers;
-  out[3] = c->ntt_ws.takeovers;
-  return H2_OK;
-}
-// host only: the sort's block -> (column, tile) mapping for `tiles` tiles per column and m columns: every block of
-// the grid is either dead or maps to a (column < m, tile < tiles) pair that no other block takes, and all pairs are taken
-extern "C" int h2_selftest_msm_tiles(uint32_t tiles, uint32_t m) {
-  if (tiles == 0 || m == 0 || (uint64_t)tiles * m > (1u << 24)) return H2_EINVAL;
-  const uint32_t grid = msm_tile_grid(tiles, m);
-  std::vector<uint8_t> seen((size_t)tiles * m, 0);
-  size_t live = 0;
-  for (uint32_t b = 0; b < grid; b++) {
-    const MsmTileId t = msm_tile_id_of(b, tiles, m);
-    if (!t.live) continue;
-    if (t.col >= m || t.tile >= tiles || t.group >= MSM_XCDS || seen[(size_t)t.col * tiles + t.tile]) return H2_EINVAL;
-    seen[(size_t)t.col * tiles + t.tile] = 1;
-    live++;
-  }
-  return live == (size_t)tiles * m ? H2_OK : H2_EINVAL;
-}
-
-// test hook: lower the sort's entry limit so that the grouped-columns path is reached at small sizes (0 = default)
-extern "C" int h2_selftest_set_msm_max_entries(uint64_t limit) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  h2::g_msm_max_entries = (limit > 0 && limit < (1ull << 31) - 1) ? limit : (1ull << 31) - 1;
-  return H2_OK;
-}
-
-// measured integer ceiling: dependent 9 x 29-bit Montgomery products of `curve`'s base field at `waves_per_simd`
-// resident waves per SIMD on every CU of the current device
-extern "C" int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* modmul_per_s) {
-  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
-  if (!g_h2.ready) return H2_ENOTINIT;
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !modmul_per_s || waves_per_simd < 1 || waves_per_simd > 8 || iters < 1 || iters > (1 << 20)) return H2_EINVAL;
-  DevCtx* c = ctx_current();
-  if (!c) return H2_EINVAL;
-  hipDeviceProp_t prop;
-  H2_TRY(hipGetDeviceProperties(&prop, c->device));
-  hipError_t e = ops->modmul_rate(prop.multiProcessorCount * waves_per_simd, iters, c->stream, modmul_per_s);
-  if (e != hipSuccess) return dev_fail(e, "modmul_rate_kernel");
-  return H2_OK;
-}

@@ -1,4 +1,4 @@
-// h2_internal.hpp -- state shared by the translation units behind the C ABI (h2_capi.hip and the C++ prover).
+// h2_internal.hpp -- state shared by the translation units behind the C ABI (h2_capi.hip, h2_selftest.hip, the C++ prover).
 //
 // One DevCtx per GPU the process drives (h2_init: one; h2_init_devices: several).  Every scratch arena remembers the
 // stream that used it last and an event recorded behind that use, so a call on ANOTHER stream first waits for it:
@@ -113,6 +113,23 @@ struct Global {
 extern Global g_h2;
 extern std::recursive_mutex g_h2_mu;
 
+// Test-only state, moved by the hooks of include/h2hip_selftest.h (h2_selftest.hip) alone: the defaults are the product's
+struct TestKnobs {
+  uint64_t msm_max_entries = (1ull << 31) - 1;   // entries one sort launch may hold (msm_cols_per_launch)
+  // guard mode: the MSM workspace is laid out with a red zone behind every region, filled with a pattern before each
+  // launch sequence and inspected after it; poke: one byte behind the second region is written first, to test the checker
+  bool msm_guard = false, msm_guard_poke = false;
+  bool sort2_pack = true;                        // false: the unpacked forms of the two-level sort and the staged scatter
+  size_t points_small_max = MSM_POINTS_SMALL_MAX;   // terms below which h2_msm_points* takes the double-and-add route
+};
+struct TestCounters {
+  uint64_t guard_launches = 0, guard_violations = 0;
+  std::string guard_first;
+  uint64_t arena_growths = 0, arena_waits = 0;
+};
+extern TestKnobs g_knobs;
+extern TestCounters g_counts;
+
 // the process's current HIP device is switched for the lifetime of the guard
 struct DeviceGuard {
   int prev = -1;
@@ -126,6 +143,8 @@ struct DeviceGuard {
 };
 
 int dev_fail(hipError_t e, const char* where);
+// the status of a launch (sequence) named `what`
+inline int launched(hipError_t e, const char* what) { return e == hipSuccess ? H2_OK : dev_fail(e, what); }
 const CurveOps* ops_of(int curve);
 bool curve_ok(int c);
 // context of the calling thread's current HIP device (the only context when there is just one); null if none
@@ -168,6 +187,32 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
 // columns of n scalars one MSM launch sequence takes under this geometry (0: a single column is already too long); a wider
 // call runs in groups of that many, and columns with their own bases (per_column) must fit one group
 size_t msm_cols_per_launch(const MsmGeom& geom, size_t n);
+// The next launch sequence of a call with m columns left: the columns it takes (0: a single column is already too long),
+// its workspace, and the bounds proof of every kernel's index range against the region it indexes (null, or the violated
+// condition).  msm_device_run / the table-free route launch what these return; the host-only hooks report it
+// (proved against the layout's own size, ws.total; msm_run_group holds the leased arena's real size against that)
+struct MsmGroupPlan {
+  size_t cols;
+  MsmWorkspace ws;
+  const char* broken;
+};
+// (n_bases is the REGISTERED length whatever the range: a sorted entry is w * n_bases + i relative to the table row of the first base)
+inline MsmGroupPlan msm_plan_group(const MsmGeom& g, size_t n_bases, size_t n, size_t m, size_t col_stride, bool guard, bool pack) {
+  MsmGroupPlan p{};
+  p.cols = std::min(m, msm_cols_per_launch(g, n));
+  if (p.cols == 0) return p;
+  p.ws = msm_workspace(n, p.cols, g, guard ? 256u : 0u, n_bases, pack);
+  p.broken = msm_check(p.ws, g, n, p.cols, col_stride, (uint32_t)n_bases, p.ws.total);
+  return p;
+}
+inline MsmGroupPlan msm_points_plan_group(const MsmGeom& g, size_t n, size_t m, size_t col_stride, bool guard) {
+  MsmGroupPlan p{};
+  p.cols = std::min(m, msm_points_cols_per_launch(g, n));
+  if (p.cols == 0) return p;
+  p.ws = msm_points_workspace(n, p.cols, g, guard ? 256u : 0u);
+  p.broken = msm_points_check(p.ws, g, n, p.cols, col_stride, p.ws.total);
+  return p;
+}
 int ntt_enqueue(DevCtx& c, int curve, void* d_a, size_t m, const uint64_t omega[4], uint32_t log_n, hipStream_t stream,
                 const uint64_t* scale = nullptr);
 // EvaluationDomain::coeff_to_extended (h2_coeff_to_extended_device; arguments checked by the caller, ext_log_n >= 1):

@@ -1,0 +1,265 @@
+// h2_selftest.hip -- the test hooks of include/h2hip_selftest.h that sit beside the drop-in C ABI (h2_capi.hip): the host and
+// device instantiations of the field / curve / 29-bit templates, the MSM workspace checks and the test knobs.  Not a compute
+// path; nothing here is called by the library itself.
+#include "h2_internal.hpp"
+
+#include <cstdio>
+
+#include "../../include/h2hip_selftest.h"
+
+using namespace h2;
+
+extern "C" int h2_selftest_field_op(int field, int op, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) {
+  if (!a || !b || !out) return H2_EINVAL;
+  int rc = -1;
+  switch (field) {
+    case 0: rc = curve_ops_bn254()->selftest_field(0, op, a, b, out); break;   // bn254 Fq
+    case 1: rc = curve_ops_bn254()->selftest_field(1, op, a, b, out); break;   // bn254 Fr
+    case 2: rc = curve_ops_pallas()->selftest_field(0, op, a, b, out); break;  // pasta Fp
+    case 3: rc = curve_ops_pallas()->selftest_field(1, op, a, b, out); break;  // pasta Fq
+  }
+  return rc == 0 ? H2_OK : H2_EINVAL;
+}
+// one operand set (a, b, c, d: 9 limbs each) through op 0..3; the host hook and the device kernel run this same source
+template <class FP>
+H2_HD void selftest_fe29_run(int op, const int32_t* in, int32_t* out) {
+  Fe29<FP> a[4];
+  for (int k = 0; k < 4; k++)
+    for (int l = 0; l < 9; l++) a[k].v[l] = in[9 * k + l];
+  Fe29<FP> r;
+  switch (op) {
+    case 0: r = fe29_mul(a[0], a[1]); break;
+    case 1: r = fe29_sqr(a[0]); break;
+    case 2: r = fe29_mul_sub(a[0], a[1], a[2], a[3]); break;
+    default: r = fe29_mul_up(a[0], a[1]); break;
+  }
+  for (int l = 0; l < 9; l++) out[l] = r.v[l];
+}
+template <class FP>
+__global__ void __launch_bounds__(64) selftest_fe29_kernel(int op, const int32_t* __restrict__ in, int32_t* __restrict__ out,
+                                                           uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  selftest_fe29_run<FP>(op, in + 36 * (size_t)i, out + 9 * (size_t)i);
+}
+extern "C" int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9]) {
+  if (!in || !out || op < 0 || op > 3) return H2_EINVAL;
+  switch (field) {
+    case 0: selftest_fe29_run<BN254_FQ>(op, in, out); return H2_OK;
+    case 1: selftest_fe29_run<BN254_FR>(op, in, out); return H2_OK;
+    case 2: selftest_fe29_run<PASTA_FP>(op, in, out); return H2_OK;
+    case 3: selftest_fe29_run<PASTA_FQ>(op, in, out); return H2_OK;
+  }
+  return H2_EINVAL;
+}
+// n operand sets through the DEVICE instantiation, one kernel launch; host pointers in (36 limbs per set) and out (9)
+extern "C" int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* out, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!in || !out || n == 0 || n > (1u << 20) || field < 0 || field > 3 || op < 0 || op > 3) return H2_EINVAL;
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  const size_t in_bytes = n * 36 * 4, out_bytes = n * 9 * 4;
+  ArenaLease stage(g_ctx.stage, in_bytes + out_bytes, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  int32_t* d_in = (int32_t*)g_ctx.stage.p;
+  int32_t* d_out = (int32_t*)((char*)g_ctx.stage.p + in_bytes);
+  H2_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, g_ctx.stream));
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  switch (field) {
+    case 0: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    case 1: hipLaunchKernelGGL(selftest_fe29_kernel<BN254_FR>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    case 2: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FP>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+    default: hipLaunchKernelGGL(selftest_fe29_kernel<PASTA_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_out, (uint32_t)n); break;
+  }
+  if (int rc = launched(hipGetLastError(), "selftest_fe29_kernel"); rc != H2_OK) return rc;
+  H2_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
+}
+extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !p || !q || !out) return H2_EINVAL;
+  return ops->selftest_curve(op, p, q, out) == 0 ? H2_OK : H2_EINVAL;
+}
+extern "C" int h2_selftest_digits(int curve, const uint64_t scalar[4], size_t n_for_geometry, uint32_t* out,
+                                  uint32_t cap) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !scalar || !out) return H2_EINVAL;
+  return ops->selftest_digits(scalar, n_for_geometry, out, cap);
+}
+// n element pairs through the DEVICE instantiation (one kernel launch); host pointers in and out
+extern "C" int h2_selftest_curve_op_device(int curve, int op, const uint64_t* p, const uint64_t* q, uint64_t* out,
+                                           size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !p || !q || !out || n == 0 || n > (1u << 20)) return H2_EINVAL;
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  ArenaLease stage(g_ctx.stage, 3 * n * 64, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  char* d = (char*)g_ctx.stage.p;
+  H2_TRY(hipMemcpyAsync(d, p, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
+  H2_TRY(hipMemcpyAsync(d + n * 64, q, n * 64, hipMemcpyHostToDevice, g_ctx.stream));
+  if (int rc = launched(ops->selftest_curve_device(op, d, d + n * 64, d + 2 * n * 64, (uint32_t)n, g_ctx.stream), "selftest_curve_kernel");
+      rc != H2_OK)
+    return rc;
+  H2_TRY(hipMemcpyAsync(out, d + 2 * n * 64, n * 64, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
+}
+
+extern "C" int h2_selftest_field_op_device(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
+                                           size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!a || !b || !out || n == 0 || n > (1u << 24) || field < 0 || field > 3) return H2_EINVAL;
+  const CurveOps* ops = field < 2 ? curve_ops_bn254() : curve_ops_pallas();
+  const int which = field & 1;
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  ArenaLease stage(g_ctx.stage, 3 * n * 32, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  char* d = (char*)g_ctx.stage.p;
+  H2_TRY(hipMemcpyAsync(d, a, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
+  H2_TRY(hipMemcpyAsync(d + n * 32, b, n * 32, hipMemcpyHostToDevice, g_ctx.stream));
+  if (int rc = launched(ops->selftest_field_device(which, op, d, d + n * 32, d + 2 * n * 32, (uint32_t)n, g_ctx.stream), "selftest_field_kernel");
+      rc != H2_OK)
+    return rc;
+  H2_TRY(hipMemcpyAsync(out, d + 2 * n * 32, n * 32, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
+}
+
+// test hooks around the MSM workspace (include/h2hip_selftest.h)
+extern "C" int h2_selftest_msm_guard(int on) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  g_knobs.msm_guard = on != 0;
+  g_knobs.msm_guard_poke = on == 2;
+  g_knobs.sort2_pack = on != 3;          // guard(3): the unpacked forms -- the two-level sort keeps the low key bits in the
+                                         // side array, the staged scatter a reference and a 16-bit bucket per entry
+  g_counts.guard_launches = g_counts.guard_violations = 0;
+  g_counts.guard_first.clear();
+  return H2_OK;
+}
+extern "C" int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!out) return H2_EINVAL;
+  out[0] = g_counts.guard_launches;
+  out[1] = g_counts.guard_violations;
+  if (first && cap) {
+    snprintf(first, cap, "%s", g_counts.guard_first.c_str());
+  }
+  return H2_OK;
+}
+// host only: msm_device_run's plan (msm_plan_group) of an (n_bases, n, m, col_stride) launch: the workspace and the bounds
+// proof on it; out[0..7] = window bits, windows, buckets, tile, staged, two-level sort, entries per thread, regions.
+// Returns H2_OK, or H2_EINVAL with the violated condition in h2_last_device_error().
+extern "C" int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || n == 0 || m == 0 || n > n_bases) return H2_EINVAL;
+  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
+  // a batch wider than one launch takes runs in column groups; the first (widest) group is checked
+  const MsmGroupPlan plan = msm_plan_group(g, n_bases, n, m, col_stride, guard != 0, true);
+  if (plan.cols == 0) return H2_EINVAL;
+  if (m > plan.cols && col_stride < n) { g_h2.last_error = "msm launch geometry: col_stride >= n"; return H2_EINVAL; }
+  const MsmWorkspace& ws = plan.ws;
+  if (out) {
+    out[0] = g.c; out[1] = g.W; out[2] = g.B; out[3] = ws.sort2 ? ws.s2.tile : ws.tile;
+    out[4] = ws.staged; out[5] = ws.sort2; out[6] = ws.T; out[7] = ws.n_regions;
+  }
+  if (plan.broken) {
+    g_h2.last_error = std::string("msm launch geometry: ") + plan.broken;
+    return H2_EINVAL;
+  }
+  return H2_OK;
+}
+// host only: the layout and the bounds proof of a table-free launch (h2_msm_points*) of m columns of n scalars, as
+// msm_points_plan_group gives them to msm_points_run; out: include/h2hip_selftest.h
+extern "C" int h2_selftest_msm_points_check(int curve, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!curve_ok(curve) || !out || n == 0 || m == 0 || n > MSM_POINTS_MAX_N) return H2_EINVAL;
+  if (col_stride < n) { g_h2.last_error = "msm points launch geometry: col_stride >= n"; return H2_EINVAL; }
+  const MsmGeom g = msm_points_geometry(n, ops_of(curve)->scalar_bits);
+  // a batch wider than one launch runs in column groups; the first (widest) group is checked
+  const MsmGroupPlan plan = msm_points_plan_group(g, n, m, col_stride, guard != 0);
+  if (plan.cols == 0) return H2_EINVAL;
+  const MsmWorkspace& ws = plan.ws;
+  out[0] = g.c; out[1] = g.W; out[2] = g.B; out[3] = ws.tile; out[4] = (uint64_t)g.W * g.B * 4; out[5] = plan.cols;
+  out[6] = ws.T; out[7] = ws.n_regions;
+  if (plan.broken) {
+    g_h2.last_error = std::string("msm points launch geometry: ") + plan.broken;
+    return H2_EDEVICE;
+  }
+  return H2_OK;
+}
+extern "C" int h2_selftest_set_msm_points_small_max(size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  g_knobs.points_small_max = n == SIZE_MAX ? MSM_POINTS_SMALL_MAX : n;
+  return H2_OK;
+}
+// host only: the sort front of a launch of m columns of n scalars against n_bases bases, as msm_plan_group lays it out
+// for msm_device_run (`pack` = 0: with the unpacked forms, as under h2_selftest_msm_guard(3)); out: include/h2hip_selftest.h
+extern "C" int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !out || n == 0 || m == 0 || n > n_bases || n_bases >= (1ull << 31)) return H2_EINVAL;
+  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
+  const MsmGroupPlan plan = msm_plan_group(g, n_bases, n, m, n, false, pack != 0);
+  if (plan.cols < m) return H2_EINVAL;        // one launch only
+  const MsmWorkspace& ws = plan.ws;
+  const char* broken = plan.broken;
+  if (broken) g_h2.last_error = std::string("msm launch geometry: ") + broken;
+  out[0] = ws.sort2 ? ws.s2.tile : ws.tile; out[1] = ws.staged; out[2] = ws.stage_lds; out[3] = ws.pack.on;
+  out[4] = ws.pack.bbits; out[5] = ws.pack.ibits; out[6] = ws.pack.wbits; out[7] = broken ? 0 : 1;
+  out[8] = msm_effective_t((uint32_t)ws.E, ws.T); out[9] = MSM_HOT_SPAN; out[10] = MSM_HOT_SEG; out[11] = ws.max_tasks;
+  return H2_OK;
+}
+// scratch arenas of the current context: out = {allocations (first use or growth), cross-stream hand-overs (event waits),
+// MSM slots taken over, NTT slots taken over}
+extern "C" int h2_selftest_arena_stats(uint64_t out[4]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  DevCtx* c = g_h2.ready ? ctx_current() : nullptr;
+  if (!c || !out) return H2_EINVAL;
+  out[0] = g_counts.arena_growths;
+  out[1] = g_counts.arena_waits;
+  out[2] = c->msm_ws.takeovers;
+  out[3] = c->ntt_ws.takeovers;
+  return H2_OK;
+}
+// host only: the sort's block -> (column, tile) mapping for `tiles` tiles per column and m columns: every block of
+// the grid is either dead or maps to a (column < m, tile < tiles) pair that no other block takes, and all pairs are taken
+extern "C" int h2_selftest_msm_tiles(uint32_t tiles, uint32_t m) {
+  if (tiles == 0 || m == 0 || (uint64_t)tiles * m > (1u << 24)) return H2_EINVAL;
+  const uint32_t grid = msm_tile_grid(tiles, m);
+  std::vector<uint8_t> seen((size_t)tiles * m, 0);
+  size_t live = 0;
+  for (uint32_t b = 0; b < grid; b++) {
+    const MsmTileId t = msm_tile_id_of(b, tiles, m);
+    if (!t.live) continue;
+    if (t.col >= m || t.tile >= tiles || t.group >= MSM_XCDS || seen[(size_t)t.col * tiles + t.tile]) return H2_EINVAL;
+    seen[(size_t)t.col * tiles + t.tile] = 1;
+    live++;
+  }
+  return live == (size_t)tiles * m ? H2_OK : H2_EINVAL;
+}
+
+// test hook: lower the sort's entry limit so that the grouped-columns path is reached at small sizes (0 = default)
+extern "C" int h2_selftest_set_msm_max_entries(uint64_t limit) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  g_knobs.msm_max_entries = (limit > 0 && limit < (1ull << 31) - 1) ? limit : (1ull << 31) - 1;
+  return H2_OK;
+}
+
+// measured integer ceiling: dependent 9 x 29-bit Montgomery products of `curve`'s base field at `waves_per_simd`
+// resident waves per SIMD on every CU of the current device
+extern "C" int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* modmul_per_s) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !modmul_per_s || waves_per_simd < 1 || waves_per_simd > 8 || iters < 1 || iters > (1 << 20)) return H2_EINVAL;
+  DevCtx* c = ctx_current();
+  if (!c) return H2_EINVAL;
+  hipDeviceProp_t prop;
+  H2_TRY(hipGetDeviceProperties(&prop, c->device));
+  return launched(ops->modmul_rate(prop.multiProcessorCount * waves_per_simd, iters, c->stream, modmul_per_s), "modmul_rate_kernel");
+}

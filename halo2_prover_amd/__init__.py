@@ -4,6 +4,7 @@ Python host layer over the C-ABI library libh2hip.so (include/h2hip.h).  Importi
 package does not touch the GPU; the first compute call (or `init()`) binds the process to
 one device.  There is no CPU fallback.
 """
-from .api import (Bases, ParamsKZG, best_fft, best_fft_batch, best_fft_group, best_multiexp, generate_proofs, init,  # noqa: F401
-                  msm_points, msm_points_device, msm_points_plan, ntt_device, points_decompress_device, verify_proofs)
+from .api import (Bases, ParamsKZG, best_fft, best_fft_batch, best_fft_group, best_multiexp, g_to_lagrange,  # noqa: F401
+                  generate_proofs, init, msm_points, msm_points_device, msm_points_plan, ntt_device, params_downsize,
+                  points_decompress_device, verify_proofs)
 from .lib import CURVES, H2Error, LIB_PATH, SYMBOLS, load  # noqa: F401

@@ -6,7 +6,7 @@ behaviour:
 
     halo2_proofs::arithmetic::best_multiexp(coeffs, bases) -> C::Curve
     halo2_proofs::arithmetic::best_fft(a, omega, log_n)            (in place)
-    ParamsKZG::{read, write, k, n, get_g, commit, commit_lagrange}
+    ParamsKZG::{read, write, k, n, get_g, downsize, commit, commit_lagrange}
         (constructed at /root/reference/circuits/src/utils.rs:59-61, read at wasm.rs:79-80)
 
 Arrays are numpy uint64 in halo2curves' in-memory layout: scalars (n, 4), affine points
@@ -246,6 +246,36 @@ def best_fft_group(points_jac, omega, log_n, curve="bn254"):
     return a
 
 
+def g_to_lagrange(g_affine, log_n, curve="bn254"):
+    """ParamsKZG::new's g_to_lagrange (h2_g_to_lagrange): (n, 8) affine points g -> the (n, 8) normalised points
+    n^-1 * best_fft(g, omega^-1, log_n), omega of the 2^log_n domain: the Lagrange-basis SRS of g without its scalar.
+    The points are not checked to be on the curve."""
+    from .domain import ifft_constants
+    _ensure_init()
+    g = _as_u64(g_affine, 8, "g")
+    if g.shape[0] != 1 << log_n:
+        raise ValueError("g_to_lagrange: g.len() != 1 << log_n (%d vs %d)" % (g.shape[0], 1 << log_n))
+    omega_inv, n_inv = ifft_constants(log_n, curve)
+    out = np.zeros_like(g)
+    st = _lib.load().h2_g_to_lagrange(_curve_id(curve), g.ctypes.data, log_n, omega_inv.ctypes.data, n_inv.ctypes.data,
+                                      out.ctypes.data)
+    _lib.check(st, "h2_g_to_lagrange")
+    return out
+
+
+def params_downsize(blob, k):
+    """Params::downsize(k) on a params blob (h2_params_downsize): k, g[..2^k], g_to_lagrange of that prefix, the G2 tail
+    -> bytes.  Nothing is registered; the points are validated when the result is used."""
+    _ensure_init()
+    blob = bytes(blob)
+    need = ctypes.c_size_t(0)
+    cap = 4 + (128 << max(0, min(int(k), 28))) + 256
+    out = ctypes.create_string_buffer(cap)
+    st = _lib.load().h2_params_downsize(blob, len(blob), int(k), out, cap, ctypes.byref(need))
+    _lib.check(st, "h2_params_downsize")
+    return out.raw[:need.value]
+
+
 def best_fft_batch(columns, omega, log_n, curve="bn254"):
     """The same transform over m independent columns in one launch sequence."""
     _ensure_init()
@@ -381,6 +411,14 @@ class ParamsKZG:
 
     def get_g(self):
         return self.g
+
+    def downsize(self, k):
+        """Params::downsize(k): a new ParamsKZG over g[..2^k] with g_lagrange recomputed from it (g_to_lagrange)."""
+        k = int(k)
+        if k < 1 or k > self.k:
+            raise ValueError("downsize: k=%d is not in 1..%d" % (k, self.k))
+        g = self.g[:1 << k].copy()
+        return ParamsKZG(k, g, g_to_lagrange(g, k, "bn254"), self.g2_tail)
 
     def commit(self, poly):
         """commit(poly in coefficient basis, blind ignored for KZG) = best_multiexp(poly, g)."""

@@ -1180,7 +1180,7 @@ int h2_fft_group_device(h2_curve_t curve, void* d_points_jac, const uint64_t ome
   const CurveOps* ops = ops_of((int)curve);
   ArenaLease A(k.c->msm_ws.of(k.stream), ops->group_fft_scratch(log_n), k.stream);      // the MSM workspace, idle here
   if (A.rc != H2_OK) return A.rc;
-  if (int rc = launched(ops->group_fft(d_points_jac, d_points_jac, A.a.p, omega, log_n, k.stream), "group fft kernels"); rc != H2_OK) return rc;
+  if (int rc = launched(ops->group_fft(d_points_jac, d_points_jac, A.a.p, omega, log_n, g_knobs.gfft_lanes, k.stream), "group fft kernels"); rc != H2_OK) return rc;
   return A.release();
 }
 
@@ -1198,6 +1198,42 @@ int h2_fft_group(h2_curve_t curve, uint64_t* points_jac, const uint64_t omega[4]
   int rc = h2_fft_group_device(curve, c.stage.p, omega, log_n, c.stream);
   if (rc != H2_OK) return rc;
   H2_TRY(hipMemcpyAsync(points_jac, c.stage.p, bytes, hipMemcpyDeviceToHost, c.stream));
+  return stage.wait();
+}
+
+// ParamsKZG's g_to_lagrange: the transform above on affine points, scaled and normalised (h2_group_fft.hpp)
+int h2_g_to_lagrange_device(h2_curve_t curve, const void* d_g_affine, uint32_t log_n, const uint64_t omega_inv[4],
+                            const uint64_t scale[4], void* d_out_affine, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !d_g_affine || !d_out_affine || !omega_inv || !scale || log_n > 26) return H2_EINVAL;
+  const uintptr_t in = (uintptr_t)d_g_affine, out = (uintptr_t)d_out_affine, bytes = (uintptr_t)64 << log_n;
+  if ((in & 15) || (out & 15)) return H2_EINVAL;
+  if (in != out && in < out + bytes && out < in + bytes) return H2_EINVAL;      // a partial overlap
+  const CurveOps* ops = ops_of((int)curve);
+  ArenaLease A(k.c->msm_ws.of(k.stream), ops->group_fft_scratch(log_n), k.stream);      // the MSM workspace, idle here
+  if (A.rc != H2_OK) return A.rc;
+  if (int rc = launched(ops->g_to_lagrange(d_g_affine, d_out_affine, A.a.p, omega_inv, scale, log_n, g_knobs.gfft_lanes, k.stream),
+                        "g_to_lagrange kernels");
+      rc != H2_OK)
+    return rc;
+  return A.release();
+}
+
+int h2_g_to_lagrange(h2_curve_t curve, const uint64_t* g_affine, uint32_t log_n, const uint64_t omega_inv[4],
+                     const uint64_t scale[4], uint64_t* out_affine) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  if (!curve_ok((int)curve) || !g_affine || !out_affine || !omega_inv || !scale || log_n > 26) return H2_EINVAL;
+  DevCtx& c = g_h2.ctx[0];
+  DeviceGuard dg(c.device);
+  const size_t bytes = ((size_t)64) << log_n;
+  ArenaLease stage(c.stage, bytes, c.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  H2_TRY(hipMemcpyAsync(c.stage.p, g_affine, bytes, hipMemcpyHostToDevice, c.stream));
+  int rc = h2_g_to_lagrange_device(curve, c.stage.p, log_n, omega_inv, scale, c.stage.p, c.stream);
+  if (rc != H2_OK) return rc;
+  H2_TRY(hipMemcpyAsync(out_affine, c.stage.p, bytes, hipMemcpyDeviceToHost, c.stream));
   return stage.wait();
 }
 

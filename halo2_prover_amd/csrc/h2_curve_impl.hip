@@ -139,10 +139,34 @@ hipError_t ntt_coeff_launch_(const void* d_src, const void* d_t, size_t t_period
                                 (U128*)d_scratch, d_tw, log_n, m, s);
 }
 size_t group_fft_scratch(uint32_t log_n) { return gfft_scratch_bytes(log_n); }
-hipError_t group_fft(const void* d_in_jac, void* d_out_jac, void* d_scratch, const uint64_t omega[4], uint32_t log_n, hipStream_t s) {
+hipError_t group_fft(const void* d_in_jac, void* d_out_jac, void* d_scratch, const uint64_t omega[4], uint32_t log_n, int lanes,
+                     hipStream_t s) {
   Fe<FS> w;
   memcpy(w.v, omega, 32);
-  return gfft_launch<CV>((const U128*)d_in_jac, (U128*)d_out_jac, d_scratch, w, log_n, s);
+  return gfft_launch<CV>((const U128*)d_in_jac, (U128*)d_out_jac, d_scratch, w, log_n, s, lanes);
+}
+hipError_t g_to_lagrange(const void* d_in_affine, void* d_out_affine, void* d_scratch, const uint64_t omega[4],
+                         const uint64_t scale[4], uint32_t log_n, int lanes, hipStream_t s) {
+  Fe<FS> w, c;
+  memcpy(w.v, omega, 32);
+  memcpy(c.v, scale, 32);
+  return gfft_to_lagrange_launch<CV>((const U128*)d_in_affine, (U128*)d_out_affine, d_scratch, w, c, log_n, s, lanes);
+}
+void selftest_glv_split(const uint64_t k_canonical[4], uint32_t out[10]) {
+  Fe<FS> k;
+  memcpy(k.v, k_canonical, 32);
+  const GlvScalar r = glv_split<FS>(k);
+  memcpy(out, r.k1, 4 * GLV_WORDS);
+  memcpy(out + GLV_WORDS, r.k2, 4 * GLV_WORDS);
+}
+void selftest_glv_constants(uint64_t lambda[4], uint64_t beta[4]) {
+  uint32_t l[8], b[8];
+  for (int i = 0; i < 8; i++) {
+    l[i] = Glv<FS>::LAMBDA(i);
+    b[i] = Glv<FS>::BETA(i);
+  }
+  memcpy(lambda, l, 32);
+  memcpy(beta, b, 32);
 }
 hipError_t poly_scale(void* d_a, size_t total, const uint64_t c[4], hipStream_t s) {
   Fe<FS> cv;
@@ -420,7 +444,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 }
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
-                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, poly_scale, poly_powers, poly_mul_periodic,
+                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 

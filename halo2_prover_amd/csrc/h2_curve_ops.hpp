@@ -76,10 +76,20 @@ struct CurveOps {
                                  const uint64_t zeta_inv[4], void* d_out, size_t out_len, size_t out_stride, void* d_scratch,
                                  const void* d_tw, uint32_t log_n, size_t m, hipStream_t s);
   // best_fft over group elements (FftGroup for the curve: g_to_lagrange): n = 2^log_n Jacobian points (API form) in,
-  // the transform out (may alias), natural order, unscaled; d_scratch: group_fft_scratch(log_n) bytes
+  // the transform out (may alias), natural order, unscaled; d_scratch: group_fft_scratch(log_n) bytes.
+  // lanes: 0 = the stage kernel's form by size, 1 or 4 = that form (h2_selftest_set_gfft_lanes)
   size_t (*group_fft_scratch)(uint32_t log_n);
   hipError_t (*group_fft)(const void* d_in_jac, void* d_out_jac, void* d_scratch, const uint64_t omega[4], uint32_t log_n,
-                          hipStream_t s);
+                          int lanes, hipStream_t s);
+  // ParamsKZG's g_to_lagrange on that transform: n affine points in (identity (0, 0)), out[i] = [scale] sum_j
+  // [omega^(ij)] in[j] normalised (may alias); same scratch
+  hipError_t (*g_to_lagrange)(const void* d_in_affine, void* d_out_affine, void* d_scratch, const uint64_t omega[4],
+                              const uint64_t scale[4], uint32_t log_n, int lanes, hipStream_t s);
+  // host: the GLV split of a canonical scalar of this curve's scalar field as the kernels take it (h2_selftest_glv_split)
+  void (*selftest_glv_split)(const uint64_t k_canonical[4], uint32_t out[10]);
+  // host: lambda (canonical, scalar field) and beta (Montgomery, base field) of the split's endomorphism
+  void (*selftest_glv_constants)(uint64_t lambda[4], uint64_t beta[4]);
+  int glv_bits;     // GLV_BITS: both magnitudes of a split are below 2^glv_bits
   // pointwise polynomial kernels over the scalar field (EvaluationDomain pieces)
   hipError_t (*poly_scale)(void* d_a, size_t total, const uint64_t c[4], hipStream_t s);
   hipError_t (*poly_powers)(void* d_a, size_t n, size_t m, const uint64_t g[4], hipStream_t s);

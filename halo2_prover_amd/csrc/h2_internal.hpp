@@ -121,6 +121,7 @@ struct TestKnobs {
   bool msm_guard = false, msm_guard_poke = false;
   bool sort2_pack = true;                        // false: the unpacked forms of the two-level sort and the staged scatter
   size_t points_small_max = MSM_POINTS_SMALL_MAX;   // terms below which h2_msm_points* takes the double-and-add route
+  int gfft_lanes = 0;                            // lanes per butterfly of the group FFT: 0 = by size, 1, 4
 };
 struct TestCounters {
   uint64_t guard_launches = 0, guard_violations = 0;

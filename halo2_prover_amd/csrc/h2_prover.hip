@@ -194,6 +194,37 @@ int h2_setup(uint32_t k, h2_rng_fill_t rng_fn, void* rng_ctx, uint8_t* out, size
   });
 }
 
+// Params::downsize(k): g truncated, g_lagrange recomputed from it (h2_g_to_lagrange_device), the G2 tail copied
+int h2_params_downsize(const uint8_t* params, size_t params_len, uint32_t k, uint8_t* out, size_t cap, size_t* out_len) {
+  return guarded([&]() -> int {
+    DevCtx* ctx = the_ctx();
+    if (!params || params_len < 4) fail(H2_EPROOF, "params: truncated");
+    uint32_t k0;
+    memcpy(&k0, params, 4);
+    if (k0 > 28) fail(H2_EPROOF, "params: k out of range");
+    const size_t n0 = (size_t)1 << k0;
+    if (params_len != 4 + 128 * n0 + 256) fail(H2_EPROOF, "params: wrong length for k");
+    if (k < 1 || k > k0 || k > 26) return H2_EINVAL;
+    const size_t n = (size_t)1 << k, total = 4 + 128 * n + 256;
+    if (out_len) *out_len = total;
+    if (!out || cap < total) return H2_EINVAL;
+    Dev d(ctx);
+    const Domain D(2, k);
+    uint64_t w[4], c[4];
+    Dev::limbs(D.omega_inv, w);
+    Dev::limbs(D.n_inv, c);
+    Col g = d.col(2 * n);
+    hip_ok(hipMemcpyAsync(g, params + 4, 64 * n, hipMemcpyHostToDevice, d.s), "H2D");
+    st_ok(h2_g_to_lagrange_device(H2_BN254, g, k, w, c, g, d.s), "h2_g_to_lagrange_device");
+    hip_ok(hipMemcpyAsync(out + 4 + 64 * n, g, 64 * n, hipMemcpyDeviceToHost, d.s), "D2H");
+    memcpy(out, &k, 4);
+    memmove(out + 4, params + 4, 64 * n);
+    memcpy(out + 4 + 128 * n, params + 4 + 128 * n0, 256);
+    d.sync();
+    return H2_OK;
+  });
+}
+
 int h2_generate_proof(const uint8_t* params, size_t params_len, const char* json, int circuit, h2_rng_fill_t rng_fn,
                       void* rng_ctx, uint8_t* out, size_t cap, size_t* out_len) {
   return guarded([&]() -> int {

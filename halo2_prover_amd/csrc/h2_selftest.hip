@@ -197,6 +197,28 @@ extern "C" int h2_selftest_set_msm_points_small_max(size_t n) {
   g_knobs.points_small_max = n == SIZE_MAX ? MSM_POINTS_SMALL_MAX : n;
   return H2_OK;
 }
+// lanes per butterfly of the group FFT's stage kernel (h2_group_fft.hpp): 1 or 4 forces that form, 0 restores by size
+extern "C" int h2_selftest_set_gfft_lanes(int lanes) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (lanes != 0 && lanes != 1 && lanes != 4) return H2_EINVAL;
+  g_knobs.gfft_lanes = lanes;
+  return H2_OK;
+}
+// host only: glv_split of `curve`'s scalar field on a canonical k; out = |k1| then |k2|, five words each, bit 31 of the
+// fifth word the sign
+extern "C" int h2_selftest_glv_split(int curve, const uint64_t k[4], uint32_t out[10]) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !k || !out) return H2_EINVAL;
+  ops->selftest_glv_split(k, out);
+  return H2_OK;
+}
+extern "C" int h2_selftest_glv_constants(int curve, uint64_t lambda[4], uint64_t beta[4], uint32_t* glv_bits) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !lambda || !beta || !glv_bits) return H2_EINVAL;
+  ops->selftest_glv_constants(lambda, beta);
+  *glv_bits = (uint32_t)ops->glv_bits;
+  return H2_OK;
+}
 // host only: the sort front of a launch of m columns of n scalars against n_bases bases, as msm_plan_group lays it out
 // for msm_device_run (`pack` = 0: with the unpacked forms, as under h2_selftest_msm_guard(3)); out: include/h2hip_selftest.h
 extern "C" int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]) {

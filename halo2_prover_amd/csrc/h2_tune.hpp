@@ -32,4 +32,11 @@ constexpr size_t PROVE_GROUP = 16;
 // carries its additions on that chain), so the constant is the sweep's first size and only n < 8 is left to that route.
 constexpr size_t MSM_POINTS_SMALL_MAX = 8;
 constexpr uint32_t PROVE_GROUP_K = 16;
+
+// Largest log n at which the group FFT (h2_group_fft.hpp) runs its stages four lanes per butterfly; above it, one lane.
+// Where the two forms cross (tools/gfft_times.py with the form forced, profiles/gfft_times.txt):
+// at 2^16 four lanes take 17.2 ms against 18.6 (BN254; Pallas 15.4 / 16.2), at 2^17 34.5 against 20.2 (31.2 / 17.6).
+// The value derived before measuring was 17 (4 lanes x n/2 butterflies <= 1024 SIMDs x 4 waves x 64 lanes); both forms
+// hold two waves a SIMD, not four (their registers), which moves the crossing one size down.
+constexpr uint32_t GFFT_QUAD_MAX_LOG_N = 16;
 }  // namespace h2

@@ -36,6 +36,17 @@ def _limbs(v):
     return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
 
+def ifft_constants(k, curve="bn254"):
+    """(omega^-1, n^-1) of the 2^k domain of the curve's scalar field as Montgomery limbs: what EvaluationDomain.ifft, and
+    ParamsKZG's g_to_lagrange, transform and scale by.  Host arithmetic only."""
+    p, gen, S, _ = _FIELDS[_curve_id(curve)]
+    if not 0 <= k <= S:
+        raise ValueError("k exceeds the field's two-adicity")
+    R = (1 << 256) % p
+    omega = pow(pow(gen, (p - 1) >> S, p), 1 << (S - k), p)
+    return _limbs(pow(omega, -1, p) * R % p), _limbs(pow(1 << k, -1, p) * R % p)
+
+
 class EvaluationDomain:
     def __init__(self, j, k, curve="bn254"):
         import torch

@@ -62,6 +62,9 @@ SYMBOLS = {
     "h2_ntt_device": (_I, [_I, _P, _Z, _P, _U32, _P]),
     "h2_fft_group": (_I, [_I, _P, _P, _U32]),
     "h2_fft_group_device": (_I, [_I, _P, _P, _U32, _P]),
+    "h2_g_to_lagrange_device": (_I, [_I, _P, _U32, _P, _P, _P, _P]),
+    "h2_g_to_lagrange": (_I, [_I, _P, _U32, _P, _P, _P]),
+    "h2_params_downsize": (_I, [_P, _Z, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_ntt_scaled_device": (_I, [_I, _P, _Z, _P, _U32, _P, _P]),
     "h2_coeff_to_extended_device": (_I, [_I, _P, _Z, _U32, _Z, _P, _P, _U32, _P, _P]),
     "h2_extended_to_coeff_device": (_I, [_I, _P, _U32, _Z, _P, _P, _P, _P, _Z, _P, _Z, _Z, _P]),
@@ -96,6 +99,10 @@ SYMBOLS = {
     # the two hooks that go with h2_msm_points*
     "h2_selftest_msm_points_check": (_I, [_I, _Z, _Z, _Z, _I, _P]),
     "h2_selftest_set_msm_points_small_max": (_I, [_Z]),
+    # the hooks that go with h2_g_to_lagrange*: the stage kernel's form and the host instantiation of the GLV split
+    "h2_selftest_set_gfft_lanes": (_I, [_I]),
+    "h2_selftest_glv_split": (_I, [_I, _P, _P]),
+    "h2_selftest_glv_constants": (_I, [_I, _P, _P, ctypes.POINTER(_U32)]),
 }
 # include/h2hip_selftest.h (host instantiation of the device templates; not a compute path)
 SELFTEST_SYMBOLS = {

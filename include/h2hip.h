@@ -328,6 +328,34 @@ int h2_msm_plan(uint64_t bases_handle, h2_msm_plan_t* out);
 int h2_fft_group(h2_curve_t curve, uint64_t* points_jac, const uint64_t omega[4], uint32_t log_n);
 int h2_fft_group_device(h2_curve_t curve, void* d_points_jac, const uint64_t omega[4], uint32_t log_n, void* stream);
 
+/* ---- g_to_lagrange and Params::downsize: a Lagrange-basis SRS without the toxic scalar ---------------------
+ * ParamsKZG::new's g_to_lagrange in one call: out[i] = [scale] sum_{j<n} [omega_inv^(i j)] g[j], n = 2^log_n,
+ * affine in (64 B, identity (0,0)), affine out (normalised, canonical Montgomery limbs, identity (0,0)).
+ * With omega_inv = omega^-1 of the 2^log_n domain and scale = n^-1 this is g_lagrange: it replaces best_fft over the
+ * projective points, the n multiplications by n^-1 and batch_normalize.  scale = 1 skips the scaling; log_n = 0 copies
+ * the point times scale.
+ * h2_g_to_lagrange_device: device pointers, asynchronous on `stream` (NULL: the library's), on the calling thread's
+ * current context; scratch is the stream's MSM workspace for the length of the call (as h2_fft_group_device), nothing is
+ * cached.  d_out_affine may EQUAL d_g_affine (the points are read into the scratch first); a partial overlap of the two
+ * n * 64-byte ranges is H2_EINVAL.  H2_EINVAL, before anything is enqueued, also for an unknown curve, a null pointer,
+ * a device pointer that is not 16-byte aligned, or log_n > 26; H2_ENOTINIT before h2_init.
+ * h2_g_to_lagrange: host pointers (out_affine may be g_affine), context 0, synchronous.
+ * The points are NOT checked to be on the curve (best_fft does not check either): garbage in, garbage out, no fault;
+ * h2_bases_register stays the checked route and checks the output when it is used.
+ * h2_version() did not change for these entry points: a host detects them by their symbols. */
+int h2_g_to_lagrange_device(h2_curve_t curve, const void* d_g_affine, uint32_t log_n, const uint64_t omega_inv[4],
+                            const uint64_t scale[4], void* d_out_affine, void* stream);
+int h2_g_to_lagrange(h2_curve_t curve, const uint64_t* g_affine /* n*8 */, uint32_t log_n, const uint64_t omega_inv[4],
+                     const uint64_t scale[4], uint64_t* out_affine /* n*8 */);
+/* Params::downsize(k) on the params wire format of h2_setup (BN254: u32 k, g, g_lagrange, 256 bytes of G2): the output
+ * holds k, g[..2^k], g_to_lagrange of that prefix (omega^-1 and n^-1 of the 2^k domain) and the G2 tail copied.  k equal
+ * to the blob's own k takes the same path and recomputes g_lagrange.  Synchronous, on the calling thread's current
+ * context.  The blob is parsed as the prove and verify entry points parse it: H2_EPROOF for a truncated blob or a length
+ * that is not its k's; H2_EINVAL for k < 1 or k above the blob's k (or above 26).  *out_len receives the output's length
+ * (also when the call returns H2_EINVAL because `out` is null or cap is too small, as h2_setup).  Nothing is registered
+ * and the params cache is not touched: the points are validated when the output is later used as params. */
+int h2_params_downsize(const uint8_t* params, size_t params_len, uint32_t k, uint8_t* out, size_t cap, size_t* out_len);
+
 /* ---- SRS generation == the g vector of ParamsKZG::new(k) -----------------------------------
  * d_out_affine[i] = [s^i] G for i < n (device memory, n*64 bytes), s in Montgomery form.
  * Counterpart of the setup loop reached from /root/reference/circuits/src/utils.rs:59-61 and

@@ -75,6 +75,17 @@ int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap);
  *   input takes buckets; SIZE_MAX restores the default (h2_msm_points_plan_t.crossover shows the value in force). */
 int h2_selftest_msm_points_check(int curve, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]);
 int h2_selftest_set_msm_points_small_max(size_t n);
+/* The group FFT (h2_fft_group*, h2_g_to_lagrange*; csrc/h2_group_fft.hpp).
+ * h2_selftest_set_gfft_lanes: tests and tools only -- lanes per butterfly of the stage kernel: 1 or 4 forces that form at
+ *   every size, 0 restores the choice by size (GFFT_QUAD_MAX_LOG_N).  H2_EINVAL for any other value.
+ * h2_selftest_glv_split: host only, no GPU -- the host instantiation of the routine the twiddle kernel runs: the
+ *   CANONICAL scalar k (4 x u64, below 2^256) of `curve`'s scalar field -> out[0..4] = |k1|, out[5..9] = |k2| as 32-bit words,
+ *   least significant first, bit 31 of out[4] / out[9] set when k1 / k2 is negative; k1 + k2 lambda = k (mod r).
+ * h2_selftest_glv_constants: host only -- lambda (canonical integer, scalar field), beta (Montgomery limbs, base field)
+ *   with (beta x, y) = [lambda](x, y), and GLV_BITS, the loop length: both magnitudes are below 2^GLV_BITS. */
+int h2_selftest_set_gfft_lanes(int lanes);
+int h2_selftest_glv_split(int curve, const uint64_t k[4], uint32_t out[10]);
+int h2_selftest_glv_constants(int curve, uint64_t lambda[4], uint64_t beta[4], uint32_t* glv_bits);
 /* the integer ceiling the MSM kernels are priced against: dependent products of the MSM's working field form
  * (9 x 29-bit limbs) over `curve`'s base field, every CU busy with `waves_per_simd` waves per SIMD; measured
  * chip-wide modmul/s (best of three launches).  bench.py reports it as `modmul_ceiling`. */

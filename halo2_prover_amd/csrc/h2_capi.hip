@@ -13,6 +13,7 @@
 #include <optional>
 
 #include "h2_host.hpp"
+#include "h2_lookup.hpp"
 #include "h2_ntt.hpp"
 #include "h2_poly.hpp"
 
@@ -1115,6 +1116,105 @@ int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs, size_t n, const uint6
   if (int rc = poly_eval_enqueue(c, (int)curve, &poly, n, point, 1, base + off_res, c.stream); rc != H2_OK) return rc;
   H2_TRY(hipMemcpyAsync(out, base + off_res, 32, hipMemcpyDeviceToHost, c.stream));
   return stage.wait();
+}
+
+// ---- the lookup argument's permute and product steps (h2_lookup.hpp) ------------------------------------------------
+int h2_lookup_tile(void) { return (int)LOOKUP_TILE; }
+
+// [first byte, one past the last byte) of m columns of `rows` elements of `elem` bytes, stride elements apart
+static std::pair<uintptr_t, uintptr_t> lookup_range(const void* p, size_t rows, size_t stride, size_t m, size_t elem = 32) {
+  const uintptr_t lo = (uintptr_t)p;
+  if (rows == 0) return {lo, lo};
+  return {lo, lo + ((m - 1) * stride + rows) * elem};
+}
+static bool lookup_overlap(const std::pair<uintptr_t, uintptr_t>& a, const std::pair<uintptr_t, uintptr_t>& b) {
+  return a.first < b.second && b.first < a.second && a.first != a.second && b.first != b.second;
+}
+
+int h2_lookup_permute_device(h2_curve_t curve, const void* d_input, const void* d_table, size_t usable_rows, size_t col_stride,
+                             size_t m, void* d_permuted_input, void* d_permuted_table, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  const size_t u = usable_rows;
+  if (!curve_ok((int)curve) || u > LOOKUP_MAX_ROWS || col_stride < u || (col_stride && m > LOOKUP_MAX_CELLS / col_stride)) return H2_EINVAL;
+  if ((((uintptr_t)d_input | (uintptr_t)d_table | (uintptr_t)d_permuted_input | (uintptr_t)d_permuted_table) & 15) || ((uintptr_t)d_status & 3))
+    return H2_EINVAL;
+  if (m == 0) return H2_OK;
+  if (!d_status || (u > 0 && (!d_input || !d_table || !d_permuted_input || !d_permuted_table))) return H2_EINVAL;
+  const auto in = lookup_range(d_input, u, col_stride, m), tab = lookup_range(d_table, u, col_stride, m);
+  const auto pin = lookup_range(d_permuted_input, u, col_stride, m), ptab = lookup_range(d_permuted_table, u, col_stride, m);
+  const auto st = lookup_range(d_status, 1, 1, m, 4);
+  for (const auto* out : {&pin, &ptab, &st})
+    if (lookup_overlap(*out, in) || lookup_overlap(*out, tab)) return H2_EINVAL;
+  if (lookup_overlap(pin, ptab) || lookup_overlap(pin, st) || lookup_overlap(ptab, st)) return H2_EINVAL;
+  // the groups' bounds are proven before the first of them is enqueued
+  const size_t group = u ? lookup_group(u, m) : m;
+  for (size_t j0 = 0; u && j0 < m; j0 += group) {
+    const size_t mm = std::min(group, m - j0);
+    const LookupWorkspace ws = lookup_workspace(u, mm);
+    if (const char* broken = lookup_check(ws, u, mm, col_stride, ws.total)) {
+      g_h2.last_error = std::string("lookup launch geometry: ") + broken;
+      return H2_EDEVICE;
+    }
+  }
+  H2_TRY(hipMemsetAsync(d_status, 0, 4 * m, k.stream));
+  if (u == 0) return H2_OK;
+  const CurveOps* ops = ops_of((int)curve);
+  for (size_t j0 = 0; j0 < m; j0 += group) {             // the groups share the workspace: the stream runs them in order
+    const size_t mm = std::min(group, m - j0);
+    const LookupWorkspace ws = lookup_workspace(u, mm);
+    ArenaLease A(k.c->msm_ws.of(k.stream), ws.total, k.stream);      // the MSM workspace, idle here
+    if (A.rc != H2_OK) return A.rc;
+    if (const char* broken = lookup_check(ws, u, mm, col_stride, A.a.bytes)) {      // the arena the lease handed out must hold the layout
+      g_h2.last_error = std::string("lookup launch geometry: ") + broken;
+      return H2_EDEVICE;
+    }
+    const size_t skip = j0 * col_stride * 32;
+    if (int rc = launched(ops->lookup_permute((const char*)d_input + skip, (const char*)d_table + skip, col_stride, ws, (char*)A.a.p,
+                                              (char*)d_permuted_input + skip, (char*)d_permuted_table + skip, (uint32_t*)d_status + j0,
+                                              k.stream),
+                          "lookup permute kernels");
+        rc != H2_OK)
+      return rc;
+    if (int rc = A.release(); rc != H2_OK) return rc;
+  }
+  return H2_OK;
+}
+
+int h2_lookup_product_device(h2_curve_t curve, const void* d_input, const void* d_table, const void* d_permuted_input,
+                             const void* d_permuted_table, size_t usable_rows, size_t col_stride, size_t m, const uint64_t beta[4],
+                             const uint64_t gamma[4], void* d_z, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  const size_t u = usable_rows;
+  if (!curve_ok((int)curve) || u > LOOKUP_MAX_ROWS || col_stride < u + 1 || m > LOOKUP_MAX_CELLS / col_stride) return H2_EINVAL;
+  if (((uintptr_t)d_input | (uintptr_t)d_table | (uintptr_t)d_permuted_input | (uintptr_t)d_permuted_table | (uintptr_t)d_z) & 15) return H2_EINVAL;
+  if (m == 0) return H2_OK;
+  if (!d_z || !beta || !gamma || (u > 0 && (!d_input || !d_table || !d_permuted_input || !d_permuted_table))) return H2_EINVAL;
+  const auto z = lookup_range(d_z, u + 1, col_stride, m);
+  for (const void* src : {d_input, d_table, d_permuted_input, d_permuted_table})
+    if (lookup_overlap(z, lookup_range(src, u, col_stride, m))) return H2_EINVAL;
+  const CurveOps* ops = ops_of((int)curve);
+  for (size_t j0 = 0; j0 < m; j0 += 65535) {             // grid.y = column
+    const size_t skip = j0 * col_stride * 32;
+    if (int rc = launched(ops->lookup_ratio((const char*)d_input + skip, (const char*)d_table + skip, (const char*)d_permuted_input + skip,
+                                            (const char*)d_permuted_table + skip, u, col_stride, std::min<size_t>(65535, m - j0), beta,
+                                            gamma, (char*)d_z + skip, k.stream),
+                          "lookup_ratio_kernel");
+        rc != H2_OK)
+      return rc;
+  }
+  // z[i] = prod_{t < i} ratio[t] over u + 1 rows, in place, SCAN_MAX_JOBS columns side by side
+  ArenaLease A(k.c->div_ws, SCAN_MAX_JOBS * SCAN_WS_BYTES, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  for (size_t j0 = 0; j0 < m; j0 += SCAN_MAX_JOBS) {     // the groups share the scratch: the stream runs them in order
+    const uint32_t cnt = (uint32_t)std::min<size_t>(SCAN_MAX_JOBS, m - j0);
+    const void* src[SCAN_MAX_JOBS];
+    void* dst[SCAN_MAX_JOBS];
+    for (uint32_t j = 0; j < cnt; j++) src[j] = dst[j] = (char*)d_z + (j0 + j) * col_stride * 32;
+    if (int rc = launched(ops->poly_scan(1, src, dst, nullptr, cnt, u + 1, A.a.p, k.stream), "poly_scan kernels"); rc != H2_OK) return rc;
+  }
+  return A.release();
 }
 
 int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_t first_block, size_t n, void* d_out,

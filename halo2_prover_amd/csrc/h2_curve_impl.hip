@@ -7,6 +7,7 @@
 #include "h2_tune.hpp"
 #include "h2_poly.hpp"
 #include "h2_group_fft.hpp"
+#include "h2_lookup.hpp"
 
 #include <cstring>
 
@@ -224,6 +225,14 @@ hipError_t poly_eval(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d
   hipLaunchKernelGGL(poly_eval_fold_kernel<FS>, dim3((jobs + 63) / 64), dim3(64), 0, s, jobs, (const int32_t*)powers,
                      (const U128*)partial, tiles, (U128*)d_out);
   return hipGetLastError();
+}
+hipError_t lookup_permute(const void* d_input, const void* d_table, size_t col_stride, const LookupWorkspace& ws, char* ws_base,
+                          void* d_permuted_input, void* d_permuted_table, uint32_t* d_status, hipStream_t s) {
+  return lookup_permute_launch<FS>(d_input, d_table, col_stride, ws, ws_base, d_permuted_input, d_permuted_table, d_status, s);
+}
+hipError_t lookup_ratio(const void* d_input, const void* d_table, const void* d_permuted_input, const void* d_permuted_table, size_t u,
+                        size_t col_stride, size_t m, const uint64_t beta[4], const uint64_t gamma[4], void* d_z, hipStream_t s) {
+  return lookup_ratio_launch<FS>(d_input, d_table, d_permuted_input, d_permuted_table, u, col_stride, m, beta, gamma, d_z, s);
 }
 hipError_t chacha20_scalars(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s) {
   ChaChaKey k;
@@ -445,7 +454,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_scan, poly_eval, chacha20_scalars, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, poly_eval, lookup_permute, lookup_ratio, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 
 }  // namespace

@@ -11,6 +11,7 @@ namespace h2 {
 struct U128;
 struct MsmGeom;
 struct MsmWorkspace;
+struct LookupWorkspace;
 
 // one evaluation: the polynomial's coefficients in HBM (API form, 16-byte aligned) and the point's 8 x 32-bit
 // Montgomery limbs.  The poly_eval kernels read a table of these from HBM (h2_poly.hpp)
@@ -104,6 +105,14 @@ struct CurveOps {
   // d_out[t] = sum_{i < n} poly_t[i] point_t^i for the 1 <= jobs <= 65535 entries of the table d_jobs (grid.y = job),
   // 1 <= n <= 2^30 coefficients each; d_ws: poly_eval_ws_bytes(jobs, n), 16-byte aligned (h2_poly.hpp); three launches
   hipError_t (*poly_eval)(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d_ws, void* d_out, hipStream_t s);
+  // permute_expression_pair of ws.mm lookups of ws.u rows (h2_lookup.hpp): inputs and tables col_stride elements apart, ws
+  // proven by lookup_check, ws_base its scratch; d_status (ws.mm words) zeroed by the caller
+  hipError_t (*lookup_permute)(const void* d_input, const void* d_table, size_t col_stride, const LookupWorkspace& ws, char* ws_base,
+                               void* d_permuted_input, void* d_permuted_table, uint32_t* d_status, hipStream_t s);
+  // commit_product's per-row ratio into rows [0, u) of the m columns of d_z, row u = 1 (m <= 65535: grid.y)
+  hipError_t (*lookup_ratio)(const void* d_input, const void* d_table, const void* d_permuted_input, const void* d_permuted_table,
+                             size_t u, size_t col_stride, size_t m, const uint64_t beta[4], const uint64_t gamma[4], void* d_z,
+                             hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)

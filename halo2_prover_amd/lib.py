@@ -77,6 +77,9 @@ SYMBOLS = {
     "h2_poly_eval_device": (_I, [_I, _P, _Z, _P, _Z, _P, _P]),
     "h2_poly_eval": (_I, [_I, _P, _Z, _P, _P]),
     "h2_poly_eval_tile": (_I, []),
+    "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
+    "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
+    "h2_lookup_tile": (_I, []),
     "h2_chacha20_scalars_device": (_I, [_I, _P, _U64, _Z, _P, _P]),
     "h2_poly_inverse_device": (_I, [_I, _P, _Z, _P]),
     "h2_msm_plan": (_I, [_U64, ctypes.POINTER(MsmPlan)]),

@@ -301,6 +301,58 @@ int h2_poly_eval_device(h2_curve_t curve, const void* const* d_polys, size_t n, 
 int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs /* n*4 */, size_t n, const uint64_t point[4], uint64_t out[4]);
 /* coefficients one workgroup covers (T above).  Host only, no h2_init needed: tests size their shapes by it. */
 int h2_poly_eval_tile(void);
+/* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
+ * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
+ * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER
+ * of field elements is that of their canonical integer value (`Ord` of halo2curves' Fr), not that of the limbs.
+ * Both calls are asynchronous on `stream` under h2_ntt_device's rules and act on the context of the calling thread's
+ * current HIP device, as h2_poly_eval_device does.  u = usable_rows (halo2: n - (blinding_factors + 1)); the blinding
+ * rows [u, n) are the caller's, as with h2_poly_prefix_product_device.
+ *
+ * h2_lookup_permute_device: halo2_proofs src/plonk/lookup/prover.rs `permute_expression_pair(A, S)` over rows [0, u):
+ *   A' = A[0..u] sorted ascending; left = sorted map value -> count over S[0..u]; S' = u zeros; rep = [];
+ *   for row in 0..u: if row == 0 or A'[row] != A'[row-1] { S'[row] = A'[row]; left has no such value: the pair FAILS
+ *   (Error::ConstraintSystemFailure), else its count drops by one } else rep.push(row);
+ *   for (value, count) of left in ascending order, count times: S'[rep.pop()] = value   (pop from the END: the smallest
+ *   leftover value lands on the largest repeated row).  Equal keys are indistinguishable, so A' and S' are unique.
+ * Out of place: rows [0, u) of d_permuted_input (A') and d_permuted_table (S') are written, rows [u, col_stride) are not
+ * touched.  d_status: m uint32 words of device memory, 0 = done, 1 = some input value is not in the table; for such a
+ * pair d_permuted_input is still the full sorted column and the u rows of d_permuted_table are unspecified, the other
+ * pairs are unaffected.  No host synchronisation: the caller reads the words when it wants them.
+ * The columns are de-Montgomerised once and sorted by an LSD radix sort of 8-bit digits over the canonical 256-bit keys,
+ * T = h2_lookup_tile() rows per workgroup and pass.  A digit on which all keys of a column agree is skipped; which of the
+ * 32 passes run is decided ON THE DEVICE from the AND and OR of the keys (every pass is enqueued, a skipped one returns
+ * at once), so nothing is read back and the call never waits: an 8-bit range table costs one or two passes, a
+ * theta-compressed column up to 32.  Then each first occurrence binary-searches the sorted table, two scans rank the
+ * repeated rows and the remaining table entries, and a scatter fills the repeated rows; outputs are re-Montgomerised.
+ * Inputs that are not canonical give an unspecified order, never an out-of-range access: every index is formed from
+ * usable_rows, m and bounded digit, rank or search values, and the launch geometry is proven on the host before anything
+ * is enqueued (H2_EDEVICE with the violated condition in h2_last_device_error otherwise).
+ * Scratch is the stream's MSM workspace for the length of the call (as h2_g_to_lagrange_device); nothing is cached or
+ * kept.  One lookup needs about 136 * u bytes; a wide m runs in groups on `stream` so that the scratch stays under
+ * max(1 GiB, what one lookup needs) and a group stays under 32767 lookups.
+ *
+ * h2_lookup_product_device: `commit_product` per lookup: z[0] = 1, z[i+1] = z[i] (A[i] + beta)(S[i] + gamma) /
+ * ((A'[i] + beta)(S'[i] + gamma)) for i < u.  Rows [0, u] of every d_z column are written (z[u] = 1 for a satisfied
+ * lookup), rows beyond are not touched; col_stride >= u + 1.  A zero denominator gives ratio 0 (batch_invert leaves zero
+ * at zero).  One kernel writes the ratios (one inversion per run of 4 rows), the batched running product of
+ * h2_poly_prefix_product_device follows in place.  beta, gamma: 4 Montgomery limbs each, host memory, read before return.
+ *
+ * H2_EINVAL, before anything is enqueued, for: an unknown curve; usable_rows > 2^26; col_stride < usable_rows (product:
+ * < usable_rows + 1) or m * col_stride > 2^57; a device pointer that is not 16-byte aligned (d_status: 4-byte); with
+ * m > 0 a null d_status / d_z / beta / gamma, and with m > 0 and usable_rows > 0 any other null pointer; permute: an
+ * output range (d_status included) that overlaps an input range or another output; product: d_z overlapping a source.
+ * H2_ENOTINIT before h2_init.  m = 0: H2_OK, nothing enqueued.  usable_rows = 0: permute writes m zero status words,
+ * product writes z[0] = 1.
+ * h2_version() did not change for these entry points: a host detects them by their symbols. */
+int h2_lookup_permute_device(h2_curve_t curve, const void* d_input, const void* d_table, size_t usable_rows,
+                             size_t col_stride, size_t m, void* d_permuted_input, void* d_permuted_table,
+                             void* d_status, void* stream);
+int h2_lookup_product_device(h2_curve_t curve, const void* d_input, const void* d_table, const void* d_permuted_input,
+                             const void* d_permuted_table, size_t usable_rows, size_t col_stride, size_t m,
+                             const uint64_t beta[4], const uint64_t gamma[4], void* d_z, void* stream);
+/* rows one workgroup handles per sort pass (T above).  Host only, no h2_init needed: tests size their shapes by it. */
+int h2_lookup_tile(void);
 /* out[i] = Scalar::random(rng) number first_block + i of rng = ChaCha20Rng::from_seed(seed), Montgomery limbs:
  * the coefficients of the vanishing argument's random_poly (halo2_proofs src/plonk/vanishing/prover.rs
  * `Argument::commit`).  Each draw consumes one 64-byte ChaCha20 block. */

@@ -7,5 +7,6 @@ one device.  There is no CPU fallback.
 from .api import (Bases, ParamsKZG, best_fft, best_fft_batch, best_fft_group, best_multiexp, g_to_lagrange,  # noqa: F401
                   generate_proofs, init, msm_points, msm_points_device, msm_points_plan, ntt_device, params_downsize,
                   points_decompress_device, verify_proofs)
+from .expr import ExprProgram  # noqa: F401
 from .lookup import lookup_product, permute_expression_pair  # noqa: F401
 from .lib import CURVES, H2Error, LIB_PATH, SYMBOLS, load  # noqa: F401

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <optional>
 
+#include "h2_expr_program.hpp"
 #include "h2_host.hpp"
 #include "h2_lookup.hpp"
 #include "h2_ntt.hpp"
@@ -647,6 +648,85 @@ int msm_host(h2_curve_t curve, uint64_t handle, const uint64_t* const* cols, siz
   return H2_OK;
 }
 
+// ---- expressions over resident columns (h2_expr_program.hpp compiles, h2_expr_kernel.hpp interprets) ----------------------
+constexpr size_t EXPR_TABLE_CAP = (size_t)256 << 20;   // bytes of constant tables one group of instances may take
+constexpr size_t EXPR_MAX_COUNT = (size_t)1 << 20;     // nodes, constants, variables
+constexpr size_t EXPR_MAX_INSTANCES = (size_t)1 << 30;
+
+// 4 x u64 Montgomery limbs: the integer they hold is below p
+template <class FP>
+bool mont_canonical(const uint64_t* v) {
+  for (int i = 3; i >= 0; i--) {
+    const uint64_t pw = (uint64_t)FP::P(2 * i) | ((uint64_t)FP::P(2 * i + 1) << 32);
+    if (v[i] != pw) return v[i] < pw;
+  }
+  return false;
+}
+// the API form x 2^256 -> the kernel's working form x 2^261 (R' = 2^261): five doublings
+template <class FP>
+void expr_working_form(const uint64_t* api, uint64_t* out) {
+  HF<FP> c = HF<FP>::from_mont_limbs(api);
+  for (int t = 0; t < 5; t++) c = c + c;
+  c.mont_limbs(out);
+}
+
+template <class FP>
+void expr_compile_t(const h2_expr_node_t* nodes, size_t n_nodes, const uint64_t* consts, size_t n_consts, uint32_t n_cols,
+                    uint32_t n_vars, ExprEntry& e) {
+  using product::fail;
+  std::vector<HF<FP>> cs(n_consts);
+  for (size_t j = 0; j < n_consts; j++) {
+    if (!mont_canonical<FP>(consts + 4 * j)) fail(H2_EINVAL, "expr: constant not canonical");
+    cs[j] = HF<FP>::from_mont_limbs(consts + 4 * j);
+  }
+  static_assert(sizeof(h2_expr_node_t) == 16, "four i32 per node");
+  product::ExprProgramT<FP> X;
+  product::program_from_nodes<FP>(X, (const int32_t*)nodes, n_nodes, cs, n_cols, n_vars, true, &e.var_slot);
+  const size_t lds = product::expr_lds_bytes(X);       // H2_EINVAL past what one workgroup may hold
+  const std::vector<uint8_t> rep = X.report();
+  uint32_t st[6];
+  memcpy(st, rep.data(), 24);
+  e.info = h2_expr_info_t{0, st[0], st[1], st[2], st[3], st[4], st[5], n_cols, n_vars, (uint32_t)lds, 0, 0};
+  bool any = false;
+  for (auto& ins : X.code)
+    for (uint32_t w : {ins.a, ins.b})
+      if ((w & (3u << 30)) == pk::X_COL) {
+        const int32_t rot = (int32_t)(w & 0xFFu) - 128;
+        e.info.min_rot = any ? std::min(e.info.min_rot, rot) : rot;
+        e.info.max_rot = any ? std::max(e.info.max_rot, rot) : rot;
+        any = true;
+      }
+  e.code.resize(3 * X.code.size());
+  memcpy(e.code.data(), X.code.data(), X.code.size() * sizeof(pk::XInstr));
+  e.table.resize(4 * X.consts.size());
+  for (size_t j = 0; j < X.consts.size(); j++) {
+    uint64_t api[4];
+    X.consts[j].mont_limbs(api);
+    expr_working_form<FP>(api, e.table.data() + 4 * j);
+  }
+  e.dump = X.report_with_table();
+  const size_t at = e.dump.size();
+  e.dump.resize(at + 4 * e.var_slot.size());
+  if (!e.var_slot.empty()) memcpy(e.dump.data() + at, e.var_slot.data(), 4 * e.var_slot.size());
+}
+
+// the constant tables of instances [p0, p0 + cnt): the program's own table with the instance's variables in their slots
+template <class FP>
+void expr_fill_tables(const ExprEntry& e, const uint64_t* vars, size_t p0, size_t cnt, uint64_t* out) {
+  const size_t words = e.table.size(), nv = e.var_slot.size();
+  for (size_t p = 0; p < cnt; p++) {
+    uint64_t* t = out + p * words;
+    memcpy(t, e.table.data(), words * 8);
+    for (size_t v = 0; v < nv; v++) expr_working_form<FP>(vars + 4 * ((p0 + p) * nv + v), t + 4 * (size_t)e.var_slot[v]);
+  }
+}
+
+// the three by the curve's scalar field
+#define H2_BY_SCALAR_FIELD(curve, call)                          \
+  ((curve) == H2_BN254    ? call<BN254_CURVE::Scalar>            \
+   : (curve) == H2_PALLAS ? call<PALLAS_CURVE::Scalar>           \
+                          : call<VESTA_CURVE::Scalar>)
+
 }  // namespace
 
 extern "C" {
@@ -702,6 +782,8 @@ int h2_shutdown(void) {
     for (auto& kv : g_h2.bases)
       if (kv.second.table[i]) (void)hipFree(kv.second.table[i]);
     for (auto& t : c.twiddles) (void)hipFree(t.tw);
+    for (auto& kv : g_h2.exprs)
+      if (i < kv.second.d_code.size() && kv.second.d_code[i]) (void)hipFree(kv.second.d_code[i]);
     for (Arena& a : c.msm_ws.slot) arena_free(a);
     for (Arena& a : c.ntt_ws.slot) arena_free(a);
     arena_free(c.stage);
@@ -717,6 +799,7 @@ int h2_shutdown(void) {
     (void)hipStreamDestroy(c.stream);
   }
   g_h2.bases.clear();
+  for (auto& kv : g_h2.exprs) kv.second.d_code.clear();      // the programs themselves are host state and stay
   g_h2.ctx.clear();
   g_h2.ready = false;
   return H2_OK;
@@ -1213,6 +1296,150 @@ int h2_lookup_product_device(h2_curve_t curve, const void* d_input, const void* 
     void* dst[SCAN_MAX_JOBS];
     for (uint32_t j = 0; j < cnt; j++) src[j] = dst[j] = (char*)d_z + (j0 + j) * col_stride * 32;
     if (int rc = launched(ops->poly_scan(1, src, dst, nullptr, cnt, u + 1, A.a.p, k.stream), "poly_scan kernels"); rc != H2_OK) return rc;
+  }
+  return A.release();
+}
+
+// ---- expressions over resident columns --------------------------------------------------------------------------------
+int h2_expr_compile(h2_curve_t curve, const h2_expr_node_t* nodes, size_t n_nodes, const uint64_t* consts, size_t n_consts,
+                    uint32_t n_cols, uint32_t n_vars, uint64_t* handle_out) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  auto refuse = [](const char* rule) {
+    g_h2.last_error = std::string("expr: ") + rule;
+    return (int)H2_EINVAL;
+  };
+  if (!curve_ok((int)curve)) return refuse("unknown curve");
+  if (!handle_out || !nodes || (n_consts && !consts)) return refuse("null pointer");
+  if (n_nodes == 0 || n_nodes > EXPR_MAX_COUNT) return refuse("n_nodes must be 1 .. 2^20");
+  if (n_consts > EXPR_MAX_COUNT || n_vars > EXPR_MAX_COUNT) return refuse("n_consts and n_vars may be at most 2^20");
+  if (n_cols > (1u << 22)) return refuse("n_cols may be at most 2^22");
+  ExprEntry e{};
+  e.curve = (int)curve;
+  try {
+    H2_BY_SCALAR_FIELD((int)curve, expr_compile_t)(nodes, n_nodes, consts, n_consts, n_cols, n_vars, e);
+  } catch (const product::Fail& f) {
+    g_h2.last_error = f.what;
+    return f.status;
+  } catch (const std::exception& x) {
+    g_h2.last_error = x.what();
+    return H2_ENOMEM;
+  }
+  e.info.curve = (uint32_t)curve;
+  const uint64_t h = g_h2.next_handle++;
+  g_h2.exprs[h] = std::move(e);
+  *handle_out = h;
+  return H2_OK;
+}
+
+int h2_expr_release(uint64_t handle) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  auto it = g_h2.exprs.find(handle);
+  if (it == g_h2.exprs.end()) return H2_EHANDLE;
+  for (size_t i = 0; i < it->second.d_code.size() && i < g_h2.ctx.size(); i++) {
+    if (!it->second.d_code[i]) continue;
+    DeviceGuard dg(g_h2.ctx[i].device);
+    (void)hipDeviceSynchronize();     // launches on caller streams may still read the code
+    (void)hipFree(it->second.d_code[i]);
+  }
+  g_h2.exprs.erase(it);
+  return H2_OK;
+}
+
+int h2_expr_info(uint64_t handle, h2_expr_info_t* out) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!out) return H2_EINVAL;
+  auto it = g_h2.exprs.find(handle);
+  if (it == g_h2.exprs.end()) return H2_EHANDLE;
+  *out = it->second.info;
+  return H2_OK;
+}
+
+int h2_expr_dump(uint64_t handle, uint8_t* out, size_t cap, size_t* out_len) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  auto it = g_h2.exprs.find(handle);
+  if (it == g_h2.exprs.end()) return H2_EHANDLE;
+  const std::vector<uint8_t>& d = it->second.dump;
+  if (out_len) *out_len = d.size();
+  if (!out || cap < d.size()) return H2_EINVAL;       // *out_len says how much is needed
+  memcpy(out, d.data(), d.size());
+  return H2_OK;
+}
+
+int h2_expr_eval_device(uint64_t handle, const void* const* d_cols, const uint32_t* log_len, const uint64_t* vars, size_t m,
+                        uint32_t log_rows, uint32_t rot_step, void* d_out, size_t out_stride, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  auto it = g_h2.exprs.find(handle);
+  if (it == g_h2.exprs.end()) return H2_EHANDLE;
+  ExprEntry& e = it->second;
+  const size_t n_cols = e.info.n_cols, n_vars = e.info.n_vars, nconsts = e.table.size() / 4;
+  if (log_rows > 28 || m > EXPR_MAX_INSTANCES) return H2_EINVAL;
+  const size_t rows = (size_t)1 << log_rows;
+  if (out_stride < rows || (m && out_stride > ((size_t)1 << 57) / m)) return H2_EINVAL;
+  if (m == 0) return H2_OK;
+  if (!d_out || ((uintptr_t)d_out & 15) || (n_cols && (!d_cols || !log_len)) || (n_vars && !vars)) return H2_EINVAL;
+  for (size_t c = 0; c < n_cols; c++)
+    if (log_len[c] > log_rows) return H2_EINVAL;
+  // every column's bytes against the rows that are written: [0, rows) of each instance's window of out_stride rows.  A
+  // column inside [d_out, the last written byte) starts in the window of one instance: it may neither start before that
+  // instance's last written row nor reach the next instance's first
+  const uintptr_t o0 = (uintptr_t)d_out, window = out_stride * 32, written = rows * 32, o1 = o0 + (m - 1) * window + written;
+  for (size_t p = 0; p < m; p++)
+    for (size_t c = 0; c < n_cols; c++) {
+      const uintptr_t s0 = (uintptr_t)d_cols[p * n_cols + c], s1 = s0 + ((uintptr_t)32 << log_len[c]);
+      if (!s0 || (s0 & 15)) return H2_EINVAL;
+      if (s0 < o1 && o0 < s1) {
+        const uintptr_t q = s0 > o0 ? (s0 - o0) / window : 0, w0 = o0 + q * window;
+        if (s0 < w0 + written || (q + 1 < m && s1 > w0 + window)) return H2_EINVAL;
+      }
+    }
+  for (size_t t = 0; t < m * n_vars; t++)
+    if (!H2_BY_SCALAR_FIELD(e.curve, mont_canonical)(vars + 4 * t)) return H2_EINVAL;
+  DevCtx& c = *k.c;
+  const size_t ci = ctx_index(&c);
+  // instances per launch: grid.y, and what keeps the group's constant tables under EXPR_TABLE_CAP
+  const size_t group = std::min<size_t>({m, (size_t)65535, std::max<size_t>(1, EXPR_TABLE_CAP / (nconsts * 32))});
+  // the host side of the tables (up to EXPR_TABLE_CAP) before anything is enqueued: nothing may throw across the C ABI
+  std::vector<uint32_t> masks;
+  std::vector<uint64_t> tables;
+  try {
+    masks.resize(n_cols);
+    tables.resize(group * nconsts * 4);
+    if (e.d_code.size() != g_h2.ctx.size()) e.d_code.assign(g_h2.ctx.size(), nullptr);
+  } catch (const std::bad_alloc&) {
+    g_h2.last_error = "expr: no host memory for the instances' constant tables";
+    return H2_ENOMEM;
+  }
+  if (!e.d_code[ci]) {
+    // uploaded on the library's stream and finished before anybody uses it: later calls bring any stream (once per context)
+    void* p = nullptr;
+    if (int rc = device_alloc(&p, e.code.size() * 4, "expr code"); rc != H2_OK) return rc;
+    DeviceBuffer owner(p);
+    H2_TRY(hipMemcpyAsync(p, e.code.data(), e.code.size() * 4, hipMemcpyHostToDevice, c.stream));
+    H2_TRY(hipStreamSynchronize(c.stream));
+    e.d_code[ci] = owner.release();
+  }
+  const size_t mask_bytes = h2_align256(n_cols * 4 + 4), ptr_bytes = h2_align256(group * n_cols * sizeof(void*) + 8);
+  ArenaLease A(c.div_ws, mask_bytes + ptr_bytes + group * nconsts * 32, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  uint32_t* d_masks = (uint32_t*)A.a.p;
+  const void** d_ptrs = (const void**)((char*)A.a.p + mask_bytes);
+  void* d_tables = (char*)A.a.p + mask_bytes + ptr_bytes;
+  // pageable sources: the runtime has read them when each call returns (it stages the bytes or waits for the copy)
+  for (size_t j = 0; j < n_cols; j++) masks[j] = (1u << log_len[j]) - 1;
+  if (n_cols) H2_TRY(hipMemcpyAsync(d_masks, masks.data(), n_cols * 4, hipMemcpyHostToDevice, k.stream));
+  const CurveOps* ops = ops_of(e.curve);
+  for (size_t p0 = 0; p0 < m; p0 += group) {             // the groups share the scratch: the stream runs them in order
+    const size_t cnt = std::min(group, m - p0);
+    H2_BY_SCALAR_FIELD(e.curve, expr_fill_tables)(e, vars, p0, cnt, tables.data());
+    if (n_cols) H2_TRY(hipMemcpyAsync(d_ptrs, d_cols + p0 * n_cols, cnt * n_cols * sizeof(void*), hipMemcpyHostToDevice, k.stream));
+    H2_TRY(hipMemcpyAsync(d_tables, tables.data(), cnt * nconsts * 32, hipMemcpyHostToDevice, k.stream));
+    if (int rc = launched(ops->expr_launch(e.d_code[ci], e.info.instructions, d_ptrs, (uint32_t)n_cols, d_masks, d_tables, (uint32_t)nconsts,
+                                           (char*)d_out + p0 * out_stride * 32, out_stride, rot_step, (uint32_t)rows, (uint32_t)cnt,
+                                           e.info.lds_bytes, k.stream),
+                          "expr_kernel");
+        rc != H2_OK)
+      return rc;
   }
   return A.release();
 }

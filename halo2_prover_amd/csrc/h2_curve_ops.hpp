@@ -113,6 +113,13 @@ struct CurveOps {
   hipError_t (*lookup_ratio)(const void* d_input, const void* d_table, const void* d_permuted_input, const void* d_permuted_table,
                              size_t u, size_t col_stride, size_t m, const uint64_t beta[4], const uint64_t gamma[4], void* d_z,
                              hipStream_t s);
+  // expr_kernel (h2_expr_kernel.hpp) over the scalar field: the compiled program d_code (ninstr x 12 bytes) on `rows` rows
+  // of 1 <= count <= 65535 instances (grid.y).  Instance p: column pointers d_cols[p ncols ...], constants in the working
+  // form d_consts + 32 (p nconsts), result at d_out + 32 (p out_stride).  d_masks: length - 1 of each column;
+  // lds_bytes = expr_lds_for_slots of the program's slots, at most EXPR_LDS_MAX
+  hipError_t (*expr_launch)(const void* d_code, uint32_t ninstr, const void* const* d_cols, uint32_t ncols, const uint32_t* d_masks,
+                            const void* d_consts, uint32_t nconsts, void* d_out, size_t out_stride, uint32_t step, uint32_t rows,
+                            uint32_t count, size_t lds_bytes, hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)

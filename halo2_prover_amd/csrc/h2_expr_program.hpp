@@ -1,16 +1,23 @@
-// h2_expr_program.hpp -- the quotient numerator as a straight-line program: the compiler (host) and the launch of the
-// kernel that interprets it (h2_prover_kernels.hpp, expr_kernel).
+// h2_expr_program.hpp -- an expression DAG as a straight-line program: the compiler (host only, generic over the scalar
+// field) of the kernel that interprets it (h2_expr_kernel.hpp, expr_kernel).  create_proof compiles its quotient
+// numerator with it (h2_keygen.hpp), h2_expr_compile a caller's DAG (h2_capi.hip).
 #pragma once
+#include <algorithm>
+#include <array>
 #include <functional>
+#include <map>
 #include <tuple>
 
-#include "h2_product_dev.hpp"
+#include "h2_expr_kernel.hpp"
+#include "h2_product_base.hpp"
 
 namespace h2 {
 namespace product {
 
-// ---- the quotient numerator compiled to a straight-line program (h2_prover_kernels.hpp expr_kernel) ------------------------
-struct ExprProgram {
+// ---- a DAG compiled to a straight-line program (h2_expr_kernel.hpp expr_kernel) -------------------------------------------
+template <class FP>
+struct ExprProgramT {
+  using Elem = HF<FP>;
   // nodes (hash-consed): 0 const, 1 column, 2 add, 3 sub, 4 mul
   struct Node {
     int op, a, b, col, rot, cidx;
@@ -20,7 +27,7 @@ struct ExprProgram {
   };
   std::vector<Node> nodes;
   std::map<Node, int> index;
-  std::vector<Fr> consts;              // constant table (proof-dependent entries are patched per proof)
+  std::vector<Elem> consts;            // constant table (the variables' entries are patched per proof / instance)
   std::map<std::array<uint8_t, 32>, int> const_index;
   int intern(const Node& nd) {
     auto it = index.find(nd);
@@ -29,7 +36,7 @@ struct ExprProgram {
     index[nd] = (int)nodes.size() - 1;
     return (int)nodes.size() - 1;
   }
-  int constant(const Fr& v) {
+  int constant(const Elem& v) {
     std::array<uint8_t, 32> key;
     memcpy(key.data(), v.v.v, 32);
     auto it = const_index.find(key);
@@ -45,7 +52,7 @@ struct ExprProgram {
   }
   // a slot of the constant table whose value is set later (challenges): never merged with another constant
   int variable(int* slot_out) {
-    consts.push_back(Fr::zero());
+    consts.push_back(Elem::zero());
     *slot_out = (int)consts.size() - 1;
     return intern({0, -1, -1, -1, 0, *slot_out});
   }
@@ -60,39 +67,41 @@ struct ExprProgram {
   // Order: depth first, the operand that needs more live values first (Sethi-Ullman numbering; shared nodes count as
   // computed).  A result that the NEXT instruction consumes is handed over in a register (operand kind X_PREV), and a
   // result with no other use is never stored: a slot costs 32 bytes of LDS per row and the slots of 128 rows decide
-  // how many blocks share a CU (h2_prover_kernels.hpp, expr_kernel).
+  // how many blocks share a CU (h2_expr_kernel.hpp, expr_kernel).
   void compile(int root) {
     for (const Node& nd : nodes)                     // the operand word has 22 bits for a column and 8 for rot + 128
       if (nd.op == 1 && (nd.col < 0 || nd.col >= (1 << 22) || nd.rot < -128 || nd.rot > 127))
         fail(H2_EINVAL, "quotient program: column index or rotation does not fit its operand word");
-    (void)constant(Fr::one());                       // the reducing product's operand: interned before the node tables are sized
-    std::vector<int> need(nodes.size(), -1);
-    std::function<int(int)> su = [&](int id) -> int {
-      if (need[id] >= 0) return need[id];
-      const Node& nd = nodes[id];
-      if (nd.op < 2) return need[id] = 0;
-      const int na = su(nd.a), nb = su(nd.b);
-      return need[id] = std::max(1, na == nb ? na + 1 : std::max(na, nb));
-    };
-    su(root);
+    (void)constant(Elem::one());                     // the reducing product's operand: interned before the node tables are sized
+    // No recursion anywhere: a y-fold over all constraints is a chain as deep as the DAG is long (2^20 nodes through
+    // h2_expr_compile).  An operand is always an earlier node (intern appends), so one forward pass numbers them all
+    std::vector<int> need(nodes.size(), 0);
+    for (size_t id = 0; id < nodes.size(); id++)
+      if (nodes[id].op >= 2) {
+        const int na = need[nodes[id].a], nb = need[nodes[id].b];
+        need[id] = std::max(1, na == nb ? na + 1 : std::max(na, nb));
+      }
+    // depth first from the root on an explicit stack: a node is emitted once both operands are
     std::vector<int> order;
     std::vector<char> seen(nodes.size(), 0);
-    std::function<void(int)> visit = [&](int id) {
-      if (seen[id]) return;
-      seen[id] = 1;
+    std::vector<std::pair<int, int>> stack;          // (node, operands entered so far)
+    seen[root] = 1;
+    if (nodes[root].op >= 2) stack.push_back({root, 0});
+    while (!stack.empty()) {
+      const int id = stack.back().first, stage = stack.back().second++;
       const Node& nd = nodes[id];
-      if (nd.op >= 2) {
-        if (need[nd.b] > need[nd.a]) {
-          visit(nd.b);
-          visit(nd.a);
-        } else {
-          visit(nd.a);
-          visit(nd.b);
-        }
+      if (stage == 2) {
         order.push_back(id);
+        stack.pop_back();
+        continue;
       }
-    };
-    visit(root);
+      const bool b_first = need[nd.b] > need[nd.a];
+      const int next = (stage == 0) == b_first ? nd.b : nd.a;
+      if (!seen[next]) {
+        seen[next] = 1;
+        if (nodes[next].op >= 2) stack.push_back({next, 0});
+      }
+    }
     if (order.empty()) fail(H2_EINVAL, "empty quotient program");
     std::vector<int> at(nodes.size(), -1);           // instruction index of a node
     for (size_t t = 0; t < order.size(); t++) at[order[t]] = (int)t;
@@ -105,14 +114,14 @@ struct ExprProgram {
       }
     std::vector<int> slot_of(nodes.size(), -1);
     std::vector<uint32_t> free_slots;
-    // magnitudes in units of p (expr_kernel's header): constants are canonical, columns below EXPR_COLUMN_BOUND, a
-    // product of a and b below a b / 128 + 1 (p^2 / 2^261 < p / 128); a sum that would pass EXPR_VALUE_BOUND is
-    // multiplied by one straight away
+    // magnitudes in units of p (expr_kernel's header, which carries the argument for every field): constants are
+    // canonical, columns within EXPR_COLUMN_BOUND, a product of a and b below a b EXPR_PRODUCT_SCALE + 1 (p^2 / 2^261 is at
+    // most that scale times p); a sum that would pass EXPR_VALUE_BOUND is multiplied by one straight away
     std::vector<double> bound(nodes.size(), 0.0);
     for (size_t id = 0; id < nodes.size(); id++)
       if (nodes[id].op == 0) bound[id] = 1.0;
       else if (nodes[id].op == 1) bound[id] = pk::EXPR_COLUMN_BOUND;
-    const uint32_t one_operand = pk::X_CONST | (uint32_t)nodes[constant(Fr::one())].cidx;
+    const uint32_t one_operand = pk::X_CONST | (uint32_t)nodes[constant(Elem::one())].cidx;
     for (size_t t = 0; t < order.size(); t++) {
       const Node& nd = nodes[order[t]];
       auto operand = [&](int id) -> uint32_t {
@@ -139,11 +148,11 @@ struct ExprProgram {
         }
         slot_of[order[t]] = (int)dst;
       }
-      double bd = nd.op == 4 ? bound[nd.a] * bound[nd.b] / 128.0 + 1.0 : bound[nd.a] + bound[nd.b];
+      double bd = nd.op == 4 ? bound[nd.a] * bound[nd.b] * pk::EXPR_PRODUCT_SCALE + 1.0 : bound[nd.a] + bound[nd.b];
       if (nd.op != 4 && bd > pk::EXPR_VALUE_BOUND) {
         code.push_back({((uint32_t)(nd.op - 2) << 24) | pk::X_NO_STORE, a, b});
         code.push_back({(2u << 24) | dst, pk::X_PREV, one_operand});
-        bd = bd / 128.0 + 1.0;
+        bd = bd * pk::EXPR_PRODUCT_SCALE + 1.0;
         nreduce++;
       } else {
         code.push_back({((uint32_t)(nd.op - 2) << 24) | dst, a, b});
@@ -166,42 +175,67 @@ struct ExprProgram {
     memcpy(r.data() + 24, code.data(), code.size() * sizeof(pk::XInstr));
     return r;
   }
+  // report(), then the constant table (32 canonical little-endian bytes each; the one compile adds included)
+  std::vector<uint8_t> report_with_table() const {
+    std::vector<uint8_t> r = report();
+    for (auto& c : consts) {
+      uint8_t b[32];
+      c.to_le_bytes(b);
+      r.insert(r.end(), b, b + 32);
+    }
+    return r;
+  }
 };
+using ExprProgram = ExprProgramT<BN254_FR>;    // the prover's: bn256::Fr
 
-// expr_kernel over en rows of `count` proofs (grid.y = proof): one program and one set of row masks; proof p's column
-// pointers at ptrs[p masks.size() ...], its constants (c, patched for the proof) at consts[p nconsts ...], uploaded in the
-// kernel's working form c 2^261, its result at out + p en; the LDS of the slots beyond the registers is checked against
-// what one workgroup may hold before anything is uploaded or launched.  create_proofs and the test hook
-// h2_selftest_expr_run (count = 1) both launch the quotient program through here.
-inline size_t expr_lds_bytes(const ExprProgram& X) {
-  const size_t lds_slots = X.nslots > (uint32_t)pk::EXPR_REG_SLOTS ? X.nslots - pk::EXPR_REG_SLOTS : 1;
-  const size_t lds = lds_slots * 9 * pk::EXPR_BLOCK * 4;
+// the LDS of the slots beyond the registers, checked against what one workgroup may hold
+template <class FP>
+inline size_t expr_lds_bytes(const ExprProgramT<FP>& X) {
+  const size_t lds = pk::expr_lds_for_slots(X.nslots);
   if (lds > pk::EXPR_LDS_MAX) fail(H2_EINVAL, "quotient program needs too many live values");
   return lds;
 }
-inline void expr_launch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, const std::vector<const U128*>& ptrs,
-                        const std::vector<uint32_t>& masks, std::vector<Fr> consts, size_t nconsts, Col out, uint32_t step,
-                        uint32_t en, size_t count) {
-  const size_t lds = expr_lds_bytes(X);
-  if (ptrs.size() != count * masks.size() || consts.size() != count * nconsts) fail(H2_EINVAL, "expr_launch: table sizes");
-  const U128* const* d_ptrs = (const U128* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
-  const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
-  for (auto& c : consts)
-    for (int t = 0; t < 5; t++) c = c + c;            // c 2^256 -> c 2^261: the kernel's working form (R' = 2^261)
-  Col d_consts = d.upload_frs(consts);
-  if (lds > 64 * 1024)                                // past 64 KiB: raised, as the MSM and NTT kernels raise theirs
-    hip_ok(hipFuncSetAttribute((const void*)pk::expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-           "hipFuncSetAttribute(expr_kernel)");
-  hipLaunchKernelGGL(pk::expr_kernel, dim3((en + pk::EXPR_BLOCK - 1) / pk::EXPR_BLOCK, (unsigned)count), dim3(pk::EXPR_BLOCK), lds,
-                     d.s, d_code, (uint32_t)X.code.size(), d_ptrs, (uint32_t)masks.size(), d_masks, d_consts, (uint32_t)nconsts, out,
-                     step, en);
-  hip_ok(hipGetLastError(), "expr_kernel");
+
+// A caller's expression DAG built through ExprProgramT's own methods and compiled as the prover compiles its quotient:
+// nn nodes of four i32 {op, a, b, x} -- op 0: constant x of `cs`; 1: column a at rotation x; 2 / 3 / 4: add / sub / mul
+// of the earlier nodes a and b; 5: variable x < n_vars -- the last node the root.  Every variable gets its own entry of
+// the constant table, ahead of the constants (var_slot, if given, receives their indices).  A column index must be below
+// n_cols.  public_rules: a root that is a leaf is multiplied by one (the test hooks refuse it, as they refuse op 5).
+template <class FP>
+inline void program_from_nodes(ExprProgramT<FP>& X, const int32_t* nd, size_t nn, const std::vector<HF<FP>>& cs, uint32_t n_cols,
+                               uint32_t n_vars, bool public_rules, std::vector<uint32_t>* var_slot) {
+  std::vector<int> var_node(n_vars);
+  for (uint32_t v = 0; v < n_vars; v++) {
+    int slot;
+    var_node[v] = X.variable(&slot);
+    if (var_slot) var_slot->push_back((uint32_t)slot);
+  }
+  std::vector<int> id(nn);
+  for (size_t i = 0; i < nn; i++) {
+    const int op = nd[4 * i], a = nd[4 * i + 1], b = nd[4 * i + 2], x = nd[4 * i + 3];
+    if (op == 0) {
+      if (x < 0 || (size_t)x >= cs.size()) fail(H2_EINVAL, "dag: no such constant");
+      id[i] = X.constant(cs[x]);
+    } else if (op == 1) {
+      if (a >= 0 && (uint32_t)a >= n_cols) fail(H2_EINVAL, "dag: no such column");
+      id[i] = X.column(a, x);                        // compile checks the operand word's column range and the rotation
+    } else if (op >= 2 && op <= 4) {
+      if (a < 0 || b < 0 || (size_t)a >= i || (size_t)b >= i) fail(H2_EINVAL, "dag: operand is not an earlier node");
+      id[i] = op == 2 ? X.add(id[a], id[b]) : op == 3 ? X.sub(id[a], id[b]) : X.mul(id[a], id[b]);
+    } else if (op == 5 && public_rules) {
+      if (x < 0 || (uint32_t)x >= n_vars) fail(H2_EINVAL, "dag: no such variable");
+      id[i] = var_node[x];
+    } else {
+      fail(H2_EINVAL, "dag: unknown op");
+    }
+  }
+  int root = id[nn - 1];
+  if (public_rules && X.nodes[root].op < 2) root = X.mul(root, X.constant(HF<FP>::one()));
+  X.compile(root);
 }
 
-// a caller's expression DAG (the test hooks h2_selftest_host what = 7 and h2_selftest_expr_run): u32 node count, u32
-// constant count, then per node four i32 {op, a, b, x} -- op 0: constant x; 1: column a at rotation x; 2 / 3 / 4: add /
-// sub / mul of the earlier nodes a and b -- then the constants, 32 canonical little-endian bytes each.  The last node
-// is the root.  Built through ExprProgram's own methods and compiled as the prover compiles its quotient.
+// the test hooks' DAG blob (h2_selftest_host what = 7 and h2_selftest_expr_run): u32 node count, u32 constant count,
+// the nodes, then the constants, 32 canonical little-endian bytes each
 inline void program_from_dag(const uint8_t* in, size_t in_len, ExprProgram& X) {
   if (!in || in_len < 8) fail(H2_EINVAL, "dag: truncated");
   uint32_t nn, nc;
@@ -212,24 +246,9 @@ inline void program_from_dag(const uint8_t* in, size_t in_len, ExprProgram& X) {
   std::vector<Fr> cs(nc);
   for (uint32_t j = 0; j < nc; j++)
     if (!Fr::from_le_bytes_canonical(in + 8 + 16 * (size_t)nn + 32 * (size_t)j, &cs[j])) fail(H2_EINVAL, "dag: constant not canonical");
-  std::vector<int> id(nn);
-  for (uint32_t i = 0; i < nn; i++) {
-    int32_t f[4];
-    memcpy(f, in + 8 + 16 * (size_t)i, 16);
-    const int op = f[0], a = f[1], b = f[2], x = f[3];
-    if (op == 0) {
-      if (x < 0 || (uint32_t)x >= nc) fail(H2_EINVAL, "dag: no such constant");
-      id[i] = X.constant(cs[x]);
-    } else if (op == 1) {
-      id[i] = X.column(a, x);                        // compile checks the column index and the rotation
-    } else if (op >= 2 && op <= 4) {
-      if (a < 0 || b < 0 || (uint32_t)a >= i || (uint32_t)b >= i) fail(H2_EINVAL, "dag: operand is not an earlier node");
-      id[i] = op == 2 ? X.add(id[a], id[b]) : op == 3 ? X.sub(id[a], id[b]) : X.mul(id[a], id[b]);
-    } else {
-      fail(H2_EINVAL, "dag: unknown op");
-    }
-  }
-  X.compile(id[nn - 1]);
+  std::vector<int32_t> nd(4 * (size_t)nn);
+  memcpy(nd.data(), in + 8, 16 * (size_t)nn);
+  program_from_nodes<BN254_FR>(X, nd.data(), nn, cs, 1u << 22, 0, false, nullptr);
 }
 
 }  // namespace product

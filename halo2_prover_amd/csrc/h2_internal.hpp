@@ -101,10 +101,22 @@ struct BasesEntry {
   size_t table_bytes;
 };
 
+// a program compiled by h2_expr_compile (h2_expr_program.hpp): host state only until a context first evaluates it
+struct ExprEntry {
+  int curve;
+  h2_expr_info_t info;
+  std::vector<uint32_t> code;         // three words per instruction (pk::XInstr)
+  std::vector<uint64_t> table;        // the constant table in the kernel's working form, 4 limbs each; variables zero
+  std::vector<uint32_t> var_slot;     // table index of each variable
+  std::vector<uint8_t> dump;          // what h2_expr_dump reports
+  std::vector<void*> d_code;          // per context: the code in HBM, uploaded by the context's first eval
+};
+
 struct Global {
   bool ready = false;
   std::vector<DevCtx> ctx;
   std::map<uint64_t, BasesEntry> bases;
+  std::map<uint64_t, ExprEntry> exprs;
   uint64_t next_handle = 1;
   bool profiling = false;
   std::string last_error;

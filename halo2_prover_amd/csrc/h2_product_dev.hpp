@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "h2_circuits.hpp"
+#include "h2_expr_program.hpp"
 #include "h2_pairing.hpp"
 #include "h2_poly.hpp"
 #include "h2_product_base.hpp"
@@ -193,6 +194,27 @@ struct Dev {
   }
   ~Dev() { release_all(); }
 };
+
+// expr_kernel over en rows of `count` proofs (grid.y = proof): one program and one set of row masks; proof p's column
+// pointers at ptrs[p masks.size() ...], its constants (c, patched for the proof) at consts[p nconsts ...], uploaded in the
+// kernel's working form c 2^261, its result at out + p en; the LDS of the slots beyond the registers is checked against
+// what one workgroup may hold before anything is uploaded or launched.  create_proofs and the test hook
+// h2_selftest_expr_run (count = 1) both launch the quotient program through here, the kernel's bn256::Fr instantiation
+// through the curve's launch table as h2_expr_eval_device launches it.
+inline void expr_launch(Dev& d, const ExprProgram& X, const pk::XInstr* d_code, const std::vector<const U128*>& ptrs,
+                        const std::vector<uint32_t>& masks, std::vector<Fr> consts, size_t nconsts, Col out, uint32_t step,
+                        uint32_t en, size_t count) {
+  const size_t lds = expr_lds_bytes(X);
+  if (ptrs.size() != count * masks.size() || consts.size() != count * nconsts) fail(H2_EINVAL, "expr_launch: table sizes");
+  const void* const* d_ptrs = (const void* const*)d.upload(ptrs.data(), ptrs.size() * sizeof(void*));
+  const uint32_t* d_masks = (const uint32_t*)d.upload(masks.data(), masks.size() * 4);
+  for (auto& c : consts)
+    for (int t = 0; t < 5; t++) c = c + c;            // c 2^256 -> c 2^261: the kernel's working form (R' = 2^261)
+  Col d_consts = d.upload_frs(consts);
+  hip_ok(d.ops->expr_launch(d_code, (uint32_t)X.code.size(), d_ptrs, (uint32_t)masks.size(), d_masks, d_consts, (uint32_t)nconsts, out,
+                            en, step, en, (uint32_t)count, lds, d.s),
+         "expr_kernel");
+}
 
 // the context an entry point works on
 inline DevCtx* the_ctx() {

@@ -461,12 +461,7 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
     } else if (what == 7) {                // a caller's DAG (program_from_dag) compiled: what 6 reports, then the
       ExprProgram X;                       // constant table (32 canonical LE bytes each; the one compile adds included)
       program_from_dag(in, in_len, X);
-      r = X.report();
-      for (auto& c : X.consts) {
-        uint8_t b[32];
-        c.to_le_bytes(b);
-        r.insert(r.end(), b, b + 32);
-      }
+      r = X.report_with_table();
     } else if (what == 8) {                // the decompression routine's host instantiation: n x 32 bytes -> n x (64 canonical
       if (in_len % 32) return H2_EINVAL;   // LE bytes x || y, one status byte)
       const CurveOps* ops = ops_of(H2_BN254);

@@ -34,6 +34,12 @@ class MsmPointsPlan(ctypes.Structure):
                 ("width", ctypes.c_uint8 * 48), ("offset", ctypes.c_uint8 * 48)]
 
 
+class ExprInfo(ctypes.Structure):
+    _fields_ = [(name, _U32) for name in ("curve", "instructions", "products", "column_reads", "slots", "constants",
+                                          "reductions", "n_cols", "n_vars", "lds_bytes")] + [
+        ("min_rot", ctypes.c_int32), ("max_rot", ctypes.c_int32)]
+
+
 SYMBOLS = {
     "h2_init": (_I, [_I]),
     "h2_init_devices": (_I, [_I, _P]),
@@ -80,6 +86,11 @@ SYMBOLS = {
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),
+    "h2_expr_compile": (_I, [_I, _P, _Z, _P, _Z, _U32, _U32, ctypes.POINTER(_U64)]),
+    "h2_expr_release": (_I, [_U64]),
+    "h2_expr_info": (_I, [_U64, ctypes.POINTER(ExprInfo)]),
+    "h2_expr_dump": (_I, [_U64, _P, _Z, ctypes.POINTER(_Z)]),
+    "h2_expr_eval_device": (_I, [_U64, _P, _P, _P, _Z, _U32, _U32, _P, _Z, _P]),
     "h2_chacha20_scalars_device": (_I, [_I, _P, _U64, _Z, _P, _P]),
     "h2_poly_inverse_device": (_I, [_I, _P, _Z, _P]),
     "h2_msm_plan": (_I, [_U64, ctypes.POINTER(MsmPlan)]),

@@ -353,6 +353,64 @@ int h2_lookup_product_device(h2_curve_t curve, const void* d_input, const void* 
                              const uint64_t beta[4], const uint64_t gamma[4], void* d_z, void* stream);
 /* rows one workgroup handles per sort pass (T above).  Host only, no h2_init needed: tests size their shapes by it. */
 int h2_lookup_tile(void);
+/* ---- expressions over resident columns: evaluate_h in one launch ---------------------------------------------------
+ * A host hands over an expression DAG once (every gate, the permutation and lookup terms, folded by y) and evaluates it
+ * on every row of the extended domain for m instances per call, over the scalar field of `curve` (all three curves).
+ * The library compiles the DAG to a straight-line program -- shared subexpressions found, ordered to need few live
+ * values, a product with one inserted where lazy magnitudes would grow too large -- and one kernel interprets it per row:
+ * no scratch column, no pass over HBM per node.
+ *
+ * Nodes: op 0 constant number x | 1 column a at rotation x | 2 add, 3 sub, 4 mul of the EARLIER nodes a and b |
+ * 5 variable number x.  The last node is the root.  halo2's Negated lowers to 0 - a, Scaled to a product with a
+ * constant; challenges (y, beta, gamma, theta, beta delta^j) are variables, set per call and instance.  A root that is a
+ * leaf is legal: the library multiplies it by one.
+ *
+ * h2_expr_compile: host only, needs neither h2_init nor a GPU, and does not recurse: a y-fold as deep as the DAG is long
+ * compiles on a small thread stack.  consts: n_consts x 4 Montgomery limbs, canonical.  The
+ * handle keeps the compiled code; every context gets a device copy at its first h2_expr_eval_device, freed by
+ * h2_expr_release or h2_shutdown (the handle itself outlives h2_shutdown).  H2_EINVAL, with the violated rule in
+ * h2_last_device_error, for: an unknown curve; a null pointer with a non-zero count; n_nodes = 0; n_nodes, n_consts
+ * or n_vars above 2^20; an operand that is not an earlier node; an unknown op; a constant, column or variable index at or beyond
+ * n_consts, n_cols, n_vars; n_cols > 2^22; a rotation outside [-128, 127]; a constant that is not canonical; a program
+ * whose live values need more LDS than one workgroup may hold (75 values: split the DAG and pass the partial result as a
+ * column of the next program).
+ * h2_expr_info: the program's counters.  h2_expr_dump: the six counters instructions, products, column reads, slots,
+ * constants, reductions (u32), the code (12 bytes per instruction), the constant table (32 canonical little-endian bytes
+ * each, zero for a variable), then n_vars u32: the table index of each variable.  *out_len receives the length; H2_EINVAL
+ * when cap is smaller.
+ *
+ * h2_expr_eval_device: for instance p < m and row i < 2^log_rows, out[p * out_stride + i] = the root's value, where
+ * column c at rotation r reads d_cols[p * n_cols + c][(i + r * rot_step) mod 2^log_len[c]] and variable v is
+ * vars[p * n_vars + v].  log_len[c] <= log_rows: a shorter column is periodic, as t_evaluations is.  With rot_step =
+ * 2^(extended_k - k) on extended columns this is one evaluate_h.  Everything is in the API form (4 x u64 Montgomery
+ * limbs); the output is canonical, written out of place, and has the same bits whatever m is.  d_cols (m * n_cols device
+ * pointers), log_len (n_cols) and vars (m * n_vars * 4 limbs) are HOST arrays, read before the call returns.
+ * Asynchronous on `stream` under h2_ntt_device's rules, on the context of the calling thread's current HIP device; the
+ * pointer table and the constant tables of the instances live in that context's scratch for the length of the call, as
+ * h2_poly_eval_device's job table does.  m > 65535 runs in groups on the same stream.
+ * H2_EINVAL, before anything is enqueued, for: log_rows > 28; log_len[c] > log_rows; out_stride < 2^log_rows,
+ * m > 2^30 or m * out_stride > 2^57; a null host array with a non-zero count; a null or not 16-byte aligned column pointer or d_out;
+ * a variable that is not canonical; a column that overlaps rows that are written (rows [0, 2^log_rows) of any instance's
+ * out_stride rows; a column inside the unwritten rows between two instances is fine).  H2_EHANDLE for an unknown handle,
+ * H2_ENOTINIT before h2_init; m = 0: H2_OK, nothing enqueued.
+ * Column CONTENTS are not checked: an element that is not canonical gives a wrong value, never an out-of-range access.
+ * Every index is formed from the row, the instruction words -- whose constant, column and slot numbers were proven
+ * against n_cols and the table sizes at compile time -- and log_len.
+ * h2_version() did not change for these entry points: a host detects them by their symbols. */
+typedef struct {
+  int32_t op, a, b, x;
+} h2_expr_node_t;
+typedef struct {
+  uint32_t curve, instructions, products, column_reads, slots, constants, reductions, n_cols, n_vars, lds_bytes;
+  int32_t min_rot, max_rot;
+} h2_expr_info_t;
+int h2_expr_compile(h2_curve_t curve, const h2_expr_node_t* nodes, size_t n_nodes, const uint64_t* consts, size_t n_consts,
+                    uint32_t n_cols, uint32_t n_vars, uint64_t* handle_out);
+int h2_expr_release(uint64_t handle);
+int h2_expr_info(uint64_t handle, h2_expr_info_t* out);
+int h2_expr_dump(uint64_t handle, uint8_t* out, size_t cap, size_t* out_len);
+int h2_expr_eval_device(uint64_t handle, const void* const* d_cols, const uint32_t* log_len, const uint64_t* vars, size_t m,
+                        uint32_t log_rows, uint32_t rot_step, void* d_out, size_t out_stride, void* stream);
 /* out[i] = Scalar::random(rng) number first_block + i of rng = ChaCha20Rng::from_seed(seed), Montgomery limbs:
  * the coefficients of the vanishing argument's random_poly (halo2_proofs src/plonk/vanishing/prover.rs
  * `Argument::commit`).  Each draw consumes one 64-byte ChaCha20 block. */

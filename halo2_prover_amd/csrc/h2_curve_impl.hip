@@ -8,6 +8,7 @@
 #include "h2_poly.hpp"
 #include "h2_group_fft.hpp"
 #include "h2_lookup.hpp"
+#include "h2_permutation.hpp"
 #include "h2_expr_kernel.hpp"
 
 #include <cstring>
@@ -235,6 +236,14 @@ hipError_t lookup_ratio(const void* d_input, const void* d_table, const void* d_
                         size_t col_stride, size_t m, const uint64_t beta[4], const uint64_t gamma[4], void* d_z, hipStream_t s) {
   return lookup_ratio_launch<FS>(d_input, d_table, d_permuted_input, d_permuted_table, u, col_stride, m, beta, gamma, d_z, s);
 }
+hipError_t perm_ratio(const PermWorkspace& w, char* base, size_t p0, size_t count, size_t u, size_t n_cols, size_t chunk_len, size_t S,
+                      const uint64_t omega[4], void* d_z, size_t col_stride, hipStream_t s) {
+  return perm_ratio_launch<FS>(w, base, p0, count, u, n_cols, chunk_len, S, omega, d_z, col_stride, s);
+}
+hipError_t perm_scan(const PermWorkspace& w, char* base, size_t p0, size_t count, size_t u, size_t S, void* d_z, size_t col_stride,
+                     hipStream_t s) {
+  return perm_scan_launch<FS>(w, base, p0, count, u, S, d_z, col_stride, s);
+}
 hipError_t expr_launch(const void* d_code, uint32_t ninstr, const void* const* d_cols, uint32_t ncols, const uint32_t* d_masks,
                        const void* d_consts, uint32_t nconsts, void* d_out, size_t out_stride, uint32_t step, uint32_t rows, uint32_t count,
                        size_t lds_bytes, hipStream_t s) {
@@ -461,7 +470,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_scan, poly_eval, lookup_permute, lookup_ratio, expr_launch, chacha20_scalars, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, poly_eval, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 
 }  // namespace

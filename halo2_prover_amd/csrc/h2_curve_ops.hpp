@@ -12,6 +12,7 @@ struct U128;
 struct MsmGeom;
 struct MsmWorkspace;
 struct LookupWorkspace;
+struct PermWorkspace;
 
 // one evaluation: the polynomial's coefficients in HBM (API form, 16-byte aligned) and the point's 8 x 32-bit
 // Montgomery limbs.  The poly_eval kernels read a table of these from HBM (h2_poly.hpp)
@@ -113,6 +114,14 @@ struct CurveOps {
   hipError_t (*lookup_ratio)(const void* d_input, const void* d_table, const void* d_permuted_input, const void* d_permuted_table,
                              size_t u, size_t col_stride, size_t m, const uint64_t beta[4], const uint64_t gamma[4], void* d_z,
                              hipStream_t s);
+  // the permutation argument's grand products (h2_permutation.hpp); w proven by perm_check, base its scratch with the tables
+  // uploaded.  perm_ratio: the ratios of `count` <= 65535 instances from p0 on into rows [0, u) of their S z columns, row u = 1
+  hipError_t (*perm_ratio)(const PermWorkspace& w, char* base, size_t p0, size_t count, size_t u, size_t n_cols, size_t chunk_len,
+                           size_t S, const uint64_t omega[4], void* d_z, size_t col_stride, hipStream_t s);
+  // perm_scan: the running product of `count` <= 256 instances from p0 on, each over its S u ratios in (set, row) order, in
+  // place; the value at every set boundary also lands in row u of the set before, the total in row u of the last.  S u > 0
+  hipError_t (*perm_scan)(const PermWorkspace& w, char* base, size_t p0, size_t count, size_t u, size_t S, void* d_z, size_t col_stride,
+                          hipStream_t s);
   // expr_kernel (h2_expr_kernel.hpp) over the scalar field: the compiled program d_code (ninstr x 12 bytes) on `rows` rows
   // of 1 <= count <= 65535 instances (grid.y).  Instance p: column pointers d_cols[p ncols ...], constants in the working
   // form d_consts + 32 (p nconsts), result at d_out + 32 (p out_stride).  d_masks: length - 1 of each column;

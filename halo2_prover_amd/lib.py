@@ -86,6 +86,8 @@ SYMBOLS = {
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),
+    "h2_permutation_product_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _Z, _P, _P, _P, _P, _P, _Z, _P]),
+    "h2_permutation_tile": (_I, []),
     "h2_expr_compile": (_I, [_I, _P, _Z, _P, _Z, _U32, _U32, ctypes.POINTER(_U64)]),
     "h2_expr_release": (_I, [_U64]),
     "h2_expr_info": (_I, [_U64, ctypes.POINTER(ExprInfo)]),

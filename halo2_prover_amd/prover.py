@@ -34,6 +34,7 @@ from . import lib as _lib
 from .api import ParamsKZG
 from . import sharded as _sharded
 from .domain import EvaluationDomain
+from .permutation import permutation_product
 
 P = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001       # bn256::Fr modulus
 Q = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47       # bn256::Fq modulus
@@ -685,24 +686,11 @@ class _Dev:
                                                        self._p(q), self.dom._stream()), "h2_poly_divide_linear_device")
         return q
 
-    def prefix_product(self, col):
-        """the column prod_{j < i} col[j] (1 in row 0)"""
-        col = col.contiguous()
-        out = self.torch.empty_like(col)
-        _lib.check(self.L.h2_poly_prefix_product_device(self.curve, self._p(col), col.shape[0], self._p(out),
-                                                        self.dom._stream()), "h2_poly_prefix_product_device")
-        return out
-
     def random_scalars(self, seed32, count):
         """`count` draws of Fr::random(ChaCha20Rng::from_seed(seed32)) as a device column"""
         t = self.torch.empty((count, 4), dtype=self.torch.int64, device="cuda")
         _lib.check(self.L.h2_chacha20_scalars_device(self.curve, seed32, 0, count, self._p(t), self.dom._stream()),
                    "h2_chacha20_scalars_device")
-        return t
-
-    def inverse_(self, t):
-        _lib.check(self.L.h2_poly_inverse_device(self.curve, self._p(t), t.numel() // 4, self.dom._stream()),
-                   "h2_poly_inverse_device")
         return t
 
     def evals(self, cols, point):
@@ -1022,30 +1010,18 @@ def _create_proof(params, pk, circuit, public_input, rng, trace, opening):
     theta, beta, gamma = tr.squeeze_challenge(), tr.squeeze_challenge(), tr.squeeze_challenge()
     trace.update(theta=theta, beta=beta, gamma=gamma)
 
-    # permutation grand products, d - 2 columns per set: per-row ratios and their running product on the device
+    # permutation grand products, d - 2 columns per set: ONE call builds every set's z on the usable rows, each set started
+    # at the last usable value of the set before it on the device (h2_permutation_product_device); the blinding rows and
+    # their draws are written here, in the order Argument::commit draws them
     values_of = {"advice": advice_values, "fixed": pk.fixed_values, "instance": instance_values}
     pcols = circuit.permutation_columns
     sets = [list(range(s, min(s + d - 2, len(pcols)))) for s in range(0, len(pcols), d - 2)]
-    gamma_col = dev.const(gamma)
-    z_cols, last_z = [], 1
-    for cols in sets:
-        num = den = None
-        for j in cols:
-            v = values_of[pcols[j][0]][pcols[j][1]]
-            vg = dev.add(v, gamma_col)
-            tn = dev.add_(dev.scale(pk.omega_col, pow(DELTA, j, P) * beta % P), vg)
-            td = dev.add_(dev.scale(pk.sigma_values[j], beta), vg)
-            num = tn if num is None else dev.mul_(num, tn)
-            den = td if den is None else dev.mul_(den, td)
-        # z[i] = last_z * prod_{j < i} ratio[j] on the usable rows: a prefix product on the device; only the 32 bytes of
-        # its last usable row come back (the next set starts from there)
-        pref = dev.prefix_product(dev.mul_(num, dev.inverse_(den)))
-        z = dev.scale(pref, last_z) if last_z != 1 else pref
-        z[n - bf:] = dev.from_ints([rng.fr_random() for _ in range(bf)])
-        last_z = last_z * dev.to_ints(pref[n - bf - 1:n - bf])[0] % P
+    z_values = permutation_product(dom, [[values_of[kind][idx] for kind, idx in pcols]],
+                                   [pk.sigma_values[j] for j in range(len(pcols))], d - 2, n - (bf + 1), [beta], [gamma],
+                                   omega, DELTA)[0]
+    for s in range(len(sets)):
+        z_values[s, n - bf:] = dev.from_ints([rng.fr_random() for _ in range(bf)])
         rng.fr_random()
-        z_cols.append(z)
-    z_values = torch.stack(z_cols)
     for pt in dev.commit(z_values, lagrange=True):
         tr.write_point(pt)
 

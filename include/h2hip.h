@@ -353,6 +353,52 @@ int h2_lookup_product_device(h2_curve_t curve, const void* d_input, const void* 
                              const uint64_t beta[4], const uint64_t gamma[4], void* d_z, void* stream);
 /* rows one workgroup handles per sort pass (T above).  Host only, no h2_init needed: tests size their shapes by it. */
 int h2_lookup_tile(void);
+/* ---- the permutation argument's grand products over resident columns, chained on the device ------------------------
+ * halo2_proofs src/plonk/permutation/prover.rs `Argument::commit` for m instances (the proofs of a batch) in one call,
+ * over the scalar field of `curve` (all three curves), columns in the API form: 4 x u64 Montgomery limbs, canonical.
+ * u = usable_rows (halo2: n - (blinding_factors + 1)); the n_cols permutation columns are cut into S = ceil(n_cols /
+ * chunk_len) sets, set s holding the columns j in [s chunk_len, min((s + 1) chunk_len, n_cols)) (halo2: chunk_len =
+ * cs.degree() - 2).  Per instance, with its own beta and gamma:
+ *   ratio_s[i] = prod_{j in set s} (v_j[i] + beta delta^j omega^i + gamma)
+ *              / prod_{j in set s} (v_j[i] + beta sigma_j[i]      + gamma)        for i < u
+ *   z_0[0] = 1;   z_s[i+1] = z_s[i] ratio_s[i]  for i < u;   z_{s+1}[0] = z_s[u]
+ * j is the column's index among ALL n_cols columns, not its position within the set.  A row whose denominator is zero has
+ * ratio 0 (batch_invert leaves zero at zero): every later row of that instance, in that set and in all later sets, is
+ * then 0; other instances are unaffected.
+ * d_values: HOST array of m * n_cols device pointers, column j of instance p at [p * n_cols + j]; d_sigma: HOST array of
+ * n_cols device pointers, the key's permutation columns in Lagrange form, shared by the instances.  Every source column
+ * has u readable rows and is 16-byte aligned; pointers may repeat, within an instance and across instances.  beta, gamma:
+ * HOST, m * 4 limbs each (one pair per instance); omega (the domain's generator), delta: HOST, 4 limbs.  All host arrays
+ * are read before the call returns.
+ * d_z: m * S output columns, column p * S + s col_stride elements after the previous one.  Rows [0, u] of every column
+ * are written, canonical; rows (u, col_stride) are NOT touched: they are the caller's blinding rows (and the RNG draws
+ * that fill them stay the caller's), as with h2_lookup_product_device.  z_{S-1}[u] = 1 when the copy constraints hold.
+ * Asynchronous on `stream` under h2_ntt_device's rules, on the context of the calling thread's current HIP device.  No
+ * host synchronisation and no device-to-host copy anywhere in the call: set s + 1 starts at the last usable value of set
+ * s, so the S columns of an instance are ONE running product over the sequence (set, row), and one scan that walks the
+ * sets in order carries the tail across them.  Four launches whatever S and n_cols are: one ratio kernel (grid: tiles of
+ * T = h2_permutation_tile() rows x S x instances; arguments -- the pointers and beta delta^j, prepared once per instance
+ * and column on the host -- from a table in HBM, so any chunk length is allowed; one Fermat inversion per run of 4 rows;
+ * omega^i from a table of the 25 powers omega^(4 2^b)), then the three launches of h2_poly_prefix_product_device's scan
+ * with element e of an instance at column e / u, row e % u, in place; the value at a set boundary also lands in row u
+ * of the set before.  The ratio kernel takes up to 65535 instances per launch, the scan 256; a wider m runs in groups on
+ * `stream`.  Results are the same bits whatever m is and however instances are grouped.
+ * Scratch comes from the context's scan arena for the length of the call: the argument table (48 bytes per instance and
+ * column, 64 per instance), the power table (800 bytes) and the scan's chunk values (256 KiB per instance of a group).
+ * Nothing is cached or kept.  The launch geometry is proven on the host before anything is enqueued (H2_EDEVICE with the
+ * violated condition in h2_last_device_error otherwise: S > 65535, m * n_cols > 2^32).
+ * m = 0 or n_cols = 0: H2_OK, nothing enqueued, nothing written.  u = 0: z_s[0] = 1 for every column.
+ * H2_EINVAL, before anything is enqueued, for: an unknown curve; chunk_len = 0 with n_cols > 0; usable_rows > 2^26;
+ * col_stride < usable_rows + 1; m * S * col_stride > 2^57; with m > 0 and n_cols > 0 a null host array, a null d_z or a
+ * d_z that is not 16-byte aligned; with usable_rows > 0 additionally a null or misaligned entry of d_values or d_sigma,
+ * or the d_z range overlapping rows [0, u) of any source column.  H2_ENOTINIT before h2_init.
+ * h2_version() did not change for these entry points: a host detects them by their symbols. */
+int h2_permutation_product_device(h2_curve_t curve, const void* const* d_values, const void* const* d_sigma, size_t n_cols,
+                                  size_t chunk_len, size_t usable_rows, size_t m, const uint64_t* beta,
+                                  const uint64_t* gamma, const uint64_t omega[4], const uint64_t delta[4], void* d_z,
+                                  size_t col_stride, void* stream);
+/* rows one workgroup of the ratio kernel covers (T above).  Host only, no h2_init needed: tests size their shapes by it. */
+int h2_permutation_tile(void);
 /* ---- expressions over resident columns: evaluate_h in one launch ---------------------------------------------------
  * A host hands over an expression DAG once (every gate, the permutation and lookup terms, folded by y) and evaluates it
  * on every row of the extended domain for m instances per call, over the scalar field of `curve` (all three curves).

@@ -10,7 +10,7 @@
 // unpacked on load; an XYZZ partial sum is 36 words (4 coordinates x 9 limbs, 144 bytes).
 #pragma once
 #include "h2_curve.hpp"
-#include "h2_field29.hpp"
+#include "h2_field29_chain.hpp"
 
 namespace h2 {
 
@@ -91,19 +91,19 @@ H2_HD Xyzz29<CV> xyzz29_from_affine(const Affine29<CV>& a) {
   return Xyzz29<CV>{a.x, fe29_norm(a.y), one, one};      // y may carry the digit's sign: store it normalised
 }
 
-// 2 * (affine point), "mdbl-2008-s-1"
-template <class CV>
+// 2 * (affine point), "mdbl-2008-s-1".  AR: the form of the products (h2_field29_chain.hpp), as in xyzz29_add_affine
+template <class CV, class AR = Fe29Compiler>
 H2_HD Xyzz29<CV> xyzz29_double_affine(const Affine29<CV>& a) {
   using F = Fe29<typename CV::Base>;
   if (a.is_identity() || fe29_is_zero_mod_p(a.y)) return Xyzz29<CV>::identity();
   const F u = fe29_norm(fe29_add(a.y, a.y));             // |u| < 2
-  const F v = fe29_sqr(u);
-  const F w = fe29_mul(u, v);
-  const F s = fe29_mul(a.x, v);
-  const F xx = fe29_sqr(a.x);
+  const F v = AR::sqr(u);
+  const F w = AR::mul(u, v);
+  const F s = AR::mul(a.x, v);
+  const F xx = AR::sqr(a.x);
   const F m = fe29_norm(fe29_add(fe29_add(xx, xx), xx)); // < 4.5
-  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sqr(m), s), s));
-  const F y3 = fe29_mul_sub(m, fe29_sub(s, x3), w, a.y);                                 // one reduction for both products
+  const F x3 = fe29_norm(fe29_sub(fe29_sub(AR::sqr(m), s), s));
+  const F y3 = AR::mul_sub(m, fe29_sub(s, x3), w, a.y);                                  // one reduction for both products
   return Xyzz29<CV>{x3, y3, v, w};
 }
 
@@ -123,26 +123,27 @@ H2_HD Xyzz29<CV> xyzz29_double(const Xyzz29<CV>& p) {
   return Xyzz29<CV>{x3, y3, fe29_mul(v, p.zz), fe29_mul(w, p.zzz)};
 }
 
-// acc + (affine q), "madd-2008-s"
-template <class CV>
+// acc + (affine q), "madd-2008-s".  AR: the form of its ten products -- the compiler's everywhere but in the accumulate
+// kernel, whose three waves per SIMD cover the latency of the single-chain form (Fe29Chain; the same limbs)
+template <class CV, class AR = Fe29Compiler>
 H2_HD Xyzz29<CV> xyzz29_add_affine(const Xyzz29<CV>& acc, const Affine29<CV>& q) {
   using F = Fe29<typename CV::Base>;
   if (q.is_identity()) return acc;
   if (acc.is_identity()) return xyzz29_from_affine(q);
-  const F u2 = fe29_mul(q.x, acc.zz);
-  const F s2 = fe29_mul(q.y, acc.zzz);
+  const F u2 = AR::mul(q.x, acc.zz);
+  const F s2 = AR::mul(q.y, acc.zzz);
   const F p = fe29_sub(u2, acc.x);                       // (-6.5, 3.5); limbs of magnitude < 2^29
   const F r = fe29_sub(s2, acc.y);                       // (-3.5, 2.5)
   if (fe29_is_zero_mod_p(p)) {
-    if (fe29_is_zero_mod_p(r)) return xyzz29_double_affine(q);
+    if (fe29_is_zero_mod_p(r)) return xyzz29_double_affine<CV, AR>(q);
     return Xyzz29<CV>::identity();
   }
-  const F pp = fe29_sqr(p);                              // 42
-  const F ppp = fe29_mul(p, pp);                         // 6.5 * 1.5
-  const F qq = fe29_mul(acc.x, pp);                      // 5 * 1.5
-  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(fe29_sqr(r), ppp), qq), qq));       // (-3, 5)
-  const F y3 = fe29_mul_sub(r, fe29_sub(qq, x3), acc.y, ppp);                            // 3.5 * 6.5 + 2 * 1.5, one reduction
-  return Xyzz29<CV>{x3, y3, fe29_mul(acc.zz, pp), fe29_mul(acc.zzz, ppp)};
+  const F pp = AR::sqr(p);                               // 42
+  const F ppp = AR::mul(p, pp);                          // 6.5 * 1.5
+  const F qq = AR::mul(acc.x, pp);                       // 5 * 1.5
+  const F x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(AR::sqr(r), ppp), qq), qq));       // (-3, 5)
+  const F y3 = AR::mul_sub(r, fe29_sub(qq, x3), acc.y, ppp);                            // 3.5 * 6.5 + 2 * 1.5, one reduction
+  return Xyzz29<CV>{x3, y3, AR::mul(acc.zz, pp), AR::mul(acc.zzz, ppp)};
 }
 
 // a + b, "add-2008-s"

@@ -35,7 +35,9 @@
 // m = acc p^-1 mod 2^29 and acc -= m p.  For p = 1 mod 2^29 (Pasta) m is acc's low 29 bits and the p[0] term is never
 // computed (acc - m only clears what the arithmetic shift drops); the top limb 2^22 is one multiply-add with a hidden
 // constant instead of a 64-bit shift and add.  What is left per column is one AND, one 64-bit shift and the one 64-bit
-// add the compiler uses to join the column's two multiply-add chains (the ISA table).
+// add the compiler uses to join the column's two multiply-add chains (the ISA table).  The two
+// kernels in which several waves share a SIMD (msm_chunk_kernel, the NTT pass) take the same products from
+// h2_field29_chain.hpp instead: one chain per column fixed in asm statements, no join, the same nine limbs.
 //
 // Conversions need no new constants: the API form x 2^256 is the R' form of x / 32, so going in is five doublings
 // in the 32-bit-limb field, and going out is one product with FP::ONE (= 2^256 mod p) read as a plain integer.
@@ -295,7 +297,9 @@ H2_HD Fe29<FP> fe29_mul_plain(const Fe29<FP>& a, const Fe29<FP>& b) {
 }
 // a b / R' rounded UP: (a b + m p) / R' in [a b / R', a b / R' + p) -- non-negative for a b >= 0.  The form of the
 // product before the subtractive one (p[0] and 2^22 terms as 64-bit adds, a negated m): where a non-negative result is
-// stored as it is (the NTT's inter-pass product) it costs less than a carry pass after the subtractive product
+// stored as it is (the NTT's inter-pass product) it costs less than a carry pass after the subtractive product.  (The
+// NTT pass itself takes it from h2_field29_chain.hpp where that form exists: there the p[0] and 2^22 terms are
+// multiply-adds of the column's one chain, 135 of them and no 64-bit add, still less than the carry pass.)
 template <class FP>
 H2_HD Fe29<FP> fe29_mul_up(const Fe29<FP>& a, const Fe29<FP>& b) {
   int64_t acc = 0;

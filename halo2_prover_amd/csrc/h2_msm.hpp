@@ -757,7 +757,8 @@ msm_chunk_kernel(const U128* __restrict__ table, const U128* const* __restrict__
       } while (e >= next);
       if (col_tables) table = col_tables[key >> log_b];
     }
-    a = xyzz29_add_affine(a, msm_fetch<CV>(table, ref));
+    // the single-chain product (h2_field29_chain.hpp): three waves per SIMD cover its latency; same limbs as everywhere
+    a = xyzz29_add_affine<CV, Fe29Chain>(a, msm_fetch<CV>(table, ref));
   }
   const bool ends_here = next == hi;
   const bool starts_here = !first || offsets[key] == lo;

@@ -73,7 +73,7 @@
 //   registers and occupancy as before the flags existed (profiles/extended_to_coeff_resources.txt).
 // LDS: 36 bytes per element in three planes (two of 16 bytes, one of 4: ds_read_b128 x 2 + ds_read_b32).
 #pragma once
-#include "h2_field29.hpp"
+#include "h2_field29_chain.hpp"
 #include "h2_ntt.hpp"
 #include <algorithm>
 
@@ -220,6 +220,9 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
                 const Fe<FP>& scale29 /* R' form, canonical; used when P.has_scale */, const NttExtend<FP>* X,
                 const NttCoeff<FP>* Y = nullptr) {
   static_assert(!(EXT && (DIV || SHR)), "the extending pass 0 neither divides nor shrinks");
+  // the products of radix4, emit and load_el: the single-chain form where it exists (the Pasta fields; four waves per
+  // SIMD cover its latency), the compiler's for BN254 -- the same limbs either way (h2_field29_chain.hpp)
+  using AR = Fe29Chain;
   extern __shared__ U128 lds[];
   const uint32_t R = 1u << P.log_r, C = 1u << P.log_c;
   const uint32_t RC = R * C;
@@ -361,7 +364,7 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
         else t = fe29_unpack(scale29);
       }
       x = negate ? fe29_sub(p32, x) : fe29_add(p32, x);
-      x = fe29_mul_up(x, t);
+      x = AR::mul_up(x, t);
       if (P.is_final) r = fe29_canonical_pack(fe29_norm(fe29_sub(x, pl)));   // a scaled final pass: canonical bytes
       else r = fe29_pack(x);
     } else {
@@ -392,7 +395,7 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
       const Fe29<FP> x = fe29_unpack(fe_load<FP>(xsrc + 2 * (size_t)si));
       const uint32_t r = si % 3;
       if (r == 0) return x;
-      return fe29_mul(x, fe29_unpack(r == 1 ? X->z1 : X->z2));
+      return AR::mul(x, fe29_unpack(r == 1 ? X->z1 : X->z2));
     } else if constexpr (DIV) {
       // the plain load times t[i & t_mask]: canonical data, a canonical constant -- EXT's product, on every element
       Fe<FP> t;
@@ -406,7 +409,7 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
       }
       const Fe29<FP> tv = fe29_unpack(t);
       const Fe29<FP> x = fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
-      return fe29_mul(x, tv);
+      return AR::mul(x, tv);
     } else {
       return fe29_unpack(fe_load<FP>(src + 2 * (((size_t)j << in_j_shift) + ((size_t)cc << in_c_shift))));
     }
@@ -415,17 +418,17 @@ ntt29_pass_body(const U128* __restrict__ in, U128* __restrict__ out, const U128*
   auto radix4 = [&](Fe29<FP>& e0, Fe29<FP>& e1, Fe29<FP>& e2, Fe29<FP>& e3, uint32_t s, uint32_t pos) {
     if (s != 0) {                        // s == 0: pos == 0, the twiddles of stage s and of the pair (e0, e2) are 1
       const Fe29<FP> ta = tw_get(pos << (P.log_r - 1 - s));
-      e1 = fe29_mul(e1, ta);
-      e3 = fe29_mul(e3, ta);
+      e1 = AR::mul(e1, ta);
+      e3 = AR::mul(e3, ta);
     }
     const uint32_t tb = pos << (P.log_r - 2 - s);
     const Fe29<FP> a0 = fe29_add(e0, e1), a1 = fe29_sub(e0, e1);
     Fe29<FP> a2 = fe29_add(e2, e3), a3 = fe29_sub(e2, e3);
-    if (s != 0) a2 = fe29_mul(a2, tw_get(tb));
+    if (s != 0) a2 = AR::mul(a2, tw_get(tb));
     // e2 - e3 of two stored values: limbs within +-2^29.  (s == 0 is the stage fused with the tile load: it runs before
     // the block's first barrier, when the LDS copy of the twiddles is still being written -- its one twiddle, the
     // fourth root of unity, comes from the table itself)
-    a3 = fe29_mul(a3, tw_get(tb + (R >> 2), s == 0));
+    a3 = AR::mul(a3, tw_get(tb + (R >> 2), s == 0));
     e0 = fe29_norm(fe29_add(a0, a2));
     e1 = fe29_norm(fe29_add(a1, a3));
     e2 = fe29_norm(fe29_sub(a0, a2));

@@ -2,6 +2,7 @@
 // device instantiations of the field / curve / 29-bit templates, the MSM workspace checks and the test knobs.  Not a compute
 // path; nothing here is called by the library itself.
 #include "h2_internal.hpp"
+#include "h2_field29_chain.hpp"
 
 #include <cstdio>
 
@@ -74,6 +75,53 @@ extern "C" int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, 
   }
   if (int rc = launched(hipGetLastError(), "selftest_fe29_kernel"); rc != H2_OK) return rc;
   H2_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
+}
+// the same operand sets through BOTH forms of the product on the device: the compiler's (h2_field29.hpp) into out_cpp, the
+// single-chain one (h2_field29_chain.hpp, as msm_chunk_kernel and the NTT pass instantiate it) into out_chain
+template <class FP>
+__global__ void __launch_bounds__(64) selftest_fe29_chain_kernel(int op, const int32_t* __restrict__ in, int32_t* __restrict__ out_cpp,
+                                                                 int32_t* __restrict__ out_chain, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fe29<FP> a[4];
+  for (int k = 0; k < 4; k++)
+    for (int l = 0; l < 9; l++) a[k].v[l] = in[36 * (size_t)i + 9 * k + l];
+  Fe29<FP> r, c;
+  switch (op) {
+    case 0: r = fe29_mul(a[0], a[1]); c = Fe29Chain::mul(a[0], a[1]); break;
+    case 1: r = fe29_sqr(a[0]); c = Fe29Chain::sqr(a[0]); break;
+    case 2: r = fe29_mul_sub(a[0], a[1], a[2], a[3]); c = Fe29Chain::mul_sub(a[0], a[1], a[2], a[3]); break;
+    default: r = fe29_mul_up(a[0], a[1]); c = Fe29Chain::mul_up(a[0], a[1]); break;
+  }
+  for (int l = 0; l < 9; l++) {
+    out_cpp[9 * (size_t)i + l] = r.v[l];
+    out_chain[9 * (size_t)i + l] = c.v[l];
+  }
+}
+extern "C" int h2_selftest_fe29_chain_device(int field, int op, const int32_t* in, int32_t* out_cpp, int32_t* out_chain, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  // the chain forms exist for the Pasta fields only (p = 1 mod 2^29)
+  if (!in || !out_cpp || !out_chain || n == 0 || n > (1u << 20) || field < 2 || field > 3 || op < 0 || op > 3) return H2_EINVAL;
+  static_assert(chain29::covers<PASTA_FP>() && chain29::covers<PASTA_FQ>(), "the Pasta fields take the chain form");
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  const size_t in_bytes = n * 36 * 4, out_bytes = n * 9 * 4;
+  ArenaLease stage(g_ctx.stage, in_bytes + 2 * out_bytes, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  int32_t* d_in = (int32_t*)g_ctx.stage.p;
+  int32_t* d_cpp = (int32_t*)((char*)g_ctx.stage.p + in_bytes);
+  int32_t* d_chain = (int32_t*)((char*)g_ctx.stage.p + in_bytes + out_bytes);
+  H2_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, g_ctx.stream));
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  if (field == 2)
+    hipLaunchKernelGGL(selftest_fe29_chain_kernel<PASTA_FP>, grid, block, 0, g_ctx.stream, op, d_in, d_cpp, d_chain, (uint32_t)n);
+  else
+    hipLaunchKernelGGL(selftest_fe29_chain_kernel<PASTA_FQ>, grid, block, 0, g_ctx.stream, op, d_in, d_cpp, d_chain, (uint32_t)n);
+  if (int rc = launched(hipGetLastError(), "selftest_fe29_chain_kernel"); rc != H2_OK) return rc;
+  H2_TRY(hipMemcpyAsync(out_cpp, d_cpp, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
+  H2_TRY(hipMemcpyAsync(out_chain, d_chain, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
   return stage.wait();
 }
 extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], const uint64_t q[8], uint64_t out[8]) {

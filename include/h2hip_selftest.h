@@ -131,6 +131,10 @@ int h2_selftest_fe29_op(int field, int op, const int32_t in[36], int32_t out[9])
 /* the same four ops through the DEVICE instantiation: n operand sets (36 limbs each, host pointer) -> n x 9 limbs,
  * one kernel launch */
 int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* out, size_t n);
+/* the same four ops through BOTH device forms of the product, Pasta fields only (field 2 or 3): out_cpp = the compiler's
+ * form (h2_field29.hpp), out_chain = the single-chain form the accumulate kernel and the NTT pass use
+ * (h2_field29_chain.hpp); n x 9 limbs each, one kernel launch.  The two must be equal limb for limb */
+int h2_selftest_fe29_chain_device(int field, int op, const int32_t* in, int32_t* out_cpp, int32_t* out_chain, size_t n);
 /* the quotient program's kernel (expr_kernel) on a caller's DAG (the format of h2_selftest_host what = 7), launched
  * as the prover launches it: ncols host columns, concatenated, column c of 2^log_len[c] elements (4 x u64, x 2^256
  * canonical) read at row (i + rot * step) & (2^log_len[c] - 1); out = the 2^log_en results (4 x u64 each, canonical);

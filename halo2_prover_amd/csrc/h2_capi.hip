@@ -481,6 +481,81 @@ int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n
   return A.release();
 }
 
+// the three by the curve's scalar field
+#define H2_BY_SCALAR_FIELD(curve, call)                          \
+  ((curve) == H2_BN254    ? call<BN254_CURVE::Scalar>            \
+   : (curve) == H2_PALLAS ? call<PALLAS_CURVE::Scalar>           \
+                          : call<VESTA_CURVE::Scalar>)
+
+// permutation_product_enqueue's tables (h2_permutation.hpp) at `out`, laid out by w: beta_p delta^j once per instance and
+// column, the challenges, and omega^(run 2^b)
+template <class FP>
+static void perm_fill_tables(const PermWorkspace& w, const void* const* d_values, const void* const* d_sigma, size_t n_cols, size_t m,
+                             const uint64_t* beta, const uint64_t* gamma, const uint64_t omega[4], const uint64_t delta[4], char* out) {
+  using H = HF<FP>;
+  PermColumn* cols = (PermColumn*)(out + w.off_columns);
+  PermChallenge* ch = (PermChallenge*)(out + w.off_challenges);
+  const H d = H::from_mont_limbs(delta);
+  for (size_t p = 0; p < m; p++) {
+    H bd = H::from_mont_limbs(beta + 4 * p);
+    memcpy(ch[p].beta, beta + 4 * p, 32);
+    memcpy(ch[p].gamma, gamma + 4 * p, 32);
+    for (size_t j = 0; j < n_cols; j++) {
+      PermColumn& c = cols[p * n_cols + j];
+      c.value = d_values[p * n_cols + j];
+      c.sigma = d_sigma[j];
+      uint64_t limbs[4];
+      bd.mont_limbs(limbs);
+      memcpy(c.beta_delta, limbs, 32);
+      bd = bd * d;
+    }
+  }
+  H pw = H::from_mont_limbs(omega);
+  for (int r = 1; r < perm_run(); r <<= 1) pw = pw.sqr();
+  for (int b = 0; b < PERM_POW_BITS; b++) {
+    uint64_t limbs[4];
+    pw.mont_limbs(limbs);
+    memcpy(out + w.off_powers + 32 * (size_t)b, limbs, 32);
+    pw = pw.sqr();
+  }
+}
+
+int permutation_product_enqueue(DevCtx& c, int curve, const void* const* d_values, const void* const* d_sigma, size_t n_cols, size_t chunk_len,
+                                size_t u, size_t m, const uint64_t* beta, const uint64_t* gamma, const uint64_t omega[4],
+                                const uint64_t delta[4], void* d_z, size_t col_stride, hipStream_t stream) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || n_cols == 0 || chunk_len == 0 || m == 0) return H2_EINVAL;
+  const size_t S = (n_cols - 1) / chunk_len + 1;
+  const size_t scan_group = std::min(m, PERM_SCAN_GROUP);
+  const PermWorkspace ws = perm_workspace(u, n_cols, S, m, scan_group);
+  if (const char* broken = perm_check(ws, u, n_cols, chunk_len, S, m, scan_group, col_stride, ws.total)) {
+    g_h2.last_error = std::string("permutation launch geometry: ") + broken;
+    return H2_EDEVICE;
+  }
+  ArenaLease A(c.div_ws, ws.total, stream);
+  if (A.rc != H2_OK) return A.rc;
+  if (const char* broken = perm_check(ws, u, n_cols, chunk_len, S, m, scan_group, col_stride, A.a.bytes)) {   // the arena the lease handed out
+    g_h2.last_error = std::string("permutation launch geometry: ") + broken;
+    return H2_EDEVICE;
+  }
+  std::vector<char> tables(ws.off_scan);
+  H2_BY_SCALAR_FIELD(curve, perm_fill_tables)(ws, d_values, d_sigma, n_cols, m, beta, gamma, omega, delta, tables.data());
+  // a pageable source: the runtime has read `tables` when the call returns (it stages the bytes or waits for the copy)
+  H2_TRY(hipMemcpyAsync(A.a.p, tables.data(), tables.size(), hipMemcpyHostToDevice, stream));
+  for (size_t p0 = 0; p0 < m; p0 += PERM_RATIO_GROUP)
+    if (int rc = launched(ops->perm_ratio(ws, (char*)A.a.p, p0, std::min(PERM_RATIO_GROUP, m - p0), u, n_cols, chunk_len, S, omega, d_z,
+                                          col_stride, stream),
+                          "perm_ratio_kernel");
+        rc != H2_OK)
+      return rc;
+  for (size_t p0 = 0; u && p0 < m; p0 += scan_group)       // the groups share the scan values: the stream runs them in order
+    if (int rc = launched(ops->perm_scan(ws, (char*)A.a.p, p0, std::min(scan_group, m - p0), u, S, d_z, col_stride, stream),
+                          "permutation scan kernels");
+        rc != H2_OK)
+      return rc;
+  return A.release();
+}
+
 }  // namespace h2
 
 namespace {
@@ -721,45 +796,6 @@ void expr_fill_tables(const ExprEntry& e, const uint64_t* vars, size_t p0, size_
     for (size_t v = 0; v < nv; v++) expr_working_form<FP>(vars + 4 * ((p0 + p) * nv + v), t + 4 * (size_t)e.var_slot[v]);
   }
 }
-
-// h2_permutation_product_device's tables (h2_permutation.hpp) at `out`, laid out by w: beta_p delta^j once per instance and
-// column, the challenges, and omega^(run 2^b)
-template <class FP>
-void perm_fill_tables(const PermWorkspace& w, const void* const* d_values, const void* const* d_sigma, size_t n_cols, size_t m,
-                      const uint64_t* beta, const uint64_t* gamma, const uint64_t omega[4], const uint64_t delta[4], char* out) {
-  using H = HF<FP>;
-  PermColumn* cols = (PermColumn*)(out + w.off_columns);
-  PermChallenge* ch = (PermChallenge*)(out + w.off_challenges);
-  const H d = H::from_mont_limbs(delta);
-  for (size_t p = 0; p < m; p++) {
-    H bd = H::from_mont_limbs(beta + 4 * p);
-    memcpy(ch[p].beta, beta + 4 * p, 32);
-    memcpy(ch[p].gamma, gamma + 4 * p, 32);
-    for (size_t j = 0; j < n_cols; j++) {
-      PermColumn& c = cols[p * n_cols + j];
-      c.value = d_values[p * n_cols + j];
-      c.sigma = d_sigma[j];
-      uint64_t limbs[4];
-      bd.mont_limbs(limbs);
-      memcpy(c.beta_delta, limbs, 32);
-      bd = bd * d;
-    }
-  }
-  H pw = H::from_mont_limbs(omega);
-  for (int r = 1; r < perm_run(); r <<= 1) pw = pw.sqr();
-  for (int b = 0; b < PERM_POW_BITS; b++) {
-    uint64_t limbs[4];
-    pw.mont_limbs(limbs);
-    memcpy(out + w.off_powers + 32 * (size_t)b, limbs, 32);
-    pw = pw.sqr();
-  }
-}
-
-// the three by the curve's scalar field
-#define H2_BY_SCALAR_FIELD(curve, call)                          \
-  ((curve) == H2_BN254    ? call<BN254_CURVE::Scalar>            \
-   : (curve) == H2_PALLAS ? call<PALLAS_CURVE::Scalar>           \
-                          : call<VESTA_CURVE::Scalar>)
 
 }  // namespace
 
@@ -1360,35 +1396,8 @@ int h2_permutation_product_device(h2_curve_t curve, const void* const* d_values,
       if (!src || ((uintptr_t)src & 15) || lookup_overlap(z, lookup_range(src, u, u, 1))) return H2_EINVAL;
     }
   }
-  const size_t scan_group = std::min(m, PERM_SCAN_GROUP);
-  const PermWorkspace ws = perm_workspace(u, n_cols, S, m, scan_group);
-  if (const char* broken = perm_check(ws, u, n_cols, chunk_len, S, m, scan_group, col_stride, ws.total)) {
-    g_h2.last_error = std::string("permutation launch geometry: ") + broken;
-    return H2_EDEVICE;
-  }
-  ArenaLease A(k.c->div_ws, ws.total, k.stream);
-  if (A.rc != H2_OK) return A.rc;
-  if (const char* broken = perm_check(ws, u, n_cols, chunk_len, S, m, scan_group, col_stride, A.a.bytes)) {   // the arena the lease handed out
-    g_h2.last_error = std::string("permutation launch geometry: ") + broken;
-    return H2_EDEVICE;
-  }
-  std::vector<char> tables(ws.off_scan);
-  H2_BY_SCALAR_FIELD(curve, perm_fill_tables)(ws, d_values, d_sigma, n_cols, m, beta, gamma, omega, delta, tables.data());
-  // a pageable source: the runtime has read `tables` when the call returns (it stages the bytes or waits for the copy)
-  H2_TRY(hipMemcpyAsync(A.a.p, tables.data(), tables.size(), hipMemcpyHostToDevice, k.stream));
-  const CurveOps* ops = ops_of((int)curve);
-  for (size_t p0 = 0; p0 < m; p0 += PERM_RATIO_GROUP)
-    if (int rc = launched(ops->perm_ratio(ws, (char*)A.a.p, p0, std::min(PERM_RATIO_GROUP, m - p0), u, n_cols, chunk_len, S, omega, d_z,
-                                          col_stride, k.stream),
-                          "perm_ratio_kernel");
-        rc != H2_OK)
-      return rc;
-  for (size_t p0 = 0; u && p0 < m; p0 += scan_group)       // the groups share the scan values: the stream runs them in order
-    if (int rc = launched(ops->perm_scan(ws, (char*)A.a.p, p0, std::min(scan_group, m - p0), u, S, d_z, col_stride, k.stream),
-                          "permutation scan kernels");
-        rc != H2_OK)
-      return rc;
-  return A.release();
+  return permutation_product_enqueue(*k.c, (int)curve, d_values, d_sigma, n_cols, chunk_len, u, m, beta, gamma, omega, delta, d_z, col_stride,
+                                     k.stream);
 }
 
 // ---- expressions over resident columns --------------------------------------------------------------------------------

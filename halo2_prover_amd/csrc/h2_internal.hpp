@@ -243,6 +243,13 @@ int poly_eval_enqueue(DevCtx& c, int curve, const void* const* d_polys, size_t n
 int extended_to_coeff_enqueue(DevCtx& c, int curve, const void* d_ext, uint32_t ext_log_n, size_t m,
                               const uint64_t ext_omega_inv[4], const uint64_t scale[4], const uint64_t zeta_inv[4], const void* d_t,
                               size_t t_period, void* d_out, size_t out_len, size_t out_stride, hipStream_t stream);
+// permutation::Argument::commit's grand products (h2_permutation_product_device; pointers, alignment and overlap checked by
+// the caller, n_cols >= 1, chunk_len >= 1, m >= 1): every launch bound proven first (H2_EDEVICE and last_error otherwise),
+// the tables (h2_permutation.hpp) in one upload and the scan values in c.div_ws for the length of the call.  d_values,
+// d_sigma, beta and gamma are host arrays, read before the call returns
+int permutation_product_enqueue(DevCtx& c, int curve, const void* const* d_values, const void* const* d_sigma, size_t n_cols,
+                                size_t chunk_len, size_t u, size_t m, const uint64_t* beta, const uint64_t* gamma, const uint64_t omega[4],
+                                const uint64_t delta[4], void* d_z, size_t col_stride, hipStream_t stream);
 int msm_common_checks(int curve, uint64_t handle, size_t first, size_t n, size_t m, const BasesEntry** be);
 
 #define H2_TRY(call)                                        \

@@ -152,8 +152,8 @@ struct Dev {
       accumulate = true;
     }
   }
-  // mode 0: q_j = (a_j - a_j(z_j)) / (X - z_j); mode 1: out_j[i] = prod_{t < i} a_j[t] -- all jobs in one launch sequence
-  void scan_batch(int mode, uint32_t n, const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
+  // q_j = (a_j - a_j(z_j)) / (X - z_j) -- all jobs in one launch sequence
+  void scan_batch(uint32_t n, const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
     for (size_t j0 = 0; j0 < in.size(); j0 += SCAN_MAX_JOBS) {
       const size_t cnt = std::min<size_t>(SCAN_MAX_JOBS, in.size() - j0);
       const void* a[SCAN_MAX_JOBS];
@@ -162,35 +162,57 @@ struct Dev {
       for (size_t j = 0; j < cnt; j++) {
         a[j] = in[j0 + j];
         o[j] = out[j0 + j];
-        if (mode == 0) limbs(z[j0 + j], zl[j]);
+        limbs(z[j0 + j], zl[j]);
       }
       void* ws = alloc(cnt * SCAN_WS_BYTES);
-      hip_ok(ops->poly_scan(mode, a, o, mode == 0 ? zl[0] : nullptr, (uint32_t)cnt, n, ws, s), "poly_scan");
+      hip_ok(ops->poly_scan(0, a, o, zl[0], (uint32_t)cnt, n, ws, s), "poly_scan");
       release(ws);
     }
   }
-  // values of `jobs` = (polynomial, point) pairs, all polynomials of n coefficients
+  // values of `jobs` = (polynomial, point) pairs, all polynomials of n coefficients: one job table, one read-back
   std::vector<Fr> evaluate(const std::vector<std::pair<Col, Fr>>& jobs, uint32_t n) {
     if (jobs.empty()) return {};
-    std::vector<pk::EvalJob> hj(jobs.size());
+    std::vector<const void*> polys(jobs.size());
+    std::vector<uint64_t> points(4 * jobs.size());
     for (size_t i = 0; i < jobs.size(); i++) {
-      hj[i].poly = jobs[i].first;
-      hj[i].point = jobs[i].second.v;
+      polys[i] = jobs[i].first;
+      limbs(jobs[i].second, points.data() + 4 * i);
     }
-    const pk::EvalJob* dj = (const pk::EvalJob*)upload(hj.data(), hj.size() * sizeof(pk::EvalJob));
-    const uint32_t threads = (n + pk::EVAL_RUN - 1) / pk::EVAL_RUN;
-    const uint32_t blocks = (threads + pk::EVAL_BLOCK - 1) / pk::EVAL_BLOCK;
-    Col partial = col((size_t)blocks * jobs.size());
     Col out = col(jobs.size());
-    hipLaunchKernelGGL(pk::poly_eval_partial_kernel, dim3(blocks, (unsigned)jobs.size()), dim3(pk::EVAL_BLOCK), 0, s, dj, n,
-                       partial, blocks);
-    hipLaunchKernelGGL(pk::poly_eval_final_kernel, dim3((unsigned)((jobs.size() + 63) / 64)), dim3(64), 0, s, partial, blocks,
-                       out, (uint32_t)jobs.size());
-    hip_ok(hipGetLastError(), "poly_eval kernels");
+    st_ok(poly_eval_enqueue(*c, H2_BN254, polys.data(), n, points.data(), jobs.size(), out, s), "poly_eval_enqueue");
     std::vector<Fr> v = download_frs(out, jobs.size());
-    release(partial);
     release(out);
     return v;
+  }
+  // m extended columns (2^ext_log_n values on the coset zeta <ext_omega>, read only) -> the first out_len coefficients of
+  // each, contiguous in `out`: the inverse transform scaled by `scale`, the coset shift undone and the cut in one call
+  void to_coeff(Col ext, uint32_t ext_log_n, size_t m, const Fr& ext_omega_inv, const Fr& scale, const Fr& zeta_inv, Col out,
+                size_t out_len) {
+    uint64_t w[4], sc[4], zi[4];
+    limbs(ext_omega_inv, w);
+    limbs(scale, sc);
+    limbs(zeta_inv, zi);
+    st_ok(extended_to_coeff_enqueue(*c, H2_BN254, ext, ext_log_n, m, w, sc, zi, nullptr, 0, out, out_len, out_len, s),
+          "extended_to_coeff_enqueue");
+  }
+  // the permutation argument's grand products of m proofs (h2_permutation.hpp): proof p's n_cols columns at
+  // values[p n_cols ...], cut into sets of chunk_len; rows [0, u] of its sets' z columns at z + (p S + set) n, chained on the
+  // device
+  void permutation_products(const std::vector<const void*>& values, const std::vector<const void*>& sigma, size_t chunk_len, uint32_t u,
+                            const std::vector<Fr>& beta, const std::vector<Fr>& gamma, const Fr& omega, const Fr& delta, Col z,
+                            uint32_t n) {
+    const size_t m = beta.size();
+    std::vector<uint64_t> b(4 * m), g(4 * m);
+    for (size_t p = 0; p < m; p++) {
+      limbs(beta[p], b.data() + 4 * p);
+      limbs(gamma[p], g.data() + 4 * p);
+    }
+    uint64_t w[4], dl[4];
+    limbs(omega, w);
+    limbs(delta, dl);
+    st_ok(permutation_product_enqueue(*c, H2_BN254, values.data(), sigma.data(), sigma.size(), chunk_len, u, m, b.data(), g.data(), w, dl,
+                                      z, n, s),
+          "permutation_product_enqueue");
   }
   ~Dev() { release_all(); }
 };

@@ -165,14 +165,12 @@ struct Proving {
   // where its tables sit, how many jobs); run() uploads the tables ONCE and issues the records in order against that one
   // buffer (an upload per table cost one Collatz proof ~50 us against arguments passed by value)
   struct Steps {
-    enum Kind { LINCOMB, SCALE, SUB_PREFIX, SCAN, PERM_RATIO, BLINDS };
+    enum Kind { LINCOMB, SCALE, SUB_PREFIX, SCAN, BLINDS };
     struct Step {
       Kind kind;
       size_t a = 0, b = 0;                      // offsets of the step's tables
       unsigned count = 0;                       // jobs (grid.y)
-      Col col = nullptr;                        // PERM_RATIO: the ratio columns
-      int mode = 0;                             // SCAN: Dev::scan_batch's arguments
-      std::vector<Col> in, out;
+      std::vector<Col> in, out;                 // SCAN: Dev::scan_batch's arguments
       std::vector<Fr> z;
     };
     Proving& B;
@@ -223,15 +221,12 @@ struct Proving {
       if (!jobs.empty()) add(SUB_PREFIX, put(jobs), put_frs(table), jobs.size());
     }
     // Dev::scan_batch in its place among the steps (its arguments travel by value, eight jobs a launch)
-    void scan(int mode, const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
+    void scan(const std::vector<Col>& in, const std::vector<Col>& out, const std::vector<Fr>& z) {
       Step& st = add(SCAN, 0, 0, in.size());
-      st.mode = mode;
       st.in = in;
       st.out = out;
       st.z = z;
     }
-    // every (proof, set)'s ratio column, grid.y = column
-    void perm_ratio(const std::vector<pk::PermArgs>& args, Col ratio) { add(PERM_RATIO, put(args), 0, args.size()).col = ratio; }
     // the blinding rows (bf each) of the `columns` permutation products
     void blinds(const std::vector<Fr>& values, size_t columns) { add(BLINDS, put_frs(values), 0, columns); }
     void run() {
@@ -252,11 +247,7 @@ struct Proving {
                    (const pk::SubPrefixJob*)(t + st.a), (const U128*)(t + st.b));
             break;
           case SCAN:
-            B.d.scan_batch(st.mode, n, st.in, st.out, st.z);
-            break;
-          case PERM_RATIO:
-            launch("perm_ratio_kernel", pk::perm_ratio_kernel, dim3((n / pk::PERM_RUN + 255) / 256 + 1, st.count),
-                   dim3(256), s, (const pk::PermArgs*)(t + st.a), B.K.omega_col, st.col, n);
+            B.d.scan_batch(n, st.in, st.out, st.z);
             break;
           case BLINDS:
             B.copy_strided(B.z_values + 2 * (size_t)(n - B.bf), (size_t)n * 32, t + st.a, (size_t)B.bf * 32, (size_t)B.bf * 32,
@@ -327,59 +318,29 @@ struct Proving {
     return column(instance_values, p * ni + (size_t)cr.second, n);
   }
 
-  // permutation grand products: every (proof, set)'s ratio column in one launch, the prefix products eight to a launch,
-  // one read-back of the N nz tails
+  // permutation grand products: rows [0, u = n - bf - 1] of every (proof, set)'s z column by one call whose scan walks a
+  // proof's sets in order (key_shape cuts the columns into consecutive sets of deg - 2, the call's chunks, so set s of
+  // proof p is column p nz + s of z_values); then the blinding rows, drawn proof by proof and set by set
   void permutation_products() {
     if (nz) {
-      const size_t m = N * nz;
-      Col ratio = d.col(m * (size_t)n);
-      std::vector<pk::PermArgs> args(m);
+      std::vector<const void*> values(N * np), sigma(np);
+      std::vector<Fr> beta(N), gamma(N);
+      for (size_t j = 0; j < np; j++) sigma[j] = column(K.sigma_values, j, n);
+      for (size_t p = 0; p < N; p++) {
+        for (size_t j = 0; j < np; j++) values[p * np + j] = values_of(p, K.circuit->permutation_columns[j]);
+        beta[p] = proofs[p].beta;
+        gamma[p] = proofs[p].gamma;
+      }
+      d.permutation_products(values, sigma, (size_t)(deg - 2), n - (uint32_t)bf - 1, beta, gamma, D.omega, delta, z_values, n);
+      std::vector<Fr> blinds;
       for (size_t p = 0; p < N; p++)
         for (size_t si = 0; si < nz; si++) {
-          pk::PermArgs& A = args[p * nz + si];
-          A.ncols = (int)K.sets[si].size();
-          if (A.ncols > pk::PERM_MAX_COLS) fail(H2_EINVAL, "permutation set too wide");
-          for (int t = 0; t < A.ncols; t++) {
-            const int j = K.sets[si][t];
-            A.value[t] = values_of(p, K.circuit->permutation_columns[j]);
-            A.sigma[t] = K.sigma_values + 2 * (size_t)j * n;
-            A.beta_delta[t] = (proofs[p].beta * delta.pow_u64((uint64_t)j)).v;
-          }
-          A.beta = proofs[p].beta.v;
-          A.gamma = proofs[p].gamma.v;
-        }
-      Steps ratios(*this);
-      ratios.perm_ratio(args, ratio);
-      {
-        std::vector<Col> in, out;
-        for (size_t q = 0; q < m; q++) {
-          in.push_back(column(ratio, q, n));
-          out.push_back(column(z_values, q, n));
-        }
-        ratios.scan(1, in, out, {});
-      }
-      ratios.run();
-      // the products over the usable rows (row n - bf - 1 of every prefix column): one strided gather, one copy back
-      Col tails_d = d.col(m);
-      copy_strided(tails_d, 32, z_values + 2 * (size_t)(n - bf - 1), (size_t)n * 32, 32, m);
-      const std::vector<Fr> tails = d.download_frs(tails_d, m);
-      // z_i = (prod_{s < i} tail_s) * prefix_i, then the blinding rows, drawn proof by proof and set by set
-      std::vector<pk::ScaleJob> scales;
-      std::vector<Fr> blinds;
-      for (size_t p = 0; p < N; p++) {
-        Fr last_z = Fr::one();
-        for (size_t si = 0; si < nz; si++) {
-          if (!(last_z == Fr::one())) scales.push_back({column(z_values, p * nz + si, n), last_z.v});
           for (int t = 0; t < bf; t++) blinds.push_back(items[p].rng.fr_random());
-          last_z = last_z * tails[p * nz + si];
           (void)items[p].rng.fr_random();
         }
-      }
       Steps finish(*this);
-      finish.scale(scales);
-      if (bf) finish.blinds(blinds, m);
+      if (bf) finish.blinds(blinds, N * nz);
       finish.run();
-      d.release(ratio);
     }
     trace.mark("grand products built");
   }
@@ -467,11 +428,9 @@ struct Proving {
     }
     d.release(ext);
     // extended -> coefficients: inverse NTT with 1 / 2^ext_k, un-shift the coset, keep n (deg - 1) coefficients a proof
-    d.ntt(h_ext, N, D.ext_omega_inv, D.ext_k, &D.en_inv);
     const uint32_t hlen = n * (uint32_t)(deg - 1);
     h_pieces = d.col(N * (size_t)hlen);
-    launch("coset_shrink_kernel", pk::coset_shrink_kernel, dim3((hlen + 255) / 256, (unsigned)N), dim3(256), d.s, h_ext,
-           (size_t)en, h_pieces, (size_t)hlen, hlen, D.zeta_inv.v, D.zeta_inv.sqr().v);
+    d.to_coeff(h_ext, D.ext_k, N, D.ext_omega_inv, D.en_inv, D.zeta_inv, h_pieces, hlen);
     d.release(h_ext);
     trace.mark("quotients enqueued");
     const std::vector<G1> pts = commit(d, P, h_pieces, n, N * (size_t)(deg - 1), false);
@@ -575,7 +534,7 @@ struct Proving {
     }
     Steps steps(*this);
     steps.lincomb(accs_of);
-    steps.scan(0, in, out, points);
+    steps.scan(in, out, points);
     steps.run();
     const std::vector<G1> pts = commit(d, P, witnesses, n, m, false);
     for (size_t p = 0; p < N; p++)
@@ -624,7 +583,7 @@ struct Proving {
           z.push_back(pts[t]);
           std::swap(src[p], dst[p]);
         }
-        first.scan(0, in, out, z);
+        first.scan(in, out, z);
       }
       Lincombs into_h;
       for (size_t p = 0; p < N; p++) {
@@ -659,7 +618,7 @@ struct Proving {
     Steps second(*this);
     second.lincomb(ls);
     second.sub_prefix(accs, lconsts);
-    second.scan(0, accs, quos, us);
+    second.scan(accs, quos, us);
     second.scale(scales);
     second.run();
     const std::vector<G1> pts = commit(d, P, quo, n, N, false);

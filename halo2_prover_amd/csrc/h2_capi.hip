@@ -1271,6 +1271,141 @@ int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs, size_t n, const uint6
   return stage.wait();
 }
 
+// ---- linear combinations of resident columns with linear factors divided out (h2_poly.hpp) -----------------------------
+int h2_poly_lincomb_max_rounds(void) { return POLY_LINCOMB_MAX_ROUNDS; }
+
+static_assert(sizeof(h2_lincomb_term_t) == sizeof(LincombTerm) && sizeof(h2_lincomb_job_t) == sizeof(LincombJob) &&
+                  offsetof(h2_lincomb_term_t, coeff) == offsetof(LincombTerm, coeff) &&
+                  offsetof(h2_lincomb_job_t, first_term) == offsetof(LincombJob, first_term),
+              "the kernels read the C ABI's tables as they are");
+
+// The overlaps h2_poly_lincomb_device rules out, every column n * 32 bytes long: an output against another job's output,
+// against another job's source, and against its own job's sources (an exact alias allowed when the job divides nothing)
+static bool lincomb_overlaps(const h2_lincomb_job_t* jobs, size_t n_jobs, const h2_lincomb_term_t* terms, size_t n) {
+  const uintptr_t len = (uintptr_t)n * 32;
+  std::vector<std::pair<uintptr_t, size_t>> src, out;      // (first byte, job)
+  for (size_t j = 0; j < n_jobs; j++) {
+    out.emplace_back((uintptr_t)jobs[j].d_out, j);
+    for (uint32_t t = 0; t < jobs[j].n_terms; t++) src.emplace_back((uintptr_t)terms[jobs[j].first_term + t].d_poly, j);
+  }
+  std::sort(out.begin(), out.end());
+  for (size_t a = 1; a < out.size(); a++)
+    if (out[a].first - out[a - 1].first < len) return true;
+  std::sort(src.begin(), src.end());
+  src.erase(std::unique(src.begin(), src.end()), src.end());
+  for (const auto& o : out) {
+    // sources that start in (o - len, o + len)
+    auto it = std::lower_bound(src.begin(), src.end(), std::make_pair(o.first >= len ? o.first - len + 1 : (uintptr_t)0, (size_t)0));
+    for (; it != src.end() && it->first < o.first + len; ++it) {
+      if (it->second != o.second) return true;
+      if (jobs[o.second].n_points > 0 || it->first != o.first) return true;
+    }
+  }
+  return false;
+}
+
+int h2_poly_lincomb_device(h2_curve_t curve, const h2_lincomb_job_t* jobs, size_t n_jobs, const h2_lincomb_term_t* terms,
+                           size_t n_terms, const uint64_t* low, size_t n_low, const uint64_t* points, size_t n_points, size_t n,
+                           void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || n > POLY_LINCOMB_MAX_N) return H2_EINVAL;
+  if (n_jobs == 0) return H2_OK;
+  if (!jobs || n_jobs > ((size_t)1 << 31) || n_terms > ((size_t)1 << 31) || n_low > ((size_t)1 << 31)) return H2_EINVAL;
+  size_t dividing = 0;
+  for (size_t j = 0; j < n_jobs; j++) {
+    const h2_lincomb_job_t& J = jobs[j];
+    if ((uint64_t)J.first_term + J.n_terms > n_terms || (uint64_t)J.first_low + J.n_low > n_low ||
+        (uint64_t)J.first_point + J.n_points > n_points)
+      return H2_EINVAL;
+    if (J.n_low > n || J.n_points > (uint32_t)POLY_LINCOMB_MAX_ROUNDS) return H2_EINVAL;
+    if ((J.n_terms && !terms) || (J.n_low && !low) || (J.n_points && !points)) return H2_EINVAL;
+    if (!J.d_out || ((uintptr_t)J.d_out & 15)) return H2_EINVAL;
+    for (uint32_t t = 0; t < J.n_terms; t++) {
+      const void* p = terms[J.first_term + t].d_poly;
+      if (!p || ((uintptr_t)p & 15)) return H2_EINVAL;
+    }
+    dividing += J.n_points > 0;
+  }
+  if (n == 0) return H2_OK;
+  if (lincomb_overlaps(jobs, n_jobs, terms, n)) return H2_EINVAL;
+
+  // A group is a run of consecutive jobs: at most 65535 (grid.y), and as many dividing jobs as keep their intermediate
+  // columns under POLY_LINCOMB_WS_CAP (always at least one).  The groups share the scratch: the stream runs them in order
+  const size_t col_bytes = h2_align256(n * 32);
+  const size_t cols_cap = std::min(std::max<size_t>(1, POLY_LINCOMB_WS_CAP / col_bytes), std::max<size_t>(1, dividing));
+  const size_t off_terms = h2_align256(n_jobs * sizeof(LincombJob));
+  const size_t off_low = off_terms + h2_align256(n_terms * sizeof(LincombTerm));
+  const size_t off_cols = off_low + h2_align256(n_low * 32);
+  const size_t off_scan = off_cols + (dividing ? cols_cap * col_bytes : 0);
+  ArenaLease A(k.c->div_ws, off_scan + (dividing ? SCAN_MAX_JOBS * SCAN_WS_BYTES : 0), k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  char* base = (char*)A.a.p;
+
+  // the tables in one upload; a job's entry names the first column it writes: d_out, or its intermediate column when an
+  // odd number of divisions follows (kate_division is out of place: the rounds alternate, the last one lands in d_out)
+  std::vector<char> host(off_cols, 0);
+  LincombJob* hj = (LincombJob*)host.data();
+  std::vector<void*> scratch_of(n_jobs, nullptr);
+  std::vector<size_t> group_end;
+  for (size_t j = 0, g0 = 0, used = 0; j < n_jobs; j++) {
+    const bool div = jobs[j].n_points > 0;
+    if (j - g0 == 65535 || (div && used == cols_cap)) {
+      group_end.push_back(j);
+      g0 = j;
+      used = 0;
+    }
+    memcpy(&hj[j], &jobs[j], sizeof(LincombJob));
+    if (div) {
+      scratch_of[j] = base + off_cols + used++ * col_bytes;
+      if (jobs[j].n_points & 1) hj[j].out = scratch_of[j];
+    }
+  }
+  group_end.push_back(n_jobs);
+  if (n_terms) memcpy(host.data() + off_terms, terms, n_terms * sizeof(LincombTerm));
+  if (n_low) memcpy(host.data() + off_low, low, n_low * 32);
+  // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
+  H2_TRY(hipMemcpyAsync(base, host.data(), off_cols, hipMemcpyHostToDevice, k.stream));
+
+  const CurveOps* ops = ops_of((int)curve);
+  for (size_t g = 0, j0 = 0; g < group_end.size(); j0 = group_end[g++]) {
+    const size_t j1 = group_end[g];
+    if (int rc = launched(ops->poly_lincomb((const LincombJob*)base + j0, (uint32_t)(j1 - j0), (const LincombTerm*)(base + off_terms),
+                                            base + off_low, n, k.stream),
+                          "poly_lincomb_kernel");
+        rc != H2_OK)
+      return rc;
+    // round r of every job that divides by more than r points, SCAN_MAX_JOBS side by side
+    for (uint32_t r = 0; r < (uint32_t)POLY_LINCOMB_MAX_ROUNDS; r++) {
+      const void* src[SCAN_MAX_JOBS];
+      void* dst[SCAN_MAX_JOBS];
+      uint64_t z[4 * SCAN_MAX_JOBS];
+      uint32_t cnt = 0;
+      bool any = false;
+      auto flush = [&]() -> int {
+        if (cnt == 0) return H2_OK;
+        const int rc = launched(ops->poly_scan(0, src, dst, z, cnt, n, base + off_scan, k.stream), "poly_scan kernels");
+        cnt = 0;
+        return rc;
+      };
+      for (size_t j = j0; j < j1; j++) {
+        const uint32_t P = jobs[j].n_points;
+        if (P <= r) continue;
+        any = true;
+        // the column before round r and the one after it: d_out when an even number of rounds is still to come
+        src[cnt] = ((P - r) & 1) ? scratch_of[j] : jobs[j].d_out;
+        dst[cnt] = ((P - r - 1) & 1) ? scratch_of[j] : jobs[j].d_out;
+        memcpy(z + 4 * cnt, points + 4 * ((size_t)jobs[j].first_point + r), 32);
+        if (++cnt == SCAN_MAX_JOBS)
+          if (int rc = flush(); rc != H2_OK) return rc;
+      }
+      if (int rc = flush(); rc != H2_OK) return rc;
+      if (!any) break;
+    }
+  }
+  return A.release();
+}
+
 // ---- the lookup argument's permute and product steps (h2_lookup.hpp) ------------------------------------------------
 int h2_lookup_tile(void) { return (int)LOOKUP_TILE; }
 

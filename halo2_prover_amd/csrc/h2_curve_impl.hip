@@ -228,6 +228,13 @@ hipError_t poly_eval(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d
                      (const U128*)partial, tiles, (U128*)d_out);
   return hipGetLastError();
 }
+hipError_t poly_lincomb(const LincombJob* d_jobs, uint32_t jobs, const LincombTerm* d_terms, const void* d_low, size_t n,
+                        hipStream_t s) {
+  if (jobs == 0 || jobs > 65535 || n == 0 || n > POLY_LINCOMB_MAX_N) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(poly_lincomb_kernel<FS>, dim3((unsigned)((n + POLY_LINCOMB_THREADS - 1) / POLY_LINCOMB_THREADS), jobs),
+                     dim3(POLY_LINCOMB_THREADS), 0, s, d_jobs, d_terms, (const U128*)d_low, n);
+  return hipGetLastError();
+}
 hipError_t lookup_permute(const void* d_input, const void* d_table, size_t col_stride, const LookupWorkspace& ws, char* ws_base,
                           void* d_permuted_input, void* d_permuted_table, uint32_t* d_status, hipStream_t s) {
   return lookup_permute_launch<FS>(d_input, d_table, col_stride, ws, ws_base, d_permuted_input, d_permuted_table, d_status, s);
@@ -470,7 +477,7 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_scan, poly_eval, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
 
 }  // namespace

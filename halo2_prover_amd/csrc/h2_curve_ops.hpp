@@ -21,6 +21,19 @@ struct PolyEvalJob {
   uint32_t point[8];
 };
 
+// one term and one job of poly_lincomb (h2_poly.hpp), laid out as h2_lincomb_term_t / h2_lincomb_job_t of the C ABI: the
+// column in HBM (API form, 16-byte aligned) and its coefficient's 8 x 32-bit Montgomery limbs; the job's output and its
+// ranges in the term table and the table of low coefficients (the kernel does not read the points)
+struct LincombTerm {
+  const void* poly;
+  uint32_t coeff[8];
+};
+struct LincombJob {
+  void* out;
+  uint32_t first_term, n_terms, first_low, n_low, first_point, n_points;
+};
+static_assert(sizeof(LincombTerm) == 40 && sizeof(LincombJob) == 32, "the C ABI's layout");
+
 struct CurveOps {
   int curve_id;
   int scalar_field_id;
@@ -106,6 +119,10 @@ struct CurveOps {
   // d_out[t] = sum_{i < n} poly_t[i] point_t^i for the 1 <= jobs <= 65535 entries of the table d_jobs (grid.y = job),
   // 1 <= n <= 2^30 coefficients each; d_ws: poly_eval_ws_bytes(jobs, n), 16-byte aligned (h2_poly.hpp); three launches
   hipError_t (*poly_eval)(const PolyEvalJob* d_jobs, uint32_t jobs, size_t n, void* d_ws, void* d_out, hipStream_t s);
+  // out_j[i] = sum_t coeff_t poly_t[i] - (i < n_low_j ? d_low[first_low_j + i] : 0) for i < n and the 1 <= jobs <= 65535
+  // entries of the table d_jobs (grid.y = job), their terms in the table d_terms; 1 <= n <= 2^30; one launch
+  hipError_t (*poly_lincomb)(const LincombJob* d_jobs, uint32_t jobs, const LincombTerm* d_terms, const void* d_low, size_t n,
+                             hipStream_t s);
   // permute_expression_pair of ws.mm lookups of ws.u rows (h2_lookup.hpp): inputs and tables col_stride elements apart, ws
   // proven by lookup_check, ws_base its scratch; d_status (ws.mm words) zeroed by the caller
   hipError_t (*lookup_permute)(const void* d_input, const void* d_table, size_t col_stride, const LookupWorkspace& ws, char* ws_base,

@@ -449,6 +449,64 @@ poly_eval_fold_kernel(uint32_t njobs, const int32_t* __restrict__ powers, const 
   fe_store<FP>(out + 2 * (size_t)job, fe29_to_api(acc));
 }
 
+// ---- linear combinations of resident columns: out_j[i] = sum_t c_t a_t[i] - low_j[i], grid.y = job -------------------------
+// The column work of the multiopen argument (halo2_proofs @6b43b6b src/poly/kzg/multiopen/{gwc,shplonk}/prover.rs: the
+// v-power sum of the polynomials opened at one point, the y-power sum of a rotation set minus its remainder, the final
+// L(X)) and the join of the quotient pieces h(X) = sum x^(n i) h_i(X) in front of it (src/plonk/vanishing/prover.rs
+// `Constructed::evaluate`).  One thread per row; jobs and terms come from tables in HBM (uniform per workgroup: scalar
+// loads), so any number of terms is one launch.  The divisions that follow a sum are the scan kernels above, mode 0.
+//
+// On the 9 x 29-bit lazy form, the data never converted (as in the scan's mode 0): a column element in HBM is the integer
+// d = x 2^256 mod p, plain-unpacked; the coefficient goes through expr_column_operand, the integer c' = c 2^261 + j p in
+// (-16 p, 16 p); fe29_mul(d, c') = d c' / R' is x c 2^256 mod p, the API form of the term, in (-9p/8, p/8] with
+// normalised limbs.  Magnitudes, in units of p (R' = 2^261 > 128 p):
+//   * two terms are added to the normalised sum limb-wise (limbs below 3 * 2^29 < 2^31) and one carry pass follows;
+//   * every POLY_LINCOMB_FOLD = 32 terms the sum is multiplied by the working form of one (2^261 mod p, canonical): the
+//     value is unchanged mod p and falls below |acc| / 128 + p.  Between folds |acc| < 1.4 p + 32 * 9p/8 < 38 p: the top
+//     limb stays below 38 * 2^23 < 2^29, a valid operand on either side;
+//   * the low coefficient (canonical, plain-unpacked) is subtracted limb-wise: |acc| < 39 p, limbs below 2^29 in magnitude;
+//   * the last product with one lands in (-39p/128 - p, 39p/128]: inside fe29_canonical_pack's (-2p, p).  One such product
+//     per stored element; the stored limbs are canonical, so the bits do not depend on how jobs share launches.
+// T + 1 products per element against T products, T canonical additions and T final subtractions of fe_add(fe_mul()).
+constexpr int POLY_LINCOMB_THREADS = 256;
+constexpr uint32_t POLY_LINCOMB_FOLD = 32;
+constexpr size_t POLY_LINCOMB_MAX_N = (size_t)1 << 30;
+constexpr int POLY_LINCOMB_MAX_ROUNDS = 8;                            // linear factors one job may divide out
+constexpr size_t POLY_LINCOMB_WS_CAP = (size_t)256 << 20;             // intermediate columns of the jobs that share a group
+static_assert(POLY_LINCOMB_FOLD % 2 == 0, "the fold follows a pair of terms");
+
+template <class FP>
+__global__ void __launch_bounds__(POLY_LINCOMB_THREADS)
+poly_lincomb_kernel(const LincombJob* __restrict__ jobs, const LincombTerm* __restrict__ terms, const U128* __restrict__ low,
+                    size_t n) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LincombJob job = jobs[blockIdx.y];
+  const LincombTerm* __restrict__ tt = terms + job.first_term;
+  auto coeff = [&](uint32_t t) {
+    F c;
+#pragma unroll
+    for (int l = 0; l < 8; l++) c.v[l] = tt[t].coeff[l];
+    return expr_column_operand(c);
+  };
+  auto column = [&](uint32_t t) { return fe_load<FP>((const U128*)tt[t].poly + 2 * i); };
+  const W one = fe29_from_api(F::one());
+  W acc = W::zero();
+  uint32_t t = 0;
+  for (; t + 2 <= job.n_terms; t += 2) {
+    const F x0 = column(t), x1 = column(t + 1);            // both loads in flight before the first product
+    const W p0 = fe29_mul(fe29_unpack(x0), coeff(t));
+    const W p1 = fe29_mul(fe29_unpack(x1), coeff(t + 1));
+    acc = fe29_norm(fe29_add(fe29_add(acc, p0), p1));
+    if ((t + 2) % POLY_LINCOMB_FOLD == 0) acc = fe29_mul(acc, one);
+  }
+  if (t < job.n_terms) acc = fe29_norm(fe29_add(acc, fe29_mul(fe29_unpack(column(t)), coeff(t))));
+  if (i < job.n_low) acc = fe29_sub(acc, fe29_unpack(fe_load<FP>(low + 2 * ((size_t)job.first_low + i))));
+  fe_store<FP>((U128*)job.out + 2 * i, fe29_canonical_pack(fe29_mul(acc, one)));
+}
+
 // ---- the blinding polynomial's coefficients ------------------------------------------------------------------
 // out[i] = Scalar::random(ChaCha20Rng::from_seed(seed)) number first + i (halo2_proofs @6b43b6b
 // src/plonk/vanishing/prover.rs `Argument::commit`: random_poly from a ChaCha20Rng seeded off the prover's rng;

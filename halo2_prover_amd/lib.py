@@ -83,6 +83,8 @@ SYMBOLS = {
     "h2_poly_eval_device": (_I, [_I, _P, _Z, _P, _Z, _P, _P]),
     "h2_poly_eval": (_I, [_I, _P, _Z, _P, _P]),
     "h2_poly_eval_tile": (_I, []),
+    "h2_poly_lincomb_device": (_I, [_I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _Z, _P]),
+    "h2_poly_lincomb_max_rounds": (_I, []),
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),

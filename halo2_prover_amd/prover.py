@@ -31,6 +31,7 @@ import os
 import numpy as np
 
 from . import lib as _lib
+from . import opening as _opening
 from .api import ParamsKZG
 from . import sharded as _sharded
 from .domain import EvaluationDomain
@@ -677,15 +678,6 @@ class _Dev:
                                                self.dom._stream()), "h2_poly_scale_device")
         return t
 
-    def divide_linear(self, col, z):
-        """(col - col(z)) / (X - z) as a new column: kate_division on the device"""
-        col = col.contiguous()
-        q = self.torch.empty_like(col)
-        zm = _limbs_of([z])
-        _lib.check(self.L.h2_poly_divide_linear_device(self.curve, self._p(col), col.shape[0], zm.ctypes.data,
-                                                       self._p(q), self.dom._stream()), "h2_poly_divide_linear_device")
-        return q
-
     def random_scalars(self, seed32, count):
         """`count` draws of Fr::random(ChaCha20Rng::from_seed(seed32)) as a device column"""
         t = self.torch.empty((count, 4), dtype=self.torch.int64, device="cuda")
@@ -878,104 +870,21 @@ def generate_proof(params, pk, circuit, rng=None, trace=None):
 
 def _interpolate(points, values):
     """coefficients of the polynomial of degree < len(points) through (points[i], values[i])"""
-    out = [0] * len(points)
-    for i, (xi, yi) in enumerate(zip(points, values)):
-        term, den = [1], 1
-        for j, xj in enumerate(points):
-            if j != i:
-                nt = [0] * (len(term) + 1)
-                for d, c in enumerate(term):
-                    nt[d] = (nt[d] - c * xj) % P
-                    nt[d + 1] = (nt[d + 1] + c) % P
-                term = nt
-                den = den * (xi - xj) % P
-        scale = yi * pow(den, -1, P) % P
-        for d, c in enumerate(term):
-            out[d] = (out[d] + c * scale) % P
-    return out
-
-
-def _divide_linear_device(dev, col, points):
-    """col / prod (X - p) for a device column known to vanish at the points: one kate_division per point, on the
-    device (the quotient keeps the column's length, its top coefficients are zero)"""
-    q = col
-    for pt in points:
-        q = dev.divide_linear(q, pt)
-    return q
+    return _opening.interpolate(P, points, values)
 
 
 def _shplonk_open(tr, dev, n, queries, evals, trace):
     """ProverSHPLONK::create_proof (SURVEY.md App. A.8).  queries: (point, device column, key); evals[(key, point)]
-    are the already computed evaluations.  Linear combinations run on the device, the two quotient MSMs too."""
+    are the already computed evaluations.  The columns of h(X) and of the final quotient are one
+    h2_poly_lincomb_device call each (opening.py); the transcript and the two quotient MSMs stay here."""
     y = tr.squeeze_challenge()
     v = tr.squeeze_challenge()
     trace.update(shplonk_y=y, v=v)
-    polys = []
-    for pt, col, key in queries:
-        for entry in polys:
-            if entry[0] == key:
-                if pt not in entry[2]:
-                    entry[2].append(pt)
-                break
-        else:
-            polys.append((key, col, [pt]))
-    groups = []
-    for key, col, pts in polys:
-        pset = sorted(pts)
-        for g in groups:
-            if g[0] == pset:
-                g[1].append((key, col))
-                break
-        else:
-            groups.append((pset, [(key, col)]))
-    T = sorted({pt for pset, _ in groups for pt in pset})
-    h, vp, per_set = None, 1, []
-    for pset, members in groups:
-        acc, yp, rems = None, 1, []
-        for key, col in members:
-            r = _interpolate(pset, [evals[(key, pt)] for pt in pset])
-            rems.append(r)
-            term = dev.scale(col, yp)
-            acc = term if acc is None else dev.add_(acc, term)
-            yp = yp * y % P
-        # subtract sum_j y^j R_ij (a polynomial of degree < |S_i|)
-        rsum = [0] * len(pset)
-        yp = 1
-        for r in rems:
-            rsum = [(a + yp * b) % P for a, b in zip(rsum, r)]
-            yp = yp * y % P
-        acc[:len(pset)] = dev.sub(acc[:len(pset)].contiguous(), dev.from_ints(rsum))
-        q = _divide_linear_device(dev, acc, pset)
-        term = dev.scale(q, vp)
-        h = term if h is None else dev.add_(h, term)
-        vp = vp * v % P
-        per_set.append((pset, members, rems))
+    h, state = _opening.shplonk_open_h(dev.dom, queries, evals, y, v)
     tr.write_point(dev.commit(h.unsqueeze(0), lagrange=False)[0])
     u = tr.squeeze_challenge()
     trace.update(u=u)
-    zt = 1
-    for pt in T:
-        zt = zt * (u - pt) % P
-    L, vp, z0 = None, 1, None
-    for pset, members, rems in per_set:
-        z_i = 1
-        for pt in T:
-            if pt not in pset:
-                z_i = z_i * (u - pt) % P
-        if z0 is None:
-            z0 = z_i
-        inner, yp, const = None, 1, 0
-        for (key, col), r in zip(members, rems):
-            term = dev.scale(col, yp)
-            inner = term if inner is None else dev.add_(inner, term)
-            const = (const + yp * _horner(r, u)) % P
-            yp = yp * y % P
-        inner[:1] = dev.sub(inner[:1].contiguous(), dev.from_ints([const]))
-        term = dev.scale(inner, vp * z_i % P)
-        L = term if L is None else dev.add_(L, term)
-        vp = vp * v % P
-    L = dev.sub(L, dev.scale(h, zt))
-    w = dev.scale(_divide_linear_device(dev, L, [u]), pow(z0, -1, P))
+    w = _opening.shplonk_open_final(state, u)
     tr.write_point(dev.commit(w.unsqueeze(0), lagrange=False)[0])
 
 
@@ -1110,9 +1019,7 @@ def _create_proof(params, pk, circuit, public_input, rng, trace, opening):
 
     # multiopen
     xn = pow(x, n, P)
-    h_poly = h_pieces[d - 2].clone()
-    for i in range(d - 3, -1, -1):
-        h_poly = dev.add_(dev.scale(h_poly, xn), h_pieces[i])
+    h_poly = _opening.poly_lincomb(dom, [(None, [(pow(xn, i, P), h_pieces[i]) for i in range(d - 1)], [], [])], n)[0]
     queries = [(rot_point(rot), advice_polys[col], ("advice", col)) for col, rot in circuit.advice_queries]
     for i in range(nz):
         queries += [(x, z_polys[i], ("z", i)), (x * omega % P, z_polys[i], ("z", i))]
@@ -1125,23 +1032,10 @@ def _create_proof(params, pk, circuit, public_input, rng, trace, opening):
         evals[(("h", 0), x)] = dev.evals(h_poly.unsqueeze(0), x)[0]
         _shplonk_open(tr, dev, n, queries, evals, trace)
         return bytes(tr.bytes)
-    # GWC: one witness polynomial per distinct point; the v-power combinations on the device
+    # GWC: one witness polynomial per distinct point, all of them in one h2_poly_lincomb_device call
     v = tr.squeeze_challenge()
     trace.update(v=v)
-    points = []
-    for pt, _, _ in queries:
-        if pt not in points:
-            points.append(pt)
-    witnesses = []
-    for pt in points:
-        acc, vp = None, 1
-        for qpt, col, _ in queries:
-            if qpt == pt:
-                term = dev.scale(col, vp)
-                acc = term if acc is None else dev.add_(acc, term)
-                vp = vp * v % P
-        witnesses.append(_divide_linear_device(dev, acc, [pt]))
-    for pt in dev.commit(torch.stack(witnesses), lagrange=False):
+    for pt in dev.commit(_opening.gwc_open(dom, queries, v), lagrange=False):
         tr.write_point(pt)
     return bytes(tr.bytes)
 

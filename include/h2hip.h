@@ -301,6 +301,51 @@ int h2_poly_eval_device(h2_curve_t curve, const void* const* d_polys, size_t n, 
 int h2_poly_eval(h2_curve_t curve, const uint64_t* coeffs /* n*4 */, size_t n, const uint64_t point[4], uint64_t out[4]);
 /* coefficients one workgroup covers (T above).  Host only, no h2_init needed: tests size their shapes by it. */
 int h2_poly_eval_tile(void);
+/* ---- linear combinations of resident columns, with linear factors divided out -----------------------------------
+ * The column work of the multiopen argument (GWC's witness polynomials, SHPLONK's h(X) and final quotient) and the join
+ * of the quotient pieces h(X) = sum x^(n i) h_i(X), over the scalar field of `curve` (all three curves).  Columns hold n
+ * elements in the API form: 4 x u64 Montgomery limbs, canonical in and out.  Per job:
+ *     s[i]  = sum_t coeff_t * d_poly_t[i]             i < n, over terms[first_term .. first_term + n_terms); no terms: zeros
+ *     s[i] -= low[4 * (first_low + i) ..]             i < n_low: the low coefficients of a remainder
+ *     for z in points[4 * (first_point + r) ..], r = 0 .. n_points - 1:   s = kate_division(s, z)
+ *                                                     q[i-1] = s[i] + z q[i] from the top, q[n-1] = 0, the remainder
+ *                                                     dropped: h2_poly_divide_linear_device's definition
+ *     d_out[0 .. n) = s
+ * jobs, terms, low and points are HOST arrays, all read before the call returns; d_poly and d_out are device pointers,
+ * 16-byte aligned.  Pointers may repeat, within a job and across jobs.  With n_points = 0 a job's d_out may be one of its
+ * own term columns (the sum is elementwise); with n_points > 0 it must not overlap any source column.  Two jobs' outputs
+ * must not overlap, and a job's output may not be another job's source in the same call.  Nothing beyond d_out[n - 1] is
+ * written.  Point 0 is allowed (a shift), a point may repeat.  Results are canonical limbs, the same bits however many
+ * jobs share a call and however they are grouped.  Asynchronous on `stream` under h2_ntt_device's rules: no host
+ * synchronisation, no device-to-host copy.
+ * One launch sums every job of a group (job in grid.y, jobs and terms read from one table in HBM, the `low` subtraction on
+ * the same pass); round r of the divisions then runs for every job with n_points > r, eight side by side per launch
+ * sequence of three, alternating between an intermediate column and d_out so that the last round lands in d_out.  A
+ * group is at most 65535 consecutive jobs and at most as many dividing jobs as keep their intermediate columns (n * 32
+ * bytes each) under 256 MiB (always at least one); a wider call runs group after group on `stream`.  The tables (32 bytes
+ * per job, 40 per term, 32 per low coefficient), those columns and 8 * 256 KiB of scan values live in the context's scan
+ * arena for the length of the call; nothing is cached.  With several contexts (h2_init_devices) the call acts on the
+ * context of the calling thread's current HIP device, as h2_poly_eval_device does.
+ * n_jobs = 0 or n = 0: H2_OK, nothing enqueued.  H2_EINVAL -- checked on the host before anything is enqueued -- for: an
+ * unknown curve; n > 2^30; a job whose ranges run past n_terms, n_low or n_points; a job with n_low > n or n_points >
+ * h2_poly_lincomb_max_rounds(); a null or misaligned d_out or d_poly; a null host array that a job refers to; the
+ * overlaps ruled out above.  H2_ENOTINIT before h2_init.
+ * h2_version() did not change for these entry points, it stays 1002: a host detects them by their symbols. */
+typedef struct {
+  const void* d_poly;
+  uint64_t coeff[4];
+} h2_lincomb_term_t; /* 40 bytes */
+typedef struct {
+  void* d_out;
+  uint32_t first_term, n_terms;   /* terms[first_term .. + n_terms) */
+  uint32_t first_low, n_low;      /* low[4 * first_low .. + 4 * n_low) */
+  uint32_t first_point, n_points; /* points[4 * first_point .. + 4 * n_points), divided out in this order */
+} h2_lincomb_job_t; /* 32 bytes */
+int h2_poly_lincomb_device(h2_curve_t curve, const h2_lincomb_job_t* jobs, size_t n_jobs, const h2_lincomb_term_t* terms,
+                           size_t n_terms, const uint64_t* low, size_t n_low, const uint64_t* points, size_t n_points,
+                           size_t n, void* stream);
+/* the largest n_points of a job.  Host only, no h2_init needed. */
+int h2_poly_lincomb_max_rounds(void);
 /* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
  * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
  * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER

@@ -14,6 +14,7 @@
 
 #include "h2_expr_program.hpp"
 #include "h2_host.hpp"
+#include "h2_ipa.hpp"
 #include "h2_lookup.hpp"
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
@@ -1690,6 +1691,61 @@ int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_
     key[i] = (uint32_t)seed[4 * i] | ((uint32_t)seed[4 * i + 1] << 8) | ((uint32_t)seed[4 * i + 2] << 16) |
              ((uint32_t)seed[4 * i + 3] << 24);
   return launched(ops_of((int)curve)->chacha20_scalars(d_out, n, first_block, key, k.stream), "chacha20_scalars_kernel");
+}
+
+// ---- the inner product argument on a registered table (h2_ipa.hpp) ---------------------------------------------------
+static_assert(H2_IPA_MAX_K == IPA_MAX_K, "the header states the kernels' maximum");
+static bool ipa_dev_ptr(const void* p) { return p && !((uintptr_t)p & 15); }
+
+int h2_ipa_state_bytes(uint32_t k, size_t* out) {
+  if (k == 0 || k > IPA_MAX_K || !out) return H2_EINVAL;
+  *out = IpaLayout(k).total * 32;
+  return H2_OK;
+}
+
+int h2_ipa_begin_device(h2_curve_t curve, uint32_t k_, const void* d_p, const uint64_t x3[4], void* d_state, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !ipa_dev_ptr(d_p) || !ipa_dev_ptr(d_state) || !x3) return H2_EINVAL;
+  return launched(ops_of((int)curve)->ipa_begin(d_p, x3, k_, d_state, k.stream), "ipa_begin_kernel");
+}
+
+int h2_ipa_round_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uint32_t j, void* d_state, const uint64_t* u_prev,
+                        const uint64_t* u_prev_inv, const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4],
+                        void* d_out_affine, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || j >= k_) return H2_EINVAL;
+  if (!ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_out_affine) || !z || !l_blind || !r_blind) return H2_EINVAL;
+  if (j == 0 ? (u_prev || u_prev_inv) : (!u_prev || !u_prev_inv)) return H2_EINVAL;
+  const IpaLayout L(k_);
+  const BasesEntry* be = nullptr;
+  if (int rc = msm_common_checks((int)curve, bases, 0, L.col_stride, 2, &be); rc != H2_OK) return rc;
+  if (be->n != L.col_stride) return H2_EINVAL;          // exactly G || U || W
+  if (int rc = launched(ops_of((int)curve)->ipa_round(k_, j, d_state, u_prev, u_prev_inv, z, l_blind, r_blind, k.stream),
+                        "ipa_round_kernel");
+      rc != H2_OK)
+    return rc;
+  return msm_device_run(*k.c, (int)curve, *be, (const char*)d_state + L.col * 32, 0, L.col_stride, L.col_stride, 2, d_out_affine,
+                        true, k.stream);
+}
+
+int h2_ipa_final_device(h2_curve_t curve, uint32_t k_, void* d_state, const uint64_t u_last[4], const uint64_t u_last_inv[4],
+                        void* d_out, void* d_s_out, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_out) || !u_last || !u_last_inv)
+    return H2_EINVAL;
+  if (d_s_out && ((uintptr_t)d_s_out & 15)) return H2_EINVAL;
+  return launched(ops_of((int)curve)->ipa_final(k_, d_state, u_last, u_last_inv, d_out, d_s_out, k.stream), "ipa_final_kernel");
+}
+
+int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k_, const uint64_t init[4], void* d_out,
+                                     void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !u || !init || !ipa_dev_ptr(d_out)) return H2_EINVAL;
+  return launched(ops_of((int)curve)->ipa_s_products(u, k_, init, d_out, k.stream), "ipa_s_kernel");
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {

@@ -148,6 +148,16 @@ struct CurveOps {
                             uint32_t count, size_t lds_bytes, hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
+  // the inner product argument on the registered generators (h2_ipa.hpp); d_state: IpaLayout(k).total elements, 1 <= k <=
+  // IPA_MAX_K.  ipa_begin: a = the 2^k coefficients d_p, b = the powers of x3, s = [1].  ipa_round: for j > 0 the fold by
+  // u_prev, then both columns of 2^k + 2 scalars (the caller runs the MSM on them).  ipa_final: the last fold, d_out = c || b[0],
+  // d_s_out (optional) = the finished s in natural order.  ipa_s_products: compute_s(u, init), u: k x 4 limbs on the host
+  hipError_t (*ipa_begin)(const void* d_p, const uint64_t x3[4], uint32_t k, void* d_state, hipStream_t s);
+  hipError_t (*ipa_round)(uint32_t k, uint32_t j, void* d_state, const uint64_t* u_prev, const uint64_t* u_prev_inv,
+                          const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4], hipStream_t s);
+  hipError_t (*ipa_final)(uint32_t k, void* d_state, const uint64_t u[4], const uint64_t uinv[4], void* d_out, void* d_s_out,
+                          hipStream_t s);
+  hipError_t (*ipa_s_products)(const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out, hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)
   int (*selftest_field)(int which /* 0 = base field, 1 = scalar field */, int op, const uint64_t* a,
                         const uint64_t* b, uint64_t* out);

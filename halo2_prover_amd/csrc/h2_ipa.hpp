@@ -1,0 +1,342 @@
+// h2_ipa.hpp -- the inner product argument's rounds on the REGISTERED generators (halo2_proofs @6b43b6b
+// src/poly/ipa/commitment/prover.rs `create_proof`, un-vendored; the algorithm is restated in DESIGN.md section 7.13).
+//
+// Upstream folds three vectors per round: a, b and the generators G' (G'[i] += [u_j] G'[i + half]), and takes L_j, R_j as
+// MSMs over the folded G'.  The folded generators are fixed combinations of the original ones,
+//     G^(j)[i] = sum_{h < 2^j} s^(j)[h] G[h 2^(k-j) + i],   s^(0) = [1], s^(j+1)[2h] = s^(j)[h], s^(j+1)[2h+1] = s^(j)[h] u_j
+// so <a[half..], G^(j)[..half]> is an MSM over the ORIGINAL G with the scalar a[half + i] s^(j)[h] at index
+// t = h 2 half + i (and zero at t + half); R_j likewise with a[i] s^(j)[h] at t + half.  No generator is ever folded: a
+// round is one two-column MSM of n + 2 terms on the table registered once as G || U || W (slot n: z <a, b>, slot n + 1: the
+// blind) plus the kernels below, O(n) field products.
+//
+// State (caller-owned, IpaLayout): a and b in two generations each (generation g = a after g folds, 2^(k-g) elements: even
+// generations in a buffer of n, odd ones in a buffer of n / 2 -- the round kernel reads one and writes the other, so its
+// threads never race), the table s, the two columns of n + 2, one partial pair per workgroup of the inner products.
+// s is kept in the APPEND-ONLY order S[rev_j(h)] = s^(j)[h] (rev_j: the low j bits reversed): doubling the table is
+// S[2^j + g] = S[g] u_j, which reads [0, 2^j) and writes [2^j, 2^(j+1)) -- no race, nothing moves.
+//
+// Arithmetic: products on the 9 x 29-bit lazy form with the data never converted, as poly_lincomb_kernel (h2_poly.hpp): an
+// element in HBM is the integer d = x 2^256 mod p, plain-unpacked; the other factor goes through expr_column_operand,
+// c' = c 2^261 + j p in (-16 p, 16 p); fe29_mul(d, c') is x c 2^256 mod p -- the API form of the product -- in (-9p/8, p/8]
+// with normalised limbs.  Magnitudes, in units of p (R' = 2^261 > 128 p):
+//   * a fold  lo + hi u  is a canonical value plus one product: in (-9p/8, 9p/8), inside w_canonical_pack's (-2p, 2p), so
+//     everything stored in a and b is canonical;
+//   * a column entry is ONE product, in (-9p/8, p/8]: inside fe29_canonical_pack's (-2p, p);
+//   * an inner product: each thread holds one product per sum; 64 lanes add up pairwise (a carry pass per level) to
+//     |v| < 72 p, the top limb below 72 * 2^23 < 2^30 and the others normalised: a valid first operand.  One product with
+//     the working form of one brings it to (-72p/128 - p, 72p/128]; the four waves' values add up in LDS to (-6.3p, 2.3p)
+//     and a second product with one lands in (-1.05p, 0.02p]: canonical_pack.  No atomics; the partials are canonical, so
+//     the finishing kernel adds them with the canonical fe_add in a fixed order and the bits do not depend on the grid.
+#pragma once
+#include "h2_curve_ops.hpp"
+#include "h2_field.hpp"
+#include "h2_field29.hpp"
+
+#include <cstring>
+
+namespace h2 {
+
+constexpr uint32_t IPA_MAX_K = 20;          // H2_IPA_MAX_K of the C ABI
+constexpr int IPA_THREADS = 256;
+constexpr uint32_t IPA_H_PER = 2;           // copies (values of h) one thread of the round kernel writes
+
+// the caller's state buffer, in 32-byte elements
+struct IpaLayout {
+  size_t n, hn, a[2], b[2], s, col, col_stride, partial, partials, total;
+  explicit IpaLayout(uint32_t k) {
+    n = (size_t)1 << k;
+    hn = n / 2;                              // >= 1
+    a[0] = 0;
+    a[1] = n;
+    b[0] = n + hn;
+    b[1] = 2 * n + hn;
+    s = 2 * n + 2 * hn;
+    col = 3 * n + 2 * hn;
+    col_stride = n + 2;
+    partial = col + 2 * col_stride;
+    partials = (hn + IPA_THREADS - 1) / IPA_THREADS;     // workgroups of the first round that hold an inner product
+    total = partial + 2 * partials;
+  }
+};
+
+// h2_ipa_begin_device: a = p, b[i] = x3^i (each thread POLY_RUN-style runs of 8 from x3^first), S[0] = 1
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_begin_kernel(const U128* __restrict__ p, U128* __restrict__ a, U128* __restrict__ b, U128* __restrict__ s, size_t n, Fe<FP> x3) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t first = t * 8;
+  if (t == 0) fe_store<FP>(s, Fe<FP>::one());
+  if (first >= n) return;
+  Fe<FP> cur = fe_pow_u64(x3, (uint64_t)first);
+  for (int q = 0; q < 8 && first + q < n; q++) {
+    fe_store<FP>(a + 2 * (first + q), fe_load<FP>(p + 2 * (first + q)));
+    fe_store<FP>(b + 2 * (first + q), cur);
+    cur = fe_mul(cur, x3);
+  }
+}
+
+// the table of challenge products doubles: S[count + g] = S[g] u for g < count.  With set_init (count = 1) S[0] = init
+// first: h2_ipa_challenge_products_device runs it k times with u_(k-1), ..., u_0 and gets compute_s in natural order
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_s_kernel(U128* __restrict__ S, uint32_t count, Fe<FP> u, Fe<FP> init, int set_init) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  Fe<FP> x;
+  if (set_init) {                      // count == 1
+    x = init;
+    fe_store<FP>(S, x);
+  } else {
+    x = fe_load<FP>(S + 2 * (size_t)g);
+  }
+  fe_store<FP>(S + 2 * ((size_t)count + g), fe_mul(x, u));
+}
+
+template <class FP>
+struct IpaRound {
+  const U128* a_old;       // generation j - 1 (j > 0) or generation 0 (j = 0)
+  const U128* b_old;
+  U128* a_new;             // generation j (j > 0)
+  U128* b_new;
+  const U128* S;           // 2^j challenge products, append-only order
+  U128* colL;
+  U128* colR;
+  U128* partial;           // pairs (L, R), one per workgroup that holds an inner product
+  Fe<FP> u, uinv;          // u_(j-1) and its inverse (j > 0)
+  uint32_t k, j;
+};
+
+// Thread T: i = T mod half, hy = T / half.  It forms a'[i], a'[i + half] (from four loads when j > 0), writes the copies
+// h in [hy IPA_H_PER, (hy + 1) IPA_H_PER) of its two products into both columns, zeros included, and -- hy = 0 only --
+// stores a', b' and adds its two terms to the inner products.
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(IpaRound<FP> A) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  __shared__ int32_t lds[2][IPA_THREADS / 64][9];
+  const uint32_t lh = A.k - A.j - 1;                       // log2(half)
+  const size_t half = (size_t)1 << lh;
+  const size_t nh = (size_t)1 << A.j;                      // entries of s
+  const size_t hy_count = (nh + IPA_H_PER - 1) / IPA_H_PER;
+  const size_t T = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = T & (half - 1), hy = T >> lh;
+  const bool active = hy < hy_count;
+  const bool owner = active && hy == 0;                    // T < half
+  W ipL = W::zero(), ipR = W::zero();
+  if (active) {
+    F lo, hi;                                              // a'[i], a'[i + half]
+    if (A.j > 0) {
+      const W ui = expr_column_operand(A.uinv);
+      const F a0 = fe_load<FP>(A.a_old + 2 * i), a1 = fe_load<FP>(A.a_old + 2 * (i + half));
+      const F a2 = fe_load<FP>(A.a_old + 2 * (i + 2 * half)), a3 = fe_load<FP>(A.a_old + 2 * (i + 3 * half));
+      lo = w_canonical_pack(fe29_add(fe29_unpack(a0), fe29_mul(fe29_unpack(a2), ui)));
+      hi = w_canonical_pack(fe29_add(fe29_unpack(a1), fe29_mul(fe29_unpack(a3), ui)));
+    } else {
+      lo = fe_load<FP>(A.a_old + 2 * i);
+      hi = fe_load<FP>(A.a_old + 2 * (i + half));
+    }
+    if (owner) {
+      F blo, bhi;
+      if (A.j > 0) {
+        const W uu = expr_column_operand(A.u);
+        const F b0 = fe_load<FP>(A.b_old + 2 * i), b1 = fe_load<FP>(A.b_old + 2 * (i + half));
+        const F b2 = fe_load<FP>(A.b_old + 2 * (i + 2 * half)), b3 = fe_load<FP>(A.b_old + 2 * (i + 3 * half));
+        blo = w_canonical_pack(fe29_add(fe29_unpack(b0), fe29_mul(fe29_unpack(b2), uu)));
+        bhi = w_canonical_pack(fe29_add(fe29_unpack(b1), fe29_mul(fe29_unpack(b3), uu)));
+        fe_store<FP>(A.a_new + 2 * i, lo);
+        fe_store<FP>(A.a_new + 2 * (i + half), hi);
+        fe_store<FP>(A.b_new + 2 * i, blo);
+        fe_store<FP>(A.b_new + 2 * (i + half), bhi);
+      } else {
+        blo = fe_load<FP>(A.b_old + 2 * i);
+        bhi = fe_load<FP>(A.b_old + 2 * (i + half));
+      }
+      ipL = fe29_mul(fe29_unpack(hi), expr_column_operand(blo));     // <a[half..], b[..half]>
+      ipR = fe29_mul(fe29_unpack(lo), expr_column_operand(bhi));     // <a[..half], b[half..]>
+    }
+    const W wlo = fe29_unpack(lo), whi = fe29_unpack(hi);
+    const F zero = F::zero();
+    for (uint32_t q = 0; q < IPA_H_PER; q++) {
+      const size_t h = hy * IPA_H_PER + q;
+      if (h >= nh) break;
+      const uint32_t idx = A.j ? (__brev((uint32_t)h) >> (32 - A.j)) : 0u;
+      const W sh = expr_column_operand(fe_load<FP>(A.S + 2 * (size_t)idx));
+      const size_t t = h * 2 * half + i;
+      fe_store<FP>(A.colL + 2 * t, fe29_canonical_pack(fe29_mul(whi, sh)));
+      fe_store<FP>(A.colL + 2 * (t + half), zero);
+      fe_store<FP>(A.colR + 2 * t, zero);
+      fe_store<FP>(A.colR + 2 * (t + half), fe29_canonical_pack(fe29_mul(wlo, sh)));
+    }
+  }
+  if ((size_t)blockIdx.x * blockDim.x >= half) return;     // uniform: this workgroup holds no inner product term
+  // in the wave (64 lanes): pairwise, a carry pass per level
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    W oL, oR;
+#pragma unroll
+    for (int l = 0; l < 9; l++) {
+      oL.v[l] = __shfl_xor(ipL.v[l], d, 64);
+      oR.v[l] = __shfl_xor(ipR.v[l], d, 64);
+    }
+    ipL = fe29_norm(fe29_add(ipL, oL));
+    ipR = fe29_norm(fe29_add(ipR, oR));
+  }
+  const W one = fe29_from_api(F::one());
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+    const W vL = fe29_mul(ipL, one), vR = fe29_mul(ipR, one);
+#pragma unroll
+    for (int l = 0; l < 9; l++) {
+      lds[0][wave][l] = vL.v[l];
+      lds[1][wave][l] = vR.v[l];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {                                   // thread 0: L, thread 1: R
+    W acc = W::zero();
+    for (int w = 0; w < IPA_THREADS / 64; w++) {
+#pragma unroll
+      for (int l = 0; l < 9; l++) acc.v[l] += lds[threadIdx.x][w][l];
+    }
+    fe_store<FP>(A.partial + 2 * ((size_t)blockIdx.x * 2 + threadIdx.x), fe29_canonical_pack(fe29_mul(fe29_norm(acc), one)));
+  }
+}
+
+// one workgroup: the sums of the `count` partial pairs times z into slot n of the columns, the blinds into slot n + 1
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_finish_kernel(const U128* __restrict__ partial, uint32_t count, Fe<FP> z, Fe<FP> l_blind, Fe<FP> r_blind,
+                  U128* __restrict__ tailL, U128* __restrict__ tailR) {
+  using F = Fe<FP>;
+  __shared__ uint32_t lds[2][8][IPA_THREADS];              // [sum][limb][thread]
+  const uint32_t t = threadIdx.x;
+  F acc[2] = {F::zero(), F::zero()};
+  for (uint32_t p = t; p < count; p += IPA_THREADS) {
+    acc[0] = fe_add(acc[0], fe_load<FP>(partial + 2 * ((size_t)p * 2)));
+    acc[1] = fe_add(acc[1], fe_load<FP>(partial + 2 * ((size_t)p * 2 + 1)));
+  }
+  for (uint32_t st = IPA_THREADS / 2; st >= 1; st >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int l = 0; l < 8; l++) lds[c][l][t] = acc[c].v[l];
+    __syncthreads();
+    if (t < st) {
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        F o;
+#pragma unroll
+        for (int l = 0; l < 8; l++) o.v[l] = lds[c][l][t + st];
+        acc[c] = fe_add(acc[c], o);
+      }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    fe_store<FP>(tailL, fe_mul(acc[0], z));
+    fe_store<FP>(tailL + 2, l_blind);
+    fe_store<FP>(tailR, fe_mul(acc[1], z));
+    fe_store<FP>(tailR + 2, r_blind);
+  }
+}
+
+// h2_ipa_final_device: the last fold, c = a[0] + a[1] / u and b[0] + b[1] u (thread 0), and the finished table in natural
+// order, s[i] = S[rev_k(i)], when the caller wants it
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_final_kernel(const U128* __restrict__ a, const U128* __restrict__ b, const U128* __restrict__ S, Fe<FP> u, Fe<FP> uinv,
+                 uint32_t k, U128* __restrict__ out, U128* __restrict__ s_out) {
+  const size_t T = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (T == 0) {
+    fe_store<FP>(out, fe_add(fe_load<FP>(a), fe_mul(fe_load<FP>(a + 2), uinv)));
+    fe_store<FP>(out + 2, fe_add(fe_load<FP>(b), fe_mul(fe_load<FP>(b + 2), u)));
+  }
+  if (s_out && T < ((size_t)1 << k))
+    fe_store<FP>(s_out + 2 * T, fe_load<FP>(S + 2 * (size_t)(__brev((uint32_t)T) >> (32 - k))));
+}
+
+// ---- launches (one per curve through CurveOps) ----------------------------------------------------------------------------
+template <class FP>
+inline Fe<FP> ipa_fe(const uint64_t* limbs) {
+  Fe<FP> r;
+  memcpy(r.v, limbs, 32);
+  return r;
+}
+
+template <class FP>
+hipError_t ipa_begin_launch(const void* d_p, const uint64_t x3[4], uint32_t k, void* d_state, hipStream_t s) {
+  const IpaLayout L(k);
+  U128* st = (U128*)d_state;
+  const size_t threads = (L.n + 7) / 8;
+  hipLaunchKernelGGL(ipa_begin_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s,
+                     (const U128*)d_p, st + 2 * L.a[0], st + 2 * L.b[0], st + 2 * L.s, L.n, ipa_fe<FP>(x3));
+  return hipGetLastError();
+}
+
+template <class FP>
+hipError_t ipa_round_launch(uint32_t k, uint32_t j, void* d_state, const uint64_t* u_prev, const uint64_t* u_prev_inv,
+                            const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4], hipStream_t s) {
+  const IpaLayout L(k);
+  U128* st = (U128*)d_state;
+  IpaRound<FP> A{};
+  A.k = k;
+  A.j = j;
+  A.S = st + 2 * L.s;
+  A.colL = st + 2 * L.col;
+  A.colR = st + 2 * (L.col + L.col_stride);
+  A.partial = st + 2 * L.partial;
+  if (j > 0) {
+    A.u = ipa_fe<FP>(u_prev);
+    A.uinv = ipa_fe<FP>(u_prev_inv);
+    A.a_old = st + 2 * L.a[(j - 1) & 1];
+    A.b_old = st + 2 * L.b[(j - 1) & 1];
+    A.a_new = st + 2 * L.a[j & 1];
+    A.b_new = st + 2 * L.b[j & 1];
+    const uint32_t count = 1u << (j - 1);
+    hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, st + 2 * L.s, count,
+                       A.u, Fe<FP>::zero(), 0);
+  } else {
+    A.u = A.uinv = Fe<FP>::zero();
+    A.a_old = st + 2 * L.a[0];
+    A.b_old = st + 2 * L.b[0];
+    A.a_new = nullptr;
+    A.b_new = nullptr;
+  }
+  const size_t half = (size_t)1 << (k - j - 1), nh = (size_t)1 << j;
+  const size_t threads = half * ((nh + IPA_H_PER - 1) / IPA_H_PER);
+  hipLaunchKernelGGL(ipa_round_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s, A);
+  const uint32_t parts = (uint32_t)((half + IPA_THREADS - 1) / IPA_THREADS);
+  hipLaunchKernelGGL(ipa_finish_kernel<FP>, dim3(1), dim3(IPA_THREADS), 0, s, (const U128*)A.partial, parts, ipa_fe<FP>(z),
+                     ipa_fe<FP>(l_blind), ipa_fe<FP>(r_blind), A.colL + 2 * L.n, A.colR + 2 * L.n);
+  return hipGetLastError();
+}
+
+template <class FP>
+hipError_t ipa_final_launch(uint32_t k, void* d_state, const uint64_t u[4], const uint64_t uinv[4], void* d_out, void* d_s_out,
+                            hipStream_t s) {
+  const IpaLayout L(k);
+  U128* st = (U128*)d_state;
+  const Fe<FP> uu = ipa_fe<FP>(u);
+  const uint32_t count = 1u << (k - 1);
+  hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, st + 2 * L.s, count, uu,
+                     Fe<FP>::zero(), 0);
+  const size_t threads = d_s_out ? L.n : 1;
+  hipLaunchKernelGGL(ipa_final_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s,
+                     (const U128*)(st + 2 * L.a[(k - 1) & 1]), (const U128*)(st + 2 * L.b[(k - 1) & 1]), (const U128*)(st + 2 * L.s), uu,
+                     ipa_fe<FP>(uinv), k, (U128*)d_out, (U128*)d_s_out);
+  return hipGetLastError();
+}
+
+// compute_s(u, init) into d_out (2^k elements): k doublings, the challenges taken from the last to the first
+template <class FP>
+hipError_t ipa_s_products_launch(const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out, hipStream_t s) {
+  const Fe<FP> in = ipa_fe<FP>(init);
+  for (uint32_t t = 0; t < k; t++) {
+    const uint32_t count = 1u << t;
+    hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, (U128*)d_out, count,
+                       ipa_fe<FP>(u + 4 * (k - 1 - t)), in, t == 0 ? 1 : 0);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace h2

@@ -1,0 +1,236 @@
+"""The inner product argument over a registered SRS table (include/h2hip.h: h2_ipa_*).
+
+Upstream (halo2_proofs, src/poly/ipa/commitment.rs and commitment/{prover,verifier}.rs -- un-vendored; the algorithm is
+restated in DESIGN.md section 7.13): the opening proof a halo2 host on the Pasta curves ends `create_proof` with.
+`ParamsIPA` registers the bases ONCE as g || u || w; `create_proof` runs the k rounds on that table through
+h2_ipa_begin_device / h2_ipa_round_device / h2_ipa_final_device -- no generator is ever folded, each round is one
+two-column MSM over the registered table -- and `verify_proof` checks
+    sum [u_j^-1] L_j + P' + sum [u_j] R_j == [c] <s, G> + [c b_0 z] U + [f] W,   P' = P - [v] G[0] + [xi] S
+with <s, G> and the U, W, G[0] terms as ONE h2_msm_device on the same table (s from h2_ipa_challenge_products_device).
+Polynomials are (n, 4) int64 CUDA tensors viewing 4 x u64 Montgomery limbs (numpy uint64 arrays are uploaded); points are
+affine (x, y) pairs of canonical ints, None for the identity.  The transcript is transcript.Blake2bTranscript on the
+curve.  `ParamsIPA::new`'s hash-to-curve is not here: the bases are the caller's.  There is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+
+from . import lib as _lib
+from .api import Bases, _as_u64, _curve_id, _ensure_init, msm_points
+from .domain import EvaluationDomain
+from .opening import poly_lincomb
+from .transcript import FIELDS, Blake2bTranscript  # noqa: F401
+
+
+def compute_s(u, init, p):
+    """upstream's compute_s: s[i] = init * prod over the set bits t of i of u[k-1-t] (mod p), 2^k entries"""
+    s = [init % p]
+    for uj in u:                                    # s^(j+1)[2h] = s^(j)[h], s^(j+1)[2h+1] = s^(j)[h] u_j
+        s = [v for x in s for v in (x, x * uj % p)]
+    return s
+
+
+def compute_b(x, u, p):
+    """upstream's compute_b: prod_t (1 + u[k-1-t] x^(2^t)) = <compute_s(u, 1), powers of x> (mod p)"""
+    out, cur = 1, x % p
+    for uj in reversed(u):
+        out = out * (1 + uj * cur) % p
+        cur = cur * cur % p
+    return out
+
+
+def _limbs(v):
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+def _ints(raw):
+    raw = bytes(raw)
+    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+def random_scalar(rng, p):
+    """ff's Field::random: 64 bytes of the rng as a little-endian integer, reduced"""
+    return int.from_bytes(bytes(rng(64)), "little") % p
+
+
+class ParamsIPA:
+    """ParamsIPA<C> for the prover and the verifier: g (n affine points), w, u, registered as g || u || w."""
+
+    def __init__(self, curve, k, g, w, u):
+        _ensure_init()
+        self.curve = _curve_id(curve)
+        self.k, self.n = int(k), 1 << int(k)
+        self.p, self.q, _ = FIELDS[self.curve]
+        self.R, self.Rq = (1 << 256) % self.p, (1 << 256) % self.q
+        self.Rq_inv = pow(self.Rq, -1, self.q)
+        g = _as_u64(g, 8, "g")
+        if g.shape[0] != self.n:
+            raise ValueError("ParamsIPA: g.len() != 1 << k")
+        self.g = g
+        self.w = _as_u64(w, 8, "w").reshape(1, 8)
+        self.u = _as_u64(u, 8, "u").reshape(1, 8)
+        self.bases = Bases(self.curve, np.concatenate([g, self.u, self.w]))
+        self.domain = EvaluationDomain(2, self.k, self.curve)
+        self._L = _lib.load()
+
+    # ---- helpers --------------------------------------------------------------------------------------------
+    def mont(self, v):
+        return _limbs(v % self.p * self.R % self.p)
+
+    def column(self, poly):
+        """a polynomial as a (rows, 4) int64 CUDA tensor"""
+        import torch
+        if isinstance(poly, torch.Tensor):
+            return poly
+        return torch.from_numpy(_as_u64(poly, 4, "poly").view(np.int64).copy()).cuda()
+
+    def affine_ints(self, limbs):
+        """8 Montgomery limbs of an affine point -> (x, y) canonical ints, None for (0, 0)"""
+        x, y = _ints(np.ascontiguousarray(limbs, dtype=np.uint64).tobytes())
+        if x == 0 and y == 0:
+            return None
+        return (x * self.Rq_inv % self.q, y * self.Rq_inv % self.q)
+
+    def affine_limbs(self, pt):
+        x, y = pt if pt is not None else (0, 0)
+        return np.concatenate([_limbs(x * self.Rq % self.q), _limbs(y * self.Rq % self.q)])
+
+    def jac_to_affine(self, jac):
+        """12 Montgomery limbs (X, Y, Z), x = X / Z^2, y = Y / Z^3 -> (x, y) canonical ints or None"""
+        X, Y, Z = [v * self.Rq_inv % self.q for v in _ints(np.ascontiguousarray(jac, dtype=np.uint64).tobytes())]
+        if Z == 0:
+            return None
+        zi = pow(Z, -1, self.q)
+        return (X * zi * zi % self.q, Y * zi * zi % self.q * zi % self.q)
+
+    def msm_table(self, d_col):
+        """ONE h2_msm_device over g || u || w: d_col a (n + 2, 4) column -> affine ints"""
+        import torch
+        out = torch.empty(12, dtype=torch.int64, device=d_col.device)
+        self.bases.msm_device(d_col.data_ptr(), self.n + 2, 1, out.data_ptr(), self.domain._stream().value or 0)
+        return self.jac_to_affine(out.cpu().numpy().view(np.uint64))
+
+    def commit(self, poly, blind):
+        """commit(poly, r) = <poly, g> + [r] w: h2_msm_device on the column poly || 0 || r"""
+        import torch
+        poly = self.column(poly)
+        if poly.shape[0] != self.n:
+            raise ValueError("commit: poly.len() != n")
+        tail = torch.from_numpy(np.stack([_limbs(0), self.mont(blind)]).view(np.int64)).to(poly.device)
+        return self.msm_table(torch.cat([poly, tail]))
+
+
+def create_proof(params, transcript, p, p_blind, x3, rng, s_poly=None):
+    """ipa::commitment::prover::create_proof: opens the polynomial p (n coefficients, committed with blind p_blind) at x3.
+    rng: a callable n -> n bytes.  Written to the transcript: S, then k x (L_j, R_j), then c, then f.
+
+    s_poly: the caller's column of n random coefficients, or None.  With None it is ONE 32-byte draw of the rng expanded on
+    the device by h2_chacha20_scalars_device -- the one deviation from upstream's draw order, which takes the n scalars
+    from the rng one by one.  Everything else is drawn in upstream's order: s_blind, then l_j and r_j of every round.
+    Each round reads 128 bytes back (L_j || R_j) for the transcript; the final call reads 64."""
+    import torch
+    L, cv, k, n, P = params._L, params.curve, params.k, params.n, params.p
+    dom = params.domain
+    stream = dom._stream()
+    p = params.column(p)
+    if p.shape[0] != n:
+        raise ValueError("create_proof: p.len() != n")
+    if s_poly is None:
+        seed = bytes(rng(32))
+        s_poly = torch.empty((n, 4), dtype=torch.int64, device=p.device)
+        _lib.check(L.h2_chacha20_scalars_device(cv, seed, 0, n, ctypes.c_void_p(s_poly.data_ptr()), stream),
+                   "h2_chacha20_scalars_device")
+    else:
+        s_poly = params.column(s_poly).clone()
+    # s_poly[0] -= s_poly(x3): the blinding polynomial has a root at x3
+    s_at = dom.eval_polynomial(s_poly.reshape(1, n, 4), x3)[0]
+    poly_lincomb(dom, [(s_poly, [(1, s_poly)], [s_at], [])], n)
+    s_blind = random_scalar(rng, P)
+    transcript.write_point(params.commit(s_poly, s_blind))
+    xi = transcript.squeeze_challenge()
+    z = transcript.squeeze_challenge()
+    # p' = s_poly xi + p, p'[0] -= v with v = p'(x3) = p(x3)
+    v = dom.eval_polynomial(p.reshape(1, n, 4), x3)[0]
+    p_prime = poly_lincomb(dom, [(None, [(xi, s_poly), (1, p)], [v], [])], n)[0]
+    f = (s_blind * xi + p_blind) % P
+
+    need = ctypes.c_size_t(0)
+    _lib.check(L.h2_ipa_state_bytes(k, ctypes.byref(need)), "h2_ipa_state_bytes")
+    state = torch.empty(need.value // 8, dtype=torch.int64, device=p.device)
+    out = torch.empty(16, dtype=torch.int64, device=p.device)
+    _lib.check(L.h2_ipa_begin_device(cv, k, ctypes.c_void_p(p_prime.data_ptr()), params.mont(x3).ctypes.data,
+                                     ctypes.c_void_p(state.data_ptr()), stream), "h2_ipa_begin_device")
+    zm = params.mont(z)
+    u = u_inv = None
+    for j in range(k):
+        l_j = random_scalar(rng, P)
+        r_j = random_scalar(rng, P)
+        um, uim = (params.mont(u), params.mont(u_inv)) if j else (None, None)
+        lm, rm = params.mont(l_j), params.mont(r_j)
+        st = L.h2_ipa_round_device(cv, params.bases.handle, k, j, ctypes.c_void_p(state.data_ptr()),
+                                   um.ctypes.data if j else None, uim.ctypes.data if j else None, zm.ctypes.data,
+                                   lm.ctypes.data, rm.ctypes.data, ctypes.c_void_p(out.data_ptr()), stream)
+        _lib.check(st, "h2_ipa_round_device")
+        lr = out.cpu().numpy().view(np.uint64)
+        transcript.write_point(params.affine_ints(lr[:8]))
+        transcript.write_point(params.affine_ints(lr[8:]))
+        u = transcript.squeeze_challenge()
+        u_inv = pow(u, -1, P)
+        f = (f + l_j * u_inv + r_j * u) % P
+    um, uim = params.mont(u), params.mont(u_inv)
+    _lib.check(L.h2_ipa_final_device(cv, k, ctypes.c_void_p(state.data_ptr()), um.ctypes.data, uim.ctypes.data,
+                                     ctypes.c_void_p(out.data_ptr()), None, stream), "h2_ipa_final_device")
+    c = _ints(out[:4].cpu().numpy().tobytes())[0] * pow(params.R, -1, P) % P
+    transcript.write_scalar(c)
+    transcript.write_scalar(f)
+    return bytes(transcript.bytes)
+
+
+def verify_proof(params, transcript, P, x3, v):
+    """ipa::commitment::verifier::verify_proof on a reading transcript: does the proof open the commitment P (affine ints)
+    to v at x3?  <s, G> and the G[0], U, W terms are one h2_msm_device on the registered table, s from
+    h2_ipa_challenge_products_device; P, S and the 2k points L_j, R_j go through h2_msm_points.  -> bool"""
+    import torch
+    from .transcript import TranscriptError
+    L, cv, k, n, p = params._L, params.curve, params.k, params.n, params.p
+    dom = params.domain
+    try:
+        S = transcript.read_point()
+        xi = transcript.squeeze_challenge()
+        z = transcript.squeeze_challenge()
+        rounds = []
+        for _ in range(k):
+            l_pt = transcript.read_point()
+            r_pt = transcript.read_point()
+            rounds.append((l_pt, r_pt, transcript.squeeze_challenge()))
+        c = transcript.read_scalar()
+        f = transcript.read_scalar()
+    except TranscriptError:
+        return False
+    u = [r[2] for r in rounds]
+    if any(x == 0 for x in u):
+        return False
+    b0 = compute_b(x3, u, p)
+    # everything on one side: sum [1/u_j] L_j + P + [xi] S + sum [u_j] R_j - [v] G[0] - [c] <s, G> - [c b0 z] U - [f] W == 0
+    um = np.concatenate([params.mont(x) for x in u])
+    col = torch.empty((n + 2, 4), dtype=torch.int64, device="cuda")
+    st = L.h2_ipa_challenge_products_device(cv, um.ctypes.data, k, params.mont(-c).ctypes.data, ctypes.c_void_p(col.data_ptr()),
+                                            dom._stream())
+    _lib.check(st, "h2_ipa_challenge_products_device")
+    poly_lincomb(dom, [(col, [(1, col)], [v % p], [])], n)                                 # col[0] -= v
+    tail = np.stack([params.mont(-c * b0 % p * z), params.mont(-f)])
+    col[n:] = torch.from_numpy(tail.view(np.int64)).to(col.device)
+    table_side = params.msm_table(col)
+    terms = [(1, P), (xi, S)]
+    for l_pt, r_pt, uj in rounds:
+        terms.append((pow(uj, -1, p), l_pt))
+        terms.append((uj, r_pt))
+    terms = [(s, pt) for s, pt in terms if pt is not None]
+    if terms:
+        other = params.jac_to_affine(msm_points(np.stack([params.mont(s) for s, _ in terms]),
+                                                np.stack([params.affine_limbs(pt) for _, pt in terms]), cv))
+    else:
+        other = None
+    if table_side is None or other is None:
+        return table_side is None and other is None
+    return table_side[0] == other[0] and (table_side[1] + other[1]) % params.q == 0

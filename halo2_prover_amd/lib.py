@@ -85,6 +85,11 @@ SYMBOLS = {
     "h2_poly_eval_tile": (_I, []),
     "h2_poly_lincomb_device": (_I, [_I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _Z, _P]),
     "h2_poly_lincomb_max_rounds": (_I, []),
+    "h2_ipa_state_bytes": (_I, [_U32, ctypes.POINTER(_Z)]),
+    "h2_ipa_begin_device": (_I, [_I, _U32, _P, _P, _P, _P]),
+    "h2_ipa_round_device": (_I, [_I, _U64, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_final_device": (_I, [_I, _U32, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_challenge_products_device": (_I, [_I, _P, _U32, _P, _P, _P]),
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),

@@ -36,6 +36,7 @@ from .api import ParamsKZG
 from . import sharded as _sharded
 from .domain import EvaluationDomain
 from .permutation import permutation_product
+from .transcript import Blake2bTranscript
 
 P = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001       # bn256::Fr modulus
 Q = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47       # bn256::Fq modulus
@@ -105,30 +106,11 @@ class OsRng:
         return v % P
 
 
-class _Transcript:
-    """Blake2bWrite<Vec<u8>, G1Affine, Challenge255<_>> (utils.rs:103-104)"""
+class _Transcript(Blake2bTranscript):
+    """Blake2bWrite<Vec<u8>, G1Affine, Challenge255<_>> (utils.rs:103-104): the shared transcript on BN254"""
 
     def __init__(self):
-        self.state = hashlib.blake2b(digest_size=64, person=b"Halo2-Transcript")
-        self.bytes = bytearray()
-
-    def common_scalar(self, s):
-        self.state.update(b"\x02" + int(s % P).to_bytes(32, "little"))
-
-    def write_scalar(self, s):
-        self.common_scalar(s)
-        self.bytes += int(s % P).to_bytes(32, "little")
-
-    def write_point(self, pt):
-        x, y = pt if pt is not None else (0, 0)
-        self.state.update(b"\x01" + x.to_bytes(32, "little") + y.to_bytes(32, "little"))
-        enc = bytearray(x.to_bytes(32, "little"))
-        enc[31] |= (y & 1) << 6
-        self.bytes += enc
-
-    def squeeze_challenge(self):
-        self.state.update(b"\x00")
-        return int.from_bytes(self.state.copy().digest(), "little") % P
+        super().__init__("bn254")
 
 
 # -------------------------------------------------------------------------------------------- expressions ----

@@ -346,6 +346,47 @@ int h2_poly_lincomb_device(h2_curve_t curve, const h2_lincomb_job_t* jobs, size_
                            size_t n, void* stream);
 /* the largest n_points of a job.  Host only, no h2_init needed. */
 int h2_poly_lincomb_max_rounds(void);
+/* ---- the inner product argument on a registered SRS table --------------------------------------------------------
+ * The k rounds of halo2's IPA opening (poly/ipa/commitment/prover.rs create_proof) over the scalar field of `curve` (all
+ * three curves), n = 2^k.  The generators are never folded: the folded generators are fixed combinations of the original
+ * ones, G^(j)[i] = sum_{h < 2^j} s^(j)[h] G[h 2^(k-j) + i], so L_j and R_j are MSMs over the ORIGINAL table with expanded
+ * scalars.  `bases` holds exactly n + 2 points registered ONCE as  G[0 .. n) || U || W;  a round is one two-column MSM of
+ * n + 2 terms on it (slot n: z times the round's inner product, slot n + 1: the blind) and O(n) field products.
+ *   h2_ipa_state_bytes      size of the caller-owned, 16-byte aligned device buffer one opening works in: a and b (two
+ *                           generations each), the table s of challenge products, two columns of n + 2 and the partial
+ *                           sums.  Host only, no h2_init needed.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K or a null out.
+ *   h2_ipa_begin_device     a = the n coefficients d_p (only read), b[i] = x3^i, s = [1].  Whatever an earlier opening
+ *                           left in d_state does not matter.
+ *   h2_ipa_round_device     round j, 0 <= j < k, half = 2^(k-j-1).  For j > 0 it first folds by the PREVIOUS challenge:
+ *                           a[i] += a[i + 2 half] u_prev_inv, b[i] += b[i + 2 half] u_prev, s doubles (s[2h] = s[h],
+ *                           s[2h+1] = s[h] u_prev); u_prev and u_prev_inv are both null for j = 0 and both required
+ *                           otherwise.  Then  L_j = <a[half..], G'[..half]> + [z <a[half..], b[..half]>] U + [l_blind] W,
+ *                           R_j = <a[..half], G'[half..]> + [z <a[..half], b[half..]>] U + [r_blind] W  with G' the folded
+ *                           generators.  d_out_affine: 128 bytes, L_j || R_j, affine Montgomery limbs, identity = (0, 0).
+ *   h2_ipa_final_device     the last fold, by u_(k-1): d_out = c = a[0], then b[0] (64 bytes); d_s_out (optional, n
+ *                           elements) = the finished s = compute_s(u, 1), s[i] = prod over the set bits t of i of u_(k-1-t).
+ *   h2_ipa_challenge_products_device   compute_s(u, init) for a verifier: d_out[i] = init prod_{bit t of i} u_(k-1-t);
+ *                           u: k * 4 limbs on the HOST, read before the call returns.  <s, G> is then one h2_msm_device.
+ * Scalars (x3, z, blinds, challenges) are 4 x u64 Montgomery limbs on the host, canonical, read before the call returns;
+ * every output is canonical.  The calls of ONE opening are issued in order -- begin, round 0 .. k - 1, final -- on ONE
+ * stream; two openings may run side by side on their own states and streams.  The MSM goes through h2_msm_device's launch
+ * path (the stream's workspace slot, the host-side bounds proof, H2_EDEVICE with the violated condition); nothing else is
+ * allocated.  Asynchronous on `stream` under h2_ntt_device's rules: no host synchronisation, no device-to-host copy.
+ * H2_EINVAL -- checked on the host before anything is enqueued -- for: an unknown curve; k = 0 or k > H2_IPA_MAX_K (bounded
+ * by what a registered table of 2^k + 2 bases takes); j >= k; a null or not 16-byte aligned device pointer; a null scalar;
+ * a missing or superfluous u_prev / u_prev_inv; a handle of another curve or one that does not hold exactly 2^k + 2 bases
+ * (H2_EHANDLE for a handle that is not registered at all).  H2_ENOTINIT before h2_init.
+ * h2_version() did not change for these entry points, it stays 1002: a host detects them by their symbols. */
+#define H2_IPA_MAX_K 20
+int h2_ipa_state_bytes(uint32_t k, size_t* out);
+int h2_ipa_begin_device(h2_curve_t curve, uint32_t k, const void* d_p, const uint64_t x3[4], void* d_state, void* stream);
+int h2_ipa_round_device(h2_curve_t curve, uint64_t bases, uint32_t k, uint32_t j, void* d_state, const uint64_t* u_prev,
+                        const uint64_t* u_prev_inv, const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4],
+                        void* d_out_affine, void* stream);
+int h2_ipa_final_device(h2_curve_t curve, uint32_t k, void* d_state, const uint64_t u_last[4], const uint64_t u_last_inv[4],
+                        void* d_out, void* d_s_out, void* stream);
+int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out,
+                                     void* stream);
 /* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
  * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
  * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER

@@ -781,6 +781,12 @@ __device__ __forceinline__ Xyzz29<CV> xyzz_shfl_down(const Xyzz29<CV>& p, uint32
   return r;
 }
 
+// lane R of every quad's point, replicated across the quad: the form xyzz29_add_quad works on (h2_curve_quad.hpp)
+template <int R, class CV>
+__device__ __forceinline__ Xyzz29<CV> xyzz_quad_bcast(const Xyzz29<CV>& p) {
+  return Xyzz29<CV>{quad_bcast<R>(p.x), quad_bcast<R>(p.y), quad_bcast<R>(p.zz), quad_bcast<R>(p.zzz)};
+}
+
 // Hand-off of a block's result to the block that arrives last at a counter (msm_final_kernel, msm_small_kernel), in the
 // form MI355X_MICROARCH.md prescribes for data written by one XCD and read on another: the storing lane waits for its
 // stores, releases at agent scope, waits again (ROCm 7.2 can drop the wait behind the write-back when it believes
@@ -826,13 +832,18 @@ __device__ __forceinline__ Xyzz29<CV> msm_piece(const uint32_t* __restrict__ hea
 // arrives LAST for a key adds the key's partials and writes xsum[key].  Last-arrival hand-off only (the form of
 // msm_final_kernel): no wave ever waits for another, so nothing can hang beside another stream's kernels.
 //
-// The blocks behind them: G lanes = G/4 quads per key (G = 2^log_g, 4 <= G <= 64).  The quads of a key share out its
-// pieces, then a shuffle tree across the quads; lane 0 writes xsum[key], the bucket's point sum.  The lanes of hot keys
-// skip: their sum comes from the task waves, which run beside these blocks rather than in front of them.
+// The blocks behind them: F lanes per key (F = 2^log_f, 4 <= F <= 64, chosen by msm_workspace), in two stages.
+// Stage 1, throughput: lane l folds pieces l, l + F, ... by itself with the one-lane xyzz29_add -- a lane's addition is
+// twice as long as a quad's (7.2 us against 3.5) but a wave of them delivers twice the additions per second (9.1 G/s
+// against 4.6 at one wave per SIMD, tools/microbench_tail.hip), and the bulk of a bucket's ~24 pieces needs the rate.
+// Stage 2, latency: quad q of the key takes the partial sums of its own four lanes in the quad form (each replicated
+// across the quad by a quad_perm broadcast) and adds them, then a shuffle tree across the key's F/4 quads; lane 0 writes
+// xsum[key], the bucket's point sum.  The lanes of hot keys skip: their sum comes from the task waves, which run beside
+// these blocks rather than in front of them.
 inline uint32_t msm_fixup_task_blocks(uint32_t max_tasks) { return std::min<uint32_t>(256u, (max_tasks + 3) / 4); }
 template <class CV>
 __global__ void __launch_bounds__(256)
-msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host, uint32_t log_g,
+msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host, uint32_t log_f,
                  const uint32_t* __restrict__ bucket_sum, const uint32_t* __restrict__ head,
                  const uint32_t* __restrict__ tail, const uint32_t* __restrict__ hot_slot,
                  const uint32_t* __restrict__ tasks, const uint32_t* __restrict__ task_count, uint32_t max_tasks,
@@ -868,12 +879,11 @@ msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host
     }
     return;
   }
-  const uint32_t G = 1u << log_g;
+  const uint32_t F = 1u << log_f;
   const size_t gt = (size_t)(blockIdx.x - task_blocks) * blockDim.x + threadIdx.x;
-  const size_t key = gt >> log_g;
-  const uint32_t lane = (uint32_t)gt & (G - 1);
-  const uint32_t quad = lane >> 2, nquad = G >> 2;
-  // all lanes of a wave stay in the shuffle tree together; out-of-range keys work on identities
+  const size_t key = gt >> log_f;
+  const uint32_t lane = (uint32_t)gt & (F - 1);
+  // all lanes of a wave stay in stage 2 and the shuffle tree together; out-of-range keys work on identities
   bool live = key < K;
   Xyzz29<CV> x = Xyzz29<CV>::identity();
   if (live) {
@@ -881,22 +891,26 @@ msm_fixup_kernel(const uint32_t* __restrict__ offsets, size_t K, uint32_t T_host
     if (e > s) {
       const uint32_t j0 = s / T, j1 = (e - 1) / T;
       if (j0 == j1) {
-        if (quad == 0) x = xyzz29_load<CV>(bucket_sum + XYZZ29_WORDS * key);
+        if (lane == 0) x = xyzz29_load<CV>(bucket_sum + XYZZ29_WORDS * key);
       } else if (hot_slot[key] != MSM_NOT_HOT) {
         live = false;                                      // summed by the task waves
-      } else if (quad <= j1 - j0) {
+      } else if (lane <= j1 - j0) {
         // the next piece is on its way while the current one is added (a piece is 144 bytes from HBM: ~1.5 us exposed
-        // per addition otherwise, the chain has nothing else to do)
-        Xyzz29<CV> nxt = msm_piece<CV>(head, tail, s, j0, T, quad);
-        for (uint32_t p = quad; p <= j1 - j0; p += nquad) {
+        // per addition otherwise, the chain has nothing else to do).  The lanes are on their own here: equal pieces,
+        // inverse pieces and the identity are xyzz29_add's business
+        Xyzz29<CV> nxt = msm_piece<CV>(head, tail, s, j0, T, lane);
+        for (uint32_t p = lane; p <= j1 - j0; p += F) {
           const Xyzz29<CV> cur = nxt;
-          if (p + nquad <= j1 - j0) nxt = msm_piece<CV>(head, tail, s, j0, T, p + nquad);
-          x = xyzz29_add_quad(x, cur);
+          if (p + F <= j1 - j0) nxt = msm_piece<CV>(head, tail, s, j0, T, p + F);
+          x = xyzz29_add(x, cur);
         }
       }
     }
   }
-  for (uint32_t d = G >> 1; d >= 4; d >>= 1) x = xyzz_fold_down(x, d, lane);
+  const Xyzz29<CV> mine = x;
+  x = xyzz29_add_quad(xyzz29_add_quad(xyzz_quad_bcast<0>(mine), xyzz_quad_bcast<1>(mine)),
+                      xyzz29_add_quad(xyzz_quad_bcast<2>(mine), xyzz_quad_bcast<3>(mine)));
+  for (uint32_t d = F >> 1; d >= 4; d >>= 1) x = xyzz_fold_down(x, d, lane);
   if (live && lane == 0) xyzz29_store<CV>(xsum + XYZZ29_WORDS * key, x);
 }
 
@@ -1293,7 +1307,8 @@ struct MsmWorkspace {
   size_t nblk;          // scan blocks
   uint32_t T;           // sorted entries per accumulate thread
   size_t nchunks;       // ceil(E / T)
-  uint32_t log_g;       // lanes per key in the fix-up kernel = 2^log_g
+  uint32_t pieces;      // pieces per key the layout assumes: list length / T + 1
+  uint32_t log_f;       // lanes per key in the fix-up kernel = 2^log_f
   uint32_t tile;        // scalars per block in the digits / scatter kernels
   uint32_t staged;      // the scatter stages its tile in LDS (msm_scatter_staged_kernel); stage_lds bytes of dynamic LDS
   size_t stage_lds;
@@ -1367,15 +1382,19 @@ inline MsmWorkspace msm_workspace(size_t n, size_t m, const MsmGeom& g, uint32_t
     if (ws.nchunks < fine) ws.nchunks = fine;
   }
   // pieces per key ~ list length / T + 1
-  const double span = (double)g.W * (double)n / (double)g.B / (double)T + 1.0;
-  // quads per key in the fix-up: no more than the pieces need, and few enough that the launch stays around
-  // two waves per SIMD (K * Q * 4 lanes <= 160k): wider groups waste most of their quads in the shuffle tree
-  uint32_t lq = 0;
-  while ((1u << lq) < span && lq < 4) lq++;
-  while (lq > 0 && (ws.K << lq) > 40960) lq--;
-  lq = (uint32_t)tune_int("H2_TUNE_LQ", (int)lq);   // tuning builds only (h2_tune.hpp)
-  uint32_t lg = lq + 2;
-  ws.log_g = lg;
+  ws.pieces = (uint32_t)std::min<uint64_t>((uint64_t)g.W * n / ((uint64_t)g.B * T) + 1, 1u << 30);
+  // Lanes per key in the fix-up, F = 2^log_f.  Stage 1 of msm_fixup_kernel is bound by the rate of one-lane
+  // additions, which is highest per wave when a SIMD holds ONE wave of them (two waves share its issue slots and
+  // each chain runs at half speed): the largest F with K * F <= 65536 lanes = 1024 SIMDs x 64.  Never more lanes
+  // than a key has pieces (the rest would only sit in the shuffle tree), and a quad at least: stage 2 works on quads.
+  // Swept at 2^16 with F = 4, 8, 16 (profiles/msm_fixup_parent_vs_branch.txt, kernel us): m = 3: 77 / 54 / 61,
+  // m = 4: 60 / 40 / 51, m = 5: 50 / 52 / 50, m = 6: 45 / 60 / 53 -- the rule's F (8, 8, 4, 4) at each m, also where
+  // the launch is short of one wave per SIMD (768 waves at m = 3, 640 at m = 5); the all-quad form it replaces took
+  // 74 / 57 / 58 / 65 and is not kept at any column count.
+  uint32_t lf = 2;
+  while (lf < 6 && (1u << lf) < ws.pieces && (ws.K << (lf + 1)) <= 65536) lf++;
+  lf = (uint32_t)tune_int("H2_TUNE_LF", (int)lf);   // tuning builds only (h2_tune.hpp)
+  ws.log_f = lf;
   ws.sort2 = msm_use_sort2(n, m, g) ? 1u : 0u;
   ws.s2 = msm_sort2_geom(n, g, allow_pack ? n_bases : 0);
   // digits / scatter tiling: about 1024 blocks over the launch, at least one wave of scalars per block
@@ -1565,7 +1584,9 @@ inline const char* msm_check(const MsmWorkspace& ws, const MsmGeom& g, size_t n,
   MSM_REQUIRE(bytes_at(ws.off_key) >= ws.nchunks * 4);
   MSM_REQUIRE(bytes_at(ws.off_head) >= ws.nchunks * (XYZZ29_WORDS * 4) && bytes_at(ws.off_tail) >= ws.nchunks * (XYZZ29_WORDS * 4));
   MSM_REQUIRE(bytes_at(ws.off_bsum) >= ws.K * (XYZZ29_WORDS * 4) && bytes_at(ws.off_xsum) >= ws.K * (XYZZ29_WORDS * 4));
-  MSM_REQUIRE(ws.log_g >= 2 && ws.log_g <= 6 && ((ws.K << ws.log_g) + 255) / 256 < (1ull << 31));
+  // a key's F lanes: whole quads (stage 2 of msm_fixup_kernel) inside one wave (its shuffle tree), so F divides the
+  // block's 256 lanes and no key is split between blocks; the lanes of the last block past K * F work on identities
+  MSM_REQUIRE(ws.log_f >= 2 && ws.log_f <= 6 && ((ws.K << ws.log_f) + 255) / 256 < (1ull << 31));
   MSM_REQUIRE(ws.lb < g.c && ws.rc == (1u << (g.c - 1 - ws.lb)) + (1u << ws.lb));
   MSM_REQUIRE(bytes_at(ws.off_rc) >= m * ws.rc * (XYZZ29_WORDS * 4));
   MSM_REQUIRE(msm_final_blocks(g.c - 1, ws.lb) <= MSM_FINAL_MAX_BLOCKS);
@@ -1576,7 +1597,7 @@ inline const char* msm_check(const MsmWorkspace& ws, const MsmGeom& g, size_t n,
   MSM_REQUIRE(bytes_at(ws.off_hot_part) >= (size_t)ws.max_tasks * (XYZZ29_WORDS * 4));
   MSM_REQUIRE(bytes_at(ws.off_hot_arrive) >= (size_t)ws.max_tasks * 4);                  // a hot key's counter sits at its first slot
   MSM_REQUIRE(ws.max_tasks >= 1 && msm_fixup_task_blocks(ws.max_tasks) >= 1);
-  MSM_REQUIRE(((ws.K << ws.log_g) + 255) / 256 + msm_fixup_task_blocks(ws.max_tasks) < (1ull << 31));
+  MSM_REQUIRE(((ws.K << ws.log_f) + 255) / 256 + msm_fixup_task_blocks(ws.max_tasks) < (1ull << 31));
   MSM_REQUIRE(m <= 65535);                                               // grid.y of the row / column and final kernels
   return nullptr;
 }
@@ -1682,10 +1703,10 @@ inline hipError_t msm_launch_back(const U128* table, const U128** d_tables, uint
                        (const U128* const*)d_tables, log_b, sref, chunk_first, offsets, ws.K, ws.T, bsum, head, tail);
   if (ev_stop && ev_tail) (void)hipEventRecord(ev_tail, stream);
   // hot tasks and the buckets' pieces in one launch: the task blocks come first in the grid
-  const size_t fix_threads = ws.K << ws.log_g;
+  const size_t fix_threads = ws.K << ws.log_f;
   const uint32_t task_blocks = msm_fixup_task_blocks(ws.max_tasks);
   hipLaunchKernelGGL(msm_fixup_kernel<CV>, dim3((unsigned)((fix_threads + 255) / 256) + task_blocks), dim3(256), 0, stream, offsets,
-                     ws.K, ws.T, ws.log_g, bsum, head, tail, hot_slot, hot_tasks, misc, ws.max_tasks, task_blocks, hot_part,
+                     ws.K, ws.T, ws.log_f, bsum, head, tail, hot_slot, hot_tasks, misc, ws.max_tasks, task_blocks, hot_part,
                      hot_arrive, xsum);
   uint32_t* part = (uint32_t*)(ws_base + ws.off_part);
   uint32_t* done = (uint32_t*)(ws_base + ws.off_done);

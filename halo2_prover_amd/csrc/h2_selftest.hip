@@ -284,6 +284,22 @@ extern "C" int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t
   out[8] = msm_effective_t((uint32_t)ws.E, ws.T); out[9] = MSM_HOT_SPAN; out[10] = MSM_HOT_SEG; out[11] = ws.max_tasks;
   return H2_OK;
 }
+// host only: the fix-up kernel's share of the same layout -- of the first launch, where msm_plan_group cuts the m
+// columns into several; out: include/h2hip_selftest.h
+extern "C" int h2_selftest_msm_fixup(int curve, size_t n_bases, size_t n, size_t m, uint64_t out[4]) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !out || n == 0 || m == 0 || n > n_bases || n_bases >= (1ull << 31)) return H2_EINVAL;
+  const MsmGeom g = msm_geometry(n_bases, ops->scalar_bits);
+  const MsmGroupPlan plan = msm_plan_group(g, n_bases, n, m, n, false, true);
+  const MsmWorkspace& ws = plan.ws;
+  if (plan.broken) {
+    g_h2.last_error = std::string("msm launch geometry: ") + plan.broken;
+    return H2_EINVAL;
+  }
+  out[0] = ws.log_f; out[1] = ws.K << ws.log_f; out[2] = ws.pieces; out[3] = ws.T;
+  return H2_OK;
+}
 // scratch arenas of the current context: out = {allocations (first use or growth), cross-stream hand-overs (event waits),
 // MSM slots taken over, NTT slots taken over}
 extern "C" int h2_selftest_arena_stats(uint64_t out[4]) {

@@ -141,6 +141,7 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_set_shard_min_rows": (_I, [_Z]),
     "h2_selftest_msm_check": (_I, [_I, _Z, _Z, _Z, _Z, _I, _P]),
     "h2_selftest_msm_front": (_I, [_I, _Z, _Z, _Z, _I, _P]),
+    "h2_selftest_msm_fixup": (_I, [_I, _Z, _Z, _Z, _P]),
     "h2_selftest_msm_tiles": (_I, [_U32, _U32]),
     "h2_selftest_msm_guard": (_I, [_I]),
     "h2_selftest_msm_guard_report": (_I, [_P, _P, _Z]),

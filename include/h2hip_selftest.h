@@ -48,6 +48,9 @@ int h2_selftest_set_msm_max_entries(uint64_t limit);
  *   bytes, packed staged entries?, bits of a packed entry's bucket, index-in-tile and window fields, 1 if the bounds
  *   proof held; out[8..11] = entries per accumulate thread when every digit of the launch is non-zero (fewer entries
  *   never give more), the pieces above which a bucket takes the hot-task path, the pieces per hot task, the task slots.
+ * h2_selftest_msm_fixup: host only -- the fix-up kernel's share of that layout (of the first launch, where the m columns
+ *   take several).  out[0..3] = log2 of the lanes per key F,
+ *   lanes of the launch (keys * F, without the task blocks), pieces per key the rule assumed, entries per accumulate thread.
  * h2_selftest_msm_tiles: host only -- the one-level sort's block -> (column, tile) mapping is a bijection onto the
  *   live pairs and every surplus block of the rounded-up grid is dead.
  * h2_selftest_msm_guard(1): from now on every MSM launch lays its arena out with a 256-byte red zone behind every
@@ -60,6 +63,7 @@ int h2_selftest_set_msm_max_entries(uint64_t limit);
  *   `first` = a description of the first one. */
 int h2_selftest_msm_check(int curve, size_t n_bases, size_t n, size_t m, size_t col_stride, int guard, uint64_t out[8]);
 int h2_selftest_msm_front(int curve, size_t n_bases, size_t n, size_t m, int pack, uint64_t out[12]);
+int h2_selftest_msm_fixup(int curve, size_t n_bases, size_t n, size_t m, uint64_t out[4]);
 int h2_selftest_msm_tiles(uint32_t tiles, uint32_t m);
 int h2_selftest_msm_guard(int on);
 int h2_selftest_msm_guard_report(uint64_t out[2], char* first, size_t cap);

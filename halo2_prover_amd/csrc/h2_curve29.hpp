@@ -6,6 +6,26 @@
 // normalised limbs; with that, each product below has one operand with limbs < 2^29 in magnitude and the other
 // < 2^30, and every pair of operand values satisfies |a| |b| <= 64 p^2 (bounds in units of p are noted on the right).
 //
+// The contract of the six routines (xyzz29_add, xyzz29_double, xyzz29_add_affine, xyzz29_double_affine here,
+// xyzz29_add_quad and xyzz29_double_quad in h2_curve_quad.hpp); the margin notes below are written against it:
+//   a STORED XYZZ point   limbs normalised (limbs 0..7 in [0, 2^29), the top limb signed);
+//                         x in (-3p, 5p), y in (-2p, 2p), zz and zzz in (-3p/2, p)   (y's range is symmetric because
+//                         xyzz29_neg, h2_group_fft.hpp, negates it; zz = zzz = the canonical one of xyzz29_from_affine
+//                         is why the upper end is p and not p/2);
+//                         identity <=> zz has all limbs zero (no other coordinate of the identity means anything).
+//   an AFFINE operand     x canonical and unpacked; y canonical, or its limb-wise negation (limbs in (-2^29, 0]: what
+//                         affine29_load hands over for a negative digit); identity <=> x and y both exactly zero.
+//   CLOSURE               every routine, on operands anywhere in these ranges, returns a stored point in them (the
+//                         one-lane forms return y in (-3p/2, p/2], the quad forms use the whole (-2p, 2p)).
+// Under it every product has |a| |b| <= 64 p^2 and every fe29_is_zero_mod_p sees |x| < 16 p.  Largest seen over the
+// operand sets of tests/test_xyzz29_ranges.py (observations, not bounds; the bounds stay 64 and 16):
+//   xyzz29_add, xyzz29_add_quad            product 25.0 p^2    zero test 1.99 p
+//   xyzz29_double, xyzz29_double_quad      product 25.0 p^2    zero test 2.00 p
+//   xyzz29_add_affine                      product 35.1 p^2    zero test 5.93 p   (u2 - acc.x = j p for j = -5 .. 3)
+//   xyzz29_double_affine                   product  8.4 p^2    zero test 1.00 p
+// A computed x lands in about (-p, 3p) (three products of small magnitude, each rounded down by less than p): the
+// ranges above are what the formulas can take, wider than what they produce.
+//
 // Memory: a table point is 64 bytes -- (x, y) as 2 x 256-bit integers in R' form, canonical, identity (0, 0) --
 // unpacked on load; an XYZZ partial sum is 36 words (4 coordinates x 9 limbs, 144 bytes).
 #pragma once
@@ -26,7 +46,7 @@ struct Affine29 {
 template <class CV>
 struct Xyzz29 {
   using F = Fe29<typename CV::Base>;
-  F x, y, zz, zzz;                                       // |x| < 5p, |y| < 2p, zz, zzz in (-3p/2, p/2]
+  F x, y, zz, zzz;                                       // x in (-3p, 5p), |y| < 2p, zz, zzz in (-3p/2, p): the contract above
   H2_HD bool is_identity() const { return zz.is_zero_exact(); }
   static H2_HD Xyzz29 identity() { return Xyzz29{F::zero(), F::zero(), F::zero(), F::zero()}; }
 };

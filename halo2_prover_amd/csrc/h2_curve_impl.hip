@@ -454,6 +454,49 @@ int selftest_curve(int op, const uint64_t* p_, const uint64_t* q_, uint64_t* out
   memcpy(out + 4, a.y.v, 32);
   return 0;
 }
+// The working-form group law on RAW operands (h2_selftest_xyzz29_op*): in = operand A then operand B as xyzz29_store
+// writes them (x, y, zz, zzz, 9 limbs each; the affine ops read B's x and y only), out = the result's 36 limbs as
+// xyzz29_store writes them -- no conversion and no normalisation on either side.  Ops 0..3 are one source for the host
+// hook and the device kernel
+H2_HD Xyzz29<CV> selftest_xyzz29_run(int op, const Xyzz29<CV>& A, const Xyzz29<CV>& B) {
+  const Affine29<CV> b{B.x, B.y};
+  switch (op) {
+    case 0: return xyzz29_add(A, B);
+    case 1: return xyzz29_double(A);
+    case 2: return xyzz29_add_affine(A, b);
+    default: return xyzz29_double_affine(b);
+  }
+}
+int selftest_xyzz29(int op, const int32_t* in, int32_t* out) {
+  if (op < 0 || op > 3) return -1;
+  const Xyzz29<CV> A = xyzz29_load<CV>((const uint32_t*)in), B = xyzz29_load<CV>((const uint32_t*)in + XYZZ29_WORDS);
+  xyzz29_store((uint32_t*)out, selftest_xyzz29_run(op, A, B));
+  return 0;
+}
+// n operand pairs, four lanes per pair; EVERY lane stores its own copy of the result (out: n x 4 x 36 words), so that
+// the quad forms' replication can be checked.  Ops 4 / 5: the quad forms, 6 / 7: the affine forms on Fe29Chain
+__global__ void __launch_bounds__(64)
+selftest_xyzz29_kernel(int op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = t >> 2;
+  if (i >= n) return;
+  const Xyzz29<CV> A = xyzz29_load<CV>(in + 2 * XYZZ29_WORDS * (size_t)i),
+                   B = xyzz29_load<CV>(in + 2 * XYZZ29_WORDS * (size_t)i + XYZZ29_WORDS);
+  const Affine29<CV> b{B.x, B.y};
+  Xyzz29<CV> r;
+  switch (op) {
+    case 4: r = xyzz29_add_quad(A, B); break;
+    case 5: r = xyzz29_double_quad(A); break;
+    case 6: r = xyzz29_add_affine<CV, Fe29Chain>(A, b); break;
+    case 7: r = xyzz29_double_affine<CV, Fe29Chain>(b); break;
+    default: r = selftest_xyzz29_run(op, A, B); break;
+  }
+  xyzz29_store(out + XYZZ29_WORDS * (size_t)t, r);
+}
+hipError_t selftest_xyzz29_device(int op, const void* d_in, void* d_out, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(selftest_xyzz29_kernel, dim3((4 * n + 63) / 64), dim3(64), 0, s, op, (const uint32_t*)d_in,
+                     (uint32_t*)d_out, n);
+  return hipGetLastError();
+}
 // out[0..3] = c, W, B, nbits; out[4 + w] = encoded digit of window w (host run of msm_digit_step);
 // out[4 + W + w] = first bit of window w; out[4 + 2W + w] = its width
 int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t* out, uint32_t cap) {
@@ -480,7 +523,8 @@ const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, tabl
                       to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_launch<FS>, ipa_round_launch<FS>, ipa_final_launch<FS>,
                       ipa_s_products_launch<FS>, selftest_field, selftest_curve,
-                      selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate};
+                      selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate,
+                      chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device};
 
 }  // namespace
 

@@ -171,6 +171,12 @@ struct CurveOps {
   int (*selftest_digits)(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t* out, uint32_t cap);
   // dependent working-form products of the base field on `blocks` x 256 threads: measured modmul/s (best of 3)
   hipError_t (*modmul_rate)(int blocks, int iters, hipStream_t s, double* modmul_per_s);
+  // the working-form group law on raw operands (h2_selftest_xyzz29_op*): in = two stored XYZZ points of 36 limbs, out = the
+  // result's 36 limbs.  Host: ops 0..3.  Device: n pairs, four lanes per pair, each lane stores its own copy (n x 4 x 36
+  // limbs); ops 4 / 5 the quad forms, 6 / 7 the affine forms on Fe29Chain (a form of its own only where base_chain29)
+  bool base_chain29;
+  int (*selftest_xyzz29)(int op, const int32_t* in, int32_t* out);
+  hipError_t (*selftest_xyzz29_device)(int op, const void* d_in, void* d_out, uint32_t n, hipStream_t s);
 };
 
 const CurveOps* curve_ops_bn254();

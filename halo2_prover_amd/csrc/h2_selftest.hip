@@ -129,6 +129,33 @@ extern "C" int h2_selftest_curve_op(int curve, int op, const uint64_t p[8], cons
   if (!ops || !p || !q || !out) return H2_EINVAL;
   return ops->selftest_curve(op, p, q, out) == 0 ? H2_OK : H2_EINVAL;
 }
+// the working-form group law on raw operands, host instantiation: no GPU and no h2_init
+extern "C" int h2_selftest_xyzz29_op(int curve, int op, const int32_t in[72], int32_t out[36]) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !in || !out || op < 0 || op > 3) return H2_EINVAL;
+  return ops->selftest_xyzz29(op, in, out) == 0 ? H2_OK : H2_EINVAL;
+}
+// n operand pairs (72 limbs each, host pointer) through the DEVICE instantiation, one kernel launch, four lanes per pair;
+// out: n x 4 x 36 limbs, a copy of the result from every lane of the quad
+extern "C" int h2_selftest_xyzz29_op_device(int curve, int op, const int32_t* in, int32_t* out, size_t n) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (!g_h2.ready) return H2_ENOTINIT;
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !in || !out || n == 0 || n > (1u << 20) || op < 0 || op > 7) return H2_EINVAL;
+  if (op >= 6 && !ops->base_chain29) return H2_EINVAL;       // the chain forms exist only for p = 1 mod 2^29
+  DevCtx& g_ctx = g_h2.ctx[0];
+  DeviceGuard dg(g_ctx.device);
+  const size_t in_bytes = n * 72 * 4, out_bytes = n * 4 * 36 * 4;
+  ArenaLease stage(g_ctx.stage, in_bytes + out_bytes, g_ctx.stream);
+  if (stage.rc != H2_OK) return stage.rc;
+  char* d = (char*)g_ctx.stage.p;
+  H2_TRY(hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, g_ctx.stream));
+  if (int rc = launched(ops->selftest_xyzz29_device(op, d, d + in_bytes, (uint32_t)n, g_ctx.stream), "selftest_xyzz29_kernel");
+      rc != H2_OK)
+    return rc;
+  H2_TRY(hipMemcpyAsync(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, g_ctx.stream));
+  return stage.wait();
+}
 extern "C" int h2_selftest_digits(int curve, const uint64_t scalar[4], size_t n_for_geometry, uint32_t* out,
                                   uint32_t cap) {
   const CurveOps* ops = ops_of(curve);

@@ -149,6 +149,8 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_fe29_op": (_I, [_I, _I, _P, _P]),
     "h2_selftest_fe29_op_device": (_I, [_I, _I, _P, _P, _Z]),
     "h2_selftest_fe29_chain_device": (_I, [_I, _I, _P, _P, _P, _Z]),
+    "h2_selftest_xyzz29_op": (_I, [_I, _I, _P, _P]),
+    "h2_selftest_xyzz29_op_device": (_I, [_I, _I, _P, _P, _Z]),
     "h2_selftest_pairing_checks": (_U64, []),
     "h2_selftest_expr_run": (_I, [_P, _Z, _P, _P, _U32, _U32, _U32, _P, _P]),
 }

@@ -139,6 +139,20 @@ int h2_selftest_fe29_op_device(int field, int op, const int32_t* in, int32_t* ou
  * form (h2_field29.hpp), out_chain = the single-chain form the accumulate kernel and the NTT pass use
  * (h2_field29_chain.hpp); n x 9 limbs each, one kernel launch.  The two must be equal limb for limb */
 int h2_selftest_fe29_chain_device(int field, int op, const int32_t* in, int32_t* out_cpp, int32_t* out_chain, size_t n);
+/* the working-form group law (csrc/h2_curve29.hpp) on RAW operands, instantiated on the host, no GPU and no h2_init:
+ * in = operand A then operand B, each a stored XYZZ point (x, y, zz, zzz of 9 signed 29-bit-radix limbs, anywhere in the
+ * ranges of the stored-point contract at the top of h2_curve29.hpp); for the affine ops B's first 18 limbs are (x, y)
+ * and the rest is ignored.  op 0: xyzz29_add(A, B), 1: xyzz29_double(A), 2: xyzz29_add_affine(A, b),
+ * 3: xyzz29_double_affine(b), the affine ops on the default product policy -> the result's 36 limbs exactly as
+ * xyzz29_store writes them (no conversion, no normalisation added) */
+int h2_selftest_xyzz29_op(int curve, int op, const int32_t in[72], int32_t out[36]);
+/* the same through the DEVICE instantiation: n operand pairs (72 limbs each, host pointer), one kernel launch, four
+ * lanes per pair; out = n x 4 x 36 limbs: EVERY lane of the quad writes its own copy of the result.  op 0..3 as on the
+ * host (the one-lane forms run in all four lanes on the same data), 4: xyzz29_add_quad(A, B), 5: xyzz29_double_quad(A)
+ * (csrc/h2_curve_quad.hpp), 6 / 7: xyzz29_add_affine / xyzz29_double_affine on the single-chain products as the
+ * accumulate kernel instantiates them (Fe29Chain) -- only where that form exists (Pallas, Vesta); H2_EINVAL and
+ * nothing written for BN254.  The limbs of 6 / 7 must equal those of 2 / 3 */
+int h2_selftest_xyzz29_op_device(int curve, int op, const int32_t* in, int32_t* out, size_t n);
 /* the quotient program's kernel (expr_kernel) on a caller's DAG (the format of h2_selftest_host what = 7), launched
  * as the prover launches it: ncols host columns, concatenated, column c of 2^log_len[c] elements (4 x u64, x 2^256
  * canonical) read at row (i + rot * step) & (2^log_len[c] - 1); out = the 2^log_en results (4 x u64 each, canonical);

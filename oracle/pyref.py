@@ -640,3 +640,223 @@ def expr_kernel_row(code, consts_working, column_at, p, steps=None):
         if steps is not None:
             steps.append((op, a, b, r, dst))
     return fe29_to_api(r, p)
+
+
+# ---- the XYZZ group law on the working form (h2_curve29.hpp, h2_curve_quad.hpp), limb for limb ----------------------------
+# A stored point is (x, y, zz, zzz), four lists of nine limbs; an affine operand is (x, y).  The operations come in the
+# order of the HIP source, so the limbs are the ones xyzz29_store writes.  `chk` (an Fe29Check, optional) asserts the
+# preconditions of every product and zero test on the way and records how close the operands came to them.
+
+def fe29_neg(a):
+    return [_i32(-x) for x in a]
+
+
+class Fe29Check:
+    """the checking mode of the xyzz29_* models: fe29_mul_limbs_ok and |a| |b| <= 64 p^2 at every product (|a b - c d| for
+    fe29_mul_sub, every limb below 2^29 for fe29_sqr and fe29_mul_sub), |x| < 16 p at every fe29_is_zero_mod_p.  Keeps
+    the largest product seen (in units of p^2), the largest |x| / p at a zero test, and the multiples j of p that the
+    zero tests met, per name"""
+
+    def __init__(self, p):
+        self.p = p
+        self.max_product = 0.0
+        self.max_zero_test = 0.0
+        self.zero_multiples = {}
+
+    def _product(self, x):
+        assert abs(x) <= 64 * self.p * self.p, "product past 64 p^2"
+        self.max_product = max(self.max_product, abs(x) / (self.p * self.p))
+
+    def mul(self, a, b):
+        assert fe29_mul_limbs_ok(a, b), "fe29_mul limb bounds"
+        self._product(fe29_value(a) * fe29_value(b))
+
+    def sqr(self, a):
+        assert all(abs(v) < 1 << 29 for v in a), "fe29_sqr limb bounds"
+        self._product(fe29_value(a) ** 2)
+
+    def mul_sub(self, a, b, c, d):
+        assert all(abs(v) < 1 << 29 for o in (a, b, c, d) for v in o), "fe29_mul_sub limb bounds"
+        self._product(fe29_value(a) * fe29_value(b) - fe29_value(c) * fe29_value(d))
+
+    def zero_test(self, a, name):
+        x = fe29_value(a)
+        assert abs(x) < 16 * self.p, "zero test past 16 p"
+        self.max_zero_test = max(self.max_zero_test, abs(x) / self.p)
+        if name and x % self.p == 0:
+            self.zero_multiples.setdefault(name, set()).add(x // self.p)
+
+
+class _Fe29Ops:
+    """the products of one model run: Fe29Compiler's (the chain forms give the same limbs), checked if chk is given"""
+
+    def __init__(self, p, chk):
+        self.p, self.chk = p, chk
+        self.pinv29 = _pinv(p) & FE29_MASK
+
+    def mul(self, a, b):
+        if self.chk:
+            self.chk.mul(a, b)
+        return fe29_mul(a, b, self.p)
+
+    def sqr(self, a):
+        if self.chk:
+            self.chk.sqr(a)
+        return fe29_reduce(fe29_value(a) ** 2, self.p)
+
+    def mul_sub(self, a, b, c, d):
+        if self.chk:
+            self.chk.mul_sub(a, b, c, d)
+        return fe29_reduce(fe29_value(a) * fe29_value(b) - fe29_value(c) * fe29_value(d), self.p)
+
+    def is_zero(self, a, name=None):
+        """fe29_is_zero_mod_p: the one-limb window, then the complete reduction"""
+        if self.chk:
+            self.chk.zero_test(a, name)
+        j = (a[0] * self.pinv29) & FE29_MASK
+        if 16 < j < (1 << 29) - 16:
+            return False
+        return fe29_to_api(a, self.p) == 0
+
+
+XYZZ29_ZERO = [0] * 9
+
+
+def xyzz29_identity():
+    return (list(XYZZ29_ZERO), list(XYZZ29_ZERO), list(XYZZ29_ZERO), list(XYZZ29_ZERO))
+
+
+def xyzz29_is_identity(a):
+    return not any(a[2])
+
+
+def affine29_is_identity(q):
+    return not any(q[0]) and not any(q[1])
+
+
+def fe29_one(p):
+    return fe29_unpack(FE29_R % p)
+
+
+def xyzz29_from_affine(q, p):
+    if affine29_is_identity(q):
+        return xyzz29_identity()
+    return (list(q[0]), fe29_norm(q[1]), fe29_one(p), fe29_one(p))
+
+
+def xyzz29_double_affine(q, p, chk=None):
+    f = _Fe29Ops(p, chk)
+    if affine29_is_identity(q) or f.is_zero(q[1]):
+        return xyzz29_identity()
+    x, y = q
+    u = fe29_norm(fe29_add(y, y))
+    v = f.sqr(u)
+    w = f.mul(u, v)
+    s = f.mul(x, v)
+    xx = f.sqr(x)
+    m = fe29_norm(fe29_add(fe29_add(xx, xx), xx))
+    x3 = fe29_norm(fe29_sub(fe29_sub(f.sqr(m), s), s))
+    y3 = f.mul_sub(m, fe29_sub(s, x3), w, y)
+    return (x3, y3, v, w)
+
+
+def xyzz29_double(a, p, chk=None):
+    f = _Fe29Ops(p, chk)
+    if xyzz29_is_identity(a) or f.is_zero(a[1]):
+        return xyzz29_identity()
+    x, y, zz, zzz = a
+    u = fe29_norm(fe29_add(y, y))
+    v = f.sqr(u)
+    w = f.mul(u, v)
+    s = f.mul(x, v)
+    xx = f.sqr(x)
+    m = fe29_norm(fe29_add(fe29_add(xx, xx), xx))
+    x3 = fe29_norm(fe29_sub(fe29_sub(f.sqr(m), s), s))
+    y3 = f.mul_sub(m, fe29_sub(s, x3), w, y)
+    return (x3, y3, f.mul(v, zz), f.mul(w, zzz))
+
+
+def xyzz29_add_affine(acc, q, p, chk=None):
+    f = _Fe29Ops(p, chk)
+    if affine29_is_identity(q):
+        return acc
+    if xyzz29_is_identity(acc):
+        return xyzz29_from_affine(q, p)
+    x, y, zz, zzz = acc
+    u2 = f.mul(q[0], zz)
+    s2 = f.mul(q[1], zzz)
+    pd = fe29_sub(u2, x)
+    r = fe29_sub(s2, y)
+    if f.is_zero(pd, "add_affine.p"):
+        if f.is_zero(r, "add_affine.r"):
+            return xyzz29_double_affine(q, p, chk)
+        return xyzz29_identity()
+    pp = f.sqr(pd)
+    ppp = f.mul(pd, pp)
+    qq = f.mul(x, pp)
+    x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(f.sqr(r), ppp), qq), qq))
+    y3 = f.mul_sub(r, fe29_sub(qq, x3), y, ppp)
+    return (x3, y3, f.mul(zz, pp), f.mul(zzz, ppp))
+
+
+def xyzz29_add(a, b, p, chk=None):
+    f = _Fe29Ops(p, chk)
+    if xyzz29_is_identity(a):
+        return b
+    if xyzz29_is_identity(b):
+        return a
+    u1 = f.mul(a[0], b[2])
+    u2 = f.mul(b[0], a[2])
+    s1 = f.mul(a[1], b[3])
+    s2 = f.mul(b[1], a[3])
+    pd = fe29_sub(u2, u1)
+    r = fe29_sub(s2, s1)
+    if f.is_zero(pd, "add.p"):
+        if f.is_zero(r, "add.r"):
+            return xyzz29_double(a, p, chk)
+        return xyzz29_identity()
+    pp = f.sqr(pd)
+    ppp = f.mul(pd, pp)
+    qq = f.mul(u1, pp)
+    x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(f.sqr(r), ppp), qq), qq))
+    y3 = f.mul_sub(r, fe29_sub(qq, x3), s1, ppp)
+    return (x3, y3, f.mul(f.mul(a[2], b[2]), pp), f.mul(f.mul(a[3], b[3]), ppp))
+
+
+def xyzz29_double_quad(a, p, chk=None):
+    """xyzz29_double_quad: every product a plain fe29_mul (the lanes share one multiplication), zz3 from level 2, y3 the
+    normalised difference of two reduced products"""
+    f = _Fe29Ops(p, chk)
+    if xyzz29_is_identity(a) or f.is_zero(a[1]):
+        return xyzz29_identity()
+    x, y, zz, zzz = a
+    u = fe29_norm(fe29_add(y, y))
+    v, xx = f.mul(u, u), f.mul(x, x)
+    m = fe29_norm(fe29_add(fe29_add(xx, xx), xx))
+    w, s, mm, zz3 = f.mul(u, v), f.mul(x, v), f.mul(m, m), f.mul(v, zz)
+    x3 = fe29_norm(fe29_sub(fe29_sub(mm, s), s))
+    t0, t1, zzz3 = f.mul(m, fe29_sub(s, x3)), f.mul(w, y), f.mul(w, zzz)
+    y3 = fe29_norm(fe29_sub(t0, t1))
+    return (x3, y3, zz3, zzz3)
+
+
+def xyzz29_add_quad(a, b, p, chk=None):
+    """xyzz29_add_quad: zz12 / zzz12 are formed at level 2, before the products with pp / ppp; y3 is the normalised
+    difference of two reduced products"""
+    f = _Fe29Ops(p, chk)
+    if xyzz29_is_identity(a):
+        return b
+    if xyzz29_is_identity(b):
+        return a
+    u1, u2, s1, s2 = f.mul(a[0], b[2]), f.mul(b[0], a[2]), f.mul(a[1], b[3]), f.mul(b[1], a[3])
+    pd, r = fe29_sub(u2, u1), fe29_sub(s2, s1)
+    if f.is_zero(pd, "add_quad.p"):
+        if f.is_zero(r, "add_quad.r"):
+            return xyzz29_double_quad(a, p, chk)
+        return xyzz29_identity()
+    pp, rr, zz12, zzz12 = f.mul(pd, pd), f.mul(r, r), f.mul(a[2], b[2]), f.mul(a[3], b[3])
+    ppp, qq, zz3 = f.mul(pd, pp), f.mul(u1, pp), f.mul(zz12, pp)
+    x3 = fe29_norm(fe29_sub(fe29_sub(fe29_sub(rr, ppp), qq), qq))
+    t0, t1, zzz3 = f.mul(r, fe29_sub(qq, x3)), f.mul(s1, ppp), f.mul(zzz12, ppp)
+    y3 = fe29_norm(fe29_sub(t0, t1))
+    return (x3, y3, zz3, zzz3)

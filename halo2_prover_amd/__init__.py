@@ -13,5 +13,6 @@ from .ipa import ParamsIPA, compute_b, compute_s  # noqa: F401
 from .lookup import lookup_product, permute_expression_pair  # noqa: F401
 from .opening import gwc_open, poly_lincomb, shplonk_open_final, shplonk_open_h  # noqa: F401
 from .permutation import permutation_product  # noqa: F401
+from . import poseidon  # noqa: F401
 from .transcript import Blake2bTranscript  # noqa: F401
 from .lib import CURVES, H2Error, LIB_PATH, SYMBOLS, load  # noqa: F401

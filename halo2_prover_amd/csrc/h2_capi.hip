@@ -19,6 +19,8 @@
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
 #include "h2_poly.hpp"
+#include "h2_poseidon.hpp"
+#include "h2_poseidon_host.hpp"
 
 using namespace h2;
 
@@ -798,6 +800,68 @@ void expr_fill_tables(const ExprEntry& e, const uint64_t* vars, size_t p0, size_
   }
 }
 
+
+// ---- Poseidon (h2_poseidon_host.hpp generates the constants, h2_poseidon.hpp holds the kernels) --------------------------
+constexpr size_t POSEIDON_TABLE_SLOTS = 8;
+
+bool poseidon_rounds_ok(uint32_t r_f, uint32_t r_p) {
+  return r_f >= 2 && !(r_f & 1) && r_f <= POSEIDON_MAX_ROUNDS && r_p <= POSEIDON_MAX_ROUNDS && r_f + r_p <= POSEIDON_MAX_ROUNDS;
+}
+// (r_f + r_p) * 3 round constants, then the MDS row-major, as Montgomery limbs
+template <class FP>
+void poseidon_constants_t(uint32_t r_f, uint32_t r_p, uint64_t* out) {
+  const poseidon::Constants<FP> k = poseidon::generate<FP>((int)r_f, (int)r_p);
+  for (auto& row : k.rcs)
+    for (int i = 0; i < 3; i++, out += 4) row[i].mont_limbs(out);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++, out += 4) k.mds[i][j].mont_limbs(out);
+}
+// ConstantLength<len>'s capacity word len 2^64 as Montgomery limbs
+template <class FP>
+void poseidon_capacity_t(uint64_t len, uint64_t out[4]) {
+  const HF<FP> two32 = HF<FP>::from_u64(1ull << 32);
+  (HF<FP>::from_u64(len) * two32 * two32).mont_limbs(out);
+}
+// The table of (curve, r_f, r_p) on context c, built by its first user.  A table is uploaded on the library's stream and
+// finished before anybody reads it, as the NTT tables are: every later caller shares it whatever stream it brings.  The
+// cache keeps POSEIDON_TABLE_SLOTS tables; the oldest one is dropped for a ninth, after the device has run everything
+// enqueued so far -- work that still reads the dropped table is finished before the memory is freed.
+int poseidon_table_get(DevCtx& c, int curve, uint32_t r_f, uint32_t r_p, const void** out) {
+  const CurveOps* ops = ops_of(curve);
+  for (auto& t : c.poseidon_tables)
+    if (t.field == ops->scalar_field_id && t.r_f == r_f && t.r_p == r_p) {
+      *out = t.d;
+      return H2_OK;
+    }
+  if (c.poseidon_tables.size() >= POSEIDON_TABLE_SLOTS) {
+    H2_TRY(hipDeviceSynchronize());
+    (void)hipFree(c.poseidon_tables.front().d);
+    c.poseidon_tables.erase(c.poseidon_tables.begin());
+  }
+  const size_t elems = poseidon_table_elems(r_f, r_p);
+  std::vector<uint64_t> api(4 * elems);
+  H2_BY_SCALAR_FIELD(curve, poseidon_constants_t)(r_f, r_p, api.data());
+  std::vector<int32_t> table(9 * elems);
+  ops->poseidon_table(api.data(), elems, table.data());
+  PoseidonTable te{ops->scalar_field_id, r_f, r_p, nullptr};
+  if (int rc = device_alloc(&te.d, table.size() * 4, "poseidon table"); rc != H2_OK) return rc;
+  DeviceBuffer owner(te.d);      // until the table is in the cache
+  hipError_t e = hipMemcpyAsync(te.d, table.data(), table.size() * 4, hipMemcpyHostToDevice, c.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+  if (e != hipSuccess) return dev_fail(e, "poseidon table upload");
+  (void)owner.release();
+  c.poseidon_tables.push_back(te);
+  *out = te.d;
+  return H2_OK;
+}
+// lanes from which a hash launch takes the single-chain products (h2_poseidon.hpp), unless a test knob fixes the form
+size_t poseidon_chain_min_n() { return g_knobs.poseidon_form == 1 ? SIZE_MAX : g_knobs.poseidon_form == 2 ? 0 : POSEIDON_CHAIN_MIN_N; }
+bool poseidon_dev_ptr(const void* p) { return p && !((uintptr_t)p & 15); }
+bool poseidon_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -853,6 +917,7 @@ int h2_shutdown(void) {
     for (auto& kv : g_h2.bases)
       if (kv.second.table[i]) (void)hipFree(kv.second.table[i]);
     for (auto& t : c.twiddles) (void)hipFree(t.tw);
+    for (auto& t : c.poseidon_tables) (void)hipFree(t.d);
     for (auto& kv : g_h2.exprs)
       if (i < kv.second.d_code.size() && kv.second.d_code[i]) (void)hipFree(kv.second.d_code[i]);
     for (Arena& a : c.msm_ws.slot) arena_free(a);
@@ -1746,6 +1811,69 @@ int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !u || !init || !ipa_dev_ptr(d_out)) return H2_EINVAL;
   return launched(ops_of((int)curve)->ipa_s_products(u, k_, init, d_out, k.stream), "ipa_s_kernel");
+}
+
+// ---- Poseidon over resident columns (h2_poseidon.hpp) --------------------------------------------------------------------
+static_assert(H2_POSEIDON_MAX_ROUNDS == POSEIDON_MAX_ROUNDS, "the header states the kernels' maximum");
+
+int h2_poseidon_constants(h2_curve_t curve, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems, size_t* n_elems) {
+  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !n_elems) return H2_EINVAL;
+  const size_t need = poseidon_table_elems(r_f, r_p);
+  *n_elems = need;
+  if (!out || cap_elems < need) return H2_EINVAL;
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_constants_t)(r_f, r_p, out);
+  return H2_OK;
+}
+
+int h2_poseidon_merkle_tail(void) { return (int)(g_knobs.poseidon_merkle_tail ? g_knobs.poseidon_merkle_tail : POSEIDON_MERKLE_TAIL); }
+
+int h2_poseidon_permute_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_in) || !poseidon_dev_ptr(d_out) ||
+      n > ((size_t)1 << 40))
+    return H2_EINVAL;
+  if (d_out != d_in && poseidon_overlap(d_in, 96 * n, d_out, 96 * n)) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, r_f, r_p, &table); rc != H2_OK) return rc;
+  return launched(ops_of((int)curve)->poseidon_permute(d_in, d_out, n, table, r_f, r_p, k.stream), "poseidon_permute_kernel");
+}
+
+int h2_poseidon_hash_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len, size_t msg_stride, size_t n,
+                            void* d_out, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_msgs) || !poseidon_dev_ptr(d_out) || len == 0 ||
+      len > 65535 || msg_stride < len || msg_stride > ((size_t)1 << 32) || n > ((size_t)1 << 40))
+    return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  if (poseidon_overlap(d_msgs, 32 * ((n - 1) * msg_stride + len), d_out, 32 * n)) return H2_EINVAL;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(len, cap);
+  return launched(ops_of((int)curve)->poseidon_hash(d_msgs, (uint32_t)len, msg_stride, n, d_out, cap, table, r_f, r_p,
+                                                    poseidon_chain_min_n(), k.stream),
+                  "poseidon_hash_kernel");
+}
+
+int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth, void* d_nodes,
+                              void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || depth == 0 ||
+      depth > 30)
+    return H2_EINVAL;
+  const size_t leaves = (size_t)1 << depth;
+  if (poseidon_overlap(d_leaves, 32 * leaves, d_nodes, 32 * (leaves - 1))) return H2_EINVAL;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap2[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(2, cap2);
+  return launched(ops_of((int)curve)->poseidon_merkle(d_leaves, depth, d_nodes, cap2, table, r_f, r_p, (uint32_t)h2_poseidon_merkle_tail(),
+                                                      poseidon_chain_min_n(), k.stream),
+                  "poseidon_merkle kernels");
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {

@@ -5,8 +5,8 @@
 //   /root/reference/circuits/src/arithmetic_circuit.rs:187-267   (3 advice, 5 fixed, 1 instance; one gate)
 //   /root/reference/circuits/src/collatz.rs:26-207               (3 advice, 2 selectors, 4 gates, 32 regions)
 //   /root/reference/circuits/src/poseidon_circuit.rs:68-149 with halo2_gadgets' Pow5 chip (the vendored copy at
-//       circuits/src/poseidon/pow5.rs:230-272,433-592) and the constant generation of
-//       circuits/src/poseidon/primitives/grain.rs:52-137, mds.rs:5-102
+//       circuits/src/poseidon/pow5.rs:230-272,433-592); the constant generation of
+//       circuits/src/poseidon/primitives/grain.rs:52-137, mds.rs:5-102 is h2_poseidon_host.hpp
 // and, from the un-vendored halo2_proofs @6b43b6b: Assembly::copy of the permutation keygen and
 // the Debug rendering of the pinned verifying key whose Blake2b digest opens every transcript.
 #pragma once
@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "h2_host.hpp"
+#include "h2_poseidon_host.hpp"
 
 namespace h2 {
 namespace plonk {
@@ -142,93 +143,11 @@ struct ArithmeticCircuit : Circuit {
   }
 };
 
-// -- Grain LFSR of the Poseidon reference parameter generation (poseidon/primitives/grain.rs:52-137)
-class Grain {
- public:
-  Grain(int num_bits, int t, int r_f, int r_p) : num_bits_(num_bits) {
-    const int widths[6] = {2, 4, 12, 12, 10, 10}, values[6] = {1, 0, num_bits, t, r_f, r_p};
-    for (int k = 0; k < 6; k++)
-      for (int i = 0; i < widths[k]; i++) st_.push_back((values[k] >> (widths[k] - 1 - i)) & 1);
-    for (int i = 0; i < 30; i++) st_.push_back(1);
-    for (int i = 0; i < 160; i++) raw();
-  }
-  // num_bits bits, most significant first, as 32 little-endian bytes
-  void take(uint8_t out[32]) {
-    memset(out, 0, 32);
-    for (int i = num_bits_ - 1; i >= 0; i--)
-      if (bit()) out[i >> 3] |= (uint8_t)(1u << (i & 7));
-  }
-
- private:
-  int raw() {
-    const int b = st_[pos_ + 62] ^ st_[pos_ + 51] ^ st_[pos_ + 38] ^ st_[pos_ + 23] ^ st_[pos_ + 13] ^ st_[pos_];
-    st_.push_back((uint8_t)b);
-    pos_++;
-    return b;
-  }
-  int bit() {
-    for (;;) {
-      if (raw()) return raw();
-      raw();
-    }
-  }
-  std::vector<uint8_t> st_;
-  size_t pos_ = 0;
-  int num_bits_;
-};
-
-struct PoseidonConstants {
-  std::vector<std::array<Fr, 3>> rcs;     // 68 rounds
-  Fr mds[3][3], minv[3][3];
-};
-// round constants, Cauchy MDS and its inverse over bn256::Fr for t = 3, R_F = 8, R_P = 60 (primitives.rs:57-84,
-// mds.rs:5-102; poseidon_circuit.rs:19-25,129-149)
+// round constants, Cauchy MDS and its inverse over bn256::Fr for t = 3, R_F = 8, R_P = 60 (poseidon_circuit.rs:19-25,
+// 129-149): the (Fr, 8, 60) instance of the shared generation (h2_poseidon_host.hpp)
+using PoseidonConstants = poseidon::Constants<BN254_FR>;
 inline const PoseidonConstants& poseidon_constants() {
-  static const PoseidonConstants pc = [] {
-    PoseidonConstants k;
-    const int t = 3, r_f = 8, r_p = 60;
-    Grain g(254, t, r_f, r_p);
-    uint8_t b[32];
-    for (int r = 0; r < r_f + r_p; r++) {
-      std::array<Fr, 3> row;
-      int have = 0;
-      while (have < t) {
-        g.take(b);
-        Fr v;
-        if (Fr::from_le_bytes_canonical(b, &v)) row[have++] = v;   // rejection sampling: values >= p are skipped
-      }
-      k.rcs.push_back(row);
-    }
-    Fr xs[3], ys[3];
-    for (;;) {
-      Fr vals[6];
-      for (int i = 0; i < 6; i++) {
-        g.take(b);
-        vals[i] = Fr::from_le_bytes_reduce(b);                     // here the bits are reduced, not rejected
-      }
-      bool distinct = true;
-      for (int i = 0; i < 6; i++)
-        for (int j = i + 1; j < 6; j++)
-          if (vals[i] == vals[j]) distinct = false;
-      if (distinct) {
-        for (int i = 0; i < 3; i++) { xs[i] = vals[i]; ys[i] = vals[3 + i]; }
-        break;
-      }
-    }
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) k.mds[i][j] = (xs[i] + ys[j]).inv();
-    auto lag = [](const Fr* pts, int j, const Fr& x) {
-      Fr acc = Fr::one();
-      for (int m = 0; m < 3; m++)
-        if (m != j) acc = acc * (x - pts[m]) * (pts[j] - pts[m]).inv();
-      return acc;
-    };
-    Fr nys[3];
-    for (int i = 0; i < 3; i++) nys[i] = -ys[i];
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) k.minv[i][j] = (xs[j] - nys[i]) * lag(xs, j, nys[i]) * lag(nys, i, xs[j]);
-    return k;
-  }();
+  static const PoseidonConstants pc = poseidon::generate<BN254_FR>(8, 60);
   return pc;
 }
 

@@ -72,6 +72,13 @@ struct TwiddleEntry {
   uint64_t stamp;
 };
 
+// the constants of one Poseidon instance (h2_poseidon.hpp) in HBM, in the kernels' working form
+struct PoseidonTable {
+  int field;
+  uint32_t r_f, r_p;
+  void* d;
+};
+
 struct DevCtx {
   int device = -1;
   hipStream_t stream = nullptr;   // the library's own (blocking) stream on this device
@@ -87,6 +94,7 @@ struct DevCtx {
   bool tail_recorded = false, tail_wanted = false;   // the event costs ~5 us per MSM: recorded once somebody asked
   std::vector<TwiddleEntry> twiddles;
   uint64_t stamp = 0;
+  std::vector<PoseidonTable> poseidon_tables;   // at most POSEIDON_TABLE_SLOTS, oldest first (poseidon_table_get)
   // kernel timing for the roofline (h2_profile_*): event pairs around the bucket-accumulate kernel
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   size_t prof_used = 0;
@@ -134,6 +142,8 @@ struct TestKnobs {
   bool sort2_pack = true;                        // false: the unpacked forms of the two-level sort and the staged scatter
   size_t points_small_max = MSM_POINTS_SMALL_MAX;   // terms below which h2_msm_points* takes the double-and-add route
   int gfft_lanes = 0;                            // lanes per butterfly of the group FFT: 0 = by size, 1, 4
+  uint32_t poseidon_merkle_tail = 0;             // nodes a Merkle level may have to be finished by the tail launch; 0: the default
+  int poseidon_form = 0;                         // the hash kernel's products: 0 = by size, 1 = the compiler's form, 2 = single-chain
 };
 struct TestCounters {
   uint64_t guard_launches = 0, guard_violations = 0;

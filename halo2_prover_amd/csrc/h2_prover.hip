@@ -48,8 +48,9 @@ Job job_for_proof(const Json& js, int idx) {
   }
   return j;
 }
-// verify side: the empty circuit, public inputs recomputed (wasm.rs:128-168)
-Job job_for_verify(const Json& js, int idx) {
+// verify side: the empty circuit, public inputs recomputed (wasm.rs:128-168).  hash = false leaves the Poseidon circuit's
+// public input, the hash of the message, to the caller (h2_verify_proofs computes a batch's hashes together)
+Job job_for_verify(const Json& js, int idx, bool hash = true) {
   Job j = make_circuit(idx);
   if (j.index == 1) {
     j.public_input = {Fr::from_u64(js.u64("constant")), Fr::from_u64(js.u64("z"))};
@@ -59,9 +60,37 @@ Job job_for_verify(const Json& js, int idx) {
     if (x.size() != 2) fail(H2_EPROOF, "poseidon: x must hold two values");
     c.message[0] = Fr::from_u64(x[0]);
     c.message[1] = Fr::from_u64(x[1]);
-    j.public_input = {c.output()};
+    if (hash) j.public_input = {c.output()};
   }
   return j;
+}
+
+// Batches of at least this many Poseidon items get their public inputs from ONE h2_poseidon_hash_device launch and one
+// read-back instead of `count` host permutations (DESIGN.md section 7.14 has the measurement behind the number)
+constexpr size_t POSEIDON_VERIFY_MIN = 64;
+size_t g_poseidon_verify_min = POSEIDON_VERIFY_MIN;
+
+// the public inputs of Poseidon jobs whose messages are set: Poseidon(message) over bn256::Fr with (8, 60), the same value
+// c.output() computes
+void poseidon_public_inputs(DevCtx* ctx, std::vector<Job>& jobs) {
+  if (jobs.size() < g_poseidon_verify_min) {
+    for (Job& j : jobs) j.public_input = {static_cast<PoseidonCircuit&>(*j.circuit).output()};
+    return;
+  }
+  Dev d(ctx);
+  std::vector<Fr> msgs;
+  msgs.reserve(2 * jobs.size());
+  for (Job& j : jobs) {
+    const auto& c = static_cast<PoseidonCircuit&>(*j.circuit);
+    msgs.push_back(c.message[0]);
+    msgs.push_back(c.message[1]);
+  }
+  Col d_msgs = d.upload_frs(msgs);
+  Col d_out = d.col(jobs.size());
+  if (int rc = h2_poseidon_hash_device(H2_BN254, 8, 60, d_msgs, 2, 2, jobs.size(), d_out, d.s); rc != H2_OK)
+    fail(rc, "poseidon public inputs: " + g_h2.last_error);
+  const std::vector<Fr> out = d.download_frs(d_out, jobs.size());
+  for (size_t i = 0; i < jobs.size(); i++) jobs[i].public_input = {out[i]};
 }
 
 template <class F>
@@ -324,10 +353,13 @@ int h2_verify_proofs(const uint8_t* params, size_t params_len, size_t count, con
     }
     const Params& P = params_get(params, params_len);
     std::vector<Job> jobs;
-    for (size_t i = 0; i < count; i++) jobs.push_back(job_for_verify(Json(jsons[i]), circuit));
+    for (size_t i = 0; i < count; i++) jobs.push_back(job_for_verify(Json(jsons[i]), circuit, false));
+    trace.mark("params, jobs");
+    if (jobs[0].index == 2) poseidon_public_inputs(ctx, jobs);
+    trace.mark("poseidon hashes");
     std::unique_ptr<ProvingKey> owner;
     ProvingKey& K = key_for(P, jobs[0].index, ctx, owner);
-    trace.mark("params, jobs, key");
+    trace.mark("key");
     if (bn::g2_on_curve(P.g2) && bn::g2_on_curve(P.s_g2)) {        // otherwise no proof verifies under these params
       Rng rng{rng_fn, rng_ctx};
       for (size_t g0 = 0; g0 < count; g0 += VERIFY_GROUP) {
@@ -392,6 +424,13 @@ uint64_t h2_selftest_commit_launches(void) {
 int h2_selftest_set_prove_group(size_t proofs) {
   std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   g_prove_group = proofs ? proofs : PROVE_GROUP;
+  return H2_OK;
+}
+
+// test hook: Poseidon items from which h2_verify_proofs hashes on the device (0 restores the default)
+int h2_selftest_set_poseidon_verify_min(size_t count) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  g_poseidon_verify_min = count ? count : POSEIDON_VERIFY_MIN;
   return H2_OK;
 }
 

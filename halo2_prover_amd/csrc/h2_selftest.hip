@@ -3,8 +3,11 @@
 // path; nothing here is called by the library itself.
 #include "h2_internal.hpp"
 #include "h2_field29_chain.hpp"
+#include "h2_host.hpp"
+#include "h2_poseidon.hpp"
 
 #include <cstdio>
+#include <vector>
 
 #include "../../include/h2hip_selftest.h"
 
@@ -375,4 +378,38 @@ extern "C" int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters,
   hipDeviceProp_t prop;
   H2_TRY(hipGetDeviceProperties(&prop, c->device));
   return launched(ops->modmul_rate(prop.multiProcessorCount * waves_per_simd, iters, c->stream, modmul_per_s), "modmul_rate_kernel");
+}
+
+// ---- Poseidon (h2_poseidon.hpp) --------------------------------------------------------------------------------------
+// host only: the permutation template instantiated on the host, on the table h2_poseidon_constants' values make
+extern "C" int h2_selftest_poseidon(int curve, uint32_t r_f, uint32_t r_p, int op, const uint64_t* in, uint64_t* out) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !in || !out || op < 0 || op > 1) return H2_EINVAL;
+  size_t elems = 0;
+  if (h2_poseidon_constants((h2_curve_t)curve, r_f, r_p, nullptr, 0, &elems) != H2_EINVAL || elems == 0) return H2_EINVAL;
+  std::vector<uint64_t> api(4 * elems);
+  if (int rc = h2_poseidon_constants((h2_curve_t)curve, r_f, r_p, api.data(), elems, &elems); rc != H2_OK) return rc;
+  std::vector<int32_t> table(9 * elems);
+  ops->poseidon_table(api.data(), elems, table.data());
+  uint64_t cap2[4];
+  const char* two65 = "0x20000000000000000";          // ConstantLength<2>: 2 2^64
+  if (curve == H2_BN254) HF<BN254_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
+  else if (curve == H2_PALLAS) HF<PALLAS_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
+  else HF<VESTA_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
+  return ops->selftest_poseidon(op, r_f, r_p, table.data(), cap2, in, out) == 0 ? H2_OK : H2_EINVAL;
+}
+// tests and tools only: the widest Merkle level the tail launch takes (a power of two up to POSEIDON_MERKLE_TAIL_MAX; 0
+// restores the default), and the product form of the hash kernel (0: by size, 1: the compiler's, 2: single-chain where the
+// field has it)
+extern "C" int h2_selftest_set_poseidon_merkle_tail(uint32_t nodes) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (nodes > POSEIDON_MERKLE_TAIL_MAX || (nodes & (nodes - 1))) return H2_EINVAL;
+  g_knobs.poseidon_merkle_tail = nodes;
+  return H2_OK;
+}
+extern "C" int h2_selftest_set_poseidon_form(int form) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (form < 0 || form > 2) return H2_EINVAL;
+  g_knobs.poseidon_form = form;
+  return H2_OK;
 }

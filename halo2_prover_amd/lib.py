@@ -90,6 +90,11 @@ SYMBOLS = {
     "h2_ipa_round_device": (_I, [_I, _U64, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_final_device": (_I, [_I, _U32, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_challenge_products_device": (_I, [_I, _P, _U32, _P, _P, _P]),
+    "h2_poseidon_constants": (_I, [_I, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
+    "h2_poseidon_permute_device": (_I, [_I, _U32, _U32, _P, _P, _Z, _P]),
+    "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),
+    "h2_poseidon_merkle_device": (_I, [_I, _U32, _U32, _P, _U32, _P, _P]),
+    "h2_poseidon_merkle_tail": (_I, []),
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),
@@ -126,6 +131,8 @@ SYMBOLS = {
     "h2_selftest_set_gfft_lanes": (_I, [_I]),
     "h2_selftest_glv_split": (_I, [_I, _P, _P]),
     "h2_selftest_glv_constants": (_I, [_I, _P, _P, ctypes.POINTER(_U32)]),
+    # the hook that goes with h2_poseidon_*: the kernels' permutation template on the host
+    "h2_selftest_poseidon": (_I, [_I, _U32, _U32, _I, _P, _P]),
 }
 # include/h2hip_selftest.h (host instantiation of the device templates; not a compute path)
 SELFTEST_SYMBOLS = {
@@ -153,6 +160,9 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_xyzz29_op_device": (_I, [_I, _I, _P, _P, _Z]),
     "h2_selftest_pairing_checks": (_U64, []),
     "h2_selftest_expr_run": (_I, [_P, _Z, _P, _P, _U32, _U32, _U32, _P, _P]),
+    "h2_selftest_set_poseidon_merkle_tail": (_I, [_U32]),
+    "h2_selftest_set_poseidon_form": (_I, [_I]),
+    "h2_selftest_set_poseidon_verify_min": (_I, [_Z]),
 }
 
 # the RNG callback of the product surface: void (*)(void* ctx, uint8_t* out, size_t n)

@@ -1,0 +1,196 @@
+"""Poseidon over device-resident columns (include/h2hip.h: h2_poseidon_*).
+
+The primitive of the reference's circuits/src/poseidon/primitives*: width 3, rate 2, S-box x^5, r_f full and r_p partial
+rounds over the scalar field of a curve, constants from the Grain / Cauchy-MDS generation.  The defaults are the two
+instances the reference uses: (8, 56) on Pallas and Vesta (P128Pow5T3, the zcash vectors) and (8, 60) on BN254
+(poseidon_circuit.rs's spec: the hash the Poseidon circuit proves).
+
+Elements are 4 x u64 Montgomery limbs, canonical.  The device functions take int64 CUDA tensors viewing those limbs, or
+numpy uint64 arrays, which are uploaded, and return the same kind: the work is enqueued on the caller's current stream
+and the columns stay in HBM.  There is no CPU fallback: `merkle_path` and `verify_path` are host helpers on Python
+integers for a membership proof's few hashes, everything else runs the kernels.
+"""
+import ctypes
+
+import numpy as np
+
+from . import lib as _lib
+from .api import _curve_id, _ensure_init
+from .domain import _FIELDS, _limbs
+
+DEFAULT_ROUNDS = {0: (8, 60), 1: (8, 56), 2: (8, 56)}
+
+
+def _rounds(curve, r_f, r_p):
+    d = DEFAULT_ROUNDS[curve]
+    return (d[0] if r_f is None else int(r_f), d[1] if r_p is None else int(r_p))
+
+
+def modulus(curve):
+    return _FIELDS[_curve_id(curve)][0]
+
+
+def to_mont(curve, values):
+    """canonical ints -> (n, 4) uint64 Montgomery limbs"""
+    p = modulus(curve)
+    R = (1 << 256) % p
+    return np.stack([_limbs(int(v) % p * R % p) for v in values]) if len(values) else np.zeros((0, 4), dtype=np.uint64)
+
+
+def from_mont(curve, limbs):
+    """Montgomery limbs (any shape ending in 4) -> a flat list of canonical ints"""
+    p = modulus(curve)
+    r_inv = pow((1 << 256) % p, -1, p)
+    raw = np.ascontiguousarray(limbs, dtype=np.uint64).tobytes()
+    return [int.from_bytes(raw[i:i + 32], "little") * r_inv % p for i in range(0, len(raw), 32)]
+
+
+def constants(curve, r_f=None, r_p=None, as_int=False):
+    """The instance's constants, host only (no GPU): (round constants (r_f + r_p, 3, 4), mds (3, 3, 4)) as Montgomery
+    limbs, or as nested lists of canonical ints with as_int."""
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    L = _lib.load()
+    need = ctypes.c_size_t(0)
+    L.h2_poseidon_constants(cid, r_f, r_p, None, 0, ctypes.byref(need))
+    if need.value == 0:
+        raise ValueError("poseidon: r_f must be even and at least 2, r_f + r_p at most 128")
+    out = np.zeros((need.value, 4), dtype=np.uint64)
+    _lib.check(L.h2_poseidon_constants(cid, r_f, r_p, out.ctypes.data, need.value, ctypes.byref(need)), "h2_poseidon_constants")
+    rounds = r_f + r_p
+    rcs, mds = out[:3 * rounds].reshape(rounds, 3, 4), out[3 * rounds:].reshape(3, 3, 4)
+    if not as_int:
+        return rcs, mds
+    ri, mi = from_mont(cid, rcs), from_mont(cid, mds)
+    return [ri[3 * r:3 * r + 3] for r in range(rounds)], [mi[3 * i:3 * i + 3] for i in range(3)]
+
+
+def _stream():
+    import torch
+    raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    if raw is not None:
+        return ctypes.c_void_p(raw(torch.cuda.current_device()))
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _device(a, name):
+    """(tensor, was_numpy): an int64 CUDA tensor viewing the limbs"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.int64 or not a.is_cuda or not a.is_contiguous():
+            raise ValueError("%s: expected a contiguous int64 CUDA tensor" % name)
+        return a, False
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    return torch.from_numpy(a.view(np.int64).copy()).cuda(), True
+
+
+def _result(t, was_numpy):
+    return t.cpu().numpy().view(np.uint64) if was_numpy else t
+
+
+def permute(curve, states, r_f=None, r_p=None, out=None):
+    """n states (n, 3, 4) -> the permuted states.  `out` (a tensor of the same shape) may be `states` itself."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    d_in, was_numpy = _device(states, "states")
+    if d_in.dim() != 3 or tuple(d_in.shape[1:]) != (3, 4):
+        raise ValueError("states: expected shape (n, 3, 4), got %r" % (tuple(d_in.shape),))
+    d_out = torch.empty_like(d_in) if out is None else out
+    if tuple(d_out.shape) != tuple(d_in.shape) or d_out.dtype != torch.int64 or not d_out.is_cuda or not d_out.is_contiguous():
+        raise ValueError("out: expected a contiguous int64 CUDA tensor of the states' shape")
+    st = _lib.load().h2_poseidon_permute_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), ctypes.c_void_p(d_out.data_ptr()),
+                                                d_in.shape[0], _stream())
+    _lib.check(st, "h2_poseidon_permute_device")
+    return _result(d_out, was_numpy)
+
+
+def hash(curve, msgs, r_f=None, r_p=None, length=None):  # noqa: A001 -- the primitive's name
+    """ConstantLength hash of n messages: msgs (n, stride, 4), the first `length` elements of each row are the message
+    (default: the whole row) -> (n, 4)."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    d_in, was_numpy = _device(msgs, "msgs")
+    if d_in.dim() != 3 or d_in.shape[2] != 4 or d_in.shape[1] == 0:
+        raise ValueError("msgs: expected shape (n, stride, 4), got %r" % (tuple(d_in.shape),))
+    n, stride = d_in.shape[0], d_in.shape[1]
+    length = stride if length is None else int(length)
+    d_out = torch.empty((n, 4), dtype=torch.int64, device=d_in.device)
+    st = _lib.load().h2_poseidon_hash_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), length, stride, n,
+                                             ctypes.c_void_p(d_out.data_ptr()), _stream())
+    _lib.check(st, "h2_poseidon_hash_device")
+    return _result(d_out, was_numpy)
+
+
+def merkle_nodes(curve, leaves, r_f=None, r_p=None):
+    """2^depth leaves (2^depth, 4), depth >= 1 -> the 2^depth - 1 inner nodes, level by level from the leaves' parents
+    up; the root is last.  A node is the ConstantLength<2> hash of its two children."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    d_in, was_numpy = _device(leaves, "leaves")
+    n = d_in.shape[0] if d_in.dim() == 2 else 0
+    if d_in.dim() != 2 or d_in.shape[1] != 4 or n < 2 or n & (n - 1):
+        raise ValueError("leaves: expected shape (2^depth, 4) with depth >= 1, got %r" % (tuple(d_in.shape),))
+    depth = n.bit_length() - 1
+    d_out = torch.empty((n - 1, 4), dtype=torch.int64, device=d_in.device)
+    st = _lib.load().h2_poseidon_merkle_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), depth,
+                                               ctypes.c_void_p(d_out.data_ptr()), _stream())
+    _lib.check(st, "h2_poseidon_merkle_device")
+    return _result(d_out, was_numpy)
+
+
+def merkle_root(curve, leaves, r_f=None, r_p=None):
+    """the root alone: (4,) limbs"""
+    return merkle_nodes(curve, leaves, r_f, r_p)[-1]
+
+
+def merkle_tail():
+    """the widest level merkle_nodes leaves to its single-workgroup launch"""
+    return _lib.load().h2_poseidon_merkle_tail()
+
+
+# ---- host helpers on Python integers ---------------------------------------------------------------------------------
+def merkle_path(nodes, depth, index):
+    """The siblings of leaf `index` from the bottom up.  nodes: the whole tree as canonical ints, the 2^depth leaves
+    followed by merkle_nodes' 2^depth - 1 inner nodes (2^(depth + 1) - 1 values)."""
+    if len(nodes) != (2 << depth) - 1 or not 0 <= index < (1 << depth):
+        raise ValueError("merkle_path: expected 2^(depth + 1) - 1 nodes and an index below 2^depth")
+    path, base, width = [], 0, 1 << depth
+    for _ in range(depth):
+        path.append(nodes[base + (index ^ 1)])
+        base += width
+        width >>= 1
+        index >>= 1
+    return path
+
+
+def hash2_int(curve, a, b, r_f=None, r_p=None):
+    """ConstantLength<2> of two canonical ints on the host (big integers; a membership proof's few hashes)"""
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    p = modulus(cid)
+    rcs, mds = constants(cid, r_f, r_p, as_int=True)
+    st = [a % p, b % p, (2 << 64) % p]
+    half = r_f // 2
+    for r in range(r_f + r_p):
+        st = [(st[i] + rcs[r][i]) % p for i in range(3)]
+        if r < half or r >= half + r_p:
+            st = [pow(x, 5, p) for x in st]
+        else:
+            st[0] = pow(st[0], 5, p)
+        st = [sum(mds[i][j] * st[j] for j in range(3)) % p for i in range(3)]
+    return st[0]
+
+
+def verify_path(curve, leaf, index, path, root, r_f=None, r_p=None):
+    """True when `path` (merkle_path's siblings) takes `leaf` at position `index` to `root`"""
+    cur = leaf
+    for sib in path:
+        cur = hash2_int(curve, sib, cur, r_f, r_p) if index & 1 else hash2_int(curve, cur, sib, r_f, r_p)
+        index >>= 1
+    return index == 0 and cur == root

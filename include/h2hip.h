@@ -387,6 +387,39 @@ int h2_ipa_final_device(h2_curve_t curve, uint32_t k, void* d_state, const uint6
                         void* d_out, void* d_s_out, void* stream);
 int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out,
                                      void* stream);
+/* ---- Poseidon over resident columns: permutation, ConstantLength hash, Merkle tree ---------------------------------
+ * The Poseidon primitive of circuits/src/poseidon/primitives*: width 3, rate 2, S-box x^5, r_f full and r_p partial
+ * rounds, over the scalar field of `curve` (all three curves), constants from the reference's Grain / Cauchy-MDS
+ * generation.  (8, 56) on H2_PALLAS or H2_VESTA is the reference's P128Pow5T3 (the zcash test vectors; Pallas's scalar field
+ * is their Fq, Vesta's their Fp); (8, 60) on H2_BN254 is poseidon_circuit.rs's spec, the hash the Poseidon circuit proves.
+ * Elements are 4 x u64 Montgomery limbs, canonical (below p) on the way in and on the way out.
+ *   h2_poseidon_constants       host only, no device and no h2_init needed: (r_f + r_p) * 3 round constants, then the 3 x 3
+ *                               MDS row-major.  *n_elems = the elements that takes, also when cap_elems is too small.
+ *   h2_poseidon_permute_device  n states of 3 elements (96 bytes each) -> n states; d_out may be d_in exactly, otherwise
+ *                               the two must not overlap.
+ *   h2_poseidon_hash_device     ConstantLength<len>: n messages of len elements, msg_stride elements apart, -> n elements.
+ *                               The state starts as (0, 0, len 2^64), the message is absorbed two words at a time,
+ *                               zero-padded to even length, one permutation per absorb, the output is word 0.
+ *   h2_poseidon_merkle_device   2^depth leaves -> the 2^depth - 1 inner nodes, level by level from the leaves' parents up,
+ *                               the root last; a node is ConstantLength<2> of its two children.  Levels of more than
+ *                               h2_poseidon_merkle_tail() nodes take one launch each, all the levels above them one
+ *                               launch of a single workgroup.
+ * The device calls are asynchronous on `stream` under h2_ntt_device's rules: no host synchronisation, no device-to-host
+ * copy -- except that the FIRST use of a (curve, r_f, r_p) on a context builds its table of constants and waits for
+ * that upload; a context keeps the tables of the eight instances used last.  They act on the context of the calling
+ * thread's current HIP device.  H2_EINVAL -- checked on the host before anything is enqueued -- for: an unknown curve; r_f
+ * odd or 0, or r_f + r_p > H2_POSEIDON_MAX_ROUNDS; a null or not 16-byte aligned device pointer; len = 0 or len > 65535;
+ * msg_stride < len or msg_stride > 2^32; n > 2^40; depth = 0 or depth > 30; an output that overlaps an input (other than
+ * d_out == d_in of the permutation).  n = 0 is H2_OK and enqueues nothing.  H2_ENOTINIT before h2_init.  h2_version() is unchanged: a host
+ * detects these entry points by their symbols. */
+#define H2_POSEIDON_MAX_ROUNDS 128      /* r_f + r_p; r_f even and >= 2; r_p >= 0 */
+int h2_poseidon_constants(h2_curve_t curve, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems, size_t* n_elems);
+int h2_poseidon_permute_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n, void* stream);
+int h2_poseidon_hash_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len, size_t msg_stride,
+                            size_t n, void* d_out, void* stream);
+int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth, void* d_nodes,
+                              void* stream);
+int h2_poseidon_merkle_tail(void);      /* host only */
 /* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
  * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
  * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER

@@ -165,6 +165,25 @@ int h2_selftest_expr_run(const uint8_t* dag, size_t dag_len, const uint64_t* col
 int h2_selftest_arena_stats(uint64_t out[4]);
 /* pairing checks the two verify entry points of the product surface have made since the library was loaded */
 uint64_t h2_selftest_pairing_checks(void);
+/* Poseidon (h2_poseidon_*; csrc/h2_poseidon.hpp).
+ * h2_selftest_poseidon: host only, no GPU and no h2_init -- the kernels' permutation template instantiated on the host,
+ *   over `curve`'s scalar field with the constants of (r_f, r_p).  op 0: in = one state of 3 elements -> out = the permuted
+ *   state; op 1: in = two elements -> out = their ConstantLength<2> hash (one element).  4 x u64 Montgomery limbs each,
+ *   canonical.  H2_EINVAL for what h2_poseidon_constants refuses or another op.
+ * h2_selftest_set_poseidon_merkle_tail: tests and tools only -- the widest level h2_poseidon_merkle_device leaves to its
+ *   single-workgroup launch: a power of two up to 512; 0 restores the default.  h2_poseidon_merkle_tail() reports the value
+ *   in force.
+ * h2_selftest_set_poseidon_form: tests and tools only -- the form of the field product in the hash launches of
+ *   h2_poseidon_hash_device and h2_poseidon_merkle_device: 1 = the compiler's form at every size, 2 = the single-chain form
+ *   (csrc/h2_field29_chain.hpp) at every size where the field has one (Pallas, Vesta), 0 restores the choice by size
+ *   (single-chain from 2^16 + 1 lanes on).  The results are the same limb for limb.  H2_EINVAL for another value. */
+int h2_selftest_poseidon(int curve, uint32_t r_f, uint32_t r_p, int op, const uint64_t* in, uint64_t* out);
+/* Poseidon items from which h2_verify_proofs computes the batch's public inputs with one h2_poseidon_hash_device launch
+ * instead of one host permutation per item; a smaller batch hashes on the host as h2_verify_proof does.  0 restores the
+ * default; SIZE_MAX keeps every batch on the host. */
+int h2_selftest_set_poseidon_verify_min(size_t count);
+int h2_selftest_set_poseidon_merkle_tail(uint32_t nodes);
+int h2_selftest_set_poseidon_form(int form);
 
 #ifdef __cplusplus
 }

@@ -4,9 +4,9 @@ Python host layer over the C-ABI library libh2hip.so (include/h2hip.h).  Importi
 package does not touch the GPU; the first compute call (or `init()`) binds the process to
 one device.  There is no CPU fallback.
 """
-from .api import (Bases, ParamsKZG, best_fft, best_fft_batch, best_fft_group, best_multiexp, g_to_lagrange,  # noqa: F401
+from .api import (Bases, ParamsKZG, base_sqrt_device, best_fft, best_fft_batch, best_fft_group, best_multiexp, g_to_lagrange,  # noqa: F401
                   generate_proofs, init, msm_points, msm_points_device, msm_points_plan, ntt_device, params_downsize,
-                  points_decompress_device, verify_proofs)
+                  pasta_points_decompress_device, points_decompress_device, verify_proofs)
 from .expr import ExprProgram  # noqa: F401
 from . import ipa  # noqa: F401
 from .ipa import ParamsIPA, compute_b, compute_s  # noqa: F401

@@ -312,6 +312,25 @@ def points_decompress_device(d_in, n, d_out, d_status, stream=0, curve="bn254"):
     _lib.check(st, "h2_points_decompress_device")
 
 
+def base_sqrt_device(d_in, n, d_out, d_status, stream=0, curve="pallas"):
+    """n elements of the curve's BASE field (32 B, Montgomery limbs) -> n square roots (the one whose canonical integer is
+    even) and n status bytes (0 root, 1 not canonical, 3 not a square); d_out may be d_in; device pointers, asynchronous
+    (h2_base_sqrt_device)."""
+    _ensure_init()
+    st = _lib.load().h2_base_sqrt_device(_curve_id(curve), ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out),
+                                         ctypes.c_void_p(d_status), ctypes.c_void_p(stream))
+    _lib.check(st, "h2_base_sqrt_device")
+
+
+def pasta_points_decompress_device(d_in, n, d_out, d_status, stream=0, curve="pallas"):
+    """points_decompress_device for the Pasta wire form (bit 255 the parity of y, 32 zero bytes the identity): Pallas and
+    Vesta only (h2_pasta_points_decompress_device)."""
+    _ensure_init()
+    st = _lib.load().h2_pasta_points_decompress_device(_curve_id(curve), ctypes.c_void_p(d_in), n, ctypes.c_void_p(d_out),
+                                                       ctypes.c_void_p(d_status), ctypes.c_void_p(stream))
+    _lib.check(st, "h2_pasta_points_decompress_device")
+
+
 def verify_proofs(params, proofs, jsons, circuit, rng=None):
     """Batch verification (h2_verify_proofs): `proofs` and `jsons` of ONE circuit under ONE params blob -> list[bool],
     entry i what verifying proof i alone gives.  rng: None (the OS) or a callable n -> n bytes for the batching weights."""

@@ -1064,6 +1064,44 @@ int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size
   return launched(ops_of((int)curve)->points_decompress(d_compressed, d_out_affine, d_status, (uint32_t)n, k.stream), "points_decompress_kernel");
 }
 
+// [a, a + la) and [b, b + lb) share bytes without being the same range
+static bool partly_overlaps(const void* a, size_t la, const void* b, size_t lb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  if (a0 == b0 && la == lb) return false;
+  return a0 < b0 + lb && b0 < a0 + la;
+}
+static bool overlaps(const void* a, size_t la, const void* b, size_t lb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + lb && b0 < a0 + la;
+}
+
+int h2_base_sqrt_device(h2_curve_t curve, const void* d_in, size_t n, void* d_out, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || n > (1u << 30)) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  // the kernel moves 16 bytes at a time; the roots may replace the elements, nothing else may share bytes
+  if (!d_in || !d_out || !d_status || ((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return H2_EINVAL;
+  if (partly_overlaps(d_in, n * 32, d_out, n * 32) || overlaps(d_status, n, d_in, n * 32) || overlaps(d_status, n, d_out, n * 32))
+    return H2_EINVAL;
+  return launched(ops_of((int)curve)->base_sqrt(d_in, d_out, d_status, (uint32_t)n, k.stream), "base_sqrt_kernel");
+}
+
+int h2_pasta_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine, void* d_status,
+                                      void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !ops_of((int)curve)->pasta_points_decompress || n > (1u << 30)) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  if (!d_compressed || !d_out_affine || !d_status || ((uintptr_t)d_compressed & 15) || ((uintptr_t)d_out_affine & 15))
+    return H2_EINVAL;
+  if (overlaps(d_compressed, n * 32, d_out_affine, n * 64) || overlaps(d_status, n, d_compressed, n * 32) ||
+      overlaps(d_status, n, d_out_affine, n * 64))
+    return H2_EINVAL;
+  return launched(ops_of((int)curve)->pasta_points_decompress(d_compressed, d_out_affine, d_status, (uint32_t)n, k.stream),
+                  "points_decompress_kernel");
+}
+
 int h2_msm(h2_curve_t curve, uint64_t handle, const uint64_t* scalars, size_t n, uint64_t out_jac[12]) {
   std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
   if (n && !scalars) return H2_EINVAL;
@@ -1811,6 +1849,38 @@ int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !u || !init || !ipa_dev_ptr(d_out)) return H2_EINVAL;
   return launched(ops_of((int)curve)->ipa_s_products(u, k_, init, d_out, k.stream), "ipa_s_kernel");
+}
+
+int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, const uint64_t* init, uint32_t k_, size_t count,
+                                         void* d_out, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !ipa_dev_ptr(d_out) || (count && (!u || !init))) return H2_EINVAL;
+  const size_t n = (size_t)1 << k_;
+  if (count == 0) {
+    H2_TRY(hipMemsetAsync(d_out, 0, n * 32, k.stream));
+    return H2_OK;
+  }
+  // the group's table in the scan arena for the length of the call; the groups share it: the stream runs them in order
+  const size_t group = std::min(count, IPA_SUM_GROUP), row = ipa_sum_stride(k_);
+  std::vector<int32_t> host;
+  try {
+    host.resize(group * row);
+  } catch (const std::bad_alloc&) {
+    g_h2.last_error = "ipa: no host memory for the challenge table";
+    return H2_ENOMEM;
+  }
+  ArenaLease A(k.c->div_ws, group * row * 4, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  const CurveOps* ops = ops_of((int)curve);
+  for (size_t p0 = 0; p0 < count; p0 += group) {
+    const size_t cnt = std::min(group, count - p0);
+    H2_BY_SCALAR_FIELD((int)curve, ipa_sum_fill)(u + 4 * p0 * k_, init + 4 * p0, k_, cnt, host.data());
+    // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
+    H2_TRY(hipMemcpyAsync(A.a.p, host.data(), cnt * row * 4, hipMemcpyHostToDevice, k.stream));
+    if (int rc = launched(ops->ipa_s_sum(A.a.p, (uint32_t)cnt, k_, d_out, p0 > 0, k.stream), "ipa_s_sum_kernel"); rc != H2_OK) return rc;
+  }
+  return A.release();
 }
 
 // ---- Poseidon over resident columns (h2_poseidon.hpp) --------------------------------------------------------------------

@@ -111,8 +111,39 @@ int selftest_decompress(const uint8_t in[32], uint64_t out_affine[8]) {
   return st;
 }
 #else
-constexpr auto points_decompress = nullptr;      // 2-adicity 32: Tonelli-Shanks, not provided
+constexpr auto points_decompress = nullptr;      // BN254's wire form: the Pasta curves have pasta_points_decompress
 constexpr auto selftest_decompress = nullptr;
+#endif
+hipError_t base_sqrt_(const void* d_in, void* d_out, void* d_status, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(base_sqrt_kernel<FB>, dim3((n + 63) / 64), dim3(64), 0, s, (const U128*)d_in, (U128*)d_out, (uint8_t*)d_status, n);
+  return hipGetLastError();
+}
+int selftest_base_sqrt(const uint64_t in_mont[4], uint64_t out_mont[4]) {
+  Fe<FB> a, r;
+  memcpy(a.v, in_mont, 32);
+  const uint8_t st = base_sqrt<FB>(a, r);
+  memcpy(out_mont, r.v, 32);
+  return st;
+}
+#if H2_CURVE_ID == 0
+constexpr auto pasta_points_decompress = nullptr;
+constexpr auto selftest_pasta_decompress = nullptr;
+#else
+hipError_t pasta_points_decompress(const void* d_compressed, void* d_out_affine, void* d_status, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(points_decompress_kernel<CV>, dim3((n + 63) / 64), dim3(64), 0, s, (const uint32_t*)d_compressed,
+                     (U128*)d_out_affine, (uint8_t*)d_status, n);
+  return hipGetLastError();
+}
+int selftest_pasta_decompress(const uint8_t in[32], uint64_t out_affine[8]) {
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++)
+    w[i] = (uint32_t)in[4 * i] | ((uint32_t)in[4 * i + 1] << 8) | ((uint32_t)in[4 * i + 2] << 16) | ((uint32_t)in[4 * i + 3] << 24);
+  Fe<FB> x, y;
+  const uint8_t st = pasta_decompress<CV>(w, x, y);
+  memcpy(out_affine, x.v, 32);
+  memcpy(out_affine + 4, y.v, 32);
+  return st;
+}
 #endif
 size_t ntt_table_bytes(uint32_t log_n) { return ntt29_tables(log_n).total; }
 bool ntt_scale_in_table(uint32_t log_n) { return ntt29_scale_in_table(log_n); }
@@ -607,9 +638,9 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 }
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
-                      to_affine,   points_sum, points_decompress, selftest_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
+                      to_affine,   points_sum, points_decompress, selftest_decompress, base_sqrt_, pasta_points_decompress, selftest_base_sqrt, selftest_pasta_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_launch<FS>, ipa_round_launch<FS>, ipa_final_launch<FS>,
-                      ipa_s_products_launch<FS>, selftest_field, selftest_curve,
+                      ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate,
                       chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device,
                       poseidon_table, poseidon_permute_launch, poseidon_hash_launch, poseidon_merkle_launch, selftest_poseidon};

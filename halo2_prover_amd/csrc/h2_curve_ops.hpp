@@ -69,6 +69,14 @@ struct CurveOps {
   hipError_t (*points_decompress)(const void* d_compressed, void* d_out_affine, void* d_status, uint32_t n, hipStream_t s);
   // the same routine instantiated on the host, one point per call (CPU tests); NULL where points_decompress is
   int (*selftest_decompress)(const uint8_t in[32], uint64_t out_affine[8]);
+  // square roots in the base field (h2_sqrt.hpp), every curve: n elements in the API form -> n even roots and n status bytes;
+  // d_out may be d_in
+  hipError_t (*base_sqrt)(const void* d_in, void* d_out, void* d_status, uint32_t n, hipStream_t s);
+  // points_decompress for the Pasta wire form (bit 255 the parity, no identity flag; h2_decompress.hpp); NULL for BN254
+  hipError_t (*pasta_points_decompress)(const void* d_compressed, void* d_out_affine, void* d_status, uint32_t n, hipStream_t s);
+  // the same two routines instantiated on the host, one element or point per call (CPU tests); the second NULL for BN254
+  int (*selftest_base_sqrt)(const uint64_t in_mont[4], uint64_t out_mont[4]);
+  int (*selftest_pasta_decompress)(const uint8_t in[32], uint64_t out_affine[8]);
   // NTT over the scalar field
   // the tables of one (omega, log n [, constant]): inter-pass twiddles, unpacked radix twiddles per pass, the
   // canonicalisation table (h2_ntt29.hpp).  ntt_scale_in_table: a transform scaled by a constant takes that constant
@@ -158,6 +166,9 @@ struct CurveOps {
   hipError_t (*ipa_final)(uint32_t k, void* d_state, const uint64_t u[4], const uint64_t uinv[4], void* d_out, void* d_s_out,
                           hipStream_t s);
   hipError_t (*ipa_s_products)(const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out, hipStream_t s);
+  // the sum of `count` <= IPA_SUM_GROUP compute_s vectors from the table ipa_sum_fill made of them (d_table, in HBM), added
+  // to what d_out holds when `accumulate`
+  hipError_t (*ipa_s_sum)(const void* d_table, uint32_t count, uint32_t k, void* d_out, bool accumulate, hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)
   int (*selftest_field)(int which /* 0 = base field, 1 = scalar field */, int op, const uint64_t* a,
                         const uint64_t* b, uint64_t* out);

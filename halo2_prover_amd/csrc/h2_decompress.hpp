@@ -3,17 +3,21 @@
 //
 // The batch verifier (h2_verify_proofs, h2_prover.hip) knows where the points of a proof sit before it has hashed a
 // byte of it, so the one square root per point -- most of what the host spends replaying a transcript: 0.06 ms per proof
-// are left without it -- is taken for the whole batch in one launch, one lane per point.  Only for base fields with q = 3 mod 4, where
-// sqrt(a) = a^((q + 1) / 4): BN254.  The Pasta fields (2-adicity 32) would need Tonelli-Shanks and have no entry in
-// their CurveOps.
+// are left without it -- is taken for the whole batch in one launch, one lane per point.  That wire
+// form is BN254's, where q = 3 mod 4 and sqrt(a) = a^((q + 1) / 4); h2_points_decompress_device and h2_verify_proofs stay
+// BN254's (the Pasta curves have no points_decompress in their CurveOps).  The Pasta wire form (transcript.py: bit 255 the
+// parity of y, 32 zero bytes the identity, no identity flag) is pasta_decompress below, behind
+// h2_pasta_points_decompress_device: the inner product argument's batch verifier (ipa.verify_proofs) is its caller.
 //
-// The arithmetic is ONE __host__ __device__ function on the 29-bit working form (h2_field29.hpp); the CPU tests run its
-// host instantiation (h2_selftest_host, what = 8) against big integers.  The exponent is a compile-time constant, so
-// every lane takes the same branches: 252 squarings and at most 126 products by a, a^2 or a^3, then one squaring for the
-// residue check, one product for the parity and one to leave the working form.
+// The arithmetic is ONE __host__ __device__ function per wire form on the 29-bit working form (h2_field29.hpp); the CPU
+// tests run the host instantiations (h2_selftest_host, what = 8 and 10) against big integers.  The square root is
+// h2_sqrt.hpp's: for BN254 a compile-time exponent, 252 squarings and at most 126 products by a, a^2 or a^3; for the Pasta
+// fields the power a^((t - 1) / 2) and a discrete logarithm in mu_(2^32) by table.  Every lane takes the same branches.
+// Then one squaring for the residue check, one product for the parity and one to leave the working form.
 #pragma once
 #include "h2_curve.hpp"
 #include "h2_field29.hpp"
+#include "h2_sqrt.hpp"
 
 namespace h2 {
 
@@ -25,8 +29,7 @@ constexpr uint8_t DECOMPRESS_OK = 0, DECOMPRESS_NOT_CANONICAL = 1, DECOMPRESS_ID
 template <class CV>
 H2_HD uint8_t g1_decompress(const uint32_t in[8], Fe<typename CV::Base>& out_x, Fe<typename CV::Base>& out_y) {
   using FP = typename CV::Base;
-  static_assert((FP::P(0) & 3u) == 3u, "square roots by one power need q = 3 mod 4");
-  static_assert((FP::P(7) >> 30) == 0 && ((FP::P(7) >> 29) & 1u) == 1u, "q has 254 bits: (q + 1) / 4 has 252");
+  static_assert(sqrt_by_one_power<FP>(), "this wire form (two flag bits) is BN254's; Pasta: pasta_decompress");
   const uint32_t sign = (in[7] >> 30) & 1u, inf = in[7] >> 31;
   Fe<FP> xi;
 #pragma unroll
@@ -46,34 +49,12 @@ H2_HD uint8_t g1_decompress(const uint32_t in[8], Fe<typename CV::Base>& out_x, 
   Fe<FP> bm;
 #pragma unroll
   for (int i = 0; i < 8; i++) bm.v[i] = CV::B(i);
-  const Fe29<FP> x = fe29_from_api(xm), one = fe29_from_api(Fe<FP>::one());
+  const Fe29<FP> x = fe29_from_api(xm);
   const Fe29<FP> x3 = fe29_mul(fe29_sqr(x), x);             // in (-3p/2, p/2]
   // a = x^3 + b: the curve constant is canonical, so |a| < 3p/2; limbs normalised for the squarings
   const Fe29<FP> a = fe29_norm(fe29_add(x3, fe29_from_api(bm)));
-  const Fe29<FP> a2 = fe29_sqr(a), a3 = fe29_mul(a2, a);
-  // y = a^((q + 1) / 4), two exponent bits at a time from the top; every operand is below 3p/2 in magnitude
-  uint32_t e[8];
-#pragma unroll
-  for (int w = 0; w < 8; w++) {                              // (q + 1) >> 2: the + 1 stays inside the lowest word (q = ...11)
-    const uint64_t lo = (uint64_t)FP::P(w) + (w == 0 ? 1u : 0u), hi = w + 1 < 8 ? FP::P(w + 1) : 0;
-    e[w] = (uint32_t)((lo | (hi << 32)) >> 2);
-  }
-  Fe29<FP> y = one;
-  for (int i = 250; i >= 0; i -= 2) {
-    y = fe29_sqr(fe29_sqr(y));
-    const uint32_t d = (e[i >> 5] >> (i & 31)) & 3u;
-    if (d == 1) y = fe29_mul(y, a);
-    else if (d == 2) y = fe29_mul(y, a2);
-    else if (d == 3) y = fe29_mul(y, a3);
-  }
-  // y^2 == a ?  |y^2 - a| < 3p: within fe29_to_api's reach
-  const bool on_curve = fe29_to_api(fe29_sub(fe29_sqr(y), a)).is_zero();
-  // the parity of y as an integer: y R' / R' through a product with the plain integer 1
-  Fe29<FP> plain_one = Fe29<FP>::zero();
-  plain_one.v[0] = 1;
-  const Fe<FP> y_int = fe29_canonical_pack(fe29_mul(y, plain_one));
-  Fe<FP> ym = fe29_to_api(y);
-  if ((y_int.v[0] & 1u) != sign) ym = fe_neg(ym);
+  Fe<FP> ym = Fe<FP>::zero();
+  const bool on_curve = fe29_sqrt_parity(a, sign, ym);      // y = a^((q + 1) / 4), y^2 == a, the parity (h2_sqrt.hpp)
   const uint8_t status = !canonical ? DECOMPRESS_NOT_CANONICAL : identity ? DECOMPRESS_IDENTITY
                          : !on_curve ? DECOMPRESS_NOT_ON_CURVE : DECOMPRESS_OK;
   out_x = status == DECOMPRESS_OK ? xm : Fe<FP>::zero();
@@ -81,7 +62,37 @@ H2_HD uint8_t g1_decompress(const uint32_t in[8], Fe<typename CV::Base>& out_x, 
   return status;
 }
 
-// one lane per point; status bytes go out as ordinary byte stores
+// The same for the Pasta wire form: bit 255 the parity of y, no identity flag, the identity is x = 0 with parity 0.  The
+// decision and the coordinates are those of transcript.decompress for every 32-byte input.
+template <class CV>
+H2_HD uint8_t pasta_decompress(const uint32_t in[8], Fe<typename CV::Base>& out_x, Fe<typename CV::Base>& out_y) {
+  using FP = typename CV::Base;
+  static_assert(!sqrt_by_one_power<FP>(), "this wire form (one flag bit) is the Pasta curves'");
+  const uint32_t sign = in[7] >> 31;
+  Fe<FP> xi;
+#pragma unroll
+  for (int i = 0; i < 8; i++) xi.v[i] = in[i];
+  xi.v[7] &= 0x7FFFFFFFu;
+  const bool canonical = fe_below_modulus(xi);
+  const bool identity = xi.is_zero() && sign == 0;
+  // a lane whose x is refused runs the chain below on zero and drops the result
+  const Fe<FP> xm = fe_to_mont(canonical ? xi : Fe<FP>::zero());
+  Fe<FP> bm;
+#pragma unroll
+  for (int i = 0; i < 8; i++) bm.v[i] = CV::B(i);
+  const Fe29<FP> x = fe29_from_api(xm);
+  const Fe29<FP> x3 = fe29_mul(fe29_sqr(x), x);             // in (-3p/2, p/2]
+  const Fe29<FP> a = fe29_norm(fe29_add(x3, fe29_from_api(bm)));     // |a| < 3p/2, limbs normalised
+  Fe<FP> ym = Fe<FP>::zero();
+  const bool on_curve = fe29_sqrt_parity(a, sign, ym);
+  const uint8_t status = !canonical ? DECOMPRESS_NOT_CANONICAL : identity ? DECOMPRESS_IDENTITY
+                         : !on_curve ? DECOMPRESS_NOT_ON_CURVE : DECOMPRESS_OK;
+  out_x = status == DECOMPRESS_OK ? xm : Fe<FP>::zero();
+  out_y = status == DECOMPRESS_OK ? ym : Fe<FP>::zero();
+  return status;
+}
+
+// one lane per point, each curve in its own wire form; status bytes go out as ordinary byte stores
 template <class CV>
 __global__ void __launch_bounds__(64)
 points_decompress_kernel(const uint32_t* __restrict__ in /* n x 8 words */, U128* __restrict__ out /* n x 64 bytes */,
@@ -92,7 +103,9 @@ points_decompress_kernel(const uint32_t* __restrict__ in /* n x 8 words */, U128
   const U128 lo = reinterpret_cast<const U128*>(in)[2 * (size_t)i], hi = reinterpret_cast<const U128*>(in)[2 * (size_t)i + 1];
   const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
   Fe<FB> x, y;
-  const uint8_t st = g1_decompress<CV>(w, x, y);
+  uint8_t st;
+  if constexpr (sqrt_by_one_power<FB>()) st = g1_decompress<CV>(w, x, y);
+  else st = pasta_decompress<CV>(w, x, y);
   fe_store<FB>(out + 4 * (size_t)i, x);
   fe_store<FB>(out + 4 * (size_t)i + 2, y);
   status[i] = st;

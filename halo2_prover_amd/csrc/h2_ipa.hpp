@@ -33,6 +33,7 @@
 #include "h2_field29.hpp"
 
 #include <cstring>
+#include <type_traits>
 
 namespace h2 {
 
@@ -336,6 +337,133 @@ hipError_t ipa_s_products_launch(const uint64_t* u, uint32_t k, const uint64_t i
     hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, (U128*)d_out, count,
                        ipa_fe<FP>(u + 4 * (k - 1 - t)), in, t == 0 ? 1 : 0);
   }
+  return hipGetLastError();
+}
+
+// ---- the weighted sum of challenge-product vectors (h2_ipa_challenge_products_sum_device) -----------------------------------
+// out[i] = sum_p init_p prod_{bit t of i} u_p[k-1-t]: what a batch verifier needs of `count` compute_s vectors -- their sum,
+// the N final equations being linear in the same table -- without any of them in memory.
+//
+// A thread owns the run of 2^4 consecutive indices [16 T, 16 T + 16).  Per proof it forms the product over the HIGH k - 4 bits
+// of its run (the proof's table entry is the same for the whole launch: scalar loads; the multiplier is a select between
+// u and one, the bits differ inside a wave), expands the run depth-first with 2^4 - 1 products (bit t of the index
+// multiplies by u[k-1-t]) and adds the sixteen values into sixteen lazy accumulators: (k - 4 + 15) / 16 < 2 products per
+// element and proof for k <= 20.  For k < 4 the levels from k up multiply by one and the indices from 2^k up are not
+// stored (r = min(4, k) with the missing levels padded: a launch of one thread, 15 products per proof whatever k).
+//
+// The table (host-made, ipa_sum_fill, in the scan arena for the length of the call): per proof the canonical init (8
+// words) and max(k, 4) multipliers, level t holding u[k-1-t] (one for t >= k) as expr_column_operand makes it, 9 limbs.
+//
+// Arithmetic as poly_lincomb_kernel's: d (canonical, plain-unpacked: x 2^256 mod p) times c' (the operand form, in
+// (-16 p, 16 p)) is d c' / R' - m p, the API form of the product.  With |d| <= B the result lies in (-B / 8 - p, B / 8]
+// (R' > 128 p), so a chain of such products that starts from a canonical value stays in (-8p/7, p/7], limbs normalised.
+// The accumulators, in units of p:
+//   * a term is added limb-wise; after every SECOND proof one carry pass: a normalised sum plus two normalised terms has
+//     limbs below 3 * 2^29 < 2^31;
+//   * every IPA_SUM_FOLD = 32 proofs the sum is multiplied by the working form of one: unchanged mod p, it falls below
+//     |acc| / 128 + p.  Between folds |acc| < 1.4 p + 32 * 8p/7 < 38.2 p (a later group starts from the canonical value
+//     already in d_out instead: < p + 36.6 p), the top limb below 39 * 2^23 < 2^29: a valid operand;
+//   * the last product with one lands in (-39p/128 - p, 39p/128], inside fe29_canonical_pack's (-2p, p).  The stored limbs
+//     are canonical, so the bits do not depend on how the proofs were grouped.  No atomics: an output has one owner.
+constexpr uint32_t IPA_SUM_RUN_LOG = 4;
+constexpr uint32_t IPA_SUM_FOLD = 32;
+constexpr size_t IPA_SUM_GROUP = 65535;                   // proofs per launch
+constexpr int IPA_SUM_THREADS = 64;
+static_assert(IPA_SUM_FOLD % 2 == 0, "the fold follows a carry pass");
+
+inline uint32_t ipa_sum_levels(uint32_t k) { return k > IPA_SUM_RUN_LOG ? k : IPA_SUM_RUN_LOG; }
+inline uint32_t ipa_sum_stride(uint32_t k) { return 8 + 9 * ipa_sum_levels(k); }     // 32-bit words per proof
+
+// the table of `count` proofs at out: u count * k * 4 limbs, init count * 4 limbs, canonical Montgomery
+template <class FP>
+void ipa_sum_fill(const uint64_t* u, const uint64_t* init, uint32_t k, size_t count, int32_t* out) {
+  const uint32_t levels = ipa_sum_levels(k), stride = ipa_sum_stride(k);
+  const Fe29<FP> one = expr_column_operand(Fe<FP>::one());
+  for (size_t p = 0; p < count; p++) {
+    int32_t* row = out + p * stride;
+    memcpy(row, init + 4 * p, 32);
+    for (uint32_t t = 0; t < levels; t++) {
+      const Fe29<FP> m = t < k ? expr_column_operand(ipa_fe<FP>(u + 4 * (p * k + (k - 1 - t)))) : one;
+      memcpy(row + 8 + 9 * t, m.v, 36);
+    }
+  }
+}
+
+// fn(integral_constant<int, 0>) ... fn(integral_constant<int, N - 1>): the accumulators are indexed by constants from the
+// front end on, so they are registers whatever the unroller decides
+template <int N, class Fn>
+__device__ __forceinline__ void ipa_static_for(Fn&& fn) {
+  if constexpr (N > 0) {
+    ipa_static_for<N - 1>(fn);
+    fn(std::integral_constant<int, N - 1>{});
+  }
+}
+
+// the run below `val` (the product over the levels from LEVEL up): level t - 1 multiplies the upper half by op[t - 1]
+template <class FP, int LEVEL, int IDX>
+__device__ __forceinline__ void ipa_sum_expand(const Fe29<FP>& val, const Fe29<FP>* op, Fe29<FP>* acc) {
+  if constexpr (LEVEL == 0) {
+    acc[IDX] = fe29_add(acc[IDX], val);
+  } else {
+    ipa_sum_expand<FP, LEVEL - 1, IDX>(val, op, acc);
+    ipa_sum_expand<FP, LEVEL - 1, IDX + (1 << (LEVEL - 1))>(fe29_mul(val, op[LEVEL - 1]), op, acc);
+  }
+}
+
+template <class FP>
+__global__ void __launch_bounds__(IPA_SUM_THREADS)
+ipa_s_sum_kernel(const int32_t* __restrict__ table, uint32_t stride, uint32_t count, uint32_t k, U128* out, int accumulate) {
+  using F = Fe<FP>;
+  using W = Fe29<FP>;
+  constexpr int RUN = 1 << IPA_SUM_RUN_LOG;
+  const size_t n = (size_t)1 << k;
+  const size_t T = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t first = T * RUN;
+  if (first >= n) return;
+  const W one = fe29_from_api(F::one()), one_op = expr_column_operand(F::one());
+  W acc[RUN];
+  ipa_static_for<RUN>([&](auto g) {
+    acc[g] = accumulate && first + g < n ? fe29_unpack(fe_load<FP>(out + 2 * (first + g))) : W::zero();
+  });
+  for (uint32_t p = 0; p < count; p++) {
+    const int32_t* __restrict__ row = table + (size_t)p * stride;
+    F init;
+#pragma unroll
+    for (int l = 0; l < 8; l++) init.v[l] = (uint32_t)row[l];
+    auto level = [&](uint32_t t) {
+      W m;
+#pragma unroll
+      for (int l = 0; l < 9; l++) m.v[l] = row[8 + 9 * t + l];
+      return m;
+    };
+    W val = fe29_unpack(init);
+    for (uint32_t t = IPA_SUM_RUN_LOG; t < k; t++) {
+      const W m = level(t);
+      const bool set = (T >> (t - IPA_SUM_RUN_LOG)) & 1;
+      W sel;
+#pragma unroll
+      for (int l = 0; l < 9; l++) sel.v[l] = set ? m.v[l] : one_op.v[l];
+      val = fe29_mul(val, sel);
+    }
+    W op[IPA_SUM_RUN_LOG];
+#pragma unroll
+    for (uint32_t t = 0; t < IPA_SUM_RUN_LOG; t++) op[t] = level(t);
+    ipa_sum_expand<FP, (int)IPA_SUM_RUN_LOG, 0>(val, op, acc);
+    if (p & 1) {
+      ipa_static_for<RUN>([&](auto g) { acc[g] = fe29_norm(acc[g]); });
+      if ((p + 1) % IPA_SUM_FOLD == 0) ipa_static_for<RUN>([&](auto g) { acc[g] = fe29_mul(acc[g], one); });
+    }
+  }
+  ipa_static_for<RUN>([&](auto g) {
+    if (first + g < n) fe_store<FP>(out + 2 * (first + g), fe29_canonical_pack(fe29_mul(fe29_norm(acc[g]), one)));
+  });
+}
+
+template <class FP>
+hipError_t ipa_s_sum_launch(const void* d_table, uint32_t count, uint32_t k, void* d_out, bool accumulate, hipStream_t s) {
+  const size_t threads = (((size_t)1 << k) + (1u << IPA_SUM_RUN_LOG) - 1) >> IPA_SUM_RUN_LOG;
+  hipLaunchKernelGGL(ipa_s_sum_kernel<FP>, dim3((unsigned)((threads + IPA_SUM_THREADS - 1) / IPA_SUM_THREADS)), dim3(IPA_SUM_THREADS), 0, s,
+                     (const int32_t*)d_table, ipa_sum_stride(k), count, k, (U128*)d_out, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 

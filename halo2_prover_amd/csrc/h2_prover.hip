@@ -123,6 +123,34 @@ int emit(const std::vector<uint8_t>& data, uint8_t* out, size_t cap, size_t* out
   return H2_OK;
 }
 
+// what = 10 / 11 of h2_selftest_host: the host instantiations of pasta_decompress and base_sqrt over the base field FB of `ops`
+template <class FB>
+static int sqrt_selftest(const CurveOps* ops, int what, const uint8_t* in, size_t n, std::vector<uint8_t>& r) {
+  for (size_t i = 0; i < n; i++) {
+    uint8_t b[65];
+    if (what == 10) {
+      if (!ops->selftest_pasta_decompress) return H2_EINVAL;
+      uint64_t aff[8];
+      const int st = ops->selftest_pasta_decompress(in + 32 * i, aff);
+      HF<FB>::from_mont_limbs(aff).to_le_bytes(b);
+      HF<FB>::from_mont_limbs(aff + 4).to_le_bytes(b + 32);
+      b[64] = (uint8_t)st;
+      r.insert(r.end(), b, b + 65);
+    } else {
+      // a canonical element goes in as its Montgomery limbs; anything else as the bytes it is, for the routine to refuse
+      uint64_t a[4], root[4];
+      HF<FB> e;
+      if (HF<FB>::from_le_bytes_canonical(in + 32 * i, &e)) memcpy(a, e.v.v, 32);
+      else memcpy(a, in + 32 * i, 32);
+      const int st = ops->selftest_base_sqrt(a, root);
+      HF<FB>::from_mont_limbs(root).to_le_bytes(b);
+      b[32] = (uint8_t)st;
+      r.insert(r.end(), b, b + 33);
+    }
+  }
+  return H2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -513,6 +541,14 @@ int h2_selftest_host(int what, const uint8_t* in, size_t in_len, uint8_t* out, s
         b[64] = (uint8_t)st;
         r.insert(r.end(), b, b + 65);
       }
+    } else if (what == 10 || what == 11) { // pasta_decompress / base_sqrt on the host: one curve byte, then n x 32 bytes ->
+      if (in_len < 1 || (in_len - 1) % 32 || !curve_ok(in[0])) return H2_EINVAL;   // n x (64 + 1) / n x (32 + 1) bytes
+      const CurveOps* ops = ops_of(in[0]);
+      const size_t n = (in_len - 1) / 32;
+      const int rc = in[0] == H2_BN254    ? sqrt_selftest<BN254_CURVE::Base>(ops, what, in + 1, n, r)
+                     : in[0] == H2_PALLAS ? sqrt_selftest<PALLAS_CURVE::Base>(ops, what, in + 1, n, r)
+                                          : sqrt_selftest<VESTA_CURVE::Base>(ops, what, in + 1, n, r);
+      if (rc != H2_OK) return rc;
     } else if (what == 5) {                // pairing check on two (G1, G2) pairs: 2 x (64 + 128) canonical bytes -> 1 byte
       if (in_len != 2 * 192) return H2_EINVAL;
       std::vector<std::pair<G1, bn::G2>> pairs;

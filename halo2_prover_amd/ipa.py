@@ -7,16 +7,21 @@ h2_ipa_begin_device / h2_ipa_round_device / h2_ipa_final_device -- no generator 
 two-column MSM over the registered table -- and `verify_proof` checks
     sum [u_j^-1] L_j + P' + sum [u_j] R_j == [c] <s, G> + [c b_0 z] U + [f] W,   P' = P - [v] G[0] + [xi] S
 with <s, G> and the U, W, G[0] terms as ONE h2_msm_device on the same table (s from h2_ipa_challenge_products_device).
+`verify_proofs` checks N such proofs behind ONE combined equation: the N equations are linear in the same table, so with
+random weights r_p they collapse into one table MSM and one points MSM; the 2k + 1 compressed
+points of every proof are decompressed by one kernel launch (h2_pasta_points_decompress_device) and the weighted sum of the
+N compute_s vectors comes from h2_ipa_challenge_products_sum_device, none of them materialised.
 Polynomials are (n, 4) int64 CUDA tensors viewing 4 x u64 Montgomery limbs (numpy uint64 arrays are uploaded); points are
 affine (x, y) pairs of canonical ints, None for the identity.  The transcript is transcript.Blake2bTranscript on the
 curve.  `ParamsIPA::new`'s hash-to-curve is not here: the bases are the caller's.  There is no CPU fallback.
 """
 import ctypes
+import os
 
 import numpy as np
 
 from . import lib as _lib
-from .api import Bases, _as_u64, _curve_id, _ensure_init, msm_points
+from .api import Bases, _as_u64, _curve_id, _ensure_init, msm_points, msm_points_device
 from .domain import EvaluationDomain
 from .opening import poly_lincomb
 from .transcript import FIELDS, Blake2bTranscript  # noqa: F401
@@ -234,3 +239,177 @@ def verify_proof(params, transcript, P, x3, v):
     if table_side is None or other is None:
         return table_side is None and other is None
     return table_side[0] == other[0] and (table_side[1] + other[1]) % params.q == 0
+
+
+def challenge_products_sum(curve, k, u, init, out=None):
+    """sum_p compute_s(u[p], init[p]) as a (2^k, 4) int64 CUDA tensor (h2_ipa_challenge_products_sum_device), over the scalar
+    field of `curve`, on the current stream: u a list of `count` challenge lists (k canonical ints each), init `count`
+    canonical ints.  out: a CUDA tensor to write into (its first 2^k rows), or None."""
+    import torch
+    from .poseidon import _stream
+    _ensure_init()
+    cv = _curve_id(curve)
+    p = FIELDS[cv][0]
+    R = (1 << 256) % p
+    count = len(u)
+    if len(init) != count or any(len(x) != k for x in u):
+        raise ValueError("challenge_products_sum: count x k challenges and count inits")
+    um = np.concatenate([_limbs(x % p * R % p) for row in u for x in row]) if count else None
+    im = np.concatenate([_limbs(x % p * R % p) for x in init]) if count else None
+    if out is None:
+        out = torch.empty((1 << k, 4), dtype=torch.int64, device="cuda")
+    st = _lib.load().h2_ipa_challenge_products_sum_device(cv, um.ctypes.data if count else None, im.ctypes.data if count else None,
+                                                          k, count, ctypes.c_void_p(out.data_ptr()), _stream())
+    _lib.check(st, "h2_ipa_challenge_products_sum_device")
+    return out
+
+
+class _Replayed:
+    """what the replay of one transcript leaves for the combined check"""
+    __slots__ = ("first", "P", "v", "xi", "z", "u", "u_inv", "c", "f", "b0")
+
+
+def verify_proofs(params, items, rng=None, stats=None):
+    """verify_proof for a batch: items = sequence of (reading transcript, P, x3, v), each transcript positioned where
+    verify_proof would start -> list[bool], entry i exactly what verify_proof(params, *items[i]) returns, every transcript
+    left where verify_proof leaves it.  rng: a callable n -> n bytes (default os.urandom) for the weights, 16 bytes per proof,
+    little-endian, a zero weight redrawn.  stats: an optional dict, filled with {"checks": combined checks run, "points":
+    points decompressed, "rejected_early": items refused before any check}.
+
+    One decompression launch and one read-back for all the points; the host replays the transcripts with the decoded points
+    (no square root on the host); then ONE combined check -- the challenge-product sum, one h2_msm_device on the registered
+    table, one h2_msm_points_device whose point operand is the decompression's own output with the commitments uploaded
+    behind it -- and 96 bytes read back.  A failing batch is halved on the replayed data until every culprit is alone."""
+    import torch
+    from .transcript import TranscriptError
+    if params.curve == 0:
+        raise ValueError("verify_proofs: the Pasta wire form; BN254 proofs go through verify_proof")
+    rng = rng or os.urandom
+    items = list(items)
+    N = len(items)
+    st = {"checks": 0, "points": 0, "rejected_early": 0}
+    if stats is not None:
+        stats.update(st)
+    if N == 0:
+        return []
+    L, cv, k, n, p, q = params._L, params.curve, params.k, params.n, params.p, params.q
+    dom = params.domain
+    stream = dom._stream()
+    per = 2 * k + 1
+    # 1. gather: the compressed points that are there, item after item
+    chunks, first = [], []
+    for tr, _, _, _ in items:
+        have = 0 if tr.buf is None else max(0, min(per, (len(tr.buf) - tr.pos) // 32))
+        first.append(len(chunks))
+        chunks.extend(tr.buf[tr.pos + 32 * j:tr.pos + 32 * j + 32] for j in range(have))
+    first.append(len(chunks))
+    G = len(chunks)
+    st["points"] = G
+    # 2. decompress: one launch, one read-back.  The affine output is the front of the points MSM's operand
+    d_points = torch.zeros((G + N, 8), dtype=torch.int64, device="cuda")
+    status = b""
+    aff = np.zeros((0, 8), dtype=np.uint64)
+    if G:
+        d_wire = torch.from_numpy(np.frombuffer(b"".join(chunks), dtype=np.int64).copy()).cuda()
+        d_status = torch.empty(G, dtype=torch.uint8, device="cuda")
+        _lib.check(L.h2_pasta_points_decompress_device(cv, ctypes.c_void_p(d_wire.data_ptr()), G, ctypes.c_void_p(d_points.data_ptr()),
+                                                       ctypes.c_void_p(d_status.data_ptr()), stream), "h2_pasta_points_decompress_device")
+        back = torch.cat([d_points[:G].reshape(-1).view(torch.uint8), d_status]).cpu().numpy()
+        aff, status = back[:64 * G].view(np.uint64).reshape(G, 8), bytes(back[64 * G:])
+    # 3. replay on the host with the decoded points
+    ok = [False] * N
+    live = {}
+    for i, (tr, P, x3, v) in enumerate(items):
+        lo, hi = first[i], first[i + 1]
+        cursor = [lo]
+
+        def point():
+            j = cursor[0]
+            cursor[0] += 1
+            if j >= hi:
+                return tr.read_point()                       # no bytes left: raises as verify_proof's read would
+            return tr.read_point_decoded(params.affine_ints(aff[j]) if status[j] == 0 else None, status[j])
+        try:
+            point()
+            xi = tr.squeeze_challenge()
+            z = tr.squeeze_challenge()
+            u = []
+            for _ in range(k):
+                point()
+                point()
+                u.append(tr.squeeze_challenge())
+            c = tr.read_scalar()
+            f = tr.read_scalar()
+        except TranscriptError:
+            st["rejected_early"] += 1
+            continue
+        if any(x == 0 for x in u):
+            st["rejected_early"] += 1
+            continue
+        r = _Replayed()
+        r.first, r.P, r.v, r.xi, r.z, r.u, r.c, r.f = lo, P, v % p, xi, z, u, c, f
+        r.u_inv = [pow(x, -1, p) for x in u]
+        r.b0 = compute_b(x3, u, p)
+        live[i] = r
+    if live:
+        d_points[G:] = torch.from_numpy(np.stack([params.affine_limbs(P) for _, P, _, _ in items]).view(np.int64)).cuda()
+    col = torch.empty((n + 2, 4), dtype=torch.int64, device="cuda")
+    jac = torch.empty(24, dtype=torch.int64, device="cuda")
+    total = torch.empty(12, dtype=torch.int64, device="cuda")
+
+    def weight():
+        while True:
+            w = int.from_bytes(bytes(rng(16)), "little")
+            if w:
+                return w
+
+    def check(subset):
+        """sum_p r_p (sum [1/u_j] L_j + P + [xi] S + sum [u_j] R_j - [v] G[0] - [c] <s, G> - [c b0 z] U - [f] W) == 0 over the subset"""
+        st["checks"] += 1
+        scal = np.zeros((G + N, 4), dtype=np.uint64)
+        inits, row0, tail_u, tail_w = [], 0, 0, 0
+        for i in subset:
+            r, w = live[i], weight()
+            inits.append(-w * r.c % p)
+            row0 += w * r.v
+            tail_u += w * r.c % p * r.b0 % p * r.z
+            tail_w += w * r.f
+            scal[r.first] = params.mont(w * r.xi)
+            for j in range(k):
+                scal[r.first + 1 + 2 * j] = params.mont(w * r.u_inv[j])
+                scal[r.first + 2 + 2 * j] = params.mont(w * r.u[j])
+            if r.P is not None:
+                scal[G + i] = params.mont(w)
+        challenge_products_sum(cv, k, [live[i].u for i in subset], inits, out=col)
+        poly_lincomb(dom, [(col, [(1, col)], [row0 % p], [])], n)                        # col[0] -= sum r_p v_p
+        col[n:] = torch.from_numpy(np.stack([params.mont(-tail_u), params.mont(-tail_w)]).view(np.int64)).to(col.device)
+        d_scal = torch.from_numpy(scal.view(np.int64)).cuda()
+        params.bases.msm_device(col.data_ptr(), n + 2, 1, jac.data_ptr(), stream.value or 0)
+        msm_points_device(d_points.data_ptr(), d_scal.data_ptr(), G + N, G + N, 1, jac.data_ptr() + 96, stream.value or 0, cv)
+        params.bases.points_sum_device(jac.data_ptr(), 2, 1, total.data_ptr(), stream.value or 0)
+        Z = total[8:].cpu().numpy()
+        return not Z.any()
+
+    def settle(subset, known_bad):
+        """the verdicts of a subset; known_bad: a combined check has already shown that it holds a culprit"""
+        if not known_bad and check(subset):
+            for i in subset:
+                ok[i] = True
+            return
+        if len(subset) == 1:
+            return                                            # a singleton's verdict is its own equation; r != 0
+        half = len(subset) // 2
+        left, right = subset[:half], subset[half:]
+        if check(left):
+            for i in left:
+                ok[i] = True
+            settle(right, len(right) > 1)                     # the culprits are on the other side; one alone is still checked
+        else:
+            settle(left, True)
+            settle(right, False)
+
+    if live:
+        settle(sorted(live), False)
+    if stats is not None:
+        stats.update(st)
+    return ok

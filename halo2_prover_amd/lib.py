@@ -58,6 +58,8 @@ SYMBOLS = {
     "h2_msm_device_range": (_I, [_I, _U64, _P, _Z, _Z, _Z, _Z, _P, _P]),
     "h2_points_sum_device": (_I, [_I, _P, _Z, _Z, _P, _P]),
     "h2_points_decompress_device": (_I, [_I, _P, _Z, _P, _P, _P]),
+    "h2_base_sqrt_device": (_I, [_I, _P, _Z, _P, _P, _P]),
+    "h2_pasta_points_decompress_device": (_I, [_I, _P, _Z, _P, _P, _P]),
     "h2_stream_wait_msm_tail": (_I, [_P]),
     "h2_msm_device_multi": (_I, [_I, _P, _P, _Z, _Z, _Z, _Z, _P, _P]),
     "h2_msm_points_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P]),
@@ -90,6 +92,7 @@ SYMBOLS = {
     "h2_ipa_round_device": (_I, [_I, _U64, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_final_device": (_I, [_I, _U32, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_challenge_products_device": (_I, [_I, _P, _U32, _P, _P, _P]),
+    "h2_ipa_challenge_products_sum_device": (_I, [_I, _P, _P, _U32, _Z, _P, _P]),
     "h2_poseidon_constants": (_I, [_I, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_poseidon_permute_device": (_I, [_I, _U32, _U32, _P, _P, _Z, _P]),
     "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),

@@ -136,3 +136,13 @@ class Blake2bTranscript:
         pt = decompress(self.curve, self._take())
         self.common_point(pt)
         return pt
+
+    def read_point_decoded(self, pt, status=0):
+        """read_point for a point whose 32 bytes were decompressed elsewhere (ipa.verify_proofs: one kernel launch for a whole
+        batch): consumes the bytes and absorbs `pt`.  status: the decompression's (0 a point, 2 the identity with pt None,
+        1 / 3 what read_point refuses: TranscriptError with the bytes consumed, as read_point leaves it)."""
+        self._take()
+        if status in (1, 3):
+            raise TranscriptError("point x not canonical" if status == 1 else "point not on the curve")
+        self.common_point(pt)
+        return pt

@@ -201,6 +201,21 @@ int h2_msm_points_plan(h2_curve_t curve, size_t n, h2_msm_points_plan_t* out);
 int h2_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine,
                                 void* d_status, void* stream);
 
+/* square roots in the BASE field of `curve` (all three curves): n elements (4 x u64 Montgomery limbs) -> n roots and n status
+ * bytes: 0 = root written (of the two, the one whose canonical integer is even; 0 for 0), 1 = input not canonical,
+ * 3 = not a square.  For status != 0 the 32 output bytes are zero.  d_out may equal d_in exactly.  One lane per element, the
+ * same instructions for every element (csrc/h2_sqrt.hpp: BN254 by one power, the Pasta fields -- q = 1 mod 2^32 -- by a power
+ * and a discrete logarithm in the 2^32-th roots of unity, four bits at a time by table).
+ * Device pointers; d_in and d_out 16-byte aligned; n <= 2^30; an output that partly overlaps an input is H2_EINVAL, as is
+ * every other bad argument, before anything is enqueued; n = 0 enqueues nothing; asynchronous on `stream`. */
+int h2_base_sqrt_device(h2_curve_t curve, const void* d_in, size_t n, void* d_out, void* d_status, void* stream);
+/* h2_points_decompress_device for the Pasta wire form (transcript.py: x little-endian, bit 255 the parity of y, 32 zero
+ * bytes the identity; no identity flag): H2_PALLAS and H2_VESTA only, H2_BN254 is H2_EINVAL.  Same outputs and status
+ * codes 0 / 1 / 2 / 3; decision and coordinates are transcript.decompress's for EVERY 32-byte input.  Same pointer rules;
+ * no output may overlap the input. */
+int h2_pasta_points_decompress_device(h2_curve_t curve, const void* d_compressed, size_t n, void* d_out_affine,
+                                      void* d_status, void* stream);
+
 /* ---- NTT == best_fft(a, omega, log_n) ---------------------------------------------------
  * In place, natural order in and out, A[i] = sum_j a[j] * omega^(i*j), unscaled, over the
  * SCALAR field of `curve` (bn256::Fr for H2_BN254).  a must hold exactly 1 << log_n elements. */
@@ -387,6 +402,13 @@ int h2_ipa_final_device(h2_curve_t curve, uint32_t k, void* d_state, const uint6
                         void* d_out, void* d_s_out, void* stream);
 int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out,
                                      void* stream);
+/* d_out[i] = sum_{p < count} init_p * prod over the set bits t of i of u_p[k-1-t],  i < 2^k: the sum of `count`
+ * compute_s(u_p, init_p) vectors, none of them materialised.  u: count * k * 4 limbs, init: count * 4 limbs, HOST, canonical
+ * Montgomery, read before the call returns.  Canonical output, the same bits however the proofs are grouped (one launch per
+ * 65535 proofs, the later ones adding into d_out).  1 <= k <= H2_IPA_MAX_K; d_out 16-byte aligned; a null u or init with
+ * count > 0 is H2_EINVAL; count = 0 writes 2^k zeros. */
+int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, const uint64_t* init, uint32_t k, size_t count,
+                                         void* d_out, void* stream);
 /* ---- Poseidon over resident columns: permutation, ConstantLength hash, Merkle tree ---------------------------------
  * The Poseidon primitive of circuits/src/poseidon/primitives*: width 3, rate 2, S-box x^5, r_f full and r_p partial
  * rounds, over the scalar field of `curve` (all three curves), constants from the reference's Grain / Cauchy-MDS

@@ -117,7 +117,13 @@ int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters, double* mo
  *    E records of three i32 {kind, index, rotation} in the order the evaluations go onto the transcript; Q records of
  *    four i32 {kind, index, rotation, index of the query's evaluation among the E, -1 for h} in the batching order of
  *    the multi-open.  kind: 0 advice, 1 fixed, 2 sigma, 3 permutation product, 4 random polynomial, 5 h; index: the
- *    column, the permutation column or the product's set; rotation in rows (signed). */
+ *    column, the permutation column or the product's set; rotation in rows (signed);
+ * 10: the host instantiation of the Pasta decompression routine (csrc/h2_decompress.hpp, pasta_decompress): one curve byte
+ *    (1 = Pallas, 2 = Vesta; BN254 is H2_EINVAL), then n x 32 bytes in the Pasta wire form -> n x (64 canonical LE bytes
+ *    x || y, then the status byte of h2_pasta_points_decompress_device);
+ * 11: the host instantiation of the base field's square root (csrc/h2_sqrt.hpp): one curve byte (0, 1 or 2), then n x 32
+ *    little-endian field elements (one that is not canonical is handed on as it is, to be refused) -> n x (32 canonical LE
+ *    bytes of the root, then the status byte of h2_base_sqrt_device). */
 /* commit phases of the C++ prover / keygen that were spread over more than one context (h2_init_devices) so far */
 uint64_t h2_selftest_sharded_commits(void);
 /* rows per context from which the C++ prover spreads a commit phase over the contexts (default 1024; 0 restores it) */

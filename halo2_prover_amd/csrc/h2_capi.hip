@@ -322,6 +322,18 @@ int msm_device_run(DevCtx& c, int curve, const BasesEntry& be, const void* d_sca
   return H2_OK;
 }
 
+// What msm_device_run would refuse with H2_EINVAL for m columns of n scalars on `be`, found on the host without enqueuing
+// anything: the same plans, in the same groups.  For a caller that enqueues work of its own in front of the MSM.
+static int msm_device_plan_check(const BasesEntry& be, size_t n, size_t col_stride, size_t m) {
+  if (msm_cols_per_launch(be.geom, n) == 0) return H2_EINVAL;
+  for (size_t j0 = 0; j0 < m;) {
+    const MsmGroupPlan plan = msm_plan_group(be.geom, be.n, n, m - j0, col_stride, g_knobs.msm_guard, g_knobs.sort2_pack);
+    if (plan.cols == 0 || plan.ws.E >= (1ull << 31) || plan.ws.K >= (1ull << 31)) return H2_EINVAL;
+    j0 += plan.cols;
+  }
+  return H2_OK;
+}
+
 // ---- table-free MSM over the caller's points (h2_msm_points.hpp) ---------------------------------------------------
 // arguments checked by the caller; n >= 1, m >= 1
 static int msm_points_run(DevCtx& c, int curve, const void* d_points, const void* d_scalars, size_t n, size_t col_stride,
@@ -1881,6 +1893,86 @@ int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, co
     if (int rc = launched(ops->ipa_s_sum(A.a.p, (uint32_t)cnt, k_, d_out, p0 > 0, k.stream), "ipa_s_sum_kernel"); rc != H2_OK) return rc;
   }
   return A.release();
+}
+
+// ---- m openings in lockstep (h2_ipa.hpp, IpaBatchLayout) -------------------------------------------------------------------
+static_assert(H2_IPA_MAX_BATCH == IPA_MAX_BATCH, "the header states the kernels' maximum");
+
+int h2_ipa_batch_state_bytes(uint32_t k, size_t m, size_t* out) {
+  if (k == 0 || k > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH || !out) return H2_EINVAL;
+  *out = IpaBatchLayout(k, m).total * 32;
+  return H2_OK;
+}
+
+// The call's scalar table: rows[r] holds m x 4 limbs (null: a row of zeros) and becomes row r of the table at the end of the
+// state; `ptrs` (begin only) are the m device pointers stored behind row 0.  One copy, enqueued before the call's kernels.
+static int ipa_batch_table(const IpaBatchLayout& L, const uint64_t* const* rows, size_t n_rows, const void* const* ptrs, void* d_state,
+                           hipStream_t stream) {
+  uint64_t host[IPA_BATCH_SCALARS * IPA_MAX_BATCH * 4];
+  const size_t m = L.m;
+  for (size_t r = 0; r < n_rows; r++) {
+    if (rows[r])
+      memcpy(host + r * m * 4, rows[r], m * 32);
+    else
+      memset(host + r * m * 4, 0, m * 32);
+  }
+  size_t words = n_rows * m * 4;
+  if (ptrs) {
+    for (size_t i = 0; i < m; i++) host[words + i] = (uint64_t)(uintptr_t)ptrs[i];
+    words += m;
+  }
+  // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
+  H2_TRY(hipMemcpyAsync((char*)d_state + L.scal * 32, host, words * 8, hipMemcpyHostToDevice, stream));
+  return H2_OK;
+}
+
+int h2_ipa_begin_batch_device(h2_curve_t curve, uint32_t k_, size_t m, const void* const* d_p, const uint64_t* x3, void* d_state,
+                              void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH || !d_p || !x3 || !ipa_dev_ptr(d_state))
+    return H2_EINVAL;
+  for (size_t i = 0; i < m; i++)
+    if (!ipa_dev_ptr(d_p[i])) return H2_EINVAL;
+  const IpaBatchLayout L(k_, m);
+  const uint64_t* rows[1] = {x3};
+  if (int rc = ipa_batch_table(L, rows, 1, d_p, d_state, k.stream); rc != H2_OK) return rc;
+  return launched(ops_of((int)curve)->ipa_begin_batch(k_, m, d_state, k.stream), "ipa_begin_batch_kernel");
+}
+
+int h2_ipa_round_batch_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uint32_t j, size_t m, void* d_state,
+                              const uint64_t* u_prev, const uint64_t* u_prev_inv, const uint64_t* z, const uint64_t* l_blind,
+                              const uint64_t* r_blind, void* d_out_affine, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || j >= k_ || m == 0 || m > IPA_MAX_BATCH) return H2_EINVAL;
+  if (!ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_out_affine) || !z || !l_blind || !r_blind) return H2_EINVAL;
+  if (j == 0 ? (u_prev || u_prev_inv) : (!u_prev || !u_prev_inv)) return H2_EINVAL;
+  const IpaBatchLayout L(k_, m);
+  const BasesEntry* be = nullptr;
+  if (int rc = msm_common_checks((int)curve, bases, 0, L.col_stride, 2 * m, &be); rc != H2_OK) return rc;
+  if (be->n != L.col_stride) return H2_EINVAL;          // exactly G || U || W
+  // the MSM's own refusals before the table copy and the kernels in front of it: nothing is enqueued for a refused call
+  if (int rc = msm_device_plan_check(*be, L.col_stride, L.col_stride, 2 * m); rc != H2_OK) return rc;
+  const uint64_t* rows[IPA_BATCH_SCALARS] = {u_prev, u_prev_inv, z, l_blind, r_blind};
+  if (int rc = ipa_batch_table(L, rows, IPA_BATCH_SCALARS, nullptr, d_state, k.stream); rc != H2_OK) return rc;
+  if (int rc = launched(ops_of((int)curve)->ipa_round_batch(k_, j, m, d_state, k.stream), "ipa_round_batch_kernel"); rc != H2_OK)
+    return rc;
+  return msm_device_run(*k.c, (int)curve, *be, (const char*)d_state + L.col * 32, 0, L.col_stride, L.col_stride, 2 * m, d_out_affine,
+                        true, k.stream);
+}
+
+int h2_ipa_final_batch_device(h2_curve_t curve, uint32_t k_, size_t m, void* d_state, const uint64_t* u_last,
+                              const uint64_t* u_last_inv, void* d_out, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH || !ipa_dev_ptr(d_state) ||
+      !ipa_dev_ptr(d_out) || !u_last || !u_last_inv)
+    return H2_EINVAL;
+  const IpaBatchLayout L(k_, m);
+  const uint64_t* rows[2] = {u_last, u_last_inv};
+  if (int rc = ipa_batch_table(L, rows, 2, nullptr, d_state, k.stream); rc != H2_OK) return rc;
+  return launched(ops_of((int)curve)->ipa_final_batch(k_, m, d_state, d_out, k.stream), "ipa_final_batch_kernel");
 }
 
 // ---- Poseidon over resident columns (h2_poseidon.hpp) --------------------------------------------------------------------

@@ -169,6 +169,12 @@ struct CurveOps {
   // the sum of `count` <= IPA_SUM_GROUP compute_s vectors from the table ipa_sum_fill made of them (d_table, in HBM), added
   // to what d_out holds when `accumulate`
   hipError_t (*ipa_s_sum)(const void* d_table, uint32_t count, uint32_t k, void* d_out, bool accumulate, hipStream_t s);
+  // m <= IPA_MAX_BATCH openings of one k in lockstep; d_state: IpaBatchLayout(k, m).total elements, its scalar table already
+  // filled for this call by a copy enqueued on s.  One launch of each kernel serves all m; the caller runs the round's MSM
+  // of 2 m columns.  ipa_final_batch: d_out = m x (c_i || b_i[0])
+  hipError_t (*ipa_begin_batch)(uint32_t k, size_t m, void* d_state, hipStream_t s);
+  hipError_t (*ipa_round_batch)(uint32_t k, uint32_t j, size_t m, void* d_state, hipStream_t s);
+  hipError_t (*ipa_final_batch)(uint32_t k, size_t m, const void* d_state, void* d_out, hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)
   int (*selftest_field)(int which /* 0 = base field, 1 = scalar field */, int op, const uint64_t* a,
                         const uint64_t* b, uint64_t* out);

@@ -60,10 +60,40 @@ struct IpaLayout {
   }
 };
 
+// m openings of one k in lockstep (h2_ipa_*_batch_device), in 32-byte elements.  Opening i owns the `per` elements from
+// i * per: a and b in two generations each, S, its partial pairs (a, b, s, partial are offsets INSIDE an opening).  Behind
+// the m openings ONE block of 2 m columns at the uniform stride n + 2, ordered L_0, R_0, L_1, R_1, ...: one MSM of 2 m columns
+// writes m x (L_i || R_i).  Last the table of per-opening scalars, IPA_BATCH_SCALARS rows of m elements, which every call
+// fills from the host before its kernels (begin: x3, then the m pointers d_p in row 1; round: u, 1/u, z, l_blind, r_blind;
+// final: u, 1/u).
+constexpr size_t IPA_MAX_BATCH = 64;        // H2_IPA_MAX_BATCH of the C ABI
+constexpr size_t IPA_BATCH_SCALARS = 5;
+struct IpaBatchLayout {
+  size_t n, hn, m, a[2], b[2], s, partial, partials, per, col, col_stride, scal, total;
+  IpaBatchLayout(uint32_t k, size_t m_) {
+    const IpaLayout one(k);
+    n = one.n;
+    hn = one.hn;
+    m = m_;
+    a[0] = one.a[0];
+    a[1] = one.a[1];
+    b[0] = one.b[0];
+    b[1] = one.b[1];
+    s = one.s;
+    partial = one.col;                       // the columns have left the opening: the partial pairs follow S
+    partials = one.partials;
+    per = partial + 2 * partials;
+    col = m * per;
+    col_stride = one.col_stride;
+    scal = col + 2 * m * col_stride;
+    total = scal + IPA_BATCH_SCALARS * m;
+  }
+};
+
 // h2_ipa_begin_device: a = p, b[i] = x3^i (each thread POLY_RUN-style runs of 8 from x3^first), S[0] = 1
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_begin_kernel(const U128* __restrict__ p, U128* __restrict__ a, U128* __restrict__ b, U128* __restrict__ s, size_t n, Fe<FP> x3) {
+__device__ __forceinline__ void ipa_begin_body(const U128* __restrict__ p, U128* __restrict__ a, U128* __restrict__ b,
+                                               U128* __restrict__ s, size_t n, const Fe<FP>& x3) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t first = t * 8;
   if (t == 0) fe_store<FP>(s, Fe<FP>::one());
@@ -74,6 +104,11 @@ ipa_begin_kernel(const U128* __restrict__ p, U128* __restrict__ a, U128* __restr
     fe_store<FP>(b + 2 * (first + q), cur);
     cur = fe_mul(cur, x3);
   }
+}
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_begin_kernel(const U128* __restrict__ p, U128* __restrict__ a, U128* __restrict__ b, U128* __restrict__ s, size_t n, Fe<FP> x3) {
+  ipa_begin_body<FP>(p, a, b, s, n, x3);
 }
 
 // the table of challenge products doubles: S[count + g] = S[g] u for g < count.  With set_init (count = 1) S[0] = init
@@ -111,7 +146,7 @@ struct IpaRound {
 // h in [hy IPA_H_PER, (hy + 1) IPA_H_PER) of its two products into both columns, zeros included, and -- hy = 0 only --
 // stores a', b' and adds its two terms to the inner products.
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(IpaRound<FP> A) {
+__device__ __forceinline__ void ipa_round_body(const IpaRound<FP>& A) {
   using F = Fe<FP>;
   using W = Fe29<FP>;
   __shared__ int32_t lds[2][IPA_THREADS / 64][9];
@@ -202,12 +237,16 @@ __global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(IpaRound<FP> A) 
     fe_store<FP>(A.partial + 2 * ((size_t)blockIdx.x * 2 + threadIdx.x), fe29_canonical_pack(fe29_mul(fe29_norm(acc), one)));
   }
 }
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(IpaRound<FP> A) {
+  ipa_round_body<FP>(A);
+}
 
 // one workgroup: the sums of the `count` partial pairs times z into slot n of the columns, the blinds into slot n + 1
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_finish_kernel(const U128* __restrict__ partial, uint32_t count, Fe<FP> z, Fe<FP> l_blind, Fe<FP> r_blind,
-                  U128* __restrict__ tailL, U128* __restrict__ tailR) {
+__device__ __forceinline__ void ipa_finish_body(const U128* __restrict__ partial, uint32_t count, const Fe<FP>& z,
+                                                const Fe<FP>& l_blind, const Fe<FP>& r_blind, U128* __restrict__ tailL,
+                                                U128* __restrict__ tailR) {
   using F = Fe<FP>;
   __shared__ uint32_t lds[2][8][IPA_THREADS];              // [sum][limb][thread]
   const uint32_t t = threadIdx.x;
@@ -240,13 +279,19 @@ ipa_finish_kernel(const U128* __restrict__ partial, uint32_t count, Fe<FP> z, Fe
     fe_store<FP>(tailR + 2, r_blind);
   }
 }
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_finish_kernel(const U128* __restrict__ partial, uint32_t count, Fe<FP> z, Fe<FP> l_blind, Fe<FP> r_blind,
+                  U128* __restrict__ tailL, U128* __restrict__ tailR) {
+  ipa_finish_body<FP>(partial, count, z, l_blind, r_blind, tailL, tailR);
+}
 
 // h2_ipa_final_device: the last fold, c = a[0] + a[1] / u and b[0] + b[1] u (thread 0), and the finished table in natural
 // order, s[i] = S[rev_k(i)], when the caller wants it
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_final_kernel(const U128* __restrict__ a, const U128* __restrict__ b, const U128* __restrict__ S, Fe<FP> u, Fe<FP> uinv,
-                 uint32_t k, U128* __restrict__ out, U128* __restrict__ s_out) {
+__device__ __forceinline__ void ipa_final_body(const U128* __restrict__ a, const U128* __restrict__ b, const U128* __restrict__ S,
+                                               const Fe<FP>& u, const Fe<FP>& uinv, uint32_t k, U128* __restrict__ out,
+                                               U128* __restrict__ s_out) {
   const size_t T = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (T == 0) {
     fe_store<FP>(out, fe_add(fe_load<FP>(a), fe_mul(fe_load<FP>(a + 2), uinv)));
@@ -254,6 +299,97 @@ ipa_final_kernel(const U128* __restrict__ a, const U128* __restrict__ b, const U
   }
   if (s_out && T < ((size_t)1 << k))
     fe_store<FP>(s_out + 2 * T, fe_load<FP>(S + 2 * (size_t)(__brev((uint32_t)T) >> (32 - k))));
+}
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_final_kernel(const U128* __restrict__ a, const U128* __restrict__ b, const U128* __restrict__ S, Fe<FP> u, Fe<FP> uinv,
+                 uint32_t k, U128* __restrict__ out, U128* __restrict__ s_out) {
+  ipa_final_body<FP>(a, b, S, u, uinv, k, out, s_out);
+}
+
+// ---- the batch forms: blockIdx.y is the opening, the bodies are the ones above (the doubling of S is restated: it has no
+// set_init form here) --------------------------------------------------------------------------------------------------------
+// An opening's scalars come from the table at the end of the state (IpaBatchLayout).  No kernel writes the table and a
+// workgroup works on one opening, so the address is the same in every lane: the loads go through the constant address
+// space, which the back end serves with scalar loads (poseidon_const's way).  Everything else -- the arithmetic, the
+// uniform early return of the inner-product reduction, the fixed order of the partial sums -- is per opening what the
+// single-opening kernels do, so every output bit is theirs.
+template <class FP>
+__device__ __forceinline__ Fe<FP> ipa_batch_scalar(const U128* tab, size_t m, size_t row, size_t opening) {
+  typedef const __attribute__((address_space(4))) uint32_t* ConstPtr;
+  const ConstPtr q = (ConstPtr)(const uint32_t*)(tab + 2 * (row * m + opening));
+  Fe<FP> r;
+#pragma unroll
+  for (int l = 0; l < 8; l++) r.v[l] = q[l];
+  return r;
+}
+
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_begin_batch_kernel(U128* st, IpaBatchLayout L) {
+  const size_t o = blockIdx.y;
+  const U128* tab = st + 2 * L.scal;
+  typedef const __attribute__((address_space(4))) uint64_t* ConstPtr;
+  typedef const __attribute__((address_space(1))) U128* GlobalPtr;       // d_p[o] is device memory: global loads, not flat ones
+  const U128* p = (const U128*)(GlobalPtr)(uintptr_t)((ConstPtr)(const uint64_t*)(tab + 2 * L.m))[o];
+  U128* base = st + 2 * o * L.per;
+  ipa_begin_body<FP>(p, base + 2 * L.a[0], base + 2 * L.b[0], base + 2 * L.s, L.n, ipa_batch_scalar<FP>(tab, L.m, 0, o));
+}
+
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_s_batch_kernel(U128* st, IpaBatchLayout L, uint32_t count) {
+  const size_t o = blockIdx.y;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count) return;
+  U128* S = st + 2 * (o * L.per + L.s);
+  fe_store<FP>(S + 2 * ((size_t)count + g), fe_mul(fe_load<FP>(S + 2 * (size_t)g), ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 0, o)));
+}
+
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_round_batch_kernel(U128* st, IpaBatchLayout L, uint32_t k, uint32_t j) {
+  const size_t o = blockIdx.y;
+  U128* base = st + 2 * o * L.per;
+  IpaRound<FP> A;
+  A.k = k;
+  A.j = j;
+  A.S = base + 2 * L.s;
+  A.colL = st + 2 * (L.col + 2 * o * L.col_stride);
+  A.colR = A.colL + 2 * L.col_stride;
+  A.partial = base + 2 * L.partial;
+  if (j > 0) {
+    A.u = ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 0, o);
+    A.uinv = ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 1, o);
+    A.a_old = base + 2 * L.a[(j - 1) & 1];
+    A.b_old = base + 2 * L.b[(j - 1) & 1];
+    A.a_new = base + 2 * L.a[j & 1];
+    A.b_new = base + 2 * L.b[j & 1];
+  } else {
+    A.u = A.uinv = Fe<FP>::zero();
+    A.a_old = base + 2 * L.a[0];
+    A.b_old = base + 2 * L.b[0];
+    A.a_new = nullptr;
+    A.b_new = nullptr;
+  }
+  ipa_round_body<FP>(A);
+}
+
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_finish_batch_kernel(U128* st, IpaBatchLayout L, uint32_t count) {
+  const size_t o = blockIdx.y;
+  const U128* tab = st + 2 * L.scal;
+  U128* colL = st + 2 * (L.col + 2 * o * L.col_stride);
+  ipa_finish_body<FP>(st + 2 * (o * L.per + L.partial), count, ipa_batch_scalar<FP>(tab, L.m, 2, o),
+                      ipa_batch_scalar<FP>(tab, L.m, 3, o), ipa_batch_scalar<FP>(tab, L.m, 4, o), colL + 2 * L.n,
+                      colL + 2 * (L.col_stride + L.n));
+}
+
+// d_out: m x (c_i || b_i[0]); the finished table s has no batch form
+template <class FP>
+__global__ void __launch_bounds__(IPA_THREADS) ipa_final_batch_kernel(const U128* st, IpaBatchLayout L, uint32_t k, U128* out) {
+  const size_t o = blockIdx.y;
+  const U128* base = st + 2 * o * L.per;
+  const U128* tab = st + 2 * L.scal;
+  ipa_final_body<FP>(base + 2 * L.a[(k - 1) & 1], base + 2 * L.b[(k - 1) & 1], base + 2 * L.s, ipa_batch_scalar<FP>(tab, L.m, 0, o),
+                     ipa_batch_scalar<FP>(tab, L.m, 1, o), k, out + 4 * o, nullptr);
 }
 
 // ---- launches (one per curve through CurveOps) ----------------------------------------------------------------------------
@@ -325,6 +461,43 @@ hipError_t ipa_final_launch(uint32_t k, void* d_state, const uint64_t u[4], cons
   hipLaunchKernelGGL(ipa_final_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s,
                      (const U128*)(st + 2 * L.a[(k - 1) & 1]), (const U128*)(st + 2 * L.b[(k - 1) & 1]), (const U128*)(st + 2 * L.s), uu,
                      ipa_fe<FP>(uinv), k, (U128*)d_out, (U128*)d_s_out);
+  return hipGetLastError();
+}
+
+// the batch launches: the caller has copied the call's scalar table into the state on `s` (IpaBatchLayout); one launch of
+// each kernel serves the m openings
+template <class FP>
+hipError_t ipa_begin_batch_launch(uint32_t k, size_t m, void* d_state, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
+  const size_t threads = (L.n + 7) / 8;
+  hipLaunchKernelGGL(ipa_begin_batch_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m),
+                     dim3(IPA_THREADS), 0, s, (U128*)d_state, L);
+  return hipGetLastError();
+}
+
+template <class FP>
+hipError_t ipa_round_batch_launch(uint32_t k, uint32_t j, size_t m, void* d_state, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
+  U128* st = (U128*)d_state;
+  if (j > 0) {
+    const uint32_t count = 1u << (j - 1);
+    hipLaunchKernelGGL(ipa_s_batch_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L,
+                       count);
+  }
+  const size_t half = (size_t)1 << (k - j - 1), nh = (size_t)1 << j;
+  const size_t threads = half * ((nh + IPA_H_PER - 1) / IPA_H_PER);
+  hipLaunchKernelGGL(ipa_round_batch_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m),
+                     dim3(IPA_THREADS), 0, s, st, L, k, j);
+  const uint32_t parts = (uint32_t)((half + IPA_THREADS - 1) / IPA_THREADS);
+  hipLaunchKernelGGL(ipa_finish_batch_kernel<FP>, dim3(1, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L, parts);
+  return hipGetLastError();
+}
+
+template <class FP>
+hipError_t ipa_final_batch_launch(uint32_t k, size_t m, const void* d_state, void* d_out, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
+  hipLaunchKernelGGL(ipa_final_batch_kernel<FP>, dim3(1, (unsigned)m), dim3(IPA_THREADS), 0, s, (const U128*)d_state, L, k,
+                     (U128*)d_out);
   return hipGetLastError();
 }
 

@@ -7,6 +7,8 @@ h2_ipa_begin_device / h2_ipa_round_device / h2_ipa_final_device -- no generator 
 two-column MSM over the registered table -- and `verify_proof` checks
     sum [u_j^-1] L_j + P' + sum [u_j] R_j == [c] <s, G> + [c b_0 z] U + [f] W,   P' = P - [v] G[0] + [xi] S
 with <s, G> and the U, W, G[0] terms as ONE h2_msm_device on the same table (s from h2_ipa_challenge_products_device).
+`create_proofs` runs m openings in lockstep through h2_ipa_*_batch_device -- a round of all of them is ONE MSM of 2 m columns
+on the table -- and returns create_proof's bytes for each.
 `verify_proofs` checks N such proofs behind ONE combined equation: the N equations are linear in the same table, so with
 random weights r_p they collapse into one table MSM and one points MSM; the 2k + 1 compressed
 points of every proof are decompressed by one kernel launch (h2_pasta_points_decompress_device) and the weighted sum of the
@@ -189,6 +191,125 @@ def create_proof(params, transcript, p, p_blind, x3, rng, s_poly=None):
     transcript.write_scalar(c)
     transcript.write_scalar(f)
     return bytes(transcript.bytes)
+
+
+MAX_BATCH = 64                                      # H2_IPA_MAX_BATCH
+
+
+def create_proofs(params, items):
+    """create_proof for a batch, in lockstep: items = sequence of (transcript, p, p_blind, x3, rng, s_poly or None), all on
+    the same params -> list[bytes], entry i exactly the bytes of create_proof(params, *items[i]), transcript i left where
+    create_proof leaves it.  Every item has its OWN transcript and its OWN rng, drawn from in create_proof's order (the
+    32-byte seed when s_poly is None, s_blind, then l_j and r_j of every round); one rng object shared between items is
+    drawn from in another order than m create_proof calls would and breaks the equality.
+
+    The m openings advance together (h2_ipa_*_batch_device): the 2 m values s_poly_i(x3_i), p_i(x3_i) are one
+    h2_poly_eval_device call; the corrections of the constant terms and the m polynomials p' are h2_poly_lincomb_device
+    calls of m jobs; the m commitments to S are ONE h2_msm_device of m columns of n + 2; a round is one call, one MSM of
+    2 m columns and one read-back of m x 128 bytes; the final is one call and m x 64 bytes.  Calls and read-backs per batch:
+    k + a constant, whatever m is -- but for the items with s_poly None, each expanded from its own seed by its own
+    h2_chacha20_scalars_device call (no read-back).  More than H2_IPA_MAX_BATCH items go through in groups of that many."""
+    items = list(items)
+    out = []
+    for first in range(0, len(items), MAX_BATCH):
+        out.extend(_create_proofs_group(params, items[first:first + MAX_BATCH]))
+    return out
+
+
+def _create_proofs_group(params, items):
+    import torch
+    L, cv, k, n, P = params._L, params.curve, params.k, params.n, params.p
+    dom = params.domain
+    stream = dom._stream()
+    m = len(items)
+    trs = [it[0] for it in items]
+    ps = [params.column(it[1]) for it in items]
+    if any(p.shape[0] != n for p in ps):
+        raise ValueError("create_proofs: p.len() != n")
+    blinds, x3s, rngs = [it[2] for it in items], [it[3] for it in items], [it[4] for it in items]
+    dev = ps[0].device
+    rinv = pow(params.R, -1, P)
+
+    def scalars(values):
+        return np.concatenate([params.mont(v) for v in values])
+
+    def upload(values):
+        return torch.from_numpy(scalars(values).reshape(-1, 4).view(np.int64)).to(dev)
+
+    # the m columns s_poly_i || 0 || s_blind_i the commitments are taken of
+    cols = torch.zeros((m, n + 2, 4), dtype=torch.int64, device=dev)
+    for i, it in enumerate(items):
+        if it[5] is None:
+            seed = bytes(rngs[i](32))
+            _lib.check(L.h2_chacha20_scalars_device(cv, seed, 0, n, ctypes.c_void_p(cols[i].data_ptr()), stream),
+                       "h2_chacha20_scalars_device")
+        else:
+            s_poly = params.column(it[5])
+            if s_poly.shape[0] != n:
+                raise ValueError("create_proofs: s_poly.len() != n")
+            cols[i, :n] = s_poly
+    # s_poly_i(x3_i) and p_i(x3_i): one call, one read-back
+    ptrs = (ctypes.c_void_p * (2 * m))(*([cols[i].data_ptr() for i in range(m)] + [p.data_ptr() for p in ps]))
+    vals = torch.empty((2 * m, 4), dtype=torch.int64, device=dev)
+    x3m = scalars(x3s + x3s)                          # a local: the array must outlive the call that reads its address
+    _lib.check(L.h2_poly_eval_device(cv, ptrs, n, x3m.ctypes.data, 2 * m, ctypes.c_void_p(vals.data_ptr()), stream),
+               "h2_poly_eval_device")
+    vals = [x * rinv % P for x in _ints(vals.cpu().numpy().tobytes())]
+    s_at, v = vals[:m], vals[m:]
+    # s_poly_i[0] -= s_poly_i(x3_i): the blinding polynomials have their roots
+    poly_lincomb(dom, [(cols[i], [(1, cols[i])], [s_at[i]], []) for i in range(m)], n)
+    s_blind = [random_scalar(rng, P) for rng in rngs]
+    cols[:, n + 1] = upload(s_blind)
+    jac = torch.empty((m, 12), dtype=torch.int64, device=dev)
+    params.bases.msm_device(cols.data_ptr(), n + 2, m, jac.data_ptr(), stream.value or 0)
+    jac = jac.cpu().numpy().view(np.uint64)
+    xi, z = [], []
+    for i, tr in enumerate(trs):
+        tr.write_point(params.jac_to_affine(jac[i]))
+        xi.append(tr.squeeze_challenge())
+        z.append(tr.squeeze_challenge())
+    # p'_i = s_poly_i xi_i + p_i, p'_i[0] -= p_i(x3_i)
+    p_prime = poly_lincomb(dom, [(None, [(xi[i], cols[i]), (1, ps[i])], [v[i]], []) for i in range(m)], n)
+    f = [(s_blind[i] * xi[i] + blinds[i]) % P for i in range(m)]
+
+    need = ctypes.c_size_t(0)
+    _lib.check(L.h2_ipa_batch_state_bytes(k, m, ctypes.byref(need)), "h2_ipa_batch_state_bytes")
+    state = torch.empty(need.value // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((m, 16), dtype=torch.int64, device=dev)
+    d_p = (ctypes.c_void_p * m)(*[t.data_ptr() for t in p_prime])
+    _lib.check(L.h2_ipa_begin_batch_device(cv, k, m, d_p, x3m.ctypes.data, ctypes.c_void_p(state.data_ptr()), stream),   # its first m
+               "h2_ipa_begin_batch_device")
+    zm = scalars(z)
+    u = u_inv = None
+    for j in range(k):
+        l_j, r_j = [], []
+        for rng in rngs:
+            l_j.append(random_scalar(rng, P))
+            r_j.append(random_scalar(rng, P))
+        um, uim = (scalars(u), scalars(u_inv)) if j else (None, None)
+        lm, rm = scalars(l_j), scalars(r_j)
+        st = L.h2_ipa_round_batch_device(cv, params.bases.handle, k, j, m, ctypes.c_void_p(state.data_ptr()),
+                                         um.ctypes.data if j else None, uim.ctypes.data if j else None, zm.ctypes.data,
+                                         lm.ctypes.data, rm.ctypes.data, ctypes.c_void_p(out.data_ptr()), stream)
+        _lib.check(st, "h2_ipa_round_batch_device")
+        lr = out.cpu().numpy().view(np.uint64)
+        u, u_inv = [], []
+        for i, tr in enumerate(trs):
+            tr.write_point(params.affine_ints(lr[i, :8]))
+            tr.write_point(params.affine_ints(lr[i, 8:]))
+            u.append(tr.squeeze_challenge())
+            u_inv.append(pow(u[i], -1, P))
+            f[i] = (f[i] + l_j[i] * u_inv[i] + r_j[i] * u[i]) % P
+    um, uim = scalars(u), scalars(u_inv)
+    _lib.check(L.h2_ipa_final_batch_device(cv, k, m, ctypes.c_void_p(state.data_ptr()), um.ctypes.data, uim.ctypes.data,
+                                           ctypes.c_void_p(out.data_ptr()), stream), "h2_ipa_final_batch_device")
+    cb = out.reshape(-1)[:8 * m].cpu().numpy().reshape(m, 8)
+    proofs = []
+    for i, tr in enumerate(trs):
+        tr.write_scalar(_ints(cb[i, :4].tobytes())[0] * rinv % P)
+        tr.write_scalar(f[i])
+        proofs.append(bytes(tr.bytes))
+    return proofs
 
 
 def verify_proof(params, transcript, P, x3, v):

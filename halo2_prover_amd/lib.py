@@ -93,6 +93,10 @@ SYMBOLS = {
     "h2_ipa_final_device": (_I, [_I, _U32, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_challenge_products_device": (_I, [_I, _P, _U32, _P, _P, _P]),
     "h2_ipa_challenge_products_sum_device": (_I, [_I, _P, _P, _U32, _Z, _P, _P]),
+    "h2_ipa_batch_state_bytes": (_I, [_U32, _Z, ctypes.POINTER(_Z)]),
+    "h2_ipa_begin_batch_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P]),
+    "h2_ipa_round_batch_device": (_I, [_I, _U64, _U32, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_final_batch_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P, _P]),
     "h2_poseidon_constants": (_I, [_I, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_poseidon_permute_device": (_I, [_I, _U32, _U32, _P, _P, _Z, _P]),
     "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),

@@ -402,6 +402,40 @@ int h2_ipa_final_device(h2_curve_t curve, uint32_t k, void* d_state, const uint6
                         void* d_out, void* d_s_out, void* stream);
 int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out,
                                      void* stream);
+/* m openings in lockstep: the calls above for m states at once.  ALL m OPENINGS SHARE k, THE CURVE AND THE TABLE `bases`;
+ * each has its own polynomial, x3, z, challenges and blinds.  One launch of every kernel serves the m openings and a round is
+ * ONE MSM of 2 m columns of n + 2 terms on the registered table (wide batches go through h2_msm_device's column groups), so
+ * the launches of a round do not grow with m.  Opening i's outputs are bit for bit what the single-opening calls give.
+ *   h2_ipa_batch_state_bytes    size of the caller-owned, 16-byte aligned device buffer m openings work in: per opening a
+ *                               and b (two generations each), s and the partial sums; then one block of 2 m columns of
+ *                               n + 2; then a table of 5 m scalars every call fills from its host arguments.  Host only, no
+ *                               h2_init needed.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K, m = 0, m > H2_IPA_MAX_BATCH, a null out.
+ *   h2_ipa_begin_batch_device   d_p: a HOST array of m device pointers, opening i's n coefficients (only read); x3: m * 4
+ *                               limbs.  Whatever an earlier use -- of any m -- left in d_state does not matter.
+ *   h2_ipa_round_batch_device   round j of every opening; u_prev, u_prev_inv (both null at j = 0, both required otherwise),
+ *                               z, l_blind, r_blind: m * 4 limbs each, entry i for opening i.  d_out_affine: m * 128 bytes,
+ *                               L_j || R_j of opening 0, then of opening 1, ...
+ *   h2_ipa_final_batch_device   the last fold; u_last, u_last_inv: m * 4 limbs.  d_out: m * 64 bytes, c_i || b_i[0].  The
+ *                               finished table s has no batch form.
+ * The contract is the single calls': host scalars are canonical Montgomery limbs, read before the call returns (one copy of
+ * the scalar table into d_state is enqueued in front of the kernels); the calls of one batch are issued in order on ONE
+ * stream; asynchronous on `stream`, no host synchronisation, no device-to-host copy, nothing allocated; the MSM goes through
+ * h2_msm_device's launch path with its bounds proof, and what that path refuses with H2_EINVAL (a column too long for the
+ * sort's 32-bit indices) is found from the same plans BEFORE the round's table copy and kernels.  H2_EINVAL, before
+ * anything is enqueued, for: m = 0 or m >
+ * H2_IPA_MAX_BATCH; k = 0 or k > H2_IPA_MAX_K; j >= k; an unknown curve; a null or not 16-byte aligned device pointer, any
+ * of the m entries of d_p included; a null scalar array; a missing or superfluous u_prev / u_prev_inv; a handle of another
+ * curve or one that does not hold exactly 2^k + 2 bases (H2_EHANDLE for a handle that is not registered at all).
+ * h2_version() stays 1002: a host detects these entry points by their symbols. */
+#define H2_IPA_MAX_BATCH 64
+int h2_ipa_batch_state_bytes(uint32_t k, size_t m, size_t* out);
+int h2_ipa_begin_batch_device(h2_curve_t curve, uint32_t k, size_t m, const void* const* d_p, const uint64_t* x3, void* d_state,
+                              void* stream);
+int h2_ipa_round_batch_device(h2_curve_t curve, uint64_t bases, uint32_t k, uint32_t j, size_t m, void* d_state,
+                              const uint64_t* u_prev, const uint64_t* u_prev_inv, const uint64_t* z, const uint64_t* l_blind,
+                              const uint64_t* r_blind, void* d_out_affine, void* stream);
+int h2_ipa_final_batch_device(h2_curve_t curve, uint32_t k, size_t m, void* d_state, const uint64_t* u_last,
+                              const uint64_t* u_last_inv, void* d_out, void* stream);
 /* d_out[i] = sum_{p < count} init_p * prod over the set bits t of i of u_p[k-1-t],  i < 2^k: the sum of `count`
  * compute_s(u_p, init_p) vectors, none of them materialised.  u: count * k * 4 limbs, init: count * 4 limbs, HOST, canonical
  * Montgomery, read before the call returns.  Canonical output, the same bits however the proofs are grouped (one launch per

@@ -9,10 +9,10 @@ from .api import (Bases, ParamsKZG, base_sqrt_device, best_fft, best_fft_batch, 
                   pasta_points_decompress_device, points_decompress_device, verify_proofs)
 from .expr import ExprProgram  # noqa: F401
 from . import ipa  # noqa: F401
-from .ipa import ParamsIPA, compute_b, compute_s  # noqa: F401
+from .ipa import ParamsIPA, compute_b, compute_s, verify_proofs_bytes  # noqa: F401
 from .lookup import lookup_product, permute_expression_pair  # noqa: F401
 from .opening import gwc_open, poly_lincomb, shplonk_open_final, shplonk_open_h  # noqa: F401
 from .permutation import permutation_product  # noqa: F401
 from . import poseidon  # noqa: F401
-from .transcript import Blake2bTranscript  # noqa: F401
+from .transcript import Blake2bMidstate, Blake2bTranscript  # noqa: F401
 from .lib import CURVES, H2Error, LIB_PATH, SYMBOLS, load  # noqa: F401

@@ -7,14 +7,18 @@
 // best_multiexp's assert_eq!(coeffs.len(), bases.len()) -- become H2_EINVAL here).
 #include "h2_internal.hpp"
 
+#include <sys/random.h>
+
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <optional>
 
 #include "h2_expr_program.hpp"
 #include "h2_host.hpp"
 #include "h2_ipa.hpp"
+#include "h2_ipa_verify.hpp"
 #include "h2_lookup.hpp"
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
@@ -875,6 +879,24 @@ bool poseidon_overlap(const void* a, size_t a_bytes, const void* b, size_t b_byt
 }
 
 }  // namespace
+
+// h2_transcript_challenge: Challenge255 of a 64-byte digest, Montgomery limbs
+template <class FP>
+static void transcript_reduce(const uint8_t digest[64], uint64_t out[4]) {
+  HF<FP>::from_le_bytes_wide(digest).mont_limbs(out);
+}
+
+// count x 4 limbs, every element below the modulus?
+template <class FP>
+static bool ipa_canonical(const uint64_t* limbs, size_t count) {
+  for (size_t i = 0; i < count; i++) {
+    HF<FP> x;
+    uint8_t b[32];
+    memcpy(b, limbs + 4 * i, 32);
+    if (!HF<FP>::from_le_bytes_canonical(b, &x)) return false;
+  }
+  return true;
+}
 
 extern "C" {
 
@@ -1863,6 +1885,21 @@ int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32
   return launched(ops_of((int)curve)->ipa_s_products(u, k_, init, d_out, k.stream), "ipa_s_kernel");
 }
 
+// the sum kernel over `count` rows of a table that is in HBM already (ipa_sum_fill's layout), in launches of IPA_SUM_GROUP
+// rows, the first one overwriting d_out unless `accumulate`: h2_ipa_challenge_products_sum_device's launch and the batch
+// verifier's, whose table the prepare kernel wrote
+static int ipa_sum_run(const CurveOps* ops, const void* d_table, size_t count, uint32_t k, void* d_out, bool accumulate, hipStream_t stream) {
+  const size_t row = ipa_sum_stride(k);
+  for (size_t p0 = 0; p0 < count; p0 += IPA_SUM_GROUP) {
+    const size_t cnt = std::min(IPA_SUM_GROUP, count - p0);
+    if (int rc = launched(ops->ipa_s_sum((const char*)d_table + p0 * row * 4, (uint32_t)cnt, k, d_out, accumulate || p0 > 0, stream),
+                          "ipa_s_sum_kernel");
+        rc != H2_OK)
+      return rc;
+  }
+  return H2_OK;
+}
+
 int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, const uint64_t* init, uint32_t k_, size_t count,
                                          void* d_out, void* stream_) {
   Call k(stream_);
@@ -1890,7 +1927,7 @@ int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, co
     H2_BY_SCALAR_FIELD((int)curve, ipa_sum_fill)(u + 4 * p0 * k_, init + 4 * p0, k_, cnt, host.data());
     // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
     H2_TRY(hipMemcpyAsync(A.a.p, host.data(), cnt * row * 4, hipMemcpyHostToDevice, k.stream));
-    if (int rc = launched(ops->ipa_s_sum(A.a.p, (uint32_t)cnt, k_, d_out, p0 > 0, k.stream), "ipa_s_sum_kernel"); rc != H2_OK) return rc;
+    if (int rc = ipa_sum_run(ops, A.a.p, cnt, k_, d_out, p0 > 0, k.stream); rc != H2_OK) return rc;
   }
   return A.release();
 }
@@ -1973,6 +2010,212 @@ int h2_ipa_final_batch_device(h2_curve_t curve, uint32_t k_, size_t m, void* d_s
   const uint64_t* rows[2] = {u_last, u_last_inv};
   if (int rc = ipa_batch_table(L, rows, 2, nullptr, d_state, k.stream); rc != H2_OK) return rc;
   return launched(ops_of((int)curve)->ipa_final_batch(k_, m, d_state, d_out, k.stream), "ipa_final_batch_kernel");
+}
+
+// ---- the transcript midstate (host only) ---------------------------------------------------------------------------------
+static_assert(sizeof(h2_transcript_state_t) == Blake2b::STATE_BYTES && sizeof(h2_transcript_state_t) == TRANSCRIPT_STATE_BYTES,
+              "the header's struct is the exported Blake2b state and the replay kernel's");
+
+int h2_transcript_init(h2_transcript_state_t* state) {
+  if (!state) return H2_EINVAL;
+  Blake2b("Halo2-Transcript").export_state((uint8_t*)state);
+  return H2_OK;
+}
+
+int h2_transcript_absorb(h2_transcript_state_t* state, const uint8_t* bytes, size_t len) {
+  if (!state || (len && !bytes)) return H2_EINVAL;
+  Blake2b b;
+  if (!b.import_state((const uint8_t*)state)) return H2_EINVAL;
+  b.update(bytes, len);
+  b.export_state((uint8_t*)state);
+  return H2_OK;
+}
+
+int h2_transcript_challenge(h2_curve_t curve, h2_transcript_state_t* state, uint64_t out[4]) {
+  if (!curve_ok((int)curve) || !state || !out) return H2_EINVAL;
+  Blake2b b;
+  if (!b.import_state((const uint8_t*)state)) return H2_EINVAL;
+  const uint8_t zero = 0;
+  b.update(&zero, 1);
+  uint8_t digest[64];
+  b.digest(digest);                                      // of a copy: the state keeps absorbing
+  b.export_state((uint8_t*)state);
+  H2_BY_SCALAR_FIELD((int)curve, transcript_reduce)(digest, out);
+  return H2_OK;
+}
+
+// ---- the IPA batch verifier (h2_ipa_verify.hpp) --------------------------------------------------------------------------
+int h2_ipa_replay_device(h2_curve_t curve, uint32_t k_, size_t count, const void* d_states, const void* d_points,
+                         const void* d_point_status, const void* d_scalars, void* d_out, void* d_status, void* d_states_out,
+                         void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !ops_of((int)curve)->ipa_replay || k_ == 0 || k_ > IPA_MAX_K || count > ((size_t)1 << 24)) return H2_EINVAL;
+  if (count == 0) return H2_OK;
+  if (!ipa_dev_ptr(d_states) || !ipa_dev_ptr(d_points) || !d_point_status || !ipa_dev_ptr(d_scalars) || !ipa_dev_ptr(d_out) || !d_status)
+    return H2_EINVAL;
+  if (d_states_out && ((uintptr_t)d_states_out & 15)) return H2_EINVAL;
+  return launched(ops_of((int)curve)->ipa_replay(k_, count, d_states, d_points, d_point_status, d_scalars, d_out, d_status, d_states_out,
+                                                 k.stream),
+                  "ipa_replay_kernel");
+}
+
+int h2_ipa_verify_proofs(h2_curve_t curve, uint64_t bases, uint32_t k_, size_t count, const h2_transcript_state_t* states,
+                         const uint8_t* const* proofs, const size_t* proof_lens, const uint64_t* commitments, const uint64_t* x3,
+                         const uint64_t* v, h2_rng_fill_t rng, void* rng_ctx, int* ok, int* all_ok, size_t* checks_out) {
+  Call k(nullptr);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !ops_of((int)curve)->ipa_replay || k_ == 0 || k_ > IPA_MAX_K) return H2_EINVAL;
+  if (count && (!states || !proofs || !proof_lens || !commitments || !x3 || !v || !ok)) return H2_EINVAL;
+  const size_t n = (size_t)1 << k_, per = 2 * (size_t)k_ + 1, need = (per + 2) * 32;
+  const BasesEntry* be = nullptr;
+  if (int rc = msm_common_checks((int)curve, bases, 0, n + 2, 1, &be); rc != H2_OK) return rc;
+  if (be->n != n + 2) return H2_EINVAL;                   // exactly G || U || W
+  if (int rc = msm_device_plan_check(*be, n + 2, n + 2, 1); rc != H2_OK) return rc;
+  if (count > ((size_t)1 << 24) || count * (per + 1) > MSM_POINTS_MAX_N) return H2_EINVAL;
+  if (!H2_BY_SCALAR_FIELD((int)curve, ipa_canonical)(x3, count) || !H2_BY_SCALAR_FIELD((int)curve, ipa_canonical)(v, count))
+    return H2_EINVAL;
+  for (size_t i = 0; i < count; i++)
+    if (states[i].buflen > 128 || (proof_lens[i] && !proofs[i])) return H2_EINVAL;
+  if (all_ok) *all_ok = 1;
+  if (checks_out) *checks_out = 0;
+  if (count == 0) return H2_OK;
+  const CurveOps* ops = ops_of((int)curve);
+  hipStream_t stream = k.stream;
+  try {
+    // a proof of any other length is refused here: a short stream fails verify_proof's reads, trailing bytes are the caller's
+    std::vector<size_t> item;                              // device proof -> item
+    for (size_t i = 0; i < count; i++) {
+      ok[i] = 0;
+      if (proof_lens[i] == need) item.push_back(i);
+    }
+    if (all_ok) *all_ok = 0;
+    const size_t M = item.size();
+    if (M == 0) return H2_OK;
+    const size_t G = M * per, row = ipa_sum_stride(k_);
+    auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    // the scratch: the decompression's output with the commitments behind it is the points MSM's operand, and everything the
+    // host uploads -- from the commitments on -- is one range
+    size_t off = 0;
+    auto region = [&](size_t bytes) { const size_t o = off; off += up16(bytes); return o; };
+    const size_t o_points = region(G * 64), o_commit = region(M * 64), o_wire = region(G * 32), o_states = region(M * sizeof(h2_transcript_state_t)),
+                 o_scalars = region(M * 64), o_x3 = region(M * 32), o_v = region(M * 32), o_upload_end = off, o_pstatus = region(G),
+                 o_replay = region(M * (k_ + 4) * 32), o_status = region(M), o_weights = region(M * IPA_WEIGHT_WORDS * 4),
+                 o_scal = region((G + M) * 32), o_table = region(M * row * 4), o_terms = region(M * 96), o_col = region((n + 2) * 32),
+                 o_jac = region(3 * 96);
+    ArenaLease A(k.c->stage, off, stream);
+    if (A.rc != H2_OK) return A.rc;
+    char* base = (char*)A.a.p;
+    std::vector<uint8_t> host(o_upload_end - o_commit, 0);
+    for (size_t j = 0; j < M; j++) {
+      const size_t i = item[j];
+      memcpy(&host[o_commit - o_commit + j * 64], commitments + 8 * i, 64);
+      memcpy(&host[o_wire - o_commit + j * per * 32], proofs[i], per * 32);
+      memcpy(&host[o_states - o_commit + j * sizeof(h2_transcript_state_t)], &states[i], sizeof(h2_transcript_state_t));
+      memcpy(&host[o_scalars - o_commit + j * 64], proofs[i] + per * 32, 64);
+      memcpy(&host[o_x3 - o_commit + j * 32], x3 + 4 * i, 32);
+      memcpy(&host[o_v - o_commit + j * 32], v + 4 * i, 32);
+    }
+    // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
+    H2_TRY(hipMemcpyAsync(base + o_commit, host.data(), host.size(), hipMemcpyHostToDevice, stream));
+    if (int rc = launched(ops->pasta_points_decompress(base + o_wire, base + o_points, base + o_pstatus, (uint32_t)G, stream),
+                          "points_decompress_kernel");
+        rc != H2_OK)
+      return rc;
+    if (int rc = launched(ops->ipa_replay(k_, M, base + o_states, base + o_points, base + o_pstatus, base + o_scalars, base + o_replay,
+                                          base + o_status, nullptr, stream),
+                          "ipa_replay_kernel");
+        rc != H2_OK)
+      return rc;
+    std::vector<uint8_t> status(M);
+    H2_TRY(hipMemcpyAsync(status.data(), base + o_status, M, hipMemcpyDeviceToHost, stream));
+    H2_TRY(hipStreamSynchronize(stream));
+    std::vector<size_t> live;                              // device proofs whose replay went through
+    for (size_t j = 0; j < M; j++)
+      if (status[j] == 0) live.push_back(j);
+
+    int rc = H2_OK;
+    size_t checks = 0;
+    std::vector<uint32_t> weights(M * IPA_WEIGHT_WORDS);
+    // sum_p w_p (sum [1/u_j] L_j + P + [xi] S + sum [u_j] R_j - [v] G[0] - [c] <s, G> - [c b0 z] U - [f] W) == 0 over the subset
+    auto check = [&](const size_t* subset, size_t cnt) -> bool {
+      if (rc != H2_OK) return false;
+      checks++;
+      std::fill(weights.begin(), weights.end(), 0u);
+      for (size_t s = 0; s < cnt; s++) {
+        uint32_t* w = &weights[subset[s] * IPA_WEIGHT_WORDS];
+        uint8_t raw[16];
+        do {
+          if (rng) {
+            rng(rng_ctx, raw, 16);
+          } else {
+            for (size_t got = 0; got < 16;) {
+              const ssize_t r = getrandom(raw + got, 16 - got, 0);
+              if (r <= 0) {
+                g_h2.last_error = "getrandom failed";
+                rc = H2_EDEVICE;
+                return false;
+              }
+              got += (size_t)r;
+            }
+          }
+          for (int i = 0; i < 4; i++)
+            w[i] = (uint32_t)raw[4 * i] | ((uint32_t)raw[4 * i + 1] << 8) | ((uint32_t)raw[4 * i + 2] << 16) | ((uint32_t)raw[4 * i + 3] << 24);
+        } while (!(w[0] | w[1] | w[2] | w[3]));
+        w[4] = (uint32_t)s;
+      }
+      auto step = [&](int st) {
+        if (rc == H2_OK) rc = st;
+        return rc == H2_OK;
+      };
+      auto copied = [&](hipError_t e, const char* what) { return e == hipSuccess ? (int)H2_OK : dev_fail(e, what); };
+      char* jac = base + o_jac;
+      if (!step(copied(hipMemcpyAsync(base + o_weights, weights.data(), weights.size() * 4, hipMemcpyHostToDevice, stream), "weights")))
+        return false;
+      if (!step(launched(ops->ipa_verify_prepare(base + o_replay, base + o_x3, base + o_v, base + o_weights, base + o_scal, base + o_table,
+                                                 base + o_terms, k_, M, stream),
+                         "ipa_verify_prepare_kernel")))
+        return false;
+      if (!step(ipa_sum_run(ops, base + o_table, cnt, k_, base + o_col, false, stream))) return false;
+      if (!step(launched(ops->ipa_verify_finish(base + o_terms, M, base + o_col, k_, stream), "ipa_verify_finish_kernel"))) return false;
+      if (!step(msm_device_run(*k.c, (int)curve, *be, base + o_col, 0, n + 2, n + 2, 1, jac, false, stream))) return false;
+      if (!step(msm_points_run(*k.c, (int)curve, base + o_points, base + o_scal, G + M, G + M, 1, jac + 96, stream))) return false;
+      if (!step(launched(ops->points_sum(jac, jac + 192, 2, 1, stream), "points_sum_kernel"))) return false;
+      uint64_t total[12];
+      if (!step(copied(hipMemcpyAsync(total, jac + 192, 96, hipMemcpyDeviceToHost, stream), "the check's sum"))) return false;
+      if (!step(copied(hipStreamSynchronize(stream), "hipStreamSynchronize"))) return false;
+      return !(total[8] | total[9] | total[10] | total[11]);
+    };
+    // the verdicts of a subset; known_bad: a combined check has already shown that it holds a culprit
+    std::function<void(const size_t*, size_t, bool)> settle = [&](const size_t* subset, size_t cnt, bool known_bad) {
+      if (rc != H2_OK) return;
+      if (!known_bad && check(subset, cnt)) {
+        for (size_t s = 0; s < cnt; s++) ok[item[subset[s]]] = 1;
+        return;
+      }
+      if (cnt == 1) return;                                // a singleton's verdict is its own equation; w != 0
+      const size_t half = cnt / 2;
+      if (check(subset, half)) {
+        for (size_t s = 0; s < half; s++) ok[item[subset[s]]] = 1;
+        settle(subset + half, cnt - half, cnt - half > 1); // the culprits are on the other side; one alone is still checked
+      } else {
+        settle(subset, half, true);
+        settle(subset + half, cnt - half, false);
+      }
+    };
+    if (!live.empty()) settle(live.data(), live.size(), false);
+    if (rc != H2_OK) return rc;
+    if (checks_out) *checks_out = checks;
+    if (all_ok) {
+      *all_ok = 1;
+      for (size_t i = 0; i < count; i++)
+        if (!ok[i]) *all_ok = 0;
+    }
+    return A.wait();
+  } catch (const std::bad_alloc&) {
+    g_h2.last_error = "ipa: no host memory for the batch";
+    return H2_ENOMEM;
+  }
 }
 
 // ---- Poseidon over resident columns (h2_poseidon.hpp) --------------------------------------------------------------------

@@ -175,6 +175,16 @@ struct CurveOps {
   hipError_t (*ipa_begin_batch)(uint32_t k, size_t m, void* d_state, hipStream_t s);
   hipError_t (*ipa_round_batch)(uint32_t k, uint32_t j, size_t m, void* d_state, hipStream_t s);
   hipError_t (*ipa_final_batch)(uint32_t k, size_t m, const void* d_state, void* d_out, hipStream_t s);
+  // the IPA batch verifier's kernels (h2_ipa_verify.hpp).  ipa_replay: the transcripts of `count` proofs, one lane each
+  // (h2_ipa_replay_device's arguments); NULL for BN254, whose wire form the batch verifier does not take.
+  // ipa_verify_prepare: the replay's rows, x3, v and count x 8 words of weights -> the points MSM's scalar column, the sum
+  // kernel's table and count x 3 terms.  ipa_verify_finish: d_col[0] -= the first terms' sum, rows 2^k and 2^k + 1 = minus
+  // the other two
+  hipError_t (*ipa_replay)(uint32_t k, size_t count, const void* d_states, const void* d_points, const void* d_point_status,
+                           const void* d_scalars, void* d_out, void* d_status, void* d_states_out, hipStream_t s);
+  hipError_t (*ipa_verify_prepare)(const void* d_replay, const void* d_x3, const void* d_v, const void* d_weights, void* d_scal,
+                                   void* d_table, void* d_terms, uint32_t k, size_t count, hipStream_t s);
+  hipError_t (*ipa_verify_finish)(const void* d_terms, size_t count, void* d_col, uint32_t k, hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)
   int (*selftest_field)(int which /* 0 = base field, 1 = scalar field */, int op, const uint64_t* a,
                         const uint64_t* b, uint64_t* out);

@@ -247,6 +247,31 @@ class Blake2b {
     c.compress(true);
     memcpy(out, c.h_, outlen_);
   }
+  // The midstate as it crosses the C ABI (h2_transcript_state_t, 208 bytes): the chaining words, the bytes compressed so far,
+  // the block buffer with everything behind `buflen` zero, buflen (0 .. 128: a FULL buffer is still uncompressed, its block
+  // may be the last one) and a reserved word.  A state that has compressed 2^64 bytes or more has no such form
+  static constexpr size_t STATE_BYTES = 208;
+  void export_state(uint8_t out[STATE_BYTES]) const {
+    memset(out, 0, STATE_BYTES);
+    memcpy(out, h_, 64);
+    memcpy(out + 64, &t_[0], 8);
+    memcpy(out + 72, buf_, buflen_);
+    const uint32_t bl = (uint32_t)buflen_;
+    memcpy(out + 200, &bl, 4);
+  }
+  // false (the object untouched) for a buflen above 128
+  bool import_state(const uint8_t in[STATE_BYTES]) {
+    uint32_t bl;
+    memcpy(&bl, in + 200, 4);
+    if (bl > 128) return false;
+    memcpy(h_, in, 64);
+    memcpy(&t_[0], in + 64, 8);
+    t_[1] = 0;
+    memset(buf_, 0, sizeof buf_);
+    memcpy(buf_, in + 72, bl);
+    buflen_ = bl;
+    return true;
+  }
 
  private:
   static uint64_t rotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }

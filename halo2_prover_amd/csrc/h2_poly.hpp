@@ -522,6 +522,17 @@ __device__ __forceinline__ uint32_t chacha_rotl(uint32_t v, int c) { return (v <
   a += b; d = chacha_rotl(d ^ a, 8);        \
   c += d; b = chacha_rotl(b ^ c, 7)
 
+// ff's from_bytes_wide / Challenge255: the 512-bit integer lo + hi 2^256 reduced, as Montgomery limbs.  lo, hi < 2^256 need
+// not be reduced: a Montgomery product with one factor < p is < 2p before its final subtraction
+template <class FP>
+__device__ __forceinline__ Fe<FP> fe_from_wide(const Fe<FP>& lo, const Fe<FP>& hi) {
+  Fe<FP> r2;
+#pragma unroll
+  for (int k = 0; k < 8; k++) r2.v[k] = FP::R2(k);
+  const Fe<FP> r3 = fe_mul(r2, r2);
+  return fe_add(fe_mul(lo, r2), fe_mul(hi, r3));
+}
+
 template <class FP>
 __global__ void __launch_bounds__(256)
 chacha20_scalars_kernel(U128* __restrict__ out, size_t n, uint64_t first_block, ChaChaKey key) {
@@ -536,16 +547,12 @@ chacha20_scalars_kernel(U128* __restrict__ out, size_t n, uint64_t first_block, 
     H2_CHACHA_QR(x0, x4, x8, x12); H2_CHACHA_QR(x1, x5, x9, x13); H2_CHACHA_QR(x2, x6, x10, x14); H2_CHACHA_QR(x3, x7, x11, x15);
     H2_CHACHA_QR(x0, x5, x10, x15); H2_CHACHA_QR(x1, x6, x11, x12); H2_CHACHA_QR(x2, x7, x8, x13); H2_CHACHA_QR(x3, x4, x9, x14);
   }
-  Fe<FP> lo, hi, r2;
+  Fe<FP> lo, hi;
   lo.v[0] = x0 + in[0]; lo.v[1] = x1 + in[1]; lo.v[2] = x2 + in[2]; lo.v[3] = x3 + in[3];
   lo.v[4] = x4 + in[4]; lo.v[5] = x5 + in[5]; lo.v[6] = x6 + in[6]; lo.v[7] = x7 + in[7];
   hi.v[0] = x8 + in[8]; hi.v[1] = x9 + in[9]; hi.v[2] = x10 + in[10]; hi.v[3] = x11 + in[11];
   hi.v[4] = x12 + in[12]; hi.v[5] = x13 + in[13]; hi.v[6] = x14 + in[14]; hi.v[7] = x15 + in[15];
-#pragma unroll
-  for (int k = 0; k < 8; k++) r2.v[k] = FP::R2(k);
-  const Fe<FP> r3 = fe_mul(r2, r2);
-  // lo, hi < 2^256 need not be reduced: a Montgomery product with one factor < p is < 2p before its final subtraction
-  fe_store<FP>(out + 2 * i, fe_add(fe_mul(lo, r2), fe_mul(hi, r3)));
+  fe_store<FP>(out + 2 * i, fe_from_wide(lo, hi));
 }
 #undef H2_CHACHA_QR
 

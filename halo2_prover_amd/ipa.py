@@ -13,6 +13,8 @@ on the table -- and returns create_proof's bytes for each (DESIGN.md section 7.1
 random weights r_p they collapse into one table MSM and one points MSM; the 2k + 1 compressed
 points of every proof are decompressed by one kernel launch (h2_pasta_points_decompress_device) and the weighted sum of the
 N compute_s vectors comes from h2_ipa_challenge_products_sum_device, none of them materialised.
+`verify_proofs_bytes` is the same verifier behind ONE C ABI call, h2_ipa_verify_proofs: the transcripts are replayed on the
+device from exported Blake2b midstates and the scalars of every combined check are made there.
 Polynomials are (n, 4) int64 CUDA tensors viewing 4 x u64 Montgomery limbs (numpy uint64 arrays are uploaded); points are
 affine (x, y) pairs of canonical ints, None for the identity.  The transcript is transcript.Blake2bTranscript on the
 curve.  `ParamsIPA::new`'s hash-to-curve is not here: the bases are the caller's.  There is no CPU fallback.
@@ -534,3 +536,49 @@ def verify_proofs(params, items, rng=None, stats=None):
     if stats is not None:
         stats.update(st)
     return ok
+
+
+def verify_proofs_bytes(params, items, rng=None, stats=None):
+    """verify_proofs through ONE C ABI call (h2_ipa_verify_proofs): items = sequence of (midstate,
+    proof, P, x3, v) -- the midstate the 208 bytes of a transcript.Blake2bMidstate export (or the object) standing where
+    verify_proof would start, the proof exactly its (2k + 3) * 32 bytes -- -> list[bool], entry i what verify_proof gives for
+    the item.  The transcripts are replayed on the device, one lane per proof, and the scalars of every combined check are
+    made there: nothing but the weights comes from the host between the upload and a check's 96 bytes.  rng: a callable
+    n -> n bytes (default: the OS) for the weights, drawn as verify_proofs draws them.  stats: an optional dict, filled with
+    {"checks": combined checks run}."""
+    if params.curve == 0:
+        raise ValueError("verify_proofs_bytes: the Pasta wire form; BN254 proofs go through verify_proof")
+    items = list(items)
+    N = len(items)
+    if stats is not None:
+        stats.update({"checks": 0})
+    if N == 0:
+        return []
+    from .transcript import STATE_BYTES
+    states = bytearray()
+    for it in items:
+        st = it[0].export() if hasattr(it[0], "export") else bytes(it[0])
+        if len(st) != STATE_BYTES:
+            raise ValueError("verify_proofs_bytes: a midstate is %d bytes" % STATE_BYTES)
+        states += st
+    states = (ctypes.c_char * len(states)).from_buffer(states)
+    bufs = [bytes(it[1]) for it in items]
+    ptrs = (ctypes.c_char_p * N)(*bufs)
+    lens = (ctypes.c_size_t * N)(*[len(b) for b in bufs])
+    commitments = np.ascontiguousarray(np.stack([params.affine_limbs(it[2]) for it in items]))
+    x3 = np.ascontiguousarray(np.stack([params.mont(it[3]) for it in items]))
+    v = np.ascontiguousarray(np.stack([params.mont(it[4]) for it in items]))
+    cb = None
+    if rng is not None:
+        def fill(_ctx, out, n):
+            ctypes.memmove(out, bytes(rng(n)), n)
+        cb = _lib.RNG_FILL(fill)
+    ok = (ctypes.c_int * N)()
+    all_ok = ctypes.c_int(0)
+    checks = ctypes.c_size_t(0)
+    st = params._L.h2_ipa_verify_proofs(params.curve, params.bases.handle, params.k, N, states, ptrs, lens, commitments.ctypes.data,
+                                        x3.ctypes.data, v.ctypes.data, cb, None, ok, ctypes.byref(all_ok), ctypes.byref(checks))
+    _lib.check(st, "h2_ipa_verify_proofs")
+    if stats is not None:
+        stats.update({"checks": int(checks.value), "all_ok": bool(all_ok.value)})
+    return [bool(x) for x in ok]

@@ -97,6 +97,11 @@ SYMBOLS = {
     "h2_ipa_begin_batch_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P]),
     "h2_ipa_round_batch_device": (_I, [_I, _U64, _U32, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_final_batch_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P, _P]),
+    "h2_transcript_init": (_I, [_P]),
+    "h2_transcript_absorb": (_I, [_P, _P, _Z]),
+    "h2_transcript_challenge": (_I, [_I, _P, _P]),
+    "h2_ipa_replay_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_verify_proofs": (_I, [_I, _U64, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_poseidon_constants": (_I, [_I, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_poseidon_permute_device": (_I, [_I, _U32, _U32, _P, _P, _Z, _P]),
     "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),

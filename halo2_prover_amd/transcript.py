@@ -7,6 +7,7 @@ scalar field.  What goes to the proof stream for a point is the curve's compress
     bn254           x little-endian, bit 6 of the last byte the parity of y (h2_points_decompress_device documents it)
     pallas, vesta   x little-endian, bit 7 of the last byte (bit 255) the parity of y; the identity is 32 zero bytes
 Host arithmetic only; the prover and the verifier of the KZG surface and the inner product argument share this class.
+Blake2bMidstate is the absorbing side over a state that can be exported (h2_transcript_state_t of the C ABI).
 """
 import hashlib
 
@@ -146,3 +147,50 @@ class Blake2bTranscript:
             raise TranscriptError("point x not canonical" if status == 1 else "point not on the curve")
         self.common_point(pt)
         return pt
+
+
+STATE_BYTES = 208                                   # sizeof(h2_transcript_state_t)
+
+
+class Blake2bMidstate:
+    """Blake2bTranscript's absorbing side over an EXPORTABLE state (include/h2hip.h: h2_transcript_state_t), for callers that
+    hand a transcript to the device where it stands -- ipa.verify_proofs_bytes; hashlib cannot export one.  The same
+    challenges as Blake2bTranscript for the same sequence of calls; `state` continues an exported midstate.  Host only."""
+
+    def __init__(self, curve="bn254", state=None):
+        import ctypes
+        from . import lib as _lib
+        self.curve = curve_id(curve)
+        self.p, self.q, _ = FIELDS[self.curve]
+        self._L = _lib.load()
+        self._check = _lib.check
+        self._st = ctypes.create_string_buffer(STATE_BYTES)
+        if state is None:
+            self._check(self._L.h2_transcript_init(self._st), "h2_transcript_init")
+        else:
+            state = bytes(state)
+            if len(state) != STATE_BYTES:
+                raise ValueError("Blake2bMidstate: a state is %d bytes" % STATE_BYTES)
+            self._st.raw = state
+        self._rinv = pow(1 << 256, -1, self.p)
+
+    def update(self, data):
+        data = bytes(data)
+        self._check(self._L.h2_transcript_absorb(self._st, data, len(data)), "h2_transcript_absorb")
+
+    def common_scalar(self, s):
+        self.update(b"\x02" + int(s % self.p).to_bytes(32, "little"))
+
+    def common_point(self, pt):
+        x, y = pt if pt is not None else (0, 0)
+        self.update(b"\x01" + x.to_bytes(32, "little") + y.to_bytes(32, "little"))
+
+    def squeeze_challenge(self):
+        import ctypes
+        out = (ctypes.c_uint64 * 4)()
+        self._check(self._L.h2_transcript_challenge(self.curve, self._st, out), "h2_transcript_challenge")
+        return sum(int(out[i]) << (64 * i) for i in range(4)) * self._rinv % self.p
+
+    def export(self):
+        """the 208 bytes of the state as it stands"""
+        return bytes(self._st.raw)

@@ -770,6 +770,68 @@ int h2_params_cache_clear(void);
  * reference's behaviour (bench.py times both); returns the previous setting. */
 int h2_key_cache(int enable);
 
+/* ---- the IPA batch verifier on the Pasta curves -------------------------------------------------------------------
+ * verify_proof of the inner product argument (poly/ipa/commitment/verifier.rs) for `count` proofs behind combined checks,
+ * in ONE call: between the upload of the proofs and the 96-byte read-back of each combined check nothing goes through the
+ * host but the random weights.  DESIGN.md section 7.17.
+ *
+ * A transcript midstate.  The device has to start where the caller's transcript stands, so the Blake2b state crosses the
+ * ABI as a plain struct: the chaining words, the bytes compressed so far, the block buffer (bytes behind buflen zero) and
+ * buflen, 0 .. 128 -- Blake2b keeps a FULL buffer uncompressed until more input arrives, because the last block is
+ * finalised with a flag.  Host only, no h2_init needed:
+ *   h2_transcript_init        the personalised "Halo2-Transcript" state with a 64-byte digest, nothing absorbed
+ *   h2_transcript_absorb      len bytes (common_point: 0x01 || x || y, common_scalar: 0x02 || s, canonical little-endian)
+ *   h2_transcript_challenge   squeeze_challenge: absorbs 0x00, finalises a COPY and reduces the 64 bytes modulo the scalar
+ *                             field of `curve` (any of the three): out = 4 Montgomery limbs.  The state keeps absorbing.
+ * H2_EINVAL for a null pointer, an unknown curve or a state whose buflen is above 128. */
+typedef struct {
+  uint64_t h[8];        /* chaining words */
+  uint64_t t;           /* bytes compressed so far (the buffer's not included) */
+  uint8_t buf[128];     /* block buffer */
+  uint32_t buflen;      /* 0 .. 128 */
+  uint32_t reserved;    /* 0 */
+} h2_transcript_state_t; /* 208 bytes */
+int h2_transcript_init(h2_transcript_state_t* state);
+int h2_transcript_absorb(h2_transcript_state_t* state, const uint8_t* bytes, size_t len);
+int h2_transcript_challenge(h2_curve_t curve, h2_transcript_state_t* state, uint64_t out[4]);
+/* The transcripts of `count` proofs of one k, one lane each, in upstream's order: absorb S, squeeze xi and z, k times absorb
+ * L_j and R_j and squeeze u_j, absorb c and f.  A point is absorbed as 0x01 || x || y, the identity (point status 2) as 64
+ * zero bytes behind the 0x01, as common_point does.
+ *   d_states        count x 208 bytes, the midstate each proof's transcript starts from (a buflen above 128 is read as 128)
+ *   d_points        count x (2k + 1) affine points of 64 bytes, S, L_0, R_0, L_1, ...: h2_pasta_points_decompress_device's output
+ *   d_point_status  count x (2k + 1) bytes: that call's status
+ *   d_scalars       count x 64 bytes: c || f as they stand in the stream
+ *   d_out           count x (k + 4) x 32 bytes: xi, z, u_0 .. u_(k-1), c, f as Montgomery limbs
+ *   d_status        count bytes, the first that applies: 1 a point of decompression status 1 or 3; 2 c or f not canonical;
+ *                   3 some u_j = 0; 0 otherwise.  The d_out row of a proof with a status other than 0 is unspecified.
+ *   d_states_out    null, or count x 208 bytes: the midstates behind f
+ * Asynchronous on `stream`, no host synchronisation, nothing allocated.  H2_EINVAL, before anything is enqueued, for
+ * H2_BN254 (the wire form is the Pasta one) or an unknown curve, k = 0, k > H2_IPA_MAX_K, count > 2^24; count = 0 is H2_OK
+ * whatever the pointers; otherwise a null pointer other than d_states_out, or one of d_states, d_points, d_scalars, d_out,
+ * d_states_out that is not 16-byte aligned, is H2_EINVAL. */
+int h2_ipa_replay_device(h2_curve_t curve, uint32_t k, size_t count, const void* d_states, const void* d_points,
+                         const void* d_point_status, const void* d_scalars, void* d_out, void* d_status, void* d_states_out,
+                         void* stream);
+/* The batch verifier.  `bases` is the handle of G || U || W (2^k + 2 points) the h2_ipa_* calls take.  Item i: the midstate
+ * states[i] its transcript stands at, its proof bytes, the commitment (8 Montgomery limbs, affine, (0, 0) the identity), x3
+ * and v (4 canonical Montgomery limbs each); all HOST arrays.  ok[i] (count ints) is exactly what verify_proof gives for the
+ * item; *all_ok (optional) is their AND (count = 0: 1); *checks_out (optional) the combined checks that ran.
+ * A proof is exactly (2k + 3) * 32 bytes -- S, k x (L_j, R_j), c, f.  Any other length is ok[i] = 0 without a device step: a
+ * shorter stream fails verify_proof's reads, and bytes behind the proof belong to the caller's transcript, so the caller
+ * passes the proof's own length.
+ * One upload, one decompression launch and one replay launch for the batch; one read-back of the status bytes decides
+ * which proofs take part.  A combined check draws 16 bytes per proof of its subset from rng, in subset order, read
+ * little-endian, a zero weight redrawn (rng = NULL: the OS; the weights must be unpredictable to whoever made the proofs),
+ * makes the scalars on the device, runs the challenge-product sum, one MSM on the registered table, one over the
+ * decompressed points with the commitments behind them, and reads 96 bytes back.  A failing subset is halved until every
+ * culprit is alone.  Synchronous, on the context's stream; scratch comes from the context's arenas.
+ * H2_EINVAL for H2_BN254 or an unknown curve, k = 0 or k > H2_IPA_MAX_K, a handle of another curve or one that does not hold
+ * exactly 2^k + 2 bases (H2_EHANDLE for one that is not registered), a null array with count > 0, a null proof of non-zero
+ * length, an x3 or v that is not canonical, a state whose buflen is above 128. */
+int h2_ipa_verify_proofs(h2_curve_t curve, uint64_t bases, uint32_t k, size_t count, const h2_transcript_state_t* states,
+                         const uint8_t* const* proofs, const size_t* proof_lens, const uint64_t* commitments, const uint64_t* x3,
+                         const uint64_t* v, h2_rng_fill_t rng, void* rng_ctx, int* ok, int* all_ok, size_t* checks_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,15 @@
 //   quad  = 4 lanes per point (h2_curve_quad.hpp), lane = one lane per point (h2_curve29.hpp)
 // at 1 / 2 / 4 waves per SIMD.  Prints microseconds per addition (latency of the chain) and chip-wide point
 // additions per second.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o microbench_tail tools/microbench_tail.hip
+// `microbench_tail ops` skips the stage stamps of the row / column tail and prints the per-operation table only.
+// k_one_add and k_one_dbl hold one quad addition (with the doubling of its P + P case inlined) and one quad doubling:
+// the kernels whose ISA is counted by class in profiles/quad_ops_isa.txt (hipcc -O3 --cuda-device-only -S); the
+// addition's own instructions are the difference of the two.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
+#include <vector>
 
 #define H2_TAIL_STAMPS 1
 #include "../halo2_prover_amd/csrc/h2_msm.hpp"
@@ -38,6 +44,27 @@ __global__ void __launch_bounds__(256) k_quad_dbl(uint32_t* out, int iters) {
   Xyzz29<CV> a = seed_point(t >> 2);
   for (int k = 0; k < iters; k++) a = xyzz29_double_quad(a);
   if ((t & 3) == 0) xyzz29_store<CV>(out + XYZZ29_WORDS * (size_t)(t >> 2), a);
+}
+// a chain of products alone, one lane per element.  AR: the product form (h2_field29_chain.hpp)
+template <class AR>
+__global__ void __launch_bounds__(256) k_mul(uint32_t* out, int iters) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  Fe29<CV::Base> a = seed_point(t).x;
+  const Fe29<CV::Base> b = seed_point(t + 77777u).y;
+  for (int k = 0; k < iters; k++) a = AR::mul(a, b);
+  for (int i = 0; i < 9; i++) out[XYZZ29_WORDS * (size_t)t + i] = (uint32_t)a.v[i];
+}
+__global__ void __launch_bounds__(256) k_one_add(uint32_t* out, const uint32_t* in) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const Xyzz29<CV> a = xyzz29_load<CV>(in + 2 * XYZZ29_WORDS * (size_t)(t >> 2)),
+                   b = xyzz29_load<CV>(in + 2 * XYZZ29_WORDS * (size_t)(t >> 2) + XYZZ29_WORDS);
+  const Xyzz29<CV> r = xyzz29_add_quad(a, b);
+  if ((t & 3) == 0) xyzz29_store<CV>(out + XYZZ29_WORDS * (size_t)(t >> 2), r);
+}
+__global__ void __launch_bounds__(256) k_one_dbl(uint32_t* out, const uint32_t* in) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const Xyzz29<CV> r = xyzz29_double_quad(xyzz29_load<CV>(in + XYZZ29_WORDS * (size_t)(t >> 2)));
+  if ((t & 3) == 0) xyzz29_store<CV>(out + XYZZ29_WORDS * (size_t)(t >> 2), r);
 }
 __global__ void __launch_bounds__(256) k_lane(uint32_t* out, int iters) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -114,9 +141,8 @@ double time_kernel(F launch) {
   return best;
 }
 
-#include <vector>
-int main() {
-  tail_stages();
+int main(int argc, char** argv) {
+  if (!(argc > 1 && !strcmp(argv[1], "ops"))) tail_stages();
   hipDeviceProp_t prop;
   hipGetDeviceProperties(&prop, 0);
   const int cus = prop.multiProcessorCount;
@@ -133,8 +159,14 @@ int main() {
     };
     rep("quad add (4 lanes/point)", time_kernel([&] { hipLaunchKernelGGL(k_quad, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 16);
     rep("quad double", time_kernel([&] { hipLaunchKernelGGL(k_quad_dbl, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 16);
+    rep("product (compiler's form)", time_kernel([&] { hipLaunchKernelGGL(k_mul<Fe29Compiler>, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 64);
+    rep("product (chain form)", time_kernel([&] { hipLaunchKernelGGL(k_mul<Fe29Chain>, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 64);
     rep("lane add (full XYZZ)", time_kernel([&] { hipLaunchKernelGGL(k_lane, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 64);
     rep("lane mixed add (affine)", time_kernel([&] { hipLaunchKernelGGL(k_lane_mixed, dim3(blocks), dim3(256), 0, 0, (uint32_t*)buf, iters); }), 64);
+  }
+  if (hipDeviceSynchronize() != hipSuccess) {
+    printf("a kernel failed: %s\n", hipGetErrorString(hipGetLastError()));
+    return 1;
   }
   hipFree(buf);
   return 0;

@@ -20,6 +20,7 @@
 #include "h2_ipa.hpp"
 #include "h2_ipa_verify.hpp"
 #include "h2_lookup.hpp"
+#include "h2_merkle_ops.hpp"
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
 #include "h2_poly.hpp"
@@ -2279,6 +2280,103 @@ int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, cons
   return launched(ops_of((int)curve)->poseidon_merkle(d_leaves, depth, d_nodes, cap2, table, r_f, r_p, (uint32_t)h2_poseidon_merkle_tail(),
                                                       poseidon_chain_min_n(), k.stream),
                   "poseidon_merkle kernels");
+}
+
+// ---- a resident Merkle tree: paths, verification, update (h2_merkle_ops.hpp) --------------------------------------------
+static_assert(H2_MERKLE_OK == MERKLE_OK && H2_MERKLE_RANGE == MERKLE_RANGE && H2_MERKLE_NONCANONICAL == MERKLE_NONCANONICAL &&
+                  H2_MERKLE_SUPERSEDED == MERKLE_SUPERSEDED && H2_MERKLE_MISMATCH == MERKLE_MISMATCH,
+              "the header states the kernels' status words");
+namespace {
+// hashes below which a launch runs one permutation on four lanes, unless a test knob fixes the form
+size_t poseidon_walk_quad_max() { return g_knobs.poseidon_walk_form == 1 ? 0 : g_knobs.poseidon_walk_form == 2 ? SIZE_MAX : POSEIDON_WALK_QUAD_MAX; }
+const MerkleOps* merkle_ops_of(int curve) { return curve == H2_BN254 ? merkle_ops_bn254() : curve == H2_PALLAS ? merkle_ops_pallas() : merkle_ops_vesta(); }
+bool merkle_args_ok(h2_curve_t curve, uint32_t depth, size_t n) {
+  return curve_ok((int)curve) && depth >= 1 && depth <= 30 && n <= ((size_t)1 << 31);
+}
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+// does a written range overlap a range that is read, or another one that is written?  (absent and empty ranges aside)
+bool merkle_overlap(std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+  auto hit = [](const Span& a, const Span& b) { return a.p && b.p && a.bytes && b.bytes && poseidon_overlap(a.p, a.bytes, b.p, b.bytes); };
+  for (auto o = outs.begin(); o != outs.end(); ++o) {
+    for (const Span& x : ins)
+      if (hit(*o, x)) return true;
+    for (auto o2 = o + 1; o2 != outs.end(); ++o2)
+      if (hit(*o, *o2)) return true;
+  }
+  return false;
+}
+}  // namespace
+
+int h2_poseidon_merkle_paths_device(h2_curve_t curve, const void* d_leaves, const void* d_nodes, uint32_t depth, const void* d_indices,
+                                    size_t n, void* d_paths, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!merkle_args_ok(curve, depth, n) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || !poseidon_dev_ptr(d_indices) ||
+      !poseidon_dev_ptr(d_paths) || !poseidon_dev_ptr(d_status))
+    return H2_EINVAL;
+  const size_t leaves = (size_t)1 << depth;
+  const Span paths{d_paths, 32 * n * depth}, status{d_status, 4 * n};
+  if (merkle_overlap({paths, status}, {Span{d_leaves, 32 * leaves}, Span{d_nodes, 32 * (leaves - 1)}, Span{d_indices, 4 * n}}))
+    return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  return launched(merkle_ops_of((int)curve)->paths(d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, k.stream),
+                  "poseidon_merkle_paths_kernel");
+}
+
+int h2_poseidon_merkle_verify_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaf_values, const void* d_indices,
+                                     const void* d_paths, uint32_t depth, size_t n, const void* d_root, void* d_roots_out, void* d_status,
+                                     void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!merkle_args_ok(curve, depth, n) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaf_values) || !poseidon_dev_ptr(d_indices) ||
+      !poseidon_dev_ptr(d_paths) || !poseidon_dev_ptr(d_status) || ((uintptr_t)d_root & 15) || ((uintptr_t)d_roots_out & 15))
+    return H2_EINVAL;
+  const Span roots{d_roots_out, 32 * n}, status{d_status, 4 * n};
+  if (merkle_overlap({roots, status}, {Span{d_leaf_values, 32 * n}, Span{d_indices, 4 * n}, Span{d_paths, 32 * n * depth},
+                                       Span{d_root, 32}}))
+    return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap2[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(2, cap2);
+  return launched(merkle_ops_of((int)curve)->verify(d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out, d_status, cap2,
+                                                    table, r_f, r_p, poseidon_walk_quad_max(), k.stream),
+                  "poseidon_merkle_verify_kernel");
+}
+
+int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, void* d_leaves, void* d_nodes, uint32_t depth,
+                                     const void* d_indices, const void* d_values, size_t n, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!merkle_args_ok(curve, depth, n) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) ||
+      !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_values) || !poseidon_dev_ptr(d_status))
+    return H2_EINVAL;
+  const size_t leaves = (size_t)1 << depth;
+  const Span lv{d_leaves, 32 * leaves}, nd{d_nodes, 32 * (leaves - 1)}, status{d_status, 4 * n};
+  if (merkle_overlap({lv, nd, status}, {Span{d_indices, 4 * n}, Span{d_values, 32 * n}})) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  const MerkleOps* ops = merkle_ops_of((int)curve);
+  const size_t scratch = ops->update_scratch(n, depth);
+  if (scratch == 0) {
+    g_h2.last_error = "poseidon merkle update: the sort gave no scratch size";
+    return H2_EDEVICE;
+  }
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap2[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(2, cap2);
+  ArenaLease A(k.c->div_ws, scratch, k.stream);
+  if (A.rc != H2_OK) return A.rc;
+  if (int rc = launched(ops->update(d_leaves, d_nodes, depth, d_indices, d_values, n, d_status, cap2, table, r_f, r_p,
+                                    poseidon_walk_quad_max(), A.a.p, A.a.bytes, k.stream),
+                        "poseidon_merkle_update kernels");
+      rc != H2_OK)
+    return rc;
+  return A.release();
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {

@@ -71,6 +71,15 @@ H2_HD void fe_store(void* p, const Fe<FP>& a) {
   q[1] = U128{a.v[4], a.v[5], a.v[6], a.v[7]};
 }
 
+// a below p?
+template <class FP>
+H2_HD bool fe_is_canonical(const Fe<FP>& a) {
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) br = (((uint64_t)a.v[i] - FP::P(i) - br) >> 63) & 1;
+  return br != 0;
+}
+
 // r = a - p if a >= p else a   (a < 2p, optional carry word `top`)
 template <class FP>
 H2_HD void fe_reduce_once(uint32_t* r, const uint32_t* t, uint32_t top) {

@@ -144,6 +144,7 @@ struct TestKnobs {
   int gfft_lanes = 0;                            // lanes per butterfly of the group FFT: 0 = by size, 1, 4
   uint32_t poseidon_merkle_tail = 0;             // nodes a Merkle level may have to be finished by the tail launch; 0: the default
   int poseidon_form = 0;                         // the hash kernel's products: 0 = by size, 1 = the compiler's form, 2 = single-chain
+  int poseidon_walk_form = 0;                    // the Merkle walker and update: 0 = by size, 1 = a lane per hash, 2 = a quad per hash
 };
 struct TestCounters {
   uint64_t guard_launches = 0, guard_violations = 0;

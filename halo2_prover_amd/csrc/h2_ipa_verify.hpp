@@ -83,15 +83,6 @@ __device__ __forceinline__ void blake2b_compress(uint64_t (&h)[8], const uint64_
 }
 #undef H2_B2B_G
 
-// a below p?
-template <class FP>
-__device__ __forceinline__ bool fe_is_canonical(const Fe<FP>& a) {
-  uint64_t br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) br = (((uint64_t)a.v[i] - FP::P(i) - br) >> 63) & 1;
-  return br != 0;
-}
-
 // Lane p replays proof p (the lanes behind `count` repeat the last proof and store nothing, so the wave stays whole).
 // states: count x 208 bytes; points: count x (2k + 1) affine points in the API form with their decompression status;
 // scalars: count x 64 bytes, c || f as they stand in the stream; out: count x (k + 4) elements xi, z, u_0 .. u_(k-1), c, f

@@ -53,6 +53,20 @@ constexpr uint32_t POSEIDON_MAX_ROUNDS = 128;       // r_f + r_p
 constexpr uint32_t POSEIDON_THREADS = 256;
 constexpr uint32_t POSEIDON_MAX_BLOCKS = 1u << 20;  // beyond that the lanes stride over the rest
 constexpr size_t POSEIDON_CHAIN_MIN_N = (1u << 16) + 1;   // more lanes than one wave on every SIMD of the device
+// The Merkle walker and update (h2_poseidon_quad.hpp): hashes (paths of a verify call, or hashes of one update level) below
+// which a launch takes the QUAD form, four lanes per permutation; from it on the lane form.  The sweep (tools/
+// poseidon_merkle_bench.py, verify at depth 20, both forms in one run, best of the windows, ms; DESIGN.md section 7.18 has
+// the whole table):
+//     n            2^4    2^10   2^12   2^13   2^14   2^15   2^16   2^17    2^18    2^20
+//     Pallas lane  6.39   5.61   5.61   5.60   5.69   5.60   5.79   10.72   21.09   83.5
+//     Pallas quad  2.69   2.72   2.81   2.94   3.15   5.54   10.01  19.38   38.47   153.6
+//     BN254 lane   8.68   7.66   7.67   7.63   7.68   7.62   7.84   14.48   28.26   111.6
+//     BN254 quad   3.51   3.53   3.61   3.73   4.17   7.22   13.22  26.03   51.79   207.1
+// Up to 2^14 paths -- 2^16 lanes, one wave per SIMD -- the quad form is its own shorter chain (0.40 - 0.55 of the lane
+// form); at 2^15 it is two waves per SIMD and level with the lane form (1 - 5 % ahead); at 2^16 the lane form, then one wave
+// per SIMD itself, is 1.7 x faster, and 1.8 x where both fill the device.  So: the quad form up to 2^15 hashes, the lane
+// form above.  The numbers are those of profiles/poseidon_merkle_times.json.
+constexpr size_t POSEIDON_WALK_QUAD_MAX = ((size_t)1 << 15) + 1;
 // Merkle tail: levels of at most this many nodes are finished by one workgroup in one launch.  The sweep of tools/
 // poseidon_bench.py cannot tell 32 .. 256 apart -- a level is one hash's latency either way -- and
 // has 512, where a lane hashes two nodes in turn, behind: the default is the widest level with one node per lane.  The LDS

@@ -413,3 +413,11 @@ extern "C" int h2_selftest_set_poseidon_form(int form) {
   g_knobs.poseidon_form = form;
   return H2_OK;
 }
+// tests and tools only: the form of h2_poseidon_merkle_verify_device's walker and of h2_poseidon_merkle_update_device's level
+// and top launches (0: by size, 1: one lane per hash, 2: four lanes per hash)
+extern "C" int h2_selftest_set_poseidon_walk_form(int form) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (form < 0 || form > 2) return H2_EINVAL;
+  g_knobs.poseidon_walk_form = form;
+  return H2_OK;
+}

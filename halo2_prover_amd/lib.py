@@ -107,6 +107,9 @@ SYMBOLS = {
     "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),
     "h2_poseidon_merkle_device": (_I, [_I, _U32, _U32, _P, _U32, _P, _P]),
     "h2_poseidon_merkle_tail": (_I, []),
+    "h2_poseidon_merkle_paths_device": (_I, [_I, _P, _P, _U32, _P, _Z, _P, _P, _P]),
+    "h2_poseidon_merkle_verify_device": (_I, [_I, _U32, _U32, _P, _P, _P, _U32, _Z, _P, _P, _P, _P]),
+    "h2_poseidon_merkle_update_device": (_I, [_I, _U32, _U32, _P, _P, _U32, _P, _P, _Z, _P, _P]),
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),
@@ -174,6 +177,7 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_expr_run": (_I, [_P, _Z, _P, _P, _U32, _U32, _U32, _P, _P]),
     "h2_selftest_set_poseidon_merkle_tail": (_I, [_U32]),
     "h2_selftest_set_poseidon_form": (_I, [_I]),
+    "h2_selftest_set_poseidon_walk_form": (_I, [_I]),
     "h2_selftest_set_poseidon_verify_min": (_I, [_Z]),
 }
 

@@ -8,7 +8,9 @@ instances the reference uses: (8, 56) on Pallas and Vesta (P128Pow5T3, the zcash
 Elements are 4 x u64 Montgomery limbs, canonical.  The device functions take int64 CUDA tensors viewing those limbs, or
 numpy uint64 arrays, which are uploaded, and return the same kind: the work is enqueued on the caller's current stream
 and the columns stay in HBM.  There is no CPU fallback: `merkle_path` and `verify_path` are host helpers on Python
-integers for a membership proof's few hashes, everything else runs the kernels.
+integers for a membership proof's few hashes, everything else runs the kernels.  `merkle_paths`, `verify_paths` and
+`merkle_update` are their device counterparts on a resident tree: many paths per call, indices as uint32 (numpy) or int32
+CUDA tensors, one status word per item.
 """
 import ctypes
 
@@ -152,6 +154,118 @@ def merkle_root(curve, leaves, r_f=None, r_p=None):
 def merkle_tail():
     """the widest level merkle_nodes leaves to its single-workgroup launch"""
     return _lib.load().h2_poseidon_merkle_tail()
+
+
+# ---- a resident tree: paths, verification, update -------------------------------------------------------------------------
+STATUS_OK, STATUS_RANGE, STATUS_NONCANONICAL, STATUS_SUPERSEDED, STATUS_MISMATCH = 0, 1, 2, 3, 4
+
+
+def _device_u32(a, name):
+    """(tensor, was_numpy): an int32 CUDA tensor viewing uint32 words"""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.int32 or not a.is_cuda or not a.is_contiguous() or a.dim() != 1:
+            raise ValueError("%s: expected a contiguous one-dimensional int32 CUDA tensor" % name)
+        return a, False
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    return torch.from_numpy(a.view(np.int32).copy()).cuda(), True
+
+
+def _status(t, as_numpy):
+    return t.cpu().numpy().view(np.uint32) if as_numpy else t
+
+
+def _tree(leaves, nodes):
+    """(d_leaves, d_nodes, depth, were_numpy) of a tree as merkle_nodes lays it out"""
+    d_leaves, np_l = _device(leaves, "leaves")
+    d_nodes, np_n = _device(nodes, "nodes")
+    n = d_leaves.shape[0] if d_leaves.dim() == 2 else 0
+    if d_leaves.dim() != 2 or d_leaves.shape[1] != 4 or n < 2 or n & (n - 1):
+        raise ValueError("leaves: expected shape (2^depth, 4) with depth >= 1, got %r" % (tuple(d_leaves.shape),))
+    if tuple(d_nodes.shape) != (n - 1, 4):
+        raise ValueError("nodes: expected shape (%d, 4), got %r" % (n - 1, tuple(d_nodes.shape)))
+    return d_leaves, d_nodes, n.bit_length() - 1, np_l or np_n
+
+
+def merkle_paths(curve, leaves, nodes, indices):
+    """The membership paths of n leaves of a resident tree, cut on the device: (paths (n, depth, 4), status (n,)).
+    paths[i] is merkle_path's list for indices[i]; an index >= 2^depth gives status 1 and a zero path."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    d_leaves, d_nodes, depth, np_tree = _tree(leaves, nodes)
+    d_idx, np_idx = _device_u32(indices, "indices")
+    n = d_idx.shape[0]
+    d_paths = torch.empty((n, depth, 4), dtype=torch.int64, device=d_leaves.device)
+    d_status = torch.empty((n,), dtype=torch.int32, device=d_leaves.device)
+    if n:              # an empty tensor has no address to pass: n = 0 is the C call's H2_OK, nothing enqueued
+        st = _lib.load().h2_poseidon_merkle_paths_device(cid, ctypes.c_void_p(d_leaves.data_ptr()), ctypes.c_void_p(d_nodes.data_ptr()),
+                                                         depth, ctypes.c_void_p(d_idx.data_ptr()), n, ctypes.c_void_p(d_paths.data_ptr()),
+                                                         ctypes.c_void_p(d_status.data_ptr()), _stream())
+        _lib.check(st, "h2_poseidon_merkle_paths_device")
+    as_numpy = np_tree and np_idx
+    return _result(d_paths, as_numpy), _status(d_status, as_numpy)
+
+
+def verify_paths(curve, leaf_values, indices, paths, root=None, r_f=None, r_p=None):
+    """n membership paths walked on the device: (roots (n, 4), status (n,)).  Status 0: index in range, every element
+    canonical and -- when `root` (4 limbs) is given -- the computed root equals it; 1: index out of range; 2: an element not
+    canonical (never reduced silently); 4: another root.  Items with status 1 or 2 get a zero root."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    d_leafs, np_v = _device(leaf_values, "leaf_values")
+    d_paths, np_p = _device(paths, "paths")
+    d_idx, np_i = _device_u32(indices, "indices")
+    n = d_idx.shape[0]
+    if d_paths.dim() != 3 or d_paths.shape[0] != n or (n and d_paths.shape[1] == 0) or d_paths.shape[2] != 4:
+        raise ValueError("paths: expected shape (%d, depth, 4) with depth >= 1, got %r" % (n, tuple(d_paths.shape)))
+    if tuple(d_leafs.shape) != (n, 4):
+        raise ValueError("leaf_values: expected shape (%d, 4), got %r" % (n, tuple(d_leafs.shape)))
+    depth = d_paths.shape[1]
+    d_root = None
+    if root is not None:
+        d_root = _device(root, "root")[0]
+        if d_root.numel() != 4:
+            raise ValueError("root: expected one element of 4 limbs")
+    d_roots = torch.empty((n, 4), dtype=torch.int64, device=d_paths.device)
+    d_status = torch.empty((n,), dtype=torch.int32, device=d_paths.device)
+    if n:
+        st = _lib.load().h2_poseidon_merkle_verify_device(cid, r_f, r_p, ctypes.c_void_p(d_leafs.data_ptr()),
+                                                          ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_paths.data_ptr()), depth, n,
+                                                          None if d_root is None else ctypes.c_void_p(d_root.data_ptr()),
+                                                          ctypes.c_void_p(d_roots.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
+                                                          _stream())
+        _lib.check(st, "h2_poseidon_merkle_verify_device")
+    as_numpy = np_v and np_p and np_i
+    return _result(d_roots, as_numpy), _status(d_status, as_numpy)
+
+
+def merkle_update(curve, leaves, nodes, indices, values, r_f=None, r_p=None):
+    """leaves[indices[i]] = values[i] IN PLACE on the device tensors `leaves` (2^depth, 4) and `nodes` (2^depth - 1, 4), the
+    nodes above the written leaves hashed again -> status (n,).  1: index out of range, 2: value not canonical (both
+    dropped), 3: a later item writes the same leaf (the last one is stored), 0: stored."""
+    import torch
+    _ensure_init()
+    cid = _curve_id(curve)
+    r_f, r_p = _rounds(cid, r_f, r_p)
+    if not isinstance(leaves, torch.Tensor) or not isinstance(nodes, torch.Tensor):
+        raise ValueError("merkle_update: leaves and nodes are updated in place and must be CUDA tensors")
+    d_leaves, d_nodes, depth, _ = _tree(leaves, nodes)
+    d_idx, np_i = _device_u32(indices, "indices")
+    d_val, np_v = _device(values, "values")
+    n = d_idx.shape[0]
+    if tuple(d_val.shape) != (n, 4):
+        raise ValueError("values: expected shape (%d, 4), got %r" % (n, tuple(d_val.shape)))
+    d_status = torch.empty((n,), dtype=torch.int32, device=d_leaves.device)
+    if n:
+        st = _lib.load().h2_poseidon_merkle_update_device(cid, r_f, r_p, ctypes.c_void_p(d_leaves.data_ptr()),
+                                                          ctypes.c_void_p(d_nodes.data_ptr()), depth, ctypes.c_void_p(d_idx.data_ptr()),
+                                                          ctypes.c_void_p(d_val.data_ptr()), n, ctypes.c_void_p(d_status.data_ptr()),
+                                                          _stream())
+        _lib.check(st, "h2_poseidon_merkle_update_device")
+    return _status(d_status, np_i and np_v)
 
 
 # ---- host helpers on Python integers ---------------------------------------------------------------------------------

@@ -476,6 +476,52 @@ int h2_poseidon_hash_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const 
 int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth, void* d_nodes,
                               void* stream);
 int h2_poseidon_merkle_tail(void);      /* host only */
+/* ---- a resident Poseidon Merkle tree: membership paths, batch verification, in-place update ------------------------
+ * The tree is h2_poseidon_merkle_device's: d_leaves holds 2^depth elements, d_nodes the 2^depth - 1 inner nodes, level by
+ * level from the leaves' parents up, the root last.  Elements are 4 x u64 Montgomery limbs; indices are uint32_t.  A path is
+ * `depth` elements, the leaf's sibling first, then the sibling of every ancestor below the root.  Every call reports
+ * per-item trouble in one uint32_t status word per item (H2_MERKLE_*), never as a host error.
+ *   h2_poseidon_merkle_paths_device    a gather, no hashing: d_paths[i * depth + l] = the sibling at level l of leaf
+ *                                      d_indices[i].  An index >= 2^depth gives status 1 and an all-zero path.
+ *   h2_poseidon_merkle_verify_device   cur = d_leaf_values[i]; for every level l, cur = H(sib, cur) if bit l of the index is
+ *                                      set, else H(cur, sib), H = ConstantLength<2> as in the tree.  d_roots_out[i] (optional)
+ *                                      = the computed root.  Status 0 when the index is below 2^depth, the leaf value and
+ *                                      every sibling are canonical and the computed root equals *d_root; d_root = NULL drops
+ *                                      the comparison.  The data is untrusted: an element that is not canonical is never
+ *                                      reduced silently -- status 2 and a zero root, as an index out of range (status 1) --
+ *                                      and a root that differs is status 4.  The first that applies of 1, 2, 4 is reported.
+ *                                      One path runs on the four lanes of a DPP quad (the permutation's three words side by
+ *                                      side) or, in large batches, on one lane; the results are the same bits.
+ *   h2_poseidon_merkle_update_device   afterwards d_leaves[d_indices[i]] = d_values[i] for the accepted items and d_nodes is
+ *                                      byte for byte what h2_poseidon_merkle_device returns for the new leaves.  Items with
+ *                                      status 1 (index) or 2 (value not canonical) are dropped first; of the remaining items
+ *                                      with one index the LAST in the array is stored, the earlier ones get status 3.  Only
+ *                                      the nodes above a stored leaf are hashed and written, everything else keeps its bytes.
+ *                                      The tree must be consistent on entry (nodes = the hashes of the leaves).  Scratch:
+ *                                      16 bytes per item and the sort's buffers, from the context's scan arena for the
+ *                                      length of the call.
+ * Asynchronous on `stream` under h2_ntt_device's rules: no host synchronisation and no device-to-host copy, except the first
+ * use of a (curve, r_f, r_p) on a context, which uploads its constants as the calls above do.  H2_EINVAL -- checked on the host
+ * before anything is enqueued -- for: an unknown curve; r_f odd or 0, or r_f + r_p > H2_POSEIDON_MAX_ROUNDS; depth = 0 or
+ * depth > 30; n > 2^31; a null or not 16-byte aligned pointer (d_root and d_roots_out may be null, not misaligned); a range
+ * that is written overlapping a range that is read or another that is written (the update's d_leaves and d_nodes count as
+ * written).  n = 0 is H2_OK and enqueues nothing.  H2_ENOTINIT before h2_init.  h2_version() is unchanged: a host detects
+ * these entry points by their symbols. */
+#define H2_MERKLE_OK 0            /* the item is fine */
+#define H2_MERKLE_RANGE 1         /* index >= 2^depth */
+#define H2_MERKLE_NONCANONICAL 2  /* an element of the item is not below p */
+#define H2_MERKLE_SUPERSEDED 3    /* update only: a later item writes the same leaf */
+#define H2_MERKLE_MISMATCH 4      /* verify only: the computed root is not *d_root */
+int h2_poseidon_merkle_paths_device(h2_curve_t curve, const void* d_leaves, const void* d_nodes, uint32_t depth,
+                                    const void* d_indices, size_t n, void* d_paths /* n*depth */, void* d_status /* n */,
+                                    void* stream);
+int h2_poseidon_merkle_verify_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaf_values /* n */,
+                                     const void* d_indices, const void* d_paths, uint32_t depth, size_t n,
+                                     const void* d_root /* 1 element or NULL */, void* d_roots_out /* n or NULL */,
+                                     void* d_status /* n */, void* stream);
+int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, void* d_leaves, void* d_nodes,
+                                     uint32_t depth, const void* d_indices, const void* d_values /* n */, size_t n,
+                                     void* d_status /* n */, void* stream);
 /* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
  * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
  * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER

@@ -190,6 +190,10 @@ int h2_selftest_poseidon(int curve, uint32_t r_f, uint32_t r_p, int op, const ui
 int h2_selftest_set_poseidon_verify_min(size_t count);
 int h2_selftest_set_poseidon_merkle_tail(uint32_t nodes);
 int h2_selftest_set_poseidon_form(int form);
+/* tests and tools only -- the form of h2_poseidon_merkle_verify_device's walker and of the level and top launches of
+ * h2_poseidon_merkle_update_device: 1 = one lane per hash at every size, 2 = the four lanes of a quad per hash at every
+ * size, 0 = by size (the default).  The results are the same bits either way.  H2_EINVAL for another value. */
+int h2_selftest_set_poseidon_walk_form(int form);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,484 @@
+"""GPU: h2_poseidon_merkle_paths_device / _verify_device / _update_device (csrc/h2_poseidon_quad.hpp).
+
+Judges: oracle/pyref.py (poseidon_hash_const_len, t = 3) for single hashes and the depth-3 tree, the existing
+h2_poseidon_merkle_device for whole trees, and poseidon.merkle_path on a host copy for the paths.  Every comparison is
+exact equality of canonical values or of bytes.  Tests that hash run under both forms of the walker (one lane per hash, the
+four lanes of a quad per hash) through h2_selftest_set_poseidon_walk_form.  The references are computed once and shared.
+
+Outputs sit in front of a red zone filled with a pattern: whatever a call was not asked to write comes back unchanged."""
+import ctypes
+import random
+
+import numpy as np
+import pytest
+
+import pyref as R
+
+pytestmark = pytest.mark.gpu
+
+FIELD = {0: R.BN_FR, 1: R.PA_FQ, 2: R.PA_FP}
+SPEC = {0: (8, 60), 1: (8, 56), 2: (8, 56)}
+H2_OK, H2_EINVAL = 0, -1
+OK, RANGE, NONCANONICAL, SUPERSEDED, MISMATCH = 0, 1, 2, 3, 4
+PATTERN = 0x5A5A5A5A5A5A5A5A
+PATTERN32 = 0x5A5A5A5A
+RED = 8
+P = ctypes.c_void_p
+
+
+def L():
+    from halo2_prover_amd import lib
+    return lib.load()
+
+
+def limbs(cid, values):
+    return np.array([FIELD[cid].limbs(v) for v in values], dtype=np.uint64).reshape(-1, 4)
+
+
+def raw_limbs(v):
+    """the integer itself as four little-endian words (NOT Montgomery): how a non-canonical element is put in"""
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+def ints(cid, a):
+    raw = np.ascontiguousarray(a).tobytes()
+    return [FIELD[cid].from_mont(int.from_bytes(raw[i:i + 32], "little")) for i in range(0, len(raw), 32)]
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).cuda()
+
+
+def dev_u32(a):
+    import torch
+    return torch.from_numpy(np.array(a, dtype=np.uint32).view(np.int32).copy()).cuda()
+
+
+def red_buffer(elems):
+    import torch
+    return torch.full((elems + RED, 4), PATTERN, dtype=torch.int64, device="cuda")
+
+
+def red_status(n):
+    import torch
+    return torch.full((n + RED,), PATTERN32, dtype=torch.int32, device="cuda")
+
+
+def split(buf, elems):
+    h = buf.cpu().numpy().view(np.uint64)
+    return h[:elems], bool((h[elems:] == PATTERN).all())
+
+
+def split_status(buf, n):
+    h = buf.cpu().numpy().view(np.uint32)
+    return [int(x) for x in h[:n]], bool((h[n:] == PATTERN32).all())
+
+
+def ptr(t):
+    return None if t is None else P(t.data_ptr())
+
+
+@pytest.fixture(params=[1, 2], ids=["lane", "quad"])
+def walk(request):
+    """the walker's form for the length of a test: 1 = one lane per hash, 2 = a quad per hash"""
+    assert L().h2_selftest_set_poseidon_walk_form(request.param) == H2_OK
+    yield request.param
+    assert L().h2_selftest_set_poseidon_walk_form(0) == H2_OK
+
+
+_CONST, _PAIRS, _TREE = {}, {}, {}
+
+
+def ref_hash(cid, msg, r_f, r_p):
+    key = (cid, r_f, r_p)
+    if key not in _CONST:
+        _CONST[key] = R.poseidon_constants(FIELD[cid], 3, r_f, r_p)
+    rcs, mds = _CONST[key]
+    return R.poseidon_hash_const_len(FIELD[cid], msg, rcs, mds, r_f, r_p)
+
+
+def ref_pairs(cid, r_f, r_p):
+    """257 (leaf, sibling, index bit) with the extremes in front, each on both sides, and the hash pyref gives (once per
+    instance): index bit 1 means H(sibling, leaf)"""
+    key = (cid, r_f, r_p)
+    if key not in _PAIRS:
+        p = FIELD[cid].p
+        rnd = random.Random(0x9A1D + 31 * cid + r_p)
+        special = [(0, 0), (1, 1), (p - 1, p - 1), (0, p - 1), (p - 1, 0), (1, p - 1)]
+        pairs = [s for s in special for _ in (0, 1)] + [(rnd.randrange(p), rnd.randrange(p)) for _ in range(257 - 2 * len(special))]
+        items = [(a, b, i & 1) for i, (a, b) in enumerate(pairs)]
+        _PAIRS[key] = (items, [ref_hash(cid, [b, a] if bit else [a, b], r_f, r_p) for a, b, bit in items])
+    return _PAIRS[key]
+
+
+def device_tree(cid, leaves_np):
+    """the inner nodes of the tree over `leaves_np` (Montgomery limbs) by h2_poseidon_merkle_device, as limbs on the host"""
+    r_f, r_p = SPEC[cid]
+    depth = leaves_np.shape[0].bit_length() - 1
+    d_leaves = dev(leaves_np)
+    d_nodes = red_buffer(leaves_np.shape[0] - 1)
+    assert L().h2_poseidon_merkle_device(cid, r_f, r_p, ptr(d_leaves), depth, ptr(d_nodes), None) == H2_OK
+    nodes, intact = split(d_nodes, leaves_np.shape[0] - 1)
+    assert intact
+    return nodes.copy()
+
+
+def tree(cid, depth):
+    """(leaf ints, leaf limbs, node limbs, the whole tree as ints) of one random tree per (field, depth), built once"""
+    key = (cid, depth)
+    if key not in _TREE:
+        p = FIELD[cid].p
+        rnd = random.Random(0x7EE0 + 64 * cid + depth)
+        leaf_ints = [0, p - 1] + [rnd.randrange(p) for _ in range((1 << depth) - 2)]
+        leaf_limbs = limbs(cid, leaf_ints)
+        nodes = device_tree(cid, leaf_limbs)
+        _TREE[key] = (leaf_ints, leaf_limbs, nodes, leaf_ints + ints(cid, nodes))
+    return _TREE[key]
+
+
+def verify_raw(cid, r_f, r_p, leaf_limbs, indices, path_limbs, depth, root_limbs=None, want_roots=True):
+    """-> (roots limbs or None, statuses); the red zones are checked here"""
+    n = len(indices)
+    d_leaf, d_idx, d_paths = dev(leaf_limbs), dev_u32(indices), dev(path_limbs)
+    d_root = None if root_limbs is None else dev(root_limbs)
+    d_roots = red_buffer(n) if want_roots else None
+    d_status = red_status(n)
+    assert L().h2_poseidon_merkle_verify_device(cid, r_f, r_p, ptr(d_leaf), ptr(d_idx), ptr(d_paths), depth, n, ptr(d_root), ptr(d_roots),
+                                                ptr(d_status), None) == H2_OK
+    status, intact = split_status(d_status, n)
+    assert intact
+    roots = None
+    if want_roots:
+        roots, intact = split(d_roots, n)
+        assert intact
+    return roots, status
+
+
+# ---- the permutation on a quad, in isolation: depth 1 without a root ----------------------------------------------------
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 63, 64, 65, 257])
+@pytest.mark.parametrize("cid,r_f,r_p", [(0, 8, 60), (1, 8, 56), (2, 8, 56), (1, 2, 0), (1, 2, 1), (1, 8, 120)])
+def test_one_hash_per_item_equals_pyref(h2, walk, cid, r_f, r_p, n):
+    items, want = ref_pairs(cid, r_f, r_p)
+    items, want = items[:n], want[:n]             # the extremes are in front: every batch of 15 or more holds them all
+    roots, status = verify_raw(cid, r_f, r_p, limbs(cid, [a for a, _, _ in items]), [bit for _, _, bit in items],
+                               limbs(cid, [b for _, b, _ in items]), 1)
+    assert status == [OK] * n
+    assert ints(cid, roots) == want
+
+
+# ---- paths ---------------------------------------------------------------------------------------------------------------
+def path_indices(depth):
+    if depth <= 3:
+        good = list(range(1 << depth))
+    else:
+        rnd = random.Random(0x1D + depth)
+        good = [0, (1 << depth) - 1] + [rnd.randrange(1 << depth) for _ in range(30)]
+    return good
+
+
+def paths_raw(cid, depth, indices):
+    _, leaf_limbs, nodes, _ = tree(cid, depth)
+    n = len(indices)
+    d_leaves, d_nodes, d_idx = dev(leaf_limbs), dev(nodes), dev_u32(indices)
+    d_paths, d_status = red_buffer(n * depth), red_status(n)
+    assert L().h2_poseidon_merkle_paths_device(cid, ptr(d_leaves), ptr(d_nodes), depth, ptr(d_idx), n, ptr(d_paths), ptr(d_status),
+                                               None) == H2_OK
+    paths, intact = split(d_paths, n * depth)
+    status, intact2 = split_status(d_status, n)
+    assert intact and intact2
+    return paths.copy(), status
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3, 10])
+@pytest.mark.parametrize("cid", [0, 1])
+def test_paths_equal_merkle_path_on_the_copied_tree(h2, cid, depth):
+    from halo2_prover_amd import poseidon
+    good = path_indices(depth)
+    indices = good[:1] + [1 << depth] + good[1:] + [0xFFFFFFFF]
+    paths, status = paths_raw(cid, depth, indices)
+    whole = tree(cid, depth)[3]
+    for j, idx in enumerate(indices):
+        got = paths[j * depth:(j + 1) * depth]
+        if idx >> depth:
+            assert status[j] == RANGE and not got.any(), idx
+        else:
+            assert status[j] == OK and ints(cid, got) == poseidon.merkle_path(whole, depth, idx), idx
+
+
+# ---- verify --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("depth", [1, 2, 3, 10])
+def test_verify_accepts_the_paths_the_device_cut(h2, walk, depth):
+    cid = 1
+    r_f, r_p = SPEC[cid]
+    leaf_ints, leaf_limbs, nodes, whole = tree(cid, depth)
+    indices = path_indices(depth)
+    paths, status = paths_raw(cid, depth, indices)
+    assert status == [OK] * len(indices)
+    roots, status = verify_raw(cid, r_f, r_p, leaf_limbs[indices], indices, paths, depth, nodes[-1])
+    assert status == [OK] * len(indices)
+    assert ints(cid, roots) == [whole[-1]] * len(indices)
+    _, status = verify_raw(cid, r_f, r_p, leaf_limbs[indices], indices, paths, depth, nodes[-1], want_roots=False)   # d_roots_out = NULL
+    assert status == [OK] * len(indices)
+    roots, status = verify_raw(cid, r_f, r_p, leaf_limbs[indices], indices, paths, depth, None)                      # d_root = NULL
+    assert status == [OK] * len(indices) and ints(cid, roots) == [whole[-1]] * len(indices)
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_verify_reports_exactly_the_item_that_is_wrong(h2, walk, cid):
+    depth = 10
+    r_f, r_p = SPEC[cid]
+    p = FIELD[cid].p
+    leaf_ints, leaf_limbs, nodes, whole = tree(cid, depth)
+    indices = path_indices(depth)[:9]
+    paths, _ = paths_raw(cid, depth, indices)
+    n = len(indices)
+    path_ints = ints(cid, paths)
+
+    def run(leaves=None, idx=None, pth=None):
+        return verify_raw(cid, r_f, r_p, leaf_limbs[indices] if leaves is None else leaves, indices if idx is None else idx,
+                          paths if pth is None else pth, depth, nodes[-1])
+
+    def only(j, code):
+        return [code if i == j else OK for i in range(n)]
+
+    for j, level in ((2, 0), (5, depth - 1)):                      # a flipped sibling at the bottom and at the top
+        bad = paths.copy()
+        bad[j * depth + level] = limbs(cid, [(path_ints[j * depth + level] + 1) % p])[0]
+        roots, status = run(pth=bad)
+        assert status == only(j, MISMATCH), (j, level)
+        assert [r == whole[-1] for r in ints(cid, roots)] == [i != j for i in range(n)]
+    for j, bit in ((3, 0), (4, depth - 1)):                        # a wrong index bit
+        idx = list(indices)
+        idx[j] ^= 1 << bit
+        assert run(idx=idx)[1] == only(j, MISMATCH), (j, bit)
+    wrong = leaf_limbs[indices].copy()                             # a wrong leaf
+    wrong[6] = limbs(cid, [(leaf_ints[indices[6]] + 1) % p])[0]
+    assert run(leaves=wrong)[1] == only(6, MISMATCH)
+    idx = list(indices)                                            # indices out of range
+    idx[1], idx[7] = 1 << depth, 0xFFFFFFFF
+    roots, status = run(idx=idx)
+    assert status == [RANGE if i in (1, 7) else OK for i in range(n)]
+    assert not roots[1].any() and not roots[7].any()
+    for value in (p, (1 << 256) - 1):                              # elements that are not canonical: never reduced silently
+        wrong = leaf_limbs[indices].copy()
+        wrong[0] = raw_limbs(value)
+        roots, status = run(leaves=wrong)
+        assert status == only(0, NONCANONICAL) and not roots[0].any(), hex(value)
+        for level in (0, 4, depth - 1):
+            bad = paths.copy()
+            bad[8 * depth + level] = raw_limbs(value)
+            roots, status = run(pth=bad)
+            assert status == only(8, NONCANONICAL) and not roots[8].any(), (hex(value), level)
+
+
+def test_verify_nothing(h2, walk):
+    buf, st = red_buffer(4), red_status(4)
+    assert L().h2_poseidon_merkle_verify_device(1, 8, 56, ptr(buf), ptr(st), ptr(buf), 3, 0, None, ptr(buf), ptr(st), None) == H2_OK
+    assert L().h2_poseidon_merkle_paths_device(1, ptr(buf), ptr(buf), 3, ptr(st), 0, ptr(buf), ptr(st), None) == H2_OK
+    assert (buf.cpu().numpy().view(np.uint64) == PATTERN).all() and (st.cpu().numpy().view(np.uint32) == PATTERN32).all()
+
+
+# ---- update --------------------------------------------------------------------------------------------------------------
+def update_cases(cid, depth):
+    """name -> list of (index, value) with value an int below p, or ('raw', integer) for limbs that are not canonical"""
+    p = FIELD[cid].p
+    width = 1 << depth
+    rnd = random.Random(0x0BDA7E + depth)
+    val = lambda: rnd.randrange(p)                                                   # noqa: E731
+    k = rnd.randrange(width)
+    return {
+        "one leaf": [(k, val())],
+        "both children of one node": [(k & ~1, val()), (k | 1, val())],
+        "all leaves, descending": [(i, val()) for i in reversed(range(width))],
+        "17 random leaves": [(rnd.randrange(width), val()) for _ in range(17)],
+        "one index three times": [(k, val()), (k ^ 1, val()), (k, val()), (k, val())],
+        "a value that is not canonical behind a valid one": [(k, val()), (k, ("raw", p)), ((k + 1) % width, ("raw", (1 << 256) - 1))],
+        "an index out of range": [(width, val()), (k, val()), (0xFFFFFFFF, val())],
+        "nothing": [],
+    }
+
+
+def expected_update(leaf_ints, depth, items):
+    """(new leaves, statuses, touched leaf indices) by the rule: drop status 1 and 2, the last item of an index wins"""
+    new, status, last = list(leaf_ints), [], {}
+    for i, (idx, v) in enumerate(items):
+        if idx >> depth:
+            status.append(RANGE)
+        elif isinstance(v, tuple):
+            status.append(NONCANONICAL)
+        else:
+            status.append(OK)
+            if idx in last:
+                status[last[idx]] = SUPERSEDED
+            last[idx] = i
+            new[idx] = v
+    return new, status, sorted(last)
+
+
+@pytest.mark.parametrize("case", sorted(update_cases(1, 3)))
+@pytest.mark.parametrize("depth", [1, 3, 10])
+def test_update_equals_a_fresh_tree_and_leaves_the_rest_alone(h2, walk, depth, case):
+    cid = 1
+    r_f, r_p = SPEC[cid]
+    leaf_ints, leaf_limbs, nodes, _ = tree(cid, depth)
+    items = update_cases(cid, depth)[case]
+    n, width = len(items), 1 << depth
+    values = np.array([raw_limbs(v[1]) if isinstance(v, tuple) else limbs(cid, [v])[0] for _, v in items], dtype=np.uint64).reshape(-1, 4)
+    d_leaves, d_nodes = red_buffer(width), red_buffer(width - 1)
+    d_leaves[:width] = dev(leaf_limbs)
+    d_nodes[:width - 1] = dev(nodes)
+    d_idx, d_val, d_status = dev_u32([i for i, _ in items] + [0]), dev(np.concatenate([values, np.zeros((1, 4), dtype=np.uint64)])), red_status(n)
+    assert L().h2_poseidon_merkle_update_device(cid, r_f, r_p, ptr(d_leaves), ptr(d_nodes), depth, ptr(d_idx), ptr(d_val), n, ptr(d_status),
+                                                None) == H2_OK
+    new_leaves, want_status, touched = expected_update(leaf_ints, depth, items)
+    status, intact = split_status(d_status, n)
+    assert intact and status == want_status
+    got_leaves, intact = split(d_leaves, width)
+    assert intact and ints(cid, got_leaves) == new_leaves
+    got_nodes, intact = split(d_nodes, width - 1)
+    assert intact
+    assert got_nodes.tobytes() == device_tree(cid, limbs(cid, new_leaves)).tobytes()
+    # nodes off every touched path: the bytes they had
+    base, dirty = 0, set()
+    for l in range(depth):
+        dirty |= {base + (i >> (l + 1)) for i in touched}
+        base += width >> (l + 1)
+    clean = [j for j in range(width - 1) if j not in dirty]
+    assert (got_nodes[clean] == nodes[clean]).all()
+    if not items:
+        assert got_leaves.tobytes() == leaf_limbs.tobytes() and got_nodes.tobytes() == nodes.tobytes()
+    if depth == 3:                                                  # and pyref's tree
+        level, want = new_leaves, []
+        while len(level) > 1:
+            level = [ref_hash(cid, level[2 * i:2 * i + 2], r_f, r_p) for i in range(len(level) // 2)]
+            want += level
+        assert ints(cid, got_nodes) == want
+
+
+def test_update_on_bn254(h2, walk):
+    cid, depth = 0, 10
+    leaf_ints, leaf_limbs, nodes, _ = tree(cid, depth)
+    items = update_cases(cid, depth)["17 random leaves"]
+    d_leaves, d_nodes, d_status = dev(leaf_limbs), dev(nodes), red_status(len(items))
+    assert L().h2_poseidon_merkle_update_device(cid, 8, 60, ptr(d_leaves), ptr(d_nodes), depth, ptr(dev_u32([i for i, _ in items])),
+                                                ptr(dev(limbs(cid, [v for _, v in items]))), len(items), ptr(d_status), None) == H2_OK
+    new_leaves, want_status, _ = expected_update(leaf_ints, depth, items)
+    assert split_status(d_status, len(items)) == (want_status, True)
+    assert d_nodes.cpu().numpy().view(np.uint64).tobytes() == device_tree(cid, limbs(cid, new_leaves)).tobytes()
+
+
+# ---- another stream, through the Python layer --------------------------------------------------------------------------
+def test_update_paths_verify_on_another_stream_without_a_host_synchronisation(h2):
+    import torch
+    from halo2_prover_amd import poseidon
+    cid, depth = 1, 10
+    p = FIELD[cid].p
+    leaf_ints, leaf_limbs, nodes, _ = tree(cid, depth)
+    rnd = random.Random(0x57EA)
+    where = rnd.sample(range(1 << depth), 40)
+    new_values = [rnd.randrange(p) for _ in where]
+    d_leaves, d_nodes = dev(leaf_limbs), dev(nodes)
+    d_idx, d_val = dev_u32(where), dev(limbs(cid, new_values))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        st_update = poseidon.merkle_update(cid, d_leaves, d_nodes, d_idx, d_val)
+        paths, st_paths = poseidon.merkle_paths(cid, d_leaves, d_nodes, d_idx)
+        roots, st_verify = poseidon.verify_paths(cid, d_val, d_idx, paths, root=d_nodes[-1])
+    stream.synchronize()
+    for st in (st_update, st_paths, st_verify):
+        assert st.dtype == torch.int32 and not st.cpu().numpy().any()
+    new_leaves = list(leaf_ints)
+    for i, v in zip(where, new_values):
+        new_leaves[i] = v
+    want_nodes = device_tree(cid, limbs(cid, new_leaves))
+    assert d_nodes.cpu().numpy().view(np.uint64).tobytes() == want_nodes.tobytes()
+    assert (roots.cpu().numpy().view(np.uint64) == want_nodes[-1]).all()
+    # numpy in, numpy out
+    np_paths, np_status = poseidon.merkle_paths(cid, limbs(cid, new_leaves), want_nodes, np.array(where[:3] + [1 << depth], dtype=np.uint32))
+    assert np_paths.dtype == np.uint64 and np_paths.shape == (4, depth, 4) and list(np_status) == [OK, OK, OK, RANGE]
+    np_roots, np_status = poseidon.verify_paths(cid, limbs(cid, new_values[:3]), np.array(where[:3], dtype=np.uint32), np_paths[:3],
+                                                root=want_nodes[-1])
+    assert list(np_status) == [OK] * 3 and (np_roots == want_nodes[-1]).all()
+
+
+def test_empty_batches_through_the_python_layer(h2):
+    """an empty tensor has no address: the Python layer answers n = 0 itself, as the C calls do -- empty results, no error"""
+    import torch
+    from halo2_prover_amd import poseidon
+    cid, depth = 1, 3
+    _, leaf_limbs, nodes, _ = tree(cid, depth)
+    d_leaves, d_nodes = dev(leaf_limbs), dev(nodes)
+    none_idx = torch.empty((0,), dtype=torch.int32, device="cuda")
+    none_val = torch.empty((0, 4), dtype=torch.int64, device="cuda")
+    paths, status = poseidon.merkle_paths(cid, d_leaves, d_nodes, none_idx)
+    assert tuple(paths.shape) == (0, depth, 4) and tuple(status.shape) == (0,)
+    roots, status = poseidon.verify_paths(cid, none_val, none_idx, paths, root=d_nodes[-1])
+    assert tuple(roots.shape) == (0, 4) and tuple(status.shape) == (0,)
+    status = poseidon.merkle_update(cid, d_leaves, d_nodes, none_idx, none_val)
+    assert tuple(status.shape) == (0,)
+    assert d_leaves.cpu().numpy().view(np.uint64).tobytes() == leaf_limbs.tobytes()
+    assert d_nodes.cpu().numpy().view(np.uint64).tobytes() == nodes.tobytes()
+    np_paths, np_status = poseidon.merkle_paths(cid, leaf_limbs, nodes, np.zeros((0,), dtype=np.uint32))
+    assert np_paths.shape == (0, depth, 4) and np_status.shape == (0,)
+
+
+# ---- errors: H2_EINVAL on the host, nothing written ---------------------------------------------------------------------
+def test_invalid_arguments_are_refused_and_nothing_is_written(h2):
+    lib = L()
+    depth = 3
+    leaf_ints, leaf_limbs, nodes, _ = tree(1, depth)
+    d_leaves, d_nodes = red_buffer(8), red_buffer(7)
+    d_leaves[:8] = dev(leaf_limbs)
+    d_nodes[:7] = dev(nodes)
+    d_idx, d_val = dev_u32([1, 2, 3, 4]), dev(limbs(1, [5, 6, 7, 8]))
+    out, st = red_buffer(4 * depth), red_status(4)
+    lv, nd, ix, va, o, s = (t.data_ptr() for t in (d_leaves, d_nodes, d_idx, d_val, out, st))
+    bad_paths = [
+        (3, P(lv), P(nd), depth, P(ix), 4, P(o), P(s)), (1, P(lv), P(nd), 0, P(ix), 4, P(o), P(s)), (1, P(lv), P(nd), 31, P(ix), 4, P(o), P(s)),
+        (1, None, P(nd), depth, P(ix), 4, P(o), P(s)), (1, P(lv), None, depth, P(ix), 4, P(o), P(s)), (1, P(lv), P(nd), depth, None, 4, P(o), P(s)),
+        (1, P(lv), P(nd), depth, P(ix), 4, None, P(s)), (1, P(lv), P(nd), depth, P(ix), 4, P(o), None),
+        (1, P(lv + 8), P(nd), depth, P(ix), 4, P(o), P(s)), (1, P(lv), P(nd), depth, P(ix + 4), 4, P(o), P(s)),
+        (1, P(lv), P(nd), depth, P(ix), 4, P(o + 8), P(s)), (1, P(lv), P(nd), depth, P(ix), 4, P(o), P(s + 4)),
+        (1, P(lv), P(nd), depth, P(ix), (1 << 31) + 1, P(o), P(s)),
+        (1, P(lv), P(nd), depth, P(ix), 4, P(lv + 32), P(s)),          # the paths over the leaves
+        (1, P(lv), P(nd), depth, P(ix), 4, P(o), P(ix)),               # the status over the indices
+        (1, P(lv), P(nd), depth, P(ix), 4, P(o), P(o + 32)),           # two outputs over each other
+    ]
+    for args in bad_paths:
+        assert lib.h2_poseidon_merkle_paths_device(*args, None) == H2_EINVAL, args
+    bad_verify = [
+        (7, 8, 56, P(va), P(ix), P(o), depth, 4, None, P(lv), P(s)), (1, 7, 56, P(va), P(ix), P(o), depth, 4, None, P(lv), P(s)),
+        (1, 0, 56, P(va), P(ix), P(o), depth, 4, None, P(lv), P(s)), (1, 8, 121, P(va), P(ix), P(o), depth, 4, None, P(lv), P(s)),
+        (1, 8, 56, P(va), P(ix), P(o), 0, 4, None, P(lv), P(s)), (1, 8, 56, P(va), P(ix), P(o), 31, 4, None, P(lv), P(s)),
+        (1, 8, 56, None, P(ix), P(o), depth, 4, None, P(lv), P(s)), (1, 8, 56, P(va), None, P(o), depth, 4, None, P(lv), P(s)),
+        (1, 8, 56, P(va), P(ix), None, depth, 4, None, P(lv), P(s)), (1, 8, 56, P(va), P(ix), P(o), depth, 4, None, P(lv), None),
+        (1, 8, 56, P(va + 8), P(ix), P(o), depth, 4, None, P(lv), P(s)), (1, 8, 56, P(va), P(ix), P(o), depth, 4, P(nd + 8), P(lv), P(s)),
+        (1, 8, 56, P(va), P(ix), P(o), depth, 4, None, P(lv + 8), P(s)), (1, 8, 56, P(va), P(ix), P(o), depth, (1 << 31) + 1, None, P(lv), P(s)),
+        (1, 8, 56, P(va), P(ix), P(o), depth, 4, None, P(o + 64), P(s)),      # the roots over the paths
+        (1, 8, 56, P(va), P(ix), P(o), depth, 4, P(lv + 32), P(lv), P(s)),    # the roots over the root
+        (1, 8, 56, P(va), P(ix), P(o), depth, 4, None, P(lv), P(ix)),         # the status over the indices
+    ]
+    for args in bad_verify:
+        assert lib.h2_poseidon_merkle_verify_device(*args, None) == H2_EINVAL, args
+    bad_update = [
+        (3, 8, 56, P(lv), P(nd), depth, P(ix), P(va), 4, P(s)), (1, 9, 56, P(lv), P(nd), depth, P(ix), P(va), 4, P(s)),
+        (1, 8, 56, P(lv), P(nd), 0, P(ix), P(va), 4, P(s)), (1, 8, 56, P(lv), P(nd), 31, P(ix), P(va), 4, P(s)),
+        (1, 8, 56, None, P(nd), depth, P(ix), P(va), 4, P(s)), (1, 8, 56, P(lv), None, depth, P(ix), P(va), 4, P(s)),
+        (1, 8, 56, P(lv), P(nd), depth, None, P(va), 4, P(s)), (1, 8, 56, P(lv), P(nd), depth, P(ix), None, 4, P(s)),
+        (1, 8, 56, P(lv), P(nd), depth, P(ix), P(va), 4, None), (1, 8, 56, P(lv + 8), P(nd), depth, P(ix), P(va), 4, P(s)),
+        (1, 8, 56, P(lv), P(nd), depth, P(ix), P(va + 8), 4, P(s)), (1, 8, 56, P(lv), P(nd), depth, P(ix), P(va), (1 << 31) + 1, P(s)),
+        (1, 8, 56, P(lv), P(lv + 64), depth, P(ix), P(va), 4, P(s)),          # the nodes over the leaves
+        (1, 8, 56, P(lv), P(nd), depth, P(ix), P(lv + 32), 4, P(s)),          # the values inside the leaves
+        (1, 8, 56, P(lv), P(nd), depth, P(ix), P(va), 4, P(ix)),              # the status over the indices
+    ]
+    for args in bad_update:
+        assert lib.h2_poseidon_merkle_update_device(*args, None) == H2_EINVAL, args
+    assert lib.h2_poseidon_merkle_update_device(1, 8, 56, P(lv), P(nd), depth, P(ix), P(va), 0, P(s), None) == H2_OK     # n = 0
+    assert split(out, 4 * depth)[0].tobytes() == np.full((4 * depth, 4), PATTERN, dtype=np.uint64).tobytes() and split(out, 4 * depth)[1]
+    assert (st.cpu().numpy().view(np.uint32) == PATTERN32).all()
+    got_leaves, intact = split(d_leaves, 8)
+    got_nodes, intact2 = split(d_nodes, 7)
+    assert intact and intact2 and got_leaves.tobytes() == leaf_limbs.tobytes() and got_nodes.tobytes() == nodes.tobytes()
+    assert d_idx.cpu().numpy().tolist() == [1, 2, 3, 4] and ints(1, d_val.cpu().numpy().view(np.uint64)) == [5, 6, 7, 8]

@@ -1,7 +1,8 @@
 """Build libh2hip.so in-tree with hipcc for gfx950.
 
 Nine translation units: csrc/h2_curve_impl.hip once per curve (-DH2_CURVE_ID=0/1/2; the kernels), csrc/h2_merkle_impl.hip
-once per curve (the resident Merkle tree's kernels, kept out of the other code objects), csrc/h2_capi.hip (host logic, the C ABI), csrc/h2_selftest.hip (the test hooks of include/h2hip_selftest.h beside it) and
+once per curve (the resident Merkle tree's kernels and the wide Poseidon family's, kept out of the other code objects),
+csrc/h2_capi.hip (host logic, the C ABI), csrc/h2_selftest.hip (the test hooks of include/h2hip_selftest.h beside it) and
 csrc/h2_prover.hip (the product surface: keygen / prove / verify).  They are compiled in parallel and linked into one shared
 library that travels to the GPU box with the repo snapshot.
 """

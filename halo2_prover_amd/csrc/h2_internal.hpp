@@ -75,6 +75,7 @@ struct TwiddleEntry {
 // the constants of one Poseidon instance (h2_poseidon.hpp) in HBM, in the kernels' working form
 struct PoseidonTable {
   int field;
+  uint32_t width;      // 3: h2_poseidon.hpp's table; 5, 9: h2_poseidon_wide.hpp's, dense and sparse part
   uint32_t r_f, r_p;
   void* d;
 };
@@ -144,6 +145,7 @@ struct TestKnobs {
   int gfft_lanes = 0;                            // lanes per butterfly of the group FFT: 0 = by size, 1, 4
   uint32_t poseidon_merkle_tail = 0;             // nodes a Merkle level may have to be finished by the tail launch; 0: the default
   int poseidon_form = 0;                         // the hash kernel's products: 0 = by size, 1 = the compiler's form, 2 = single-chain
+  int poseidon_wide_form = 0;                    // the wide permutation kernel's partial rounds: 0 = the width's own, 1 = dense, 2 = sparse
   int poseidon_walk_form = 0;                    // the Merkle walker and update: 0 = by size, 1 = a lane per hash, 2 = a quad per hash
 };
 struct TestCounters {
@@ -177,6 +179,11 @@ size_t ctx_index(const DevCtx* c);
 
 // hipMalloc of the buffer named `what`: H2_ENOMEM (sticky error cleared, last_error set, *p = null) if it fails
 int device_alloc(void** p, size_t bytes, const char* what);
+// The wide Poseidon table of (curve, width 5 | 9, r_f, r_p) as Montgomery limbs (host): the dense part, h2_poseidon_wide_
+// constants' elements, and with `sparse` the sparse part behind it (h2_poseidon_wide.hpp: poseidon_wide_table_elems in all).
+// ConstantLength<len>'s capacity word len 2^64.  False when the partial rounds do not factor (h2_poseidon_host.hpp)
+bool poseidon_wide_table_mont(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, bool sparse, uint64_t* out);
+void poseidon_capacity_mont(int curve, uint64_t len, uint64_t out[4]);
 // scratch device memory owned by one call: freed on every way out of it
 struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
 using DeviceBuffer = std::unique_ptr<void, HipFree>;

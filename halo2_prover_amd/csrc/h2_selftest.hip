@@ -5,6 +5,7 @@
 #include "h2_field29_chain.hpp"
 #include "h2_host.hpp"
 #include "h2_poseidon.hpp"
+#include "h2_poseidon_wide.hpp"
 
 #include <cstdio>
 #include <vector>
@@ -397,6 +398,46 @@ extern "C" int h2_selftest_poseidon(int curve, uint32_t r_f, uint32_t r_p, int o
   else if (curve == H2_PALLAS) HF<PALLAS_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
   else HF<VESTA_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
   return ops->selftest_poseidon(op, r_f, r_p, table.data(), cap2, in, out) == 0 ? H2_OK : H2_EINVAL;
+}
+// ---- the wide family (h2_poseidon_wide.hpp) ----------------------------------------------------------------------------
+namespace {
+const PoseidonWideOps* wide_ops_of(int curve) {
+  return curve == H2_BN254 ? poseidon_wide_ops_bn254() : curve == H2_PALLAS ? poseidon_wide_ops_pallas() : poseidon_wide_ops_vesta();
+}
+}  // namespace
+// host only: the table as the kernels read it (before the change to the working form)
+extern "C" int h2_selftest_poseidon_wide_table(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
+                                               size_t* n_elems) {
+  size_t dense = 0;
+  if (!n_elems || (width != 5 && width != 9) ||
+      h2_poseidon_wide_constants((h2_curve_t)curve, width, r_f, r_p, nullptr, 0, &dense) != H2_EINVAL || dense == 0)
+    return H2_EINVAL;
+  const size_t need = poseidon_wide_table_elems(width, r_f, r_p);
+  *n_elems = need;
+  if (!out || cap_elems < need) return H2_EINVAL;
+  return poseidon_wide_table_mont(curve, width, r_f, r_p, true, out) ? H2_OK : H2_EINVAL;
+}
+// host only: the kernels' permutation and sponge templates instantiated on the host
+extern "C" int h2_selftest_poseidon_wide(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, int form, int op, uint32_t len,
+                                         const uint64_t* in, uint64_t* out) {
+  const CurveOps* ops = ops_of(curve);
+  if (!ops || !in || !out || op < 0 || op > 1 || (op == 1 && (len == 0 || len > 65535))) return H2_EINVAL;
+  size_t elems = 0;
+  if (h2_selftest_poseidon_wide_table(curve, width, r_f, r_p, nullptr, 0, &elems) != H2_EINVAL || elems == 0) return H2_EINVAL;
+  std::vector<uint64_t> api(4 * elems);
+  if (int rc = h2_selftest_poseidon_wide_table(curve, width, r_f, r_p, api.data(), elems, &elems); rc != H2_OK) return rc;
+  std::vector<int32_t> table(9 * elems);
+  ops->poseidon_table(api.data(), elems, table.data());
+  uint64_t cap[4];
+  poseidon_capacity_mont(curve, len, cap);
+  return wide_ops_of(curve)->selftest(width, form, op, len, r_f, r_p, table.data(), cap, in, out) == 0 ? H2_OK : H2_EINVAL;
+}
+// tests and tools only: the partial rounds of h2_poseidon_wide_permute_device's kernel (0: the width's own form, 1: dense, 2: sparse)
+extern "C" int h2_selftest_set_poseidon_wide_form(int form) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (form < 0 || form > 2) return H2_EINVAL;
+  g_knobs.poseidon_wide_form = form;
+  return H2_OK;
 }
 // tests and tools only: the widest Merkle level the tail launch takes (a power of two up to POSEIDON_MERKLE_TAIL_MAX; 0
 // restores the default), and the product form of the hash kernel (0: by size, 1: the compiler's, 2: single-chain where the

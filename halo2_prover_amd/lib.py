@@ -110,6 +110,12 @@ SYMBOLS = {
     "h2_poseidon_merkle_paths_device": (_I, [_I, _P, _P, _U32, _P, _Z, _P, _P, _P]),
     "h2_poseidon_merkle_verify_device": (_I, [_I, _U32, _U32, _P, _P, _P, _U32, _Z, _P, _P, _P, _P]),
     "h2_poseidon_merkle_update_device": (_I, [_I, _U32, _U32, _P, _P, _U32, _P, _P, _Z, _P, _P]),
+    "h2_poseidon_wide_constants": (_I, [_I, _U32, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
+    "h2_poseidon_wide_permute_device": (_I, [_I, _U32, _U32, _U32, _P, _P, _Z, _P]),
+    "h2_poseidon_wide_hash_device": (_I, [_I, _U32, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),
+    "h2_poseidon_wide_merkle_device": (_I, [_I, _U32, _U32, _U32, _P, _U32, _P, _P]),
+    "h2_poseidon_wide_merkle_paths_device": (_I, [_I, _U32, _P, _P, _U32, _P, _Z, _P, _P, _P]),
+    "h2_poseidon_wide_merkle_verify_device": (_I, [_I, _U32, _U32, _U32, _P, _P, _P, _U32, _Z, _P, _P, _P, _P]),
     "h2_lookup_permute_device": (_I, [_I, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_product_device": (_I, [_I, _P, _P, _P, _P, _Z, _Z, _Z, _P, _P, _P, _P]),
     "h2_lookup_tile": (_I, []),
@@ -179,6 +185,9 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_set_poseidon_form": (_I, [_I]),
     "h2_selftest_set_poseidon_walk_form": (_I, [_I]),
     "h2_selftest_set_poseidon_verify_min": (_I, [_Z]),
+    "h2_selftest_poseidon_wide_table": (_I, [_I, _U32, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
+    "h2_selftest_poseidon_wide": (_I, [_I, _U32, _U32, _U32, _I, _I, _U32, _P, _P]),
+    "h2_selftest_set_poseidon_wide_form": (_I, [_I]),
 }
 
 # the RNG callback of the product surface: void (*)(void* ctx, uint8_t* out, size_t n)

@@ -522,6 +522,63 @@ int h2_poseidon_merkle_verify_device(h2_curve_t curve, uint32_t r_f, uint32_t r_
 int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, void* d_leaves, void* d_nodes,
                                      uint32_t depth, const void* d_indices, const void* d_values /* n */, size_t n,
                                      void* d_status /* n */, void* stream);
+/* ---- Poseidon at widths 3, 5 and 9: 4-ary and 8-ary hashes and Merkle trees ---------------------------------------
+ * The same primitive (primitives.rs's Spec<F, T, RATE>) with the width as an argument: `width` = 3, 5 or 9, rate = width - 1
+ * = 2, 4 or 8, S-box x^5, constants from the same Grain / Cauchy-MDS generation with t = width, over the scalar field of
+ * `curve` (all three curves).  Width 3 is the family above, bit for bit (the calls hand it on); widths 5 and 9 are the two
+ * the Poseidon paper proposes for Merkle trees of arity a = width - 1 = 4 and 8.  The caller supplies (r_f, r_p) under the
+ * rules above; the library picks none.  The Poseidon paper's parameter script gives (8, 60) at t = 5 and (8, 63) at t = 9
+ * for 128-bit security with x^5 on fields of about 255 bits -- NOT checked here: choosing round numbers is the caller's.
+ * Elements are 4 x u64 Montgomery limbs, canonical; indices and status words are uint32_t, the status words H2_MERKLE_*.
+ *   h2_poseidon_wide_constants            host only, no device and no h2_init needed: (r_f + r_p) * width round constants,
+ *                                         then the width x width MDS row-major.  *n_elems = the elements that takes, also
+ *                                         when cap_elems is too small.  At width 3: h2_poseidon_constants' elements.
+ *   h2_poseidon_wide_permute_device       n states of `width` elements -> n states; d_out may be d_in exactly, otherwise
+ *                                         the two must not overlap.
+ *   h2_poseidon_wide_hash_device          ConstantLength<len> at rate width - 1: n messages of len elements, msg_stride
+ *                                         elements apart, -> n elements.  The state starts as (0, .., 0, len 2^64), the
+ *                                         capacity word LAST; `rate` words are absorbed per permutation, zero-padded; the
+ *                                         output is word 0.
+ *   h2_poseidon_wide_merkle_device        a^depth leaves -> the (a^depth - 1) / (a - 1) inner nodes, level by level from
+ *                                         the leaves' parents up, the root last; a node is ConstantLength<a> of its a
+ *                                         children in order.  Levels of more than h2_poseidon_merkle_tail() nodes take one
+ *                                         launch each, all the levels above them one launch of a single workgroup.
+ *   h2_poseidon_wide_merkle_paths_device  a gather, no hashing.  A path is depth * (a - 1) elements: at level l the a - 1
+ *                                         siblings of the leaf's ancestor in child order, the ancestor's own position
+ *                                         ((index / a^l) mod a) left out.  An index >= a^depth gives status 1 and an
+ *                                         all-zero path.
+ *   h2_poseidon_wide_merkle_verify_device cur = d_leaf_values[i]; at every level cur is inserted at its position among the
+ *                                         level's siblings and the a words are hashed.  d_roots_out[i] (optional) = the
+ *                                         computed root.  The rules of h2_poseidon_merkle_verify_device: untrusted data; an
+ *                                         element that is not canonical is never reduced silently -- status 2 and a zero
+ *                                         root, as an index out of range (status 1); another root than *d_root is status 4;
+ *                                         the first that applies of 1, 2, 4 is reported; d_root = NULL drops the comparison.
+ *                                         One path runs on one lane.
+ * There is no in-place update of a wide tree and no form with several lanes per permutation.
+ * Asynchronous on `stream` under h2_ntt_device's rules, on the context of the calling thread's current HIP device; the first
+ * use of a (curve, width, r_f, r_p) on a context builds and uploads its table and waits for that (the eight tables used last
+ * are kept; a width-3 table is shared with the family above).  H2_EINVAL -- checked on the host before anything is enqueued
+ * -- for: an unknown curve; a width other than 3, 5, 9; r_f odd or 0, or r_f + r_p > H2_POSEIDON_MAX_ROUNDS; a null or not
+ * 16-byte aligned device pointer (d_root and d_roots_out may be null, not misaligned); len = 0 or len > 65535; msg_stride
+ * < len or > 2^32; n > 2^40 (permute, hash) or 2^31 (paths, verify); depth = 0 or a^depth > 2^30; a range that is written
+ * overlapping one that is read or another that is written (other than d_out == d_in of the permutation).  n = 0 is H2_OK
+ * and enqueues nothing.  H2_ENOTINIT before h2_init.  h2_version() is unchanged: a host detects these entry points by their
+ * symbols. */
+int h2_poseidon_wide_constants(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
+                               size_t* n_elems);
+int h2_poseidon_wide_permute_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out,
+                                    size_t n, void* stream);
+int h2_poseidon_wide_hash_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len,
+                                 size_t msg_stride, size_t n, void* d_out, void* stream);
+int h2_poseidon_wide_merkle_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_leaves,
+                                   uint32_t depth, void* d_nodes, void* stream);
+int h2_poseidon_wide_merkle_paths_device(h2_curve_t curve, uint32_t width, const void* d_leaves, const void* d_nodes,
+                                         uint32_t depth, const void* d_indices, size_t n,
+                                         void* d_paths /* n*depth*(width-2) */, void* d_status /* n */, void* stream);
+int h2_poseidon_wide_merkle_verify_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p,
+                                          const void* d_leaf_values /* n */, const void* d_indices, const void* d_paths,
+                                          uint32_t depth, size_t n, const void* d_root /* 1 element or NULL */,
+                                          void* d_roots_out /* n or NULL */, void* d_status /* n */, void* stream);
 /* ---- the lookup argument's permute and product steps over resident columns -----------------------------------
  * m lookups per call (those of one proof or of a batch).  Every column array holds m columns, col_stride elements apart,
  * over the scalar field of `curve` (all three curves), in the API form: 4 x u64 Montgomery limbs, canonical.  The ORDER

@@ -194,6 +194,25 @@ int h2_selftest_set_poseidon_form(int form);
  * h2_poseidon_merkle_update_device: 1 = one lane per hash at every size, 2 = the four lanes of a quad per hash at every
  * size, 0 = by size (the default).  The results are the same bits either way.  H2_EINVAL for another value. */
 int h2_selftest_set_poseidon_walk_form(int form);
+/* The wide Poseidon family (h2_poseidon_wide_*; csrc/h2_poseidon_wide.hpp), widths 5 and 9.
+ * h2_selftest_poseidon_wide_table: host only, no GPU and no h2_init -- the whole table the kernels read, as 4 x u64
+ *   Montgomery limbs: h2_poseidon_wide_constants' (r_f + r_p) * width + width^2 elements, then the SPARSE form of the partial
+ *   rounds: the width x width pre-matrix (row-major) that the last full round in front of them takes in place of the MDS;
+ *   the `width` constants added to the state in front of partial round 0 (element 0 of them is round 0's `a`); per partial
+ *   round 2 * width + 1 elements (a, b, m00, vhat[1 .. width - 1], w[1 .. width - 1]) for
+ *       z = (s_0 + a)^5 + b;   s_0 <- m00 z + sum_j vhat_j s_j;   s_j <- s_j + w_j z   (j >= 1, the old s_j in the sum);
+ *   and the field's one.  *n_elems as h2_poseidon_wide_constants reports it.  H2_EINVAL for a width other than 5 or 9 and
+ *   for what h2_poseidon_wide_constants refuses.
+ * h2_selftest_poseidon_wide: host only -- the kernels' templates instantiated on the host over that table.  op 0: in = one
+ *   state of `width` elements -> out = the permuted state (len ignored); op 1: in = len elements -> out = their
+ *   ConstantLength<len> hash.  form 0 = the width's own partial rounds, 1 = dense, 2 = sparse (op 1: the width's own only).
+ * h2_selftest_set_poseidon_wide_form: tests and tools only -- the partial rounds of h2_poseidon_wide_permute_device's kernel,
+ *   form as above; the results are the same bits.  Every other wide launch runs the width's own form. */
+int h2_selftest_poseidon_wide_table(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
+                                    size_t* n_elems);
+int h2_selftest_poseidon_wide(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, int form, int op, uint32_t len,
+                              const uint64_t* in, uint64_t* out);
+int h2_selftest_set_poseidon_wide_form(int form);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Build libh2hip.so in-tree with hipcc for gfx950.
 
-Nine translation units: csrc/h2_curve_impl.hip once per curve (-DH2_CURVE_ID=0/1/2; the kernels), csrc/h2_merkle_impl.hip
-once per curve (the resident Merkle tree's kernels and the wide Poseidon family's, kept out of the other code objects),
+Nine translation units: csrc/h2_curve_impl.hip once per curve (-DH2_CURVE_ID=0/1/2; the kernels), csrc/h2_poseidon_impl.hip
+once per curve (the Poseidon family's kernels at every width and its Merkle trees', kept out of the other code objects),
 csrc/h2_capi.hip (host logic, the C ABI), csrc/h2_selftest.hip (the test hooks of include/h2hip_selftest.h beside it) and
 csrc/h2_prover.hip (the product surface: keygen / prove / verify).  They are compiled in parallel and linked into one shared
 library that travels to the GPU box with the repo snapshot.
@@ -42,9 +42,9 @@ def build(force=False, verbose=False, extra_flags=()):
         jobs.append(([hipcc] + FLAGS + list(extra_flags) + ["-DH2_CURVE_ID=%d" % cid, "-c",
                      os.path.join(CSRC, "h2_curve_impl.hip"), "-o", obj], obj))
     for cid, name in ((0, "bn254"), (1, "pallas"), (2, "vesta")):
-        obj = os.path.join(OBJ, "merkle_%s.o" % name)
+        obj = os.path.join(OBJ, "poseidon_%s.o" % name)
         jobs.append(([hipcc] + FLAGS + list(extra_flags) + ["-DH2_CURVE_ID=%d" % cid, "-c",
-                     os.path.join(CSRC, "h2_merkle_impl.hip"), "-o", obj], obj))
+                     os.path.join(CSRC, "h2_poseidon_impl.hip"), "-o", obj], obj))
     for name in ("capi", "selftest", "prover"):
         obj = os.path.join(OBJ, name + ".o")
         jobs.append(([hipcc] + FLAGS + list(extra_flags) + ["-c", os.path.join(CSRC, "h2_%s.hip" % name), "-o", obj], obj))

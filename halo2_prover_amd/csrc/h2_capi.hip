@@ -20,13 +20,11 @@
 #include "h2_ipa.hpp"
 #include "h2_ipa_verify.hpp"
 #include "h2_lookup.hpp"
-#include "h2_merkle_ops.hpp"
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
 #include "h2_poly.hpp"
 #include "h2_poseidon.hpp"
 #include "h2_poseidon_host.hpp"
-#include "h2_poseidon_wide.hpp"
 
 using namespace h2;
 
@@ -53,6 +51,9 @@ const CurveOps* ops_of(int curve) {
     case H2_VESTA: return curve_ops_vesta();
   }
   return nullptr;
+}
+const PoseidonOps* poseidon_ops_of(int curve) {
+  return curve == H2_BN254 ? poseidon_ops_bn254() : curve == H2_PALLAS ? poseidon_ops_pallas() : poseidon_ops_vesta();
 }
 
 DevCtx* ctx_current() {
@@ -825,25 +826,16 @@ constexpr size_t POSEIDON_TABLE_SLOTS = 8;
 bool poseidon_rounds_ok(uint32_t r_f, uint32_t r_p) {
   return r_f >= 2 && !(r_f & 1) && r_f <= POSEIDON_MAX_ROUNDS && r_p <= POSEIDON_MAX_ROUNDS && r_f + r_p <= POSEIDON_MAX_ROUNDS;
 }
-// (r_f + r_p) * 3 round constants, then the MDS row-major, as Montgomery limbs
-template <class FP>
-void poseidon_constants_t(uint32_t r_f, uint32_t r_p, uint64_t* out) {
-  const poseidon::Constants<FP> k = poseidon::generate<FP>((int)r_f, (int)r_p);
-  for (auto& row : k.rcs)
-    for (int i = 0; i < 3; i++, out += 4) row[i].mont_limbs(out);
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++, out += 4) k.mds[i][j].mont_limbs(out);
-}
 // ConstantLength<len>'s capacity word len 2^64 as Montgomery limbs
 template <class FP>
 void poseidon_capacity_t(uint64_t len, uint64_t out[4]) {
   const HF<FP> two32 = HF<FP>::from_u64(1ull << 32);
   (HF<FP>::from_u64(len) * two32 * two32).mont_limbs(out);
 }
-// the wide family's widths (h2_poseidon_wide.hpp); width 3 goes to the calls above
 bool poseidon_width_ok(uint32_t width) { return width == 3 || width == 5 || width == 9; }
 // (r_f + r_p) * width round constants, then the width x width MDS row-major, as Montgomery limbs; with `sparse` the sparse
-// part of the kernels' table behind them (poseidon_wide_table_elems in all).  False when the partial rounds do not factor
+// part of the kernels' table behind them (poseidon_table_elems in all; widths 5 and 9).  False when the partial rounds do
+// not factor
 template <class FP>
 bool poseidon_wide_constants_t(uint32_t width, uint32_t r_f, uint32_t r_p, bool sparse, uint64_t* out) {
   const poseidon::WideConstants<FP> k = poseidon::generate_wide<FP>((int)width, (int)r_f, (int)r_p);
@@ -873,16 +865,14 @@ int poseidon_table_get(DevCtx& c, int curve, uint32_t width, uint32_t r_f, uint3
     (void)hipFree(c.poseidon_tables.front().d);
     c.poseidon_tables.erase(c.poseidon_tables.begin());
   }
-  const size_t elems = width == 3 ? poseidon_table_elems(r_f, r_p) : poseidon_wide_table_elems(width, r_f, r_p);
+  const size_t elems = poseidon_table_elems(width, r_f, r_p);
   std::vector<uint64_t> api(4 * elems);
-  if (width == 3) {
-    H2_BY_SCALAR_FIELD(curve, poseidon_constants_t)(r_f, r_p, api.data());
-  } else if (!H2_BY_SCALAR_FIELD(curve, poseidon_wide_constants_t)(width, r_f, r_p, true, api.data())) {
+  if (!H2_BY_SCALAR_FIELD(curve, poseidon_wide_constants_t)(width, r_f, r_p, width != 3, api.data())) {
     g_h2.last_error = "poseidon: the partial rounds of this instance do not factor";
     return H2_EINVAL;
   }
   std::vector<int32_t> table(9 * elems);
-  ops->poseidon_table(api.data(), elems, table.data());
+  poseidon_ops_of(curve)->table(api.data(), elems, table.data());
   PoseidonTable te{ops->scalar_field_id, width, r_f, r_p, nullptr};
   if (int rc = device_alloc(&te.d, table.size() * 4, "poseidon table"); rc != H2_OK) return rc;
   DeviceBuffer owner(te.d);      // until the table is in the cache
@@ -2247,80 +2237,17 @@ int h2_ipa_verify_proofs(h2_curve_t curve, uint64_t bases, uint32_t k_, size_t c
   }
 }
 
-// ---- Poseidon over resident columns (h2_poseidon.hpp) --------------------------------------------------------------------
+// ---- Poseidon over resident columns (h2_poseidon.hpp, h2_poseidon_merkle.hpp) -----------------------------------------------
+// One body per operation, the width an argument: the h2_poseidon_X names are the h2_poseidon_wide_X calls at width 3.
 static_assert(H2_POSEIDON_MAX_ROUNDS == POSEIDON_MAX_ROUNDS, "the header states the kernels' maximum");
-
-int h2_poseidon_constants(h2_curve_t curve, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems, size_t* n_elems) {
-  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !n_elems) return H2_EINVAL;
-  const size_t need = poseidon_table_elems(r_f, r_p);
-  *n_elems = need;
-  if (!out || cap_elems < need) return H2_EINVAL;
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_constants_t)(r_f, r_p, out);
-  return H2_OK;
-}
-
-int h2_poseidon_merkle_tail(void) { return (int)(g_knobs.poseidon_merkle_tail ? g_knobs.poseidon_merkle_tail : POSEIDON_MERKLE_TAIL); }
-
-int h2_poseidon_permute_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_in) || !poseidon_dev_ptr(d_out) ||
-      n > ((size_t)1 << 40))
-    return H2_EINVAL;
-  if (d_out != d_in && poseidon_overlap(d_in, 96 * n, d_out, 96 * n)) return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, 3, r_f, r_p, &table); rc != H2_OK) return rc;
-  return launched(ops_of((int)curve)->poseidon_permute(d_in, d_out, n, table, r_f, r_p, k.stream), "poseidon_permute_kernel");
-}
-
-int h2_poseidon_hash_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len, size_t msg_stride, size_t n,
-                            void* d_out, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_msgs) || !poseidon_dev_ptr(d_out) || len == 0 ||
-      len > 65535 || msg_stride < len || msg_stride > ((size_t)1 << 32) || n > ((size_t)1 << 40))
-    return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  if (poseidon_overlap(d_msgs, 32 * ((n - 1) * msg_stride + len), d_out, 32 * n)) return H2_EINVAL;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, 3, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(len, cap);
-  return launched(ops_of((int)curve)->poseidon_hash(d_msgs, (uint32_t)len, msg_stride, n, d_out, cap, table, r_f, r_p,
-                                                    poseidon_chain_min_n(), k.stream),
-                  "poseidon_hash_kernel");
-}
-
-int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth, void* d_nodes,
-                              void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || depth == 0 ||
-      depth > 30)
-    return H2_EINVAL;
-  const size_t leaves = (size_t)1 << depth;
-  if (poseidon_overlap(d_leaves, 32 * leaves, d_nodes, 32 * (leaves - 1))) return H2_EINVAL;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, 3, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap2[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(2, cap2);
-  return launched(ops_of((int)curve)->poseidon_merkle(d_leaves, depth, d_nodes, cap2, table, r_f, r_p, (uint32_t)h2_poseidon_merkle_tail(),
-                                                      poseidon_chain_min_n(), k.stream),
-                  "poseidon_merkle kernels");
-}
-
-// ---- a resident Merkle tree: paths, verification, update (h2_merkle_ops.hpp) --------------------------------------------
 static_assert(H2_MERKLE_OK == MERKLE_OK && H2_MERKLE_RANGE == MERKLE_RANGE && H2_MERKLE_NONCANONICAL == MERKLE_NONCANONICAL &&
                   H2_MERKLE_SUPERSEDED == MERKLE_SUPERSEDED && H2_MERKLE_MISMATCH == MERKLE_MISMATCH,
               "the header states the kernels' status words");
 namespace {
-// hashes below which a launch runs one permutation on four lanes, unless a test knob fixes the form
+// hashes below which a width-3 launch runs one permutation on four lanes, unless a test knob fixes the form
 size_t poseidon_walk_quad_max() { return g_knobs.poseidon_walk_form == 1 ? 0 : g_knobs.poseidon_walk_form == 2 ? SIZE_MAX : POSEIDON_WALK_QUAD_MAX; }
-const MerkleOps* merkle_ops_of(int curve) { return curve == H2_BN254 ? merkle_ops_bn254() : curve == H2_PALLAS ? merkle_ops_pallas() : merkle_ops_vesta(); }
-bool merkle_args_ok(h2_curve_t curve, uint32_t depth, size_t n) {
-  return curve_ok((int)curve) && depth >= 1 && depth <= 30 && n <= ((size_t)1 << 31);
-}
+// depth >= 1 and a^depth <= 2^30
+bool poseidon_depth_ok(uint32_t width, uint32_t depth) { return depth >= 1 && depth <= 30 / merkle_lg(width); }
 struct Span {
   const void* p;
   size_t bytes;
@@ -2338,56 +2265,149 @@ bool merkle_overlap(std::initializer_list<Span> outs, std::initializer_list<Span
 }
 }  // namespace
 
-int h2_poseidon_merkle_paths_device(h2_curve_t curve, const void* d_leaves, const void* d_nodes, uint32_t depth, const void* d_indices,
-                                    size_t n, void* d_paths, void* d_status, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!merkle_args_ok(curve, depth, n) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || !poseidon_dev_ptr(d_indices) ||
-      !poseidon_dev_ptr(d_paths) || !poseidon_dev_ptr(d_status))
-    return H2_EINVAL;
-  const size_t leaves = (size_t)1 << depth;
-  const Span paths{d_paths, 32 * n * depth}, status{d_status, 4 * n};
-  if (merkle_overlap({paths, status}, {Span{d_leaves, 32 * leaves}, Span{d_nodes, 32 * (leaves - 1)}, Span{d_indices, 4 * n}}))
-    return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  return launched(merkle_ops_of((int)curve)->paths(d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, k.stream),
-                  "poseidon_merkle_paths_kernel");
+int h2_poseidon_merkle_tail(void) { return (int)(g_knobs.poseidon_merkle_tail ? g_knobs.poseidon_merkle_tail : POSEIDON_MERKLE_TAIL); }
+
+int h2_poseidon_wide_constants(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
+                               size_t* n_elems) {
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !n_elems) return H2_EINVAL;
+  const size_t need = poseidon_dense_elems(width, r_f, r_p);
+  *n_elems = need;
+  if (!out || cap_elems < need) return H2_EINVAL;
+  (void)poseidon_wide_table_mont((int)curve, width, r_f, r_p, false, out);
+  return H2_OK;
+}
+int h2_poseidon_constants(h2_curve_t curve, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems, size_t* n_elems) {
+  return h2_poseidon_wide_constants(curve, 3, r_f, r_p, out, cap_elems, n_elems);
 }
 
-int h2_poseidon_merkle_verify_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaf_values, const void* d_indices,
-                                     const void* d_paths, uint32_t depth, size_t n, const void* d_root, void* d_roots_out, void* d_status,
-                                     void* stream_) {
+int h2_poseidon_wide_permute_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n,
+                                    void* stream_) {
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
-  if (!merkle_args_ok(curve, depth, n) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaf_values) || !poseidon_dev_ptr(d_indices) ||
-      !poseidon_dev_ptr(d_paths) || !poseidon_dev_ptr(d_status) || ((uintptr_t)d_root & 15) || ((uintptr_t)d_roots_out & 15))
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_in) ||
+      !poseidon_dev_ptr(d_out) || n > ((size_t)1 << 40))
+    return H2_EINVAL;
+  if (d_out != d_in && poseidon_overlap(d_in, 32 * width * n, d_out, 32 * width * n)) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
+  // the partial rounds: the width's own form, unless a test knob fixes it (1: dense, 2: sparse)
+  return launched(poseidon_ops_of((int)curve)->permute(width, g_knobs.poseidon_wide_form, d_in, d_out, n, table, r_f, r_p, k.stream),
+                  "poseidon_permute_kernel");
+}
+int h2_poseidon_permute_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n, void* stream_) {
+  return h2_poseidon_wide_permute_device(curve, 3, r_f, r_p, d_in, d_out, n, stream_);
+}
+
+int h2_poseidon_wide_hash_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len,
+                                 size_t msg_stride, size_t n, void* d_out, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_msgs) ||
+      !poseidon_dev_ptr(d_out) || len == 0 || len > 65535 || msg_stride < len || msg_stride > ((size_t)1 << 32) || n > ((size_t)1 << 40))
+    return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  if (poseidon_overlap(d_msgs, 32 * ((n - 1) * msg_stride + len), d_out, 32 * n)) return H2_EINVAL;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(len, cap);
+  return launched(poseidon_ops_of((int)curve)->hash(width, d_msgs, (uint32_t)len, msg_stride, n, d_out, cap, table, r_f, r_p,
+                                                    poseidon_chain_min_n(), k.stream),
+                  "poseidon_hash_kernel");
+}
+int h2_poseidon_hash_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len, size_t msg_stride, size_t n,
+                            void* d_out, void* stream_) {
+  return h2_poseidon_wide_hash_device(curve, 3, r_f, r_p, d_msgs, len, msg_stride, n, d_out, stream_);
+}
+
+int h2_poseidon_wide_merkle_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth,
+                                   void* d_nodes, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) ||
+      !poseidon_dev_ptr(d_nodes) || !poseidon_depth_ok(width, depth))
+    return H2_EINVAL;
+  const uint32_t lg = merkle_lg(width);
+  const size_t leaves = merkle_pow(lg, depth), nodes = merkle_level_offset(lg, depth, depth);
+  if (poseidon_overlap(d_leaves, 32 * leaves, d_nodes, 32 * nodes)) return H2_EINVAL;
+  const void* table = nullptr;
+  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(width - 1, cap);
+  return launched(poseidon_ops_of((int)curve)->merkle(width, d_leaves, depth, d_nodes, cap, table, r_f, r_p,
+                                                      (uint32_t)h2_poseidon_merkle_tail(), poseidon_chain_min_n(), k.stream),
+                  "poseidon_merkle kernels");
+}
+int h2_poseidon_merkle_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth, void* d_nodes,
+                              void* stream_) {
+  return h2_poseidon_wide_merkle_device(curve, 3, r_f, r_p, d_leaves, depth, d_nodes, stream_);
+}
+
+int h2_poseidon_wide_merkle_paths_device(h2_curve_t curve, uint32_t width, const void* d_leaves, const void* d_nodes, uint32_t depth,
+                                         const void* d_indices, size_t n, void* d_paths, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_depth_ok(width, depth) || n > ((size_t)1 << 31) ||
+      !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_paths) ||
+      !poseidon_dev_ptr(d_status))
+    return H2_EINVAL;
+  const uint32_t lg = merkle_lg(width);
+  const size_t leaves = merkle_pow(lg, depth), nodes = merkle_level_offset(lg, depth, depth);
+  const Span paths{d_paths, 32 * n * depth * (width - 2)}, status{d_status, 4 * n};
+  if (merkle_overlap({paths, status}, {Span{d_leaves, 32 * leaves}, Span{d_nodes, 32 * nodes}, Span{d_indices, 4 * n}})) return H2_EINVAL;
+  if (n == 0) return H2_OK;
+  return launched(poseidon_ops_of((int)curve)->paths(width, d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, k.stream),
+                  "poseidon_merkle_paths_kernel");
+}
+int h2_poseidon_merkle_paths_device(h2_curve_t curve, const void* d_leaves, const void* d_nodes, uint32_t depth, const void* d_indices,
+                                    size_t n, void* d_paths, void* d_status, void* stream_) {
+  return h2_poseidon_wide_merkle_paths_device(curve, 3, d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, stream_);
+}
+
+int h2_poseidon_wide_merkle_verify_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_leaf_values,
+                                          const void* d_indices, const void* d_paths, uint32_t depth, size_t n, const void* d_root,
+                                          void* d_roots_out, void* d_status, void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_depth_ok(width, depth) || n > ((size_t)1 << 31) ||
+      !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaf_values) || !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_paths) ||
+      !poseidon_dev_ptr(d_status) || ((uintptr_t)d_root & 15) || ((uintptr_t)d_roots_out & 15))
     return H2_EINVAL;
   const Span roots{d_roots_out, 32 * n}, status{d_status, 4 * n};
-  if (merkle_overlap({roots, status}, {Span{d_leaf_values, 32 * n}, Span{d_indices, 4 * n}, Span{d_paths, 32 * n * depth},
-                                       Span{d_root, 32}}))
+  if (merkle_overlap({roots, status}, {Span{d_leaf_values, 32 * n}, Span{d_indices, 4 * n},
+                                       Span{d_paths, 32 * n * depth * (width - 2)}, Span{d_root, 32}}))
     return H2_EINVAL;
   if (n == 0) return H2_OK;
   const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, 3, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap2[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(2, cap2);
-  return launched(merkle_ops_of((int)curve)->verify(d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out, d_status, cap2,
-                                                    table, r_f, r_p, poseidon_walk_quad_max(), k.stream),
+  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
+  uint64_t cap[4];
+  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(width - 1, cap);
+  return launched(poseidon_ops_of((int)curve)->verify(width, d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out, d_status,
+                                                      cap, table, r_f, r_p, poseidon_walk_quad_max(), k.stream),
                   "poseidon_merkle_verify_kernel");
 }
+int h2_poseidon_merkle_verify_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, const void* d_leaf_values, const void* d_indices,
+                                     const void* d_paths, uint32_t depth, size_t n, const void* d_root, void* d_roots_out, void* d_status,
+                                     void* stream_) {
+  return h2_poseidon_wide_merkle_verify_device(curve, 3, r_f, r_p, d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out,
+                                               d_status, stream_);
+}
 
+// binary trees only
 int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_p, void* d_leaves, void* d_nodes, uint32_t depth,
                                      const void* d_indices, const void* d_values, size_t n, void* d_status, void* stream_) {
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
-  if (!merkle_args_ok(curve, depth, n) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) ||
-      !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_values) || !poseidon_dev_ptr(d_status))
+  if (!curve_ok((int)curve) || !poseidon_depth_ok(3, depth) || n > ((size_t)1 << 31) || !poseidon_rounds_ok(r_f, r_p) ||
+      !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_values) ||
+      !poseidon_dev_ptr(d_status))
     return H2_EINVAL;
   const size_t leaves = (size_t)1 << depth;
   const Span lv{d_leaves, 32 * leaves}, nd{d_nodes, 32 * (leaves - 1)}, status{d_status, 4 * n};
   if (merkle_overlap({lv, nd, status}, {Span{d_indices, 4 * n}, Span{d_values, 32 * n}})) return H2_EINVAL;
   if (n == 0) return H2_OK;
-  const MerkleOps* ops = merkle_ops_of((int)curve);
+  const PoseidonOps* ops = poseidon_ops_of((int)curve);
   const size_t scratch = ops->update_scratch(n, depth);
   if (scratch == 0) {
     g_h2.last_error = "poseidon merkle update: the sort gave no scratch size";
@@ -2405,128 +2425,6 @@ int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_
       rc != H2_OK)
     return rc;
   return A.release();
-}
-
-// ---- the wide family: widths 3, 5, 9 (h2_poseidon_wide.hpp; width 3 is handed to the calls above) ------------------------
-namespace {
-const PoseidonWideOps* poseidon_wide_ops_of(int curve) {
-  return curve == H2_BN254 ? poseidon_wide_ops_bn254() : curve == H2_PALLAS ? poseidon_wide_ops_pallas() : poseidon_wide_ops_vesta();
-}
-// the permutation kernel's partial rounds, unless a test knob fixes the form (0: the width's own, 1: dense, 2: sparse)
-int poseidon_wide_form() { return g_knobs.poseidon_wide_form; }
-// log2 of the arity width - 1
-uint32_t poseidon_wide_lg(uint32_t width) { return width == 9 ? 3 : width == 5 ? 2 : 1; }
-// depth >= 1 and a^depth <= 2^30
-bool poseidon_wide_depth_ok(uint32_t width, uint32_t depth) { return depth >= 1 && depth <= 30 / poseidon_wide_lg(width); }
-}  // namespace
-
-int h2_poseidon_wide_constants(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
-                               size_t* n_elems) {
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !n_elems) return H2_EINVAL;
-  const size_t need = poseidon_wide_dense_elems(width, r_f, r_p);
-  *n_elems = need;
-  if (!out || cap_elems < need) return H2_EINVAL;
-  (void)poseidon_wide_table_mont((int)curve, width, r_f, r_p, false, out);
-  return H2_OK;
-}
-
-int h2_poseidon_wide_permute_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_in, void* d_out, size_t n,
-                                    void* stream_) {
-  if (width == 3) return h2_poseidon_permute_device(curve, r_f, r_p, d_in, d_out, n, stream_);
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_in) ||
-      !poseidon_dev_ptr(d_out) || n > ((size_t)1 << 40))
-    return H2_EINVAL;
-  if (d_out != d_in && poseidon_overlap(d_in, 32 * width * n, d_out, 32 * width * n)) return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
-  return launched(poseidon_wide_ops_of((int)curve)->permute(width, poseidon_wide_form(), d_in, d_out, n, table, r_f, r_p, k.stream),
-                  "poseidon_wide_permute_kernel");
-}
-
-int h2_poseidon_wide_hash_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_msgs, size_t len,
-                                 size_t msg_stride, size_t n, void* d_out, void* stream_) {
-  if (width == 3) return h2_poseidon_hash_device(curve, r_f, r_p, d_msgs, len, msg_stride, n, d_out, stream_);
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_msgs) ||
-      !poseidon_dev_ptr(d_out) || len == 0 || len > 65535 || msg_stride < len || msg_stride > ((size_t)1 << 32) || n > ((size_t)1 << 40))
-    return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  if (poseidon_overlap(d_msgs, 32 * ((n - 1) * msg_stride + len), d_out, 32 * n)) return H2_EINVAL;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(len, cap);
-  return launched(poseidon_wide_ops_of((int)curve)->hash(width, d_msgs, (uint32_t)len, msg_stride, n, d_out, cap, table, r_f, r_p,
-                                                         poseidon_chain_min_n(), k.stream),
-                  "poseidon_wide_hash_kernel");
-}
-
-int h2_poseidon_wide_merkle_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_leaves, uint32_t depth,
-                                   void* d_nodes, void* stream_) {
-  if (width == 3) return h2_poseidon_merkle_device(curve, r_f, r_p, d_leaves, depth, d_nodes, stream_);
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaves) ||
-      !poseidon_dev_ptr(d_nodes) || !poseidon_wide_depth_ok(width, depth))
-    return H2_EINVAL;
-  const uint32_t lg = poseidon_wide_lg(width);
-  const size_t leaves = merkle_wide_pow(lg, depth), nodes = merkle_wide_level_offset(lg, depth, depth);
-  if (poseidon_overlap(d_leaves, 32 * leaves, d_nodes, 32 * nodes)) return H2_EINVAL;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(width - 1, cap);
-  return launched(poseidon_wide_ops_of((int)curve)->merkle(width, d_leaves, depth, d_nodes, cap, table, r_f, r_p,
-                                                           (uint32_t)h2_poseidon_merkle_tail(), poseidon_chain_min_n(), k.stream),
-                  "poseidon_wide_merkle kernels");
-}
-
-int h2_poseidon_wide_merkle_paths_device(h2_curve_t curve, uint32_t width, const void* d_leaves, const void* d_nodes, uint32_t depth,
-                                         const void* d_indices, size_t n, void* d_paths, void* d_status, void* stream_) {
-  if (width == 3) return h2_poseidon_merkle_paths_device(curve, d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, stream_);
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_wide_depth_ok(width, depth) || n > ((size_t)1 << 31) ||
-      !poseidon_dev_ptr(d_leaves) || !poseidon_dev_ptr(d_nodes) || !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_paths) ||
-      !poseidon_dev_ptr(d_status))
-    return H2_EINVAL;
-  const uint32_t lg = poseidon_wide_lg(width);
-  const size_t leaves = merkle_wide_pow(lg, depth), nodes = merkle_wide_level_offset(lg, depth, depth);
-  const Span paths{d_paths, 32 * n * depth * (width - 2)}, status{d_status, 4 * n};
-  if (merkle_overlap({paths, status}, {Span{d_leaves, 32 * leaves}, Span{d_nodes, 32 * nodes}, Span{d_indices, 4 * n}})) return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  return launched(poseidon_wide_ops_of((int)curve)->paths(width, d_leaves, d_nodes, depth, d_indices, n, d_paths, d_status, k.stream),
-                  "poseidon_wide_merkle_paths_kernel");
-}
-
-int h2_poseidon_wide_merkle_verify_device(h2_curve_t curve, uint32_t width, uint32_t r_f, uint32_t r_p, const void* d_leaf_values,
-                                          const void* d_indices, const void* d_paths, uint32_t depth, size_t n, const void* d_root,
-                                          void* d_roots_out, void* d_status, void* stream_) {
-  if (width == 3)
-    return h2_poseidon_merkle_verify_device(curve, r_f, r_p, d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out, d_status,
-                                            stream_);
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || !poseidon_width_ok(width) || !poseidon_wide_depth_ok(width, depth) || n > ((size_t)1 << 31) ||
-      !poseidon_rounds_ok(r_f, r_p) || !poseidon_dev_ptr(d_leaf_values) || !poseidon_dev_ptr(d_indices) || !poseidon_dev_ptr(d_paths) ||
-      !poseidon_dev_ptr(d_status) || ((uintptr_t)d_root & 15) || ((uintptr_t)d_roots_out & 15))
-    return H2_EINVAL;
-  const Span roots{d_roots_out, 32 * n}, status{d_status, 4 * n};
-  if (merkle_overlap({roots, status}, {Span{d_leaf_values, 32 * n}, Span{d_indices, 4 * n},
-                                       Span{d_paths, 32 * n * depth * (width - 2)}, Span{d_root, 32}}))
-    return H2_EINVAL;
-  if (n == 0) return H2_OK;
-  const void* table = nullptr;
-  if (int rc = poseidon_table_get(*k.c, (int)curve, width, r_f, r_p, &table); rc != H2_OK) return rc;
-  uint64_t cap[4];
-  H2_BY_SCALAR_FIELD((int)curve, poseidon_capacity_t)(width - 1, cap);
-  return launched(poseidon_wide_ops_of((int)curve)->verify(width, d_leaf_values, d_indices, d_paths, depth, n, d_root, d_roots_out,
-                                                           d_status, cap, table, r_f, r_p, k.stream),
-                  "poseidon_wide_merkle_verify_kernel");
 }
 
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream_) {

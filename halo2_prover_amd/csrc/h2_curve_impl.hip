@@ -12,7 +12,6 @@
 #include "h2_expr_kernel.hpp"
 #include "h2_ipa.hpp"
 #include "h2_ipa_verify.hpp"
-#include "h2_poseidon.hpp"
 
 #include <cstring>
 
@@ -304,92 +303,6 @@ hipError_t poly_pointwise(void* d_a, const void* d_b, size_t total, int op, hipS
   return hipGetLastError();
 }
 
-// ---- Poseidon over the scalar field (h2_poseidon.hpp) ------------------------------------------------------------------
-// n constants in the API form -> the kernels' table entries (working form, 9 limbs each); host
-void poseidon_table(const uint64_t* api, size_t n, int32_t* out) {
-  for (size_t i = 0; i < n; i++) {
-    Fe<FS> a;
-    memcpy(a.v, api + 4 * i, 32);
-    const Fe29<FS> w = fe29_from_api(a);
-    memcpy(out + 9 * i, w.v, 36);
-  }
-}
-unsigned poseidon_grid(size_t n) {
-  return (unsigned)std::min<size_t>((n + POSEIDON_THREADS - 1) / POSEIDON_THREADS, POSEIDON_MAX_BLOCKS);
-}
-Fe29<FS> poseidon_capacity(const uint64_t cap_mont[4]) {
-  Fe<FS> c;
-  memcpy(c.v, cap_mont, 32);
-  return fe29_from_api(c);
-}
-hipError_t poseidon_permute_launch(const void* d_in, void* d_out, size_t n, const void* d_table, uint32_t r_f, uint32_t r_p,
-                                   hipStream_t s) {
-  hipLaunchKernelGGL(poseidon_permute_kernel<FS>, dim3(poseidon_grid(n)), dim3(POSEIDON_THREADS), 0, s, (const U128*)d_in, (U128*)d_out,
-                     n, (const Fe29<FS>*)d_table, r_f, r_p);
-  return hipGetLastError();
-}
-void poseidon_hash_enqueue(const U128* d_msgs, uint32_t len, size_t msg_stride, size_t n, U128* d_out, const Fe29<FS>& cap,
-                           const void* d_table, uint32_t r_f, uint32_t r_p, size_t chain_min_n, hipStream_t s) {
-  if (chain29::covers<FS>() && n >= chain_min_n)
-    hipLaunchKernelGGL((poseidon_hash_kernel<FS, Fe29Chain>), dim3(poseidon_grid(n)), dim3(POSEIDON_THREADS), 0, s, d_msgs, len,
-                       msg_stride, n, d_out, cap, (const Fe29<FS>*)d_table, r_f, r_p);
-  else
-    hipLaunchKernelGGL((poseidon_hash_kernel<FS, Fe29Compiler>), dim3(poseidon_grid(n)), dim3(POSEIDON_THREADS), 0, s, d_msgs, len,
-                       msg_stride, n, d_out, cap, (const Fe29<FS>*)d_table, r_f, r_p);
-}
-hipError_t poseidon_hash_launch(const void* d_msgs, uint32_t len, size_t msg_stride, size_t n, void* d_out, const uint64_t cap_mont[4],
-                                const void* d_table, uint32_t r_f, uint32_t r_p, size_t chain_min_n, hipStream_t s) {
-  poseidon_hash_enqueue((const U128*)d_msgs, len, msg_stride, n, (U128*)d_out, poseidon_capacity(cap_mont), d_table, r_f, r_p,
-                        chain_min_n, s);
-  return hipGetLastError();
-}
-// 2^depth leaves -> the 2^depth - 1 inner nodes, level by level, the root last: one hash launch per level of more than
-// `tail` nodes (a power of two, at most POSEIDON_MERKLE_TAIL_MAX), then one workgroup for all the levels that are left
-hipError_t poseidon_merkle_launch(const void* d_leaves, uint32_t depth, void* d_nodes, const uint64_t cap2_mont[4], const void* d_table,
-                                  uint32_t r_f, uint32_t r_p, uint32_t tail, size_t chain_min_n, hipStream_t s) {
-  if (depth == 0 || depth > 30 || tail == 0 || tail > POSEIDON_MERKLE_TAIL_MAX || (tail & (tail - 1))) return hipErrorInvalidValue;
-  const Fe29<FS> cap2 = poseidon_capacity(cap2_mont);
-  const U128* in = (const U128*)d_leaves;
-  U128* out = (U128*)d_nodes;
-  size_t w = (size_t)1 << (depth - 1);          // nodes of the level being written
-  for (; w > tail; w >>= 1) {
-    poseidon_hash_enqueue(in, 2, 2, w, out, cap2, d_table, r_f, r_p, chain_min_n, s);
-    in = out;
-    out += 2 * w;
-  }
-  hipLaunchKernelGGL(poseidon_merkle_tail_kernel<FS>, dim3(1), dim3(POSEIDON_THREADS), 0, s, in, out, (uint32_t)w, cap2,
-                     (const Fe29<FS>*)d_table, r_f, r_p);
-  return hipGetLastError();
-}
-// the host instantiation of the same templates on a table in the working form.  op 0: permute one state (3 elements in,
-// 3 out); op 1: ConstantLength<2> of two elements (cap2_mont = 2 2^64) -> one element
-int selftest_poseidon(int op, uint32_t r_f, uint32_t r_p, const int32_t* table, const uint64_t* cap2_mont, const uint64_t* in,
-                      uint64_t* out) {
-  const Fe29<FS>* tb = (const Fe29<FS>*)table;
-  if (op == 0) {
-    Fe29<FS> st[3];
-    for (int j = 0; j < 3; j++) {
-      Fe<FS> a;
-      memcpy(a.v, in + 4 * j, 32);
-      st[j] = fe29_from_api(a);
-    }
-    poseidon_permute<FS>(st, tb, r_f, r_p);
-    for (int j = 0; j < 3; j++) {
-      const Fe<FS> r = fe29_to_api(st[j]);
-      memcpy(out + 4 * j, r.v, 32);
-    }
-    return 0;
-  }
-  if (op == 1) {
-    U128 msg[4];
-    memcpy(msg, in, 64);
-    const Fe<FS> r = fe29_to_api(poseidon_hash<FS>(msg, 2, poseidon_capacity(cap2_mont), tb, r_f, r_p));
-    memcpy(out, r.v, 32);
-    return 0;
-  }
-  return -1;
-}
-
 // the ceiling the MSM kernels are priced against (bench.py `modmul_ceiling`): dependent products of the working
 // form (h2_field29.hpp) over the base field, `blocks` x 256 threads, best of three launches
 template <bool PLAIN>
@@ -654,8 +567,7 @@ const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, tabl
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_launch<FS>, ipa_round_launch<FS>, ipa_final_launch<FS>,
                       ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, ipa_begin_batch_launch<FS>, ipa_round_batch_launch<FS>, ipa_final_batch_launch<FS>, IPA_REPLAY, IPA_VERIFY_PREPARE, IPA_VERIFY_FINISH, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate,
-                      chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device,
-                      poseidon_table, poseidon_permute_launch, poseidon_hash_launch, poseidon_merkle_launch, selftest_poseidon};
+                      chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device};
 
 }  // namespace
 

@@ -204,22 +204,6 @@ struct CurveOps {
   bool base_chain29;
   int (*selftest_xyzz29)(int op, const int32_t* in, int32_t* out);
   hipError_t (*selftest_xyzz29_device)(int op, const void* d_in, void* d_out, uint32_t n, hipStream_t s);
-  // Poseidon over the scalar field, width 3 / rate 2 / x^5 (h2_poseidon.hpp).  d_table: (r_f + r_p) * 3 round constants then
-  // the 3 x 3 MDS in the working form, 36 bytes each, as poseidon_table (host) makes them from Montgomery limbs.
-  // poseidon_permute: n states of three elements, d_out == d_in allowed.  poseidon_hash: ConstantLength<len> of n messages
-  // msg_stride elements apart, cap_mont = len 2^64 as Montgomery limbs; a launch of chain_min_n lanes or more runs on the
-  // single-chain products where the field has them (0: always, SIZE_MAX: never).  poseidon_merkle: 2^depth leaves -> 2^depth - 1
-  // nodes, levels of more than `tail` nodes one hash launch each, the rest in one launch of one workgroup; cap2_mont = 2 2^64
-  void (*poseidon_table)(const uint64_t* api, size_t n, int32_t* out);
-  hipError_t (*poseidon_permute)(const void* d_in, void* d_out, size_t n, const void* d_table, uint32_t r_f, uint32_t r_p,
-                                 hipStream_t s);
-  hipError_t (*poseidon_hash)(const void* d_msgs, uint32_t len, size_t msg_stride, size_t n, void* d_out, const uint64_t cap_mont[4],
-                              const void* d_table, uint32_t r_f, uint32_t r_p, size_t chain_min_n, hipStream_t s);
-  hipError_t (*poseidon_merkle)(const void* d_leaves, uint32_t depth, void* d_nodes, const uint64_t cap2_mont[4], const void* d_table,
-                                uint32_t r_f, uint32_t r_p, uint32_t tail, size_t chain_min_n, hipStream_t s);
-  // host: the same templates on a host copy of the table; op 0 permutes one state, op 1 hashes two words
-  int (*selftest_poseidon)(int op, uint32_t r_f, uint32_t r_p, const int32_t* table, const uint64_t* cap2_mont, const uint64_t* in,
-                           uint64_t* out);
 };
 
 const CurveOps* curve_ops_bn254();

@@ -16,6 +16,7 @@
 #include "../../include/h2hip.h"
 #include "h2_curve_ops.hpp"
 #include "h2_msm.hpp"
+#include "h2_poseidon_ops.hpp"
 
 namespace h2 {
 
@@ -75,7 +76,7 @@ struct TwiddleEntry {
 // the constants of one Poseidon instance (h2_poseidon.hpp) in HBM, in the kernels' working form
 struct PoseidonTable {
   int field;
-  uint32_t width;      // 3: h2_poseidon.hpp's table; 5, 9: h2_poseidon_wide.hpp's, dense and sparse part
+  uint32_t width;      // 3: the dense part alone; 5, 9: dense and sparse part (h2_poseidon.hpp: poseidon_table_elems)
   uint32_t r_f, r_p;
   void* d;
 };
@@ -172,6 +173,7 @@ int dev_fail(hipError_t e, const char* where);
 // the status of a launch (sequence) named `what`
 inline int launched(hipError_t e, const char* what) { return e == hipSuccess ? H2_OK : dev_fail(e, what); }
 const CurveOps* ops_of(int curve);
+const PoseidonOps* poseidon_ops_of(int curve);
 bool curve_ok(int c);
 // context of the calling thread's current HIP device (the only context when there is just one); null if none
 DevCtx* ctx_current();
@@ -179,8 +181,8 @@ size_t ctx_index(const DevCtx* c);
 
 // hipMalloc of the buffer named `what`: H2_ENOMEM (sticky error cleared, last_error set, *p = null) if it fails
 int device_alloc(void** p, size_t bytes, const char* what);
-// The wide Poseidon table of (curve, width 5 | 9, r_f, r_p) as Montgomery limbs (host): the dense part, h2_poseidon_wide_
-// constants' elements, and with `sparse` the sparse part behind it (h2_poseidon_wide.hpp: poseidon_wide_table_elems in all).
+// The Poseidon table of (curve, width 3 | 5 | 9, r_f, r_p) as Montgomery limbs (host): the dense part, h2_poseidon_wide_
+// constants' elements, and with `sparse` (widths 5, 9) the sparse part behind it (h2_poseidon.hpp: poseidon_table_elems in all).
 // ConstantLength<len>'s capacity word len 2^64.  False when the partial rounds do not factor (h2_poseidon_host.hpp)
 bool poseidon_wide_table_mont(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, bool sparse, uint64_t* out);
 void poseidon_capacity_mont(int curve, uint64_t len, uint64_t out[4]);

@@ -58,7 +58,7 @@ struct Constants {
   std::vector<std::array<HF<FP>, 3>> rcs;     // r_f + r_p rounds
   HF<FP> mds[3][3], minv[3][3];
 };
-// the same for any width t: rcs[r * t + i], mds[i * t + j]; no inverse (the wide family, h2_poseidon_wide.hpp, needs none)
+// the same for any width t: rcs[r * t + i], mds[i * t + j]; no inverse (the kernels, h2_poseidon.hpp, need none)
 template <class FP>
 struct WideConstants {
   int t = 0;
@@ -98,7 +98,7 @@ WideConstants<FP> generate_wide(int t, int r_f, int r_p) {
   return k;
 }
 
-// ---- the sparse form of the partial rounds (h2_poseidon_wide.hpp) ------------------------------------------------------
+// ---- the sparse form of the partial rounds (h2_poseidon.hpp, widths 5 and 9) ------------------------------------------
 // The r_p partial rounds  s <- M sigma(s + c_k)  (sigma: x^5 on word 0 alone) cost t^2 products each.  Split a matrix
 //     N = [ n00  v ]  =  S N',     S = [ n00  v Nh^-1 ],   N' = [ 1  0  ]
 //         [ w   Nh ]                   [ w    I       ]         [ 0  Nh ]

@@ -5,7 +5,6 @@
 #include "h2_field29_chain.hpp"
 #include "h2_host.hpp"
 #include "h2_poseidon.hpp"
-#include "h2_poseidon_wide.hpp"
 
 #include <cstdio>
 #include <vector>
@@ -382,55 +381,48 @@ extern "C" int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters,
 }
 
 // ---- Poseidon (h2_poseidon.hpp) --------------------------------------------------------------------------------------
-// host only: the permutation template instantiated on the host, on the table h2_poseidon_constants' values make
+namespace {
+// host only: the kernels' permutation and sponge templates instantiated on the host, on `elems` table entries as Montgomery
+// limbs
+int poseidon_selftest_run(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, int form, int op, uint32_t len,
+                          const std::vector<uint64_t>& api, size_t elems, const uint64_t* in, uint64_t* out) {
+  const PoseidonOps* ops = poseidon_ops_of(curve);
+  std::vector<int32_t> table(9 * elems);
+  ops->table(api.data(), elems, table.data());
+  uint64_t cap[4];
+  poseidon_capacity_mont(curve, len, cap);
+  return ops->selftest(width, form, op, len, r_f, r_p, table.data(), cap, in, out) == 0 ? H2_OK : H2_EINVAL;
+}
+}  // namespace
+// width 3, on the table h2_poseidon_constants' values make: op 0 permutes one state, op 1 is ConstantLength<2> of two elements
 extern "C" int h2_selftest_poseidon(int curve, uint32_t r_f, uint32_t r_p, int op, const uint64_t* in, uint64_t* out) {
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !in || !out || op < 0 || op > 1) return H2_EINVAL;
+  if (!curve_ok(curve) || !in || !out || op < 0 || op > 1) return H2_EINVAL;
   size_t elems = 0;
   if (h2_poseidon_constants((h2_curve_t)curve, r_f, r_p, nullptr, 0, &elems) != H2_EINVAL || elems == 0) return H2_EINVAL;
   std::vector<uint64_t> api(4 * elems);
   if (int rc = h2_poseidon_constants((h2_curve_t)curve, r_f, r_p, api.data(), elems, &elems); rc != H2_OK) return rc;
-  std::vector<int32_t> table(9 * elems);
-  ops->poseidon_table(api.data(), elems, table.data());
-  uint64_t cap2[4];
-  const char* two65 = "0x20000000000000000";          // ConstantLength<2>: 2 2^64
-  if (curve == H2_BN254) HF<BN254_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
-  else if (curve == H2_PALLAS) HF<PALLAS_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
-  else HF<VESTA_CURVE::Scalar>::from_hex(two65).mont_limbs(cap2);
-  return ops->selftest_poseidon(op, r_f, r_p, table.data(), cap2, in, out) == 0 ? H2_OK : H2_EINVAL;
+  return poseidon_selftest_run(curve, 3, r_f, r_p, 0, op, 2, api, elems, in, out);
 }
-// ---- the wide family (h2_poseidon_wide.hpp) ----------------------------------------------------------------------------
-namespace {
-const PoseidonWideOps* wide_ops_of(int curve) {
-  return curve == H2_BN254 ? poseidon_wide_ops_bn254() : curve == H2_PALLAS ? poseidon_wide_ops_pallas() : poseidon_wide_ops_vesta();
-}
-}  // namespace
-// host only: the table as the kernels read it (before the change to the working form)
+// the widths 5 and 9: the table as the kernels read it (before the change to the working form)
 extern "C" int h2_selftest_poseidon_wide_table(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, uint64_t* out, size_t cap_elems,
                                                size_t* n_elems) {
   size_t dense = 0;
   if (!n_elems || (width != 5 && width != 9) ||
       h2_poseidon_wide_constants((h2_curve_t)curve, width, r_f, r_p, nullptr, 0, &dense) != H2_EINVAL || dense == 0)
     return H2_EINVAL;
-  const size_t need = poseidon_wide_table_elems(width, r_f, r_p);
+  const size_t need = poseidon_table_elems(width, r_f, r_p);
   *n_elems = need;
   if (!out || cap_elems < need) return H2_EINVAL;
   return poseidon_wide_table_mont(curve, width, r_f, r_p, true, out) ? H2_OK : H2_EINVAL;
 }
-// host only: the kernels' permutation and sponge templates instantiated on the host
 extern "C" int h2_selftest_poseidon_wide(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, int form, int op, uint32_t len,
                                          const uint64_t* in, uint64_t* out) {
-  const CurveOps* ops = ops_of(curve);
-  if (!ops || !in || !out || op < 0 || op > 1 || (op == 1 && (len == 0 || len > 65535))) return H2_EINVAL;
+  if (!curve_ok(curve) || !in || !out || op < 0 || op > 1 || (op == 1 && (len == 0 || len > 65535))) return H2_EINVAL;
   size_t elems = 0;
   if (h2_selftest_poseidon_wide_table(curve, width, r_f, r_p, nullptr, 0, &elems) != H2_EINVAL || elems == 0) return H2_EINVAL;
   std::vector<uint64_t> api(4 * elems);
   if (int rc = h2_selftest_poseidon_wide_table(curve, width, r_f, r_p, api.data(), elems, &elems); rc != H2_OK) return rc;
-  std::vector<int32_t> table(9 * elems);
-  ops->poseidon_table(api.data(), elems, table.data());
-  uint64_t cap[4];
-  poseidon_capacity_mont(curve, len, cap);
-  return wide_ops_of(curve)->selftest(width, form, op, len, r_f, r_p, table.data(), cap, in, out) == 0 ? H2_OK : H2_EINVAL;
+  return poseidon_selftest_run(curve, width, r_f, r_p, form, op, len, api, elems, in, out);
 }
 // tests and tools only: the partial rounds of h2_poseidon_wide_permute_device's kernel (0: the width's own form, 1: dense, 2: sparse)
 extern "C" int h2_selftest_set_poseidon_wide_form(int form) {

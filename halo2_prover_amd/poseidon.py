@@ -6,7 +6,8 @@ instances the reference uses: (8, 56) on Pallas and Vesta (P128Pow5T3, the zcash
 (poseidon_circuit.rs's spec: the hash the Poseidon circuit proves).
 
 `width=5` and `width=9` (rate 4 and 8; h2_poseidon_wide_*) are the same primitive for 4-ary and 8-ary hashes and trees.
-They have no default rounds: r_f and r_p must be given.  `width=3` keeps calling the entry points it always called.
+They have no default rounds: r_f and r_p must be given.  Every width goes through the width-taking entry points
+(h2_poseidon_wide_*); the h2_poseidon_* names are those calls at width 3.
 
 Elements are 4 x u64 Montgomery limbs, canonical.  The device functions take int64 CUDA tensors viewing those limbs, or
 numpy uint64 arrays, which are uploaded, and return the same kind: the work is enqueued on the caller's current stream
@@ -72,17 +73,14 @@ def constants(curve, r_f=None, r_p=None, as_int=False, width=3):
     r_f, r_p = _rounds(cid, r_f, r_p, width)
     L = _lib.load()
     need = ctypes.c_size_t(0)
-    if width == 3:
-        def call(out, cap):
-            return L.h2_poseidon_constants(cid, r_f, r_p, out, cap, ctypes.byref(need))
-    else:
-        def call(out, cap):
-            return L.h2_poseidon_wide_constants(cid, width, r_f, r_p, out, cap, ctypes.byref(need))
+
+    def call(out, cap):
+        return L.h2_poseidon_wide_constants(cid, width, r_f, r_p, out, cap, ctypes.byref(need))
     call(None, 0)
     if need.value == 0:
         raise ValueError("poseidon: r_f must be even and at least 2, r_f + r_p at most 128")
     out = np.zeros((need.value, 4), dtype=np.uint64)
-    _lib.check(call(out.ctypes.data, need.value), "h2_poseidon_constants" if width == 3 else "h2_poseidon_wide_constants")
+    _lib.check(call(out.ctypes.data, need.value), "h2_poseidon_wide_constants")
     rounds, t = r_f + r_p, width
     rcs, mds = out[:t * rounds].reshape(rounds, t, 4), out[t * rounds:].reshape(t, t, 4)
     if not as_int:
@@ -126,14 +124,9 @@ def permute(curve, states, r_f=None, r_p=None, out=None, width=3):
     d_out = torch.empty_like(d_in) if out is None else out
     if tuple(d_out.shape) != tuple(d_in.shape) or d_out.dtype != torch.int64 or not d_out.is_cuda or not d_out.is_contiguous():
         raise ValueError("out: expected a contiguous int64 CUDA tensor of the states' shape")
-    if width == 3:
-        st = _lib.load().h2_poseidon_permute_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()),
-                                                    ctypes.c_void_p(d_out.data_ptr()), d_in.shape[0], _stream())
-        _lib.check(st, "h2_poseidon_permute_device")
-    else:
-        st = _lib.load().h2_poseidon_wide_permute_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()),
-                                                         ctypes.c_void_p(d_out.data_ptr()), d_in.shape[0], _stream())
-        _lib.check(st, "h2_poseidon_wide_permute_device")
+    st = _lib.load().h2_poseidon_wide_permute_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()),
+                                                     ctypes.c_void_p(d_out.data_ptr()), d_in.shape[0], _stream())
+    _lib.check(st, "h2_poseidon_wide_permute_device")
     return _result(d_out, was_numpy)
 
 
@@ -150,14 +143,9 @@ def hash(curve, msgs, r_f=None, r_p=None, length=None, width=3):  # noqa: A001 -
     n, stride = d_in.shape[0], d_in.shape[1]
     length = stride if length is None else int(length)
     d_out = torch.empty((n, 4), dtype=torch.int64, device=d_in.device)
-    if width == 3:
-        st = _lib.load().h2_poseidon_hash_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), length, stride, n,
-                                                 ctypes.c_void_p(d_out.data_ptr()), _stream())
-        _lib.check(st, "h2_poseidon_hash_device")
-    else:
-        st = _lib.load().h2_poseidon_wide_hash_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), length, stride, n,
-                                                      ctypes.c_void_p(d_out.data_ptr()), _stream())
-        _lib.check(st, "h2_poseidon_wide_hash_device")
+    st = _lib.load().h2_poseidon_wide_hash_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), length, stride, n,
+                                                  ctypes.c_void_p(d_out.data_ptr()), _stream())
+    _lib.check(st, "h2_poseidon_wide_hash_device")
     return _result(d_out, was_numpy)
 
 
@@ -174,14 +162,9 @@ def merkle_nodes(curve, leaves, r_f=None, r_p=None, width=3):
     if d_in.dim() != 2 or d_in.shape[1] != 4 or depth is None:
         raise ValueError("leaves: expected shape (%d^depth, 4) with depth >= 1, got %r" % (width - 1, tuple(d_in.shape)))
     d_out = torch.empty(((n - 1) // (width - 2), 4), dtype=torch.int64, device=d_in.device)
-    if width == 3:
-        st = _lib.load().h2_poseidon_merkle_device(cid, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), depth,
-                                                   ctypes.c_void_p(d_out.data_ptr()), _stream())
-        _lib.check(st, "h2_poseidon_merkle_device")
-    else:
-        st = _lib.load().h2_poseidon_wide_merkle_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), depth,
-                                                        ctypes.c_void_p(d_out.data_ptr()), _stream())
-        _lib.check(st, "h2_poseidon_wide_merkle_device")
+    st = _lib.load().h2_poseidon_wide_merkle_device(cid, width, r_f, r_p, ctypes.c_void_p(d_in.data_ptr()), depth,
+                                                    ctypes.c_void_p(d_out.data_ptr()), _stream())
+    _lib.check(st, "h2_poseidon_wide_merkle_device")
     return _result(d_out, was_numpy)
 
 
@@ -229,7 +212,7 @@ def _tree(leaves, nodes, width=3):
 
 def merkle_paths(curve, leaves, nodes, indices, width=3):
     """The membership paths of n leaves of a resident tree, cut on the device: (paths (n, depth, 4), status (n,)); at
-    widths 5 and 9 paths (n, depth * (width - 2), 4).  paths[i] is merkle_path's (merkle_path_wide's) list for indices[i];
+    widths 5 and 9 paths (n, depth * (width - 2), 4).  paths[i] is merkle_path_wide's list for indices[i] (width 3: merkle_path's);
     an index >= a^depth gives status 1 and a zero path."""
     import torch
     _ensure_init()
@@ -241,12 +224,7 @@ def merkle_paths(curve, leaves, nodes, indices, width=3):
     n = d_idx.shape[0]
     d_paths = torch.empty((n, depth * (width - 2), 4), dtype=torch.int64, device=d_leaves.device)
     d_status = torch.empty((n,), dtype=torch.int32, device=d_leaves.device)
-    if n and width == 3:   # an empty tensor has no address to pass: n = 0 is the C call's H2_OK, nothing enqueued
-        st = _lib.load().h2_poseidon_merkle_paths_device(cid, ctypes.c_void_p(d_leaves.data_ptr()), ctypes.c_void_p(d_nodes.data_ptr()),
-                                                         depth, ctypes.c_void_p(d_idx.data_ptr()), n, ctypes.c_void_p(d_paths.data_ptr()),
-                                                         ctypes.c_void_p(d_status.data_ptr()), _stream())
-        _lib.check(st, "h2_poseidon_merkle_paths_device")
-    elif n:
+    if n:   # an empty tensor has no address to pass: n = 0 is the C call's H2_OK, nothing enqueued
         st = _lib.load().h2_poseidon_wide_merkle_paths_device(cid, width, ctypes.c_void_p(d_leaves.data_ptr()),
                                                               ctypes.c_void_p(d_nodes.data_ptr()), depth, ctypes.c_void_p(d_idx.data_ptr()),
                                                               n, ctypes.c_void_p(d_paths.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
@@ -281,14 +259,7 @@ def verify_paths(curve, leaf_values, indices, paths, root=None, r_f=None, r_p=No
             raise ValueError("root: expected one element of 4 limbs")
     d_roots = torch.empty((n, 4), dtype=torch.int64, device=d_paths.device)
     d_status = torch.empty((n,), dtype=torch.int32, device=d_paths.device)
-    if n and width == 3:
-        st = _lib.load().h2_poseidon_merkle_verify_device(cid, r_f, r_p, ctypes.c_void_p(d_leafs.data_ptr()),
-                                                          ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_paths.data_ptr()), depth, n,
-                                                          None if d_root is None else ctypes.c_void_p(d_root.data_ptr()),
-                                                          ctypes.c_void_p(d_roots.data_ptr()), ctypes.c_void_p(d_status.data_ptr()),
-                                                          _stream())
-        _lib.check(st, "h2_poseidon_merkle_verify_device")
-    elif n:
+    if n:
         st = _lib.load().h2_poseidon_wide_merkle_verify_device(cid, width, r_f, r_p, ctypes.c_void_p(d_leafs.data_ptr()),
                                                                ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_paths.data_ptr()),
                                                                depth, n, None if d_root is None else ctypes.c_void_p(d_root.data_ptr()),
@@ -325,49 +296,7 @@ def merkle_update(curve, leaves, nodes, indices, values, r_f=None, r_p=None):
     return _status(d_status, np_i and np_v)
 
 
-# ---- host helpers on Python integers ---------------------------------------------------------------------------------
-def merkle_path(nodes, depth, index):
-    """The siblings of leaf `index` from the bottom up.  nodes: the whole tree as canonical ints, the 2^depth leaves
-    followed by merkle_nodes' 2^depth - 1 inner nodes (2^(depth + 1) - 1 values)."""
-    if len(nodes) != (2 << depth) - 1 or not 0 <= index < (1 << depth):
-        raise ValueError("merkle_path: expected 2^(depth + 1) - 1 nodes and an index below 2^depth")
-    path, base, width = [], 0, 1 << depth
-    for _ in range(depth):
-        path.append(nodes[base + (index ^ 1)])
-        base += width
-        width >>= 1
-        index >>= 1
-    return path
-
-
-def hash2_int(curve, a, b, r_f=None, r_p=None):
-    """ConstantLength<2> of two canonical ints on the host (big integers; a membership proof's few hashes)"""
-    cid = _curve_id(curve)
-    r_f, r_p = _rounds(cid, r_f, r_p)
-    p = modulus(cid)
-    rcs, mds = constants(cid, r_f, r_p, as_int=True)
-    st = [a % p, b % p, (2 << 64) % p]
-    half = r_f // 2
-    for r in range(r_f + r_p):
-        st = [(st[i] + rcs[r][i]) % p for i in range(3)]
-        if r < half or r >= half + r_p:
-            st = [pow(x, 5, p) for x in st]
-        else:
-            st[0] = pow(st[0], 5, p)
-        st = [sum(mds[i][j] * st[j] for j in range(3)) % p for i in range(3)]
-    return st[0]
-
-
-def verify_path(curve, leaf, index, path, root, r_f=None, r_p=None):
-    """True when `path` (merkle_path's siblings) takes `leaf` at position `index` to `root`"""
-    cur = leaf
-    for sib in path:
-        cur = hash2_int(curve, sib, cur, r_f, r_p) if index & 1 else hash2_int(curve, cur, sib, r_f, r_p)
-        index >>= 1
-    return index == 0 and cur == root
-
-
-# ---- the same for a-ary trees (widths 5 and 9; arity 2 works too) -----------------------------------------------------------
+# ---- host helpers on Python integers, for a membership proof's few hashes ------------------------------------------------
 def merkle_path_wide(nodes, arity, depth, index):
     """The siblings of leaf `index` from the bottom up, arity - 1 per level in child order with the ancestor's own position
     left out.  nodes: the whole tree as canonical ints, the arity^depth leaves followed by merkle_nodes' inner nodes."""
@@ -414,3 +343,20 @@ def verify_path_wide(curve, arity, leaf, index, path, root, r_f, r_p):
         cur = hashn_int(curve, sibs, r_f, r_p)
         index //= arity
     return index == 0 and cur == root
+
+
+# ---- the same at arity 2 (width 3, which has default rounds) ------------------------------------------------------------
+def merkle_path(nodes, depth, index):
+    """The siblings of leaf `index` from the bottom up.  nodes: the whole tree as canonical ints, the 2^depth leaves
+    followed by merkle_nodes' 2^depth - 1 inner nodes (2^(depth + 1) - 1 values)."""
+    return merkle_path_wide(nodes, 2, depth, index)
+
+
+def hash2_int(curve, a, b, r_f=None, r_p=None):
+    """ConstantLength<2> of two canonical ints on the host"""
+    return hashn_int(curve, [a, b], r_f, r_p)
+
+
+def verify_path(curve, leaf, index, path, root, r_f=None, r_p=None):
+    """True when `path` (merkle_path's siblings) takes `leaf` at position `index` to `root`"""
+    return verify_path_wide(curve, 2, leaf, index, path, root, r_f, r_p)

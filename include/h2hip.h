@@ -525,7 +525,7 @@ int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_
 /* ---- Poseidon at widths 3, 5 and 9: 4-ary and 8-ary hashes and Merkle trees ---------------------------------------
  * The same primitive (primitives.rs's Spec<F, T, RATE>) with the width as an argument: `width` = 3, 5 or 9, rate = width - 1
  * = 2, 4 or 8, S-box x^5, constants from the same Grain / Cauchy-MDS generation with t = width, over the scalar field of
- * `curve` (all three curves).  Width 3 is the family above, bit for bit (the calls hand it on); widths 5 and 9 are the two
+ * `curve` (all three curves).  Width 3 is the family above, bit for bit (its calls are these at width 3); widths 5 and 9 are the two
  * the Poseidon paper proposes for Merkle trees of arity a = width - 1 = 4 and 8.  The caller supplies (r_f, r_p) under the
  * rules above; the library picks none.  The Poseidon paper's parameter script gives (8, 60) at t = 5 and (8, 63) at t = 9
  * for 128-bit security with x^5 on fields of about 255 bits -- NOT checked here: choosing round numbers is the caller's.
@@ -553,7 +553,7 @@ int h2_poseidon_merkle_update_device(h2_curve_t curve, uint32_t r_f, uint32_t r_
  *                                         element that is not canonical is never reduced silently -- status 2 and a zero
  *                                         root, as an index out of range (status 1); another root than *d_root is status 4;
  *                                         the first that applies of 1, 2, 4 is reported; d_root = NULL drops the comparison.
- *                                         One path runs on one lane.
+ *                                         One path runs on one lane (width 3: or on four, as above).
  * There is no in-place update of a wide tree and no form with several lanes per permutation.
  * Asynchronous on `stream` under h2_ntt_device's rules, on the context of the calling thread's current HIP device; the first
  * use of a (curve, width, r_f, r_p) on a context builds and uploads its table and waits for that (the eight tables used last

@@ -194,7 +194,7 @@ int h2_selftest_set_poseidon_form(int form);
  * h2_poseidon_merkle_update_device: 1 = one lane per hash at every size, 2 = the four lanes of a quad per hash at every
  * size, 0 = by size (the default).  The results are the same bits either way.  H2_EINVAL for another value. */
 int h2_selftest_set_poseidon_walk_form(int form);
-/* The wide Poseidon family (h2_poseidon_wide_*; csrc/h2_poseidon_wide.hpp), widths 5 and 9.
+/* The wide Poseidon family (h2_poseidon_wide_*; csrc/h2_poseidon.hpp), widths 5 and 9.
  * h2_selftest_poseidon_wide_table: host only, no GPU and no h2_init -- the whole table the kernels read, as 4 x u64
  *   Montgomery limbs: h2_poseidon_wide_constants' (r_f + r_p) * width + width^2 elements, then the SPARSE form of the partial
  *   rounds: the width x width pre-matrix (row-major) that the last full round in front of them takes in place of the MDS;

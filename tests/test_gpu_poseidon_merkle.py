@@ -1,4 +1,4 @@
-"""GPU: h2_poseidon_merkle_paths_device / _verify_device / _update_device (csrc/h2_poseidon_quad.hpp).
+"""GPU: h2_poseidon_merkle_paths_device / _verify_device / _update_device (csrc/h2_poseidon_merkle.hpp).
 
 Judges: oracle/pyref.py (poseidon_hash_const_len, t = 3) for single hashes and the depth-3 tree, the existing
 h2_poseidon_merkle_device for whole trees, and poseidon.merkle_path on a host copy for the paths.  Every comparison is
@@ -222,6 +222,47 @@ def test_verify_accepts_the_paths_the_device_cut(h2, walk, depth):
     assert status == [OK] * len(indices)
     roots, status = verify_raw(cid, r_f, r_p, leaf_limbs[indices], indices, paths, depth, None)                      # d_root = NULL
     assert status == [OK] * len(indices) and ints(cid, roots) == [whole[-1]] * len(indices)
+
+
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("cid", [0, 1, 2])
+def test_shallow_trees_equal_pyref_and_each_other_in_both_walk_forms(h2, cid, depth):
+    """paths, then verify, on the smallest trees: the gather shared by every arity at its arity-2 corner (lg = 1, ONE sibling
+    a level), then the binary walker in both of its forms.  Every leaf, one index out of range and one sibling that is not
+    canonical; the judge is pyref's tree"""
+    r_f, r_p = SPEC[cid]
+    leaf_ints, leaf_limbs, nodes, _ = tree(cid, depth)
+    level, whole = leaf_ints, list(leaf_ints)
+    while len(level) > 1:
+        level = [ref_hash(cid, level[2 * i:2 * i + 2], r_f, r_p) for i in range(len(level) // 2)]
+        whole += level
+    assert ints(cid, nodes) == whole[1 << depth:]
+    width = 1 << depth
+    indices = list(range(width)) + [width]                         # every leaf, then one index out of range
+    paths, status = paths_raw(cid, depth, indices)
+    assert status == [OK] * width + [RANGE] and not paths[width * depth:].any()
+    for idx in range(width):
+        want, base = [], 0
+        for l in range(depth):
+            want.append(whole[base + ((idx >> l) ^ 1)])
+            base += width >> l
+        assert ints(cid, paths[idx * depth:(idx + 1) * depth]) == want, idx
+    # the item behind them: leaf 0 and its path, the top sibling replaced by p itself (not canonical)
+    bad = paths[:depth].copy()
+    bad[depth - 1] = raw_limbs(FIELD[cid].p)
+    v_leaves = np.concatenate([leaf_limbs, leaf_limbs[:1], leaf_limbs[:1]])
+    v_paths = np.concatenate([paths, bad])
+    got = {}
+    for form in (1, 2):
+        assert L().h2_selftest_set_poseidon_walk_form(form) == H2_OK
+        try:
+            roots, status = verify_raw(cid, r_f, r_p, v_leaves, indices + [0], v_paths, depth)
+        finally:
+            assert L().h2_selftest_set_poseidon_walk_form(0) == H2_OK
+        assert status == [OK] * width + [RANGE, NONCANONICAL], form
+        assert ints(cid, roots) == [whole[-1]] * width + [0, 0], form
+        got[form] = (roots.tobytes(), status)
+    assert got[1] == got[2]
 
 
 @pytest.mark.parametrize("cid", [0, 1])

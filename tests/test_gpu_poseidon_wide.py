@@ -1,4 +1,4 @@
-"""GPU: the wide Poseidon family h2_poseidon_wide_* (csrc/h2_poseidon_wide.hpp) at widths 5 and 9 on all three scalar fields.
+"""GPU: the wide Poseidon family h2_poseidon_wide_* (csrc/h2_poseidon.hpp, csrc/h2_poseidon_merkle.hpp) at widths 5 and 9 on all three scalar fields.
 
 The judge is oracle/pyref.py (poseidon_permute, poseidon_hash_const_len with t = 5, 9); paths are judged by
 poseidon.merkle_path_wide on a host copy of the tree and flipped paths by poseidon.hashn_int.  Every comparison is exact

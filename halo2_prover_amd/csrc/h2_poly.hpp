@@ -63,7 +63,9 @@ poly_pointwise_kernel(U128* __restrict__ a, const U128* __restrict__ b, size_t t
   }
 }
 
-// a[i] = a[i]^-1 (0 stays 0): the denominators of the permutation grand product
+// a[i] = a[i]^-1 (0 stays 0): the denominators of the permutation grand product.  The is_zero test is not what keeps a
+// zero: fe_inv(0) = 0^(p-2) is canonical 0 anyway (the chain's first multiplication is by a); it only saves the
+// exponentiation and the store
 template <class FP>
 __global__ void __launch_bounds__(256) poly_inverse_kernel(U128* __restrict__ a, size_t total) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {

@@ -275,16 +275,28 @@ int h2_extended_to_coeff_device(h2_curve_t curve, const void* d_ext, uint32_t ex
                                 const uint64_t ext_omega_inv[4], const uint64_t scale[4], const uint64_t zeta_inv[4],
                                 const void* d_t, size_t t_period,
                                 void* d_out, size_t out_len, size_t out_stride, void* stream);
-/* a[i] *= c */
+/* The elementwise calls below work in place on canonical Montgomery elements of the SCALAR field of `curve`, asynchronously
+ * on `stream`.  Where a call takes n and m, d_a holds m columns of n elements, column stride n.  n * m = 0 (n = 0 where
+ * there is no m) is H2_OK and enqueues nothing.  A null d_a, constant, table or d_b, a curve id out of range, a pointwise
+ * op outside 0..2 and a period that is zero or no power of two are H2_EINVAL, checked on the host before anything is
+ * enqueued and BEFORE the length is looked at: n * m = 0 with one of these is H2_EINVAL, not H2_OK
+ * (tests/test_gpu_poly_elementwise.py pins all of this). */
+/* a[i] *= c for every i < n * m: the columns are one flat run, m only multiplies the length */
 int h2_poly_scale_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t c[4], void* stream);
-/* a[i] *= g^i : distribute_powers_zeta / the coset shift before an extended-domain NTT (and its inverse) */
+/* a[col][i] *= g^i for i < n, the exponent restarting at 0 in every column: distribute_powers_zeta / the coset shift
+ * before an extended-domain NTT (and its inverse) */
 int h2_poly_coset_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const uint64_t g[4], void* stream);
-/* a[i] *= t[i mod period], period a power of two: divide_by_vanishing_poly with t = t_evaluations */
+/* a[i] *= t[i mod period], period a power of two (else H2_EINVAL): divide_by_vanishing_poly with t = t_evaluations.
+ * The index i runs over the FLATTENED n * m elements: column c starts at t[(c * n) mod period], which is t[0] -- the
+ * per-column meaning a[col][i] *= t[i mod period] -- exactly when the period divides n.  A period above n * m is legal
+ * (no wrap); d_t holds `period` elements and is only read. */
 int h2_poly_mul_periodic_device(h2_curve_t curve, void* d_a, size_t n, size_t m, const void* d_t, size_t period,
                                 void* stream);
-/* a[i] = 1 / a[i] over n elements (zero stays zero): the permutation argument's denominators */
+/* a[i] = 1 / a[i] over n elements; a zero element is left as zero, whatever its neighbours hold: the permutation
+ * argument's denominators.  There is no m: several columns are one call with n the total. */
 int h2_poly_inverse_device(h2_curve_t curve, void* d_a, size_t n, void* stream);
-/* a[i] = a[i] op b[i] over n elements; op 0 = add, 1 = sub, 2 = mul */
+/* a[i] = a[i] op b[i] over n elements; op 0 = add, 1 = sub, 2 = mul, any other op is H2_EINVAL.  d_b == d_a is legal
+ * (2a, 0, a^2); d_b is only read. */
 int h2_poly_pointwise_device(h2_curve_t curve, int op, void* d_a, const void* d_b, size_t n, void* stream);
 /* q = (a - a(z)) / (X - z) over n coefficients, q[n-1] = 0: halo2_proofs src/arithmetic.rs `kate_division(a, z)`
  * (the witness polynomials of the GWC / SHPLONK openings).  d_q must not alias d_a. */

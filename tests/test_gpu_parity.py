@@ -116,6 +116,162 @@ def test_scaled_ntt_all_plan_shapes(h2, curve):
             assert np.array_equal(d2.cpu().numpy().view(np.uint64), plain), log_n
 
 
+# ------------------------------------------------------- structured columns through the plain pass ----
+# The pass's magnitude analysis (the header comment of csrc/h2_ntt29.hpp) is written for worst cases: inputs below 3p/2,
+# |x| <= 18p after the five double stages of a tile, a canonicalisation table indexed by the signed top limb.  The pass
+# works on the STORED integer (x 2^256 mod p, never converted), so the bounds are about the stored limbs: the "raw" columns
+# below store the integer p - 1 itself, the top of the canonical range -- the field value (p - 1) / 2^256.  A raw column of
+# p - 1 makes the first, all-ones stage add four stored values of one sign at full magnitude; random data essentially never
+# does.  The columns without "raw" hold the field VALUE p - 1, whose stored integer p - (2^256 mod p) is 0.71 p on BN254
+# and about 2^128 on the Pasta fields (a low-magnitude column with the upper limbs empty).  A delta makes every output a
+# bare twiddle; the alternating and half-filled columns cancel or pile up whole stages.
+# Closed forms (omega = w, n = 2^log_n, c the column's field value: p - 1, or (p - 1) / 2^256 for a raw column):
+#   constant c           ->  [n c, 0, 0, ...]
+#   delta at j           ->  A[k] = w^(j k)
+#   c at the odd rows    ->  A[0] = c n/2, A[n/2] = -c n/2, 0 elsewhere;   c at the even rows -> A[0] = A[n/2] = c n/2
+#   c on the first half  ->  A[0] = c n/2, A[k] = 0 for even k > 0, A[k] = 2 c / (1 - w^k) for odd k
+STRUCTURED = ["all p-1", "zero", "all mid", "delta 0", "delta 1", "delta n-1", "0, p-1", "p-1, 0", "half",
+              "raw all p-1", "raw 0, p-1", "raw p-1, 0", "raw half"]
+
+
+def raw_limbs(v):
+    """the integer v as the four stored limbs, no Montgomery conversion"""
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+def structured_column(curve, log_n, name):
+    """(n, 4) limbs of the named column; "all p-1" is the constant column c = p - 1, "all mid" a second constant,
+    (p - 1) / 2; a "raw" column stores the integer p - 1 where its namesake stores the Montgomery form of p - 1"""
+    f = scalar_field(curve)
+    n = 1 << log_n
+    lim = lambda v: np.array(f.limbs(v), dtype=np.uint64)  # noqa: E731
+    top = lim(f.p - 1)
+    if name.startswith("raw "):
+        name, top = name[4:], raw_limbs(f.p - 1)
+    a = np.zeros((n, 4), dtype=np.uint64)
+    if name == "all p-1":
+        a[:] = top
+    elif name == "all mid":
+        a[:] = lim((f.p - 1) // 2)
+    elif name.startswith("delta"):
+        a[{"0": 0, "1": 1, "n-1": n - 1}[name.split()[1]]] = lim(1)
+    elif name == "0, p-1":
+        a[1::2] = top
+    elif name == "p-1, 0":
+        a[0::2] = top
+    elif name == "half":
+        a[: n // 2] = top
+    else:
+        assert name == "zero"
+    return a
+
+
+def structured_closed_form(curve, log_n, name):
+    """the transform of the named column under omega(log_n), as (n, 4) limbs"""
+    f = scalar_field(curve)
+    p, n = f.p, 1 << log_n
+    c, w = p - 1, f.omega(log_n)
+    if name.startswith("raw "):
+        name, c = name[4:], (p - 1) * f.Rinv % p
+    pw = [1] * n
+    for k in range(1, n):
+        pw[k] = pw[k - 1] * w % p
+    out = [0] * n
+    if name.startswith("all"):
+        out[0] = n * (c if name == "all p-1" else (p - 1) // 2) % p
+    elif name.startswith("delta"):
+        j = {"0": 0, "1": 1, "n-1": n - 1}[name.split()[1]]
+        out = [pw[j * k % n] for k in range(n)]
+    elif name == "0, p-1":
+        out[0], out[n // 2] = c * (n // 2) % p, -c * (n // 2) % p
+    elif name == "p-1, 0":
+        out[0] = out[n // 2] = c * (n // 2) % p
+    elif name == "half":
+        out = [0 if k % 2 == 0 else 2 * c * pow(1 - pw[k], -1, p) % p for k in range(n)]
+        out[0] = c * (n // 2) % p
+    else:
+        assert name == "zero"
+    return np.array([f.limbs(v) for v in out], dtype=np.uint64)
+
+
+def _structured_cases(small, large):
+    """(curve, log n, columns): all nine columns in one case up to log n = 16 on the three fields; above that one field
+    and one column per case (a reference transform of 2^21 rows takes about a second)"""
+    cases = [(curve, log_n, tuple(STRUCTURED)) for curve in CURVES for log_n in small]
+    cases += [("pallas", log_n, (name,)) for log_n in large for name in STRUCTURED]
+    return cases
+
+
+def _structured_id(v):
+    return v if isinstance(v, str) else str(v) if isinstance(v, int) else ("all" if len(v) > 1 else v[0].replace(" ", ""))
+
+
+@pytest.mark.parametrize("curve,log_n,names", _structured_cases((4, 9, 10, 11, 16), (19, 21)), ids=_structured_id)
+def test_ntt_structured_columns(h2, curve, log_n, names):
+    """h2_ntt_device on worst-case columns, bytewise against the oracle's best_fft, and against the closed form where
+    log n <= 11 so that the oracle is not the only witness.  log n = 4: the unfused tile; 9, 10: one pass, odd and even
+    radix; 11: two passes, a small second radix; 16: two passes, twiddles in LDS; on one field 19 (the 1024-row tile with
+    twiddles in global memory) and 21 (three passes)."""
+    import torch
+    n = 1 << log_n
+    fid = O.CURVE_SCALAR_FIELD[CID[curve]]
+    w = omega_limbs(curve, log_n)
+    for name in names:
+        a = structured_column(curve, log_n, name)
+        want = O.best_fft(fid, a, w, log_n, threads=8).reshape(n, 4)
+        d = torch.from_numpy(a.view(np.int64)).cuda()
+        h2.ntt_device(d.data_ptr(), 1, w, log_n, curve)
+        torch.cuda.synchronize()
+        got = d.cpu().numpy().view(np.uint64)
+        assert np.array_equal(got, want), name
+        if log_n <= 11:
+            assert np.array_equal(got, structured_closed_form(curve, log_n, name)), name
+        if name == "zero":
+            assert not got.any()
+
+
+@pytest.mark.parametrize("curve,log_n,names", _structured_cases((9, 11, 16), (21,)), ids=_structured_id)
+def test_scaled_ntt_structured_columns(h2, curve, log_n, names):
+    """the same columns through h2_ntt_scaled_device with the inverse omega, one plan per place the scale can take (the
+    final pass's product at 9 and 21, the inter-pass twiddles at 11 and 16); the scale is 1/n and p - 1.  As above, the
+    three fields up to log n = 16 and one field at 21."""
+    import ctypes
+    import torch
+    f = scalar_field(curve)
+    n = 1 << log_n
+    fid = O.CURVE_SCALAR_FIELD[CID[curve]]
+    w = omega_limbs(curve, log_n, inverse=True)
+    L = h2.load()
+    for name in names:
+        a = structured_column(curve, log_n, name)
+        plain = O.best_fft(fid, a, w, log_n, threads=8)
+        for c in (pow(n, -1, f.p), f.p - 1):
+            cm = np.array(f.limbs(c), dtype=np.uint64)
+            d = torch.from_numpy(a.view(np.int64)).cuda()
+            assert L.h2_ntt_scaled_device(CID[curve], ctypes.c_void_p(d.data_ptr()), 1, w.ctypes.data, log_n,
+                                          cm.ctypes.data, None) == 0
+            torch.cuda.synchronize()
+            want = O.field_mul_many(fid, plain, np.tile(cm, n)).reshape(n, 4)
+            assert np.array_equal(d.cpu().numpy().view(np.uint64), want), (name, hex(c))
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_ntt_batch_extreme_column_beside_a_random_one(h2, curve):
+    """one h2_ntt_batch call over a column of stored p - 1 (the top of the canonical range), a random column and a column
+    of zeros: the extreme columns come out as the oracle has them and do not disturb their neighbour"""
+    log_n = 12
+    n = 1 << log_n
+    f = scalar_field(curve)
+    fid = O.CURVE_SCALAR_FIELD[CID[curve]]
+    w = omega_limbs(curve, log_n)
+    cols = [np.tile(raw_limbs(f.p - 1), (n, 1)), rand_scalars(curve, n, seed=0x77), np.zeros((n, 4), dtype=np.uint64)]
+    want = [O.best_fft(fid, c, w, log_n).reshape(n, 4) for c in cols]
+    h2.best_fft_batch(cols, w, log_n, curve)
+    for j in range(3):
+        assert np.array_equal(cols[j], want[j]), j
+    assert not cols[2].any() and not cols[0][1:].any()
+
+
 # ---------------------------------------------------------------------- group-element FFT ----
 def _affine_to_jac(curve, aff):
     """(n, 8) affine points -> (n, 12) Jacobian with z = 1 (Montgomery), identity (0, 0) -> z = 0"""

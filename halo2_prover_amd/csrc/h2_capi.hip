@@ -1853,49 +1853,6 @@ int h2_chacha20_scalars_device(h2_curve_t curve, const uint8_t seed[32], uint64_
 static_assert(H2_IPA_MAX_K == IPA_MAX_K, "the header states the kernels' maximum");
 static bool ipa_dev_ptr(const void* p) { return p && !((uintptr_t)p & 15); }
 
-int h2_ipa_state_bytes(uint32_t k, size_t* out) {
-  if (k == 0 || k > IPA_MAX_K || !out) return H2_EINVAL;
-  *out = IpaLayout(k).total * 32;
-  return H2_OK;
-}
-
-int h2_ipa_begin_device(h2_curve_t curve, uint32_t k_, const void* d_p, const uint64_t x3[4], void* d_state, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !ipa_dev_ptr(d_p) || !ipa_dev_ptr(d_state) || !x3) return H2_EINVAL;
-  return launched(ops_of((int)curve)->ipa_begin(d_p, x3, k_, d_state, k.stream), "ipa_begin_kernel");
-}
-
-int h2_ipa_round_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uint32_t j, void* d_state, const uint64_t* u_prev,
-                        const uint64_t* u_prev_inv, const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4],
-                        void* d_out_affine, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || j >= k_) return H2_EINVAL;
-  if (!ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_out_affine) || !z || !l_blind || !r_blind) return H2_EINVAL;
-  if (j == 0 ? (u_prev || u_prev_inv) : (!u_prev || !u_prev_inv)) return H2_EINVAL;
-  const IpaLayout L(k_);
-  const BasesEntry* be = nullptr;
-  if (int rc = msm_common_checks((int)curve, bases, 0, L.col_stride, 2, &be); rc != H2_OK) return rc;
-  if (be->n != L.col_stride) return H2_EINVAL;          // exactly G || U || W
-  if (int rc = launched(ops_of((int)curve)->ipa_round(k_, j, d_state, u_prev, u_prev_inv, z, l_blind, r_blind, k.stream),
-                        "ipa_round_kernel");
-      rc != H2_OK)
-    return rc;
-  return msm_device_run(*k.c, (int)curve, *be, (const char*)d_state + L.col * 32, 0, L.col_stride, L.col_stride, 2, d_out_affine,
-                        true, k.stream);
-}
-
-int h2_ipa_final_device(h2_curve_t curve, uint32_t k_, void* d_state, const uint64_t u_last[4], const uint64_t u_last_inv[4],
-                        void* d_out, void* d_s_out, void* stream_) {
-  Call k(stream_);
-  if (k.rc != H2_OK) return k.rc;
-  if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || !ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_out) || !u_last || !u_last_inv)
-    return H2_EINVAL;
-  if (d_s_out && ((uintptr_t)d_s_out & 15)) return H2_EINVAL;
-  return launched(ops_of((int)curve)->ipa_final(k_, d_state, u_last, u_last_inv, d_out, d_s_out, k.stream), "ipa_final_kernel");
-}
-
 int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k_, const uint64_t init[4], void* d_out,
                                      void* stream_) {
   Call k(stream_);
@@ -1951,7 +1908,7 @@ int h2_ipa_challenge_products_sum_device(h2_curve_t curve, const uint64_t* u, co
   return A.release();
 }
 
-// ---- m openings in lockstep (h2_ipa.hpp, IpaBatchLayout) -------------------------------------------------------------------
+// ---- the prover's rounds: m openings in lockstep (h2_ipa.hpp, IpaBatchLayout); the single calls are m = 1 -----------------
 static_assert(H2_IPA_MAX_BATCH == IPA_MAX_BATCH, "the header states the kernels' maximum");
 
 int h2_ipa_batch_state_bytes(uint32_t k, size_t m, size_t* out) {
@@ -1960,12 +1917,22 @@ int h2_ipa_batch_state_bytes(uint32_t k, size_t m, size_t* out) {
   return H2_OK;
 }
 
-// The call's scalar table: rows[r] holds m x 4 limbs (null: a row of zeros) and becomes row r of the table at the end of the
-// state; `ptrs` (begin only) are the m device pointers stored behind row 0.  One copy, enqueued before the call's kernels.
-static int ipa_batch_table(const IpaBatchLayout& L, const uint64_t* const* rows, size_t n_rows, const void* const* ptrs, void* d_state,
-                           hipStream_t stream) {
-  uint64_t host[IPA_BATCH_SCALARS * IPA_MAX_BATCH * 4];
+int h2_ipa_state_bytes(uint32_t k, size_t* out) { return h2_ipa_batch_state_bytes(k, 1, out); }
+
+// The call's scalars: rows[r] holds m x 4 limbs (null: a row of zeros); `ptrs` (begin only) are the m device pointers.  For
+// m >= 2 they become the table at the end of the state, the pointers behind row 0: one copy, enqueued before the call's
+// kernels.  For m = 1 they go into `one`, which travels in the kernels' arguments, and nothing is enqueued.
+static int ipa_scalars(const IpaBatchLayout& L, const uint64_t* const* rows, size_t n_rows, const void* const* ptrs, void* d_state,
+                       hipStream_t stream, IpaOne& one) {
   const size_t m = L.m;
+  memset(&one, 0, sizeof one);
+  if (m == 1) {
+    for (size_t r = 0; r < n_rows; r++)
+      if (rows[r]) memcpy(one.v[r], rows[r], 32);
+    if (ptrs) one.p = ptrs[0];
+    return H2_OK;
+  }
+  uint64_t host[IPA_BATCH_SCALARS * IPA_MAX_BATCH * 4];
   for (size_t r = 0; r < n_rows; r++) {
     if (rows[r])
       memcpy(host + r * m * 4, rows[r], m * 32);
@@ -1992,8 +1959,9 @@ int h2_ipa_begin_batch_device(h2_curve_t curve, uint32_t k_, size_t m, const voi
     if (!ipa_dev_ptr(d_p[i])) return H2_EINVAL;
   const IpaBatchLayout L(k_, m);
   const uint64_t* rows[1] = {x3};
-  if (int rc = ipa_batch_table(L, rows, 1, d_p, d_state, k.stream); rc != H2_OK) return rc;
-  return launched(ops_of((int)curve)->ipa_begin_batch(k_, m, d_state, k.stream), "ipa_begin_batch_kernel");
+  IpaOne one;
+  if (int rc = ipa_scalars(L, rows, 1, d_p, d_state, k.stream, one); rc != H2_OK) return rc;
+  return launched(ops_of((int)curve)->ipa_begin(k_, m, one, d_state, k.stream), "ipa_begin_kernel");
 }
 
 int h2_ipa_round_batch_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uint32_t j, size_t m, void* d_state,
@@ -2011,24 +1979,48 @@ int h2_ipa_round_batch_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uin
   // the MSM's own refusals before the table copy and the kernels in front of it: nothing is enqueued for a refused call
   if (int rc = msm_device_plan_check(*be, L.col_stride, L.col_stride, 2 * m); rc != H2_OK) return rc;
   const uint64_t* rows[IPA_BATCH_SCALARS] = {u_prev, u_prev_inv, z, l_blind, r_blind};
-  if (int rc = ipa_batch_table(L, rows, IPA_BATCH_SCALARS, nullptr, d_state, k.stream); rc != H2_OK) return rc;
-  if (int rc = launched(ops_of((int)curve)->ipa_round_batch(k_, j, m, d_state, k.stream), "ipa_round_batch_kernel"); rc != H2_OK)
-    return rc;
+  IpaOne one;
+  if (int rc = ipa_scalars(L, rows, IPA_BATCH_SCALARS, nullptr, d_state, k.stream, one); rc != H2_OK) return rc;
+  if (int rc = launched(ops_of((int)curve)->ipa_round(k_, j, m, one, d_state, k.stream), "ipa_round_kernel"); rc != H2_OK) return rc;
   return msm_device_run(*k.c, (int)curve, *be, (const char*)d_state + L.col * 32, 0, L.col_stride, L.col_stride, 2 * m, d_out_affine,
                         true, k.stream);
 }
 
-int h2_ipa_final_batch_device(h2_curve_t curve, uint32_t k_, size_t m, void* d_state, const uint64_t* u_last,
-                              const uint64_t* u_last_inv, void* d_out, void* stream_) {
+// d_s_out: m x 2^k elements or null; only h2_ipa_final_device has an argument for it
+static int ipa_final_run(h2_curve_t curve, uint32_t k_, size_t m, void* d_state, const uint64_t* u_last, const uint64_t* u_last_inv,
+                         void* d_out, void* d_s_out, void* stream_) {
   Call k(stream_);
   if (k.rc != H2_OK) return k.rc;
   if (!curve_ok((int)curve) || k_ == 0 || k_ > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH || !ipa_dev_ptr(d_state) ||
       !ipa_dev_ptr(d_out) || !u_last || !u_last_inv)
     return H2_EINVAL;
+  if (d_s_out && ((uintptr_t)d_s_out & 15)) return H2_EINVAL;
   const IpaBatchLayout L(k_, m);
   const uint64_t* rows[2] = {u_last, u_last_inv};
-  if (int rc = ipa_batch_table(L, rows, 2, nullptr, d_state, k.stream); rc != H2_OK) return rc;
-  return launched(ops_of((int)curve)->ipa_final_batch(k_, m, d_state, d_out, k.stream), "ipa_final_batch_kernel");
+  IpaOne one;
+  if (int rc = ipa_scalars(L, rows, 2, nullptr, d_state, k.stream, one); rc != H2_OK) return rc;
+  return launched(ops_of((int)curve)->ipa_final(k_, m, one, d_state, d_out, d_s_out, k.stream), "ipa_final_kernel");
+}
+
+int h2_ipa_final_batch_device(h2_curve_t curve, uint32_t k_, size_t m, void* d_state, const uint64_t* u_last,
+                              const uint64_t* u_last_inv, void* d_out, void* stream_) {
+  return ipa_final_run(curve, k_, m, d_state, u_last, u_last_inv, d_out, nullptr, stream_);
+}
+
+// the single opening: the batch of one
+int h2_ipa_begin_device(h2_curve_t curve, uint32_t k_, const void* d_p, const uint64_t x3[4], void* d_state, void* stream_) {
+  return h2_ipa_begin_batch_device(curve, k_, 1, &d_p, x3, d_state, stream_);
+}
+
+int h2_ipa_round_device(h2_curve_t curve, uint64_t bases, uint32_t k_, uint32_t j, void* d_state, const uint64_t* u_prev,
+                        const uint64_t* u_prev_inv, const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4],
+                        void* d_out_affine, void* stream_) {
+  return h2_ipa_round_batch_device(curve, bases, k_, j, 1, d_state, u_prev, u_prev_inv, z, l_blind, r_blind, d_out_affine, stream_);
+}
+
+int h2_ipa_final_device(h2_curve_t curve, uint32_t k_, void* d_state, const uint64_t u_last[4], const uint64_t u_last_inv[4],
+                        void* d_out, void* d_s_out, void* stream_) {
+  return ipa_final_run(curve, k_, 1, d_state, u_last, u_last_inv, d_out, d_s_out, stream_);
 }
 
 // ---- the transcript midstate (host only) ---------------------------------------------------------------------------------

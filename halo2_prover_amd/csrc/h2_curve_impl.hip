@@ -564,8 +564,8 @@ constexpr decltype(CurveOps::ipa_verify_finish) IPA_VERIFY_FINISH = ipa_verify_f
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, base_sqrt_, pasta_points_decompress, selftest_base_sqrt, selftest_pasta_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
-                      poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_launch<FS>, ipa_round_launch<FS>, ipa_final_launch<FS>,
-                      ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, ipa_begin_batch_launch<FS>, ipa_round_batch_launch<FS>, ipa_final_batch_launch<FS>, IPA_REPLAY, IPA_VERIFY_PREPARE, IPA_VERIFY_FINISH, selftest_field, selftest_curve,
+                      poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_batch_launch<FS>, ipa_round_batch_launch<FS>, ipa_final_batch_launch<FS>,
+                      ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, IPA_REPLAY, IPA_VERIFY_PREPARE, IPA_VERIFY_FINISH, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate,
                       chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device};
 

@@ -13,6 +13,7 @@ struct MsmGeom;
 struct MsmWorkspace;
 struct LookupWorkspace;
 struct PermWorkspace;
+struct IpaOne;
 
 // one evaluation: the polynomial's coefficients in HBM (API form, 16-byte aligned) and the point's 8 x 32-bit
 // Montgomery limbs.  The poly_eval kernels read a table of these from HBM (h2_poly.hpp)
@@ -156,25 +157,20 @@ struct CurveOps {
                             uint32_t count, size_t lds_bytes, hipStream_t s);
   // d_out[i] = Scalar::random of ChaCha20 block first_block + i (key = the 32 seed bytes as 8 little-endian words)
   hipError_t (*chacha20_scalars)(void* d_out, size_t n, uint64_t first_block, const uint32_t key[8], hipStream_t s);
-  // the inner product argument on the registered generators (h2_ipa.hpp); d_state: IpaLayout(k).total elements, 1 <= k <=
-  // IPA_MAX_K.  ipa_begin: a = the 2^k coefficients d_p, b = the powers of x3, s = [1].  ipa_round: for j > 0 the fold by
-  // u_prev, then both columns of 2^k + 2 scalars (the caller runs the MSM on them).  ipa_final: the last fold, d_out = c || b[0],
-  // d_s_out (optional) = the finished s in natural order.  ipa_s_products: compute_s(u, init), u: k x 4 limbs on the host
-  hipError_t (*ipa_begin)(const void* d_p, const uint64_t x3[4], uint32_t k, void* d_state, hipStream_t s);
-  hipError_t (*ipa_round)(uint32_t k, uint32_t j, void* d_state, const uint64_t* u_prev, const uint64_t* u_prev_inv,
-                          const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4], hipStream_t s);
-  hipError_t (*ipa_final)(uint32_t k, void* d_state, const uint64_t u[4], const uint64_t uinv[4], void* d_out, void* d_s_out,
-                          hipStream_t s);
+  // the inner product argument on the registered generators (h2_ipa.hpp): m <= IPA_MAX_BATCH openings of one k <= IPA_MAX_K
+  // in lockstep, a single opening being m = 1; d_state: IpaBatchLayout(k, m).total elements.  The call's scalars: for
+  // m >= 2 the state's table, already filled by a copy enqueued on s; for m = 1 `one`.  One launch of each kernel serves all
+  // m.  ipa_begin: a_i = the 2^k coefficients d_p[i], b_i = the powers of x3_i, s_i = [1].  ipa_round: for j > 0 the fold by
+  // u_prev, then the 2 m columns of 2^k + 2 scalars (the caller runs the MSM on them).  ipa_final: the last fold, d_out =
+  // m x (c_i || b_i[0]), d_s_out (optional) = m x the finished s in natural order
+  hipError_t (*ipa_begin)(uint32_t k, size_t m, const IpaOne& one, void* d_state, hipStream_t s);
+  hipError_t (*ipa_round)(uint32_t k, uint32_t j, size_t m, const IpaOne& one, void* d_state, hipStream_t s);
+  hipError_t (*ipa_final)(uint32_t k, size_t m, const IpaOne& one, void* d_state, void* d_out, void* d_s_out, hipStream_t s);
+  // ipa_s_products: compute_s(u, init), u: k x 4 limbs on the host
   hipError_t (*ipa_s_products)(const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out, hipStream_t s);
   // the sum of `count` <= IPA_SUM_GROUP compute_s vectors from the table ipa_sum_fill made of them (d_table, in HBM), added
   // to what d_out holds when `accumulate`
   hipError_t (*ipa_s_sum)(const void* d_table, uint32_t count, uint32_t k, void* d_out, bool accumulate, hipStream_t s);
-  // m <= IPA_MAX_BATCH openings of one k in lockstep; d_state: IpaBatchLayout(k, m).total elements, its scalar table already
-  // filled for this call by a copy enqueued on s.  One launch of each kernel serves all m; the caller runs the round's MSM
-  // of 2 m columns.  ipa_final_batch: d_out = m x (c_i || b_i[0])
-  hipError_t (*ipa_begin_batch)(uint32_t k, size_t m, void* d_state, hipStream_t s);
-  hipError_t (*ipa_round_batch)(uint32_t k, uint32_t j, size_t m, void* d_state, hipStream_t s);
-  hipError_t (*ipa_final_batch)(uint32_t k, size_t m, const void* d_state, void* d_out, hipStream_t s);
   // the IPA batch verifier's kernels (h2_ipa_verify.hpp).  ipa_replay: the transcripts of `count` proofs, one lane each
   // (h2_ipa_replay_device's arguments); NULL for BN254, whose wire form the batch verifier does not take.
   // ipa_verify_prepare: the replay's rows, x3, v and count x 8 words of weights -> the points MSM's scalar column, the sum

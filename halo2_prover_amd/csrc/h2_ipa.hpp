@@ -9,9 +9,10 @@
 // round is one two-column MSM of n + 2 terms on the table registered once as G || U || W (slot n: z <a, b>, slot n + 1: the
 // blind) plus the kernels below, O(n) field products.
 //
-// State (caller-owned, IpaLayout): a and b in two generations each (generation g = a after g folds, 2^(k-g) elements: even
-// generations in a buffer of n, odd ones in a buffer of n / 2 -- the round kernel reads one and writes the other, so its
-// threads never race), the table s, the two columns of n + 2, one partial pair per workgroup of the inner products.
+// State (caller-owned, IpaBatchLayout; a single opening is a batch of one).  Per opening: a and b in two generations each
+// (generation g = a after g folds, 2^(k-g) elements: even generations in a buffer of n, odd ones in a buffer of n / 2 -- the
+// round kernel reads one and writes the other, so its threads never race), the table s, one partial pair per workgroup of
+// the inner products; behind the openings the two columns of n + 2 of each.
 // s is kept in the APPEND-ONLY order S[rev_j(h)] = s^(j)[h] (rev_j: the low j bits reversed): doubling the table is
 // S[2^j + g] = S[g] u_j, which reads [0, 2^j) and writes [2^j, 2^(j+1)) -- no race, nothing moves.
 //
@@ -41,53 +42,40 @@ constexpr uint32_t IPA_MAX_K = 20;          // H2_IPA_MAX_K of the C ABI
 constexpr int IPA_THREADS = 256;
 constexpr uint32_t IPA_H_PER = 2;           // copies (values of h) one thread of the round kernel writes
 
-// the caller's state buffer, in 32-byte elements
-struct IpaLayout {
-  size_t n, hn, a[2], b[2], s, col, col_stride, partial, partials, total;
-  explicit IpaLayout(uint32_t k) {
-    n = (size_t)1 << k;
-    hn = n / 2;                              // >= 1
-    a[0] = 0;
-    a[1] = n;
-    b[0] = n + hn;
-    b[1] = 2 * n + hn;
-    s = 2 * n + 2 * hn;
-    col = 3 * n + 2 * hn;
-    col_stride = n + 2;
-    partial = col + 2 * col_stride;
-    partials = (hn + IPA_THREADS - 1) / IPA_THREADS;     // workgroups of the first round that hold an inner product
-    total = partial + 2 * partials;
-  }
-};
-
-// m openings of one k in lockstep (h2_ipa_*_batch_device), in 32-byte elements.  Opening i owns the `per` elements from
-// i * per: a and b in two generations each, S, its partial pairs (a, b, s, partial are offsets INSIDE an opening).  Behind
-// the m openings ONE block of 2 m columns at the uniform stride n + 2, ordered L_0, R_0, L_1, R_1, ...: one MSM of 2 m columns
-// writes m x (L_i || R_i).  Last the table of per-opening scalars, IPA_BATCH_SCALARS rows of m elements, which every call
-// fills from the host before its kernels (begin: x3, then the m pointers d_p in row 1; round: u, 1/u, z, l_blind, r_blind;
-// final: u, 1/u).
+// The caller's state buffer: m openings of one k in lockstep, in 32-byte elements; a single opening is m = 1.  Opening i
+// owns the `per` elements from i * per: a and b in two generations each, S, its partial pairs (a, b, s, partial are offsets
+// INSIDE an opening).  Behind the m openings ONE block of 2 m columns at the uniform stride n + 2, ordered L_0, R_0, L_1,
+// R_1, ...: one MSM of 2 m columns writes m x (L_i || R_i).  Last the table of per-opening scalars, IPA_BATCH_SCALARS rows of
+// m elements, which every call of m >= 2 fills from the host before its kernels (begin: x3, then the m pointers d_p in row 1;
+// round: u, 1/u, z, l_blind, r_blind; final: u, 1/u).  At m = 1 the table is there and nothing touches it (IpaOne).
 constexpr size_t IPA_MAX_BATCH = 64;        // H2_IPA_MAX_BATCH of the C ABI
 constexpr size_t IPA_BATCH_SCALARS = 5;
 struct IpaBatchLayout {
   size_t n, hn, m, a[2], b[2], s, partial, partials, per, col, col_stride, scal, total;
   IpaBatchLayout(uint32_t k, size_t m_) {
-    const IpaLayout one(k);
-    n = one.n;
-    hn = one.hn;
+    n = (size_t)1 << k;
+    hn = n / 2;                              // >= 1
     m = m_;
-    a[0] = one.a[0];
-    a[1] = one.a[1];
-    b[0] = one.b[0];
-    b[1] = one.b[1];
-    s = one.s;
-    partial = one.col;                       // the columns have left the opening: the partial pairs follow S
-    partials = one.partials;
+    a[0] = 0;
+    a[1] = n;
+    b[0] = n + hn;
+    b[1] = 2 * n + hn;
+    s = 2 * n + 2 * hn;
+    partial = 3 * n + 2 * hn;
+    partials = (hn + IPA_THREADS - 1) / IPA_THREADS;     // workgroups of the first round that hold an inner product
     per = partial + 2 * partials;
     col = m * per;
-    col_stride = one.col_stride;
+    col_stride = n + 2;
     scal = col + 2 * m * col_stride;
     total = scal + IPA_BATCH_SCALARS * m;
   }
+};
+
+// The table's rows for a batch of ONE, by value in every kernel's arguments: the call's scalars (Montgomery limbs) and d_p.
+// The host fills it instead of the table and enqueues no copy; the kernels take the argument when L.m == 1 (ipa_scalar).
+struct IpaOne {
+  uint32_t v[IPA_BATCH_SCALARS][8];
+  const void* p;
 };
 
 // h2_ipa_begin_device: a = p, b[i] = x3^i (each thread POLY_RUN-style runs of 8 from x3^first), S[0] = 1
@@ -104,11 +92,6 @@ __device__ __forceinline__ void ipa_begin_body(const U128* __restrict__ p, U128*
     fe_store<FP>(b + 2 * (first + q), cur);
     cur = fe_mul(cur, x3);
   }
-}
-template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_begin_kernel(const U128* __restrict__ p, U128* __restrict__ a, U128* __restrict__ b, U128* __restrict__ s, size_t n, Fe<FP> x3) {
-  ipa_begin_body<FP>(p, a, b, s, n, x3);
 }
 
 // the table of challenge products doubles: S[count + g] = S[g] u for g < count.  With set_init (count = 1) S[0] = init
@@ -237,10 +220,6 @@ __device__ __forceinline__ void ipa_round_body(const IpaRound<FP>& A) {
     fe_store<FP>(A.partial + 2 * ((size_t)blockIdx.x * 2 + threadIdx.x), fe29_canonical_pack(fe29_mul(fe29_norm(acc), one)));
   }
 }
-template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(IpaRound<FP> A) {
-  ipa_round_body<FP>(A);
-}
 
 // one workgroup: the sums of the `count` partial pairs times z into slot n of the columns, the blinds into slot n + 1
 template <class FP>
@@ -279,12 +258,6 @@ __device__ __forceinline__ void ipa_finish_body(const U128* __restrict__ partial
     fe_store<FP>(tailR + 2, r_blind);
   }
 }
-template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_finish_kernel(const U128* __restrict__ partial, uint32_t count, Fe<FP> z, Fe<FP> l_blind, Fe<FP> r_blind,
-                  U128* __restrict__ tailL, U128* __restrict__ tailR) {
-  ipa_finish_body<FP>(partial, count, z, l_blind, r_blind, tailL, tailR);
-}
 
 // h2_ipa_final_device: the last fold, c = a[0] + a[1] / u and b[0] + b[1] u (thread 0), and the finished table in natural
 // order, s[i] = S[rev_k(i)], when the caller wants it
@@ -300,52 +273,46 @@ __device__ __forceinline__ void ipa_final_body(const U128* __restrict__ a, const
   if (s_out && T < ((size_t)1 << k))
     fe_store<FP>(s_out + 2 * T, fe_load<FP>(S + 2 * (size_t)(__brev((uint32_t)T) >> (32 - k))));
 }
-template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS)
-ipa_final_kernel(const U128* __restrict__ a, const U128* __restrict__ b, const U128* __restrict__ S, Fe<FP> u, Fe<FP> uinv,
-                 uint32_t k, U128* __restrict__ out, U128* __restrict__ s_out) {
-  ipa_final_body<FP>(a, b, S, u, uinv, k, out, s_out);
-}
 
-// ---- the batch forms: blockIdx.y is the opening, the bodies are the ones above (the doubling of S is restated: it has no
-// set_init form here) --------------------------------------------------------------------------------------------------------
-// An opening's scalars come from the table at the end of the state (IpaBatchLayout).  No kernel writes the table and a
-// workgroup works on one opening, so the address is the same in every lane: the loads go through the constant address
-// space, which the back end serves with scalar loads (poseidon_const's way).  Everything else -- the arithmetic, the
-// uniform early return of the inner-product reduction, the fixed order of the partial sums -- is per opening what the
-// single-opening kernels do, so every output bit is theirs.
+// ---- the kernels: blockIdx.y is the opening, blockIdx.x what the bodies above take it for -----------------------------------
+// An opening's scalars come from the table at the end of the state (IpaBatchLayout), or at m = 1 from the kernel's
+// arguments (IpaOne); L.m is an argument, so the choice is uniform across the launch.  No kernel writes the table and a
+// workgroup works on one opening, so the table address is the same in every lane: the loads go through the constant
+// address space, which the back end serves with scalar loads (poseidon_const's way), as it does the arguments.
 template <class FP>
-__device__ __forceinline__ Fe<FP> ipa_batch_scalar(const U128* tab, size_t m, size_t row, size_t opening) {
+__device__ __forceinline__ Fe<FP> ipa_scalar(const U128* st, const IpaBatchLayout& L, const IpaOne& one, size_t row,
+                                             size_t opening) {
   typedef const __attribute__((address_space(4))) uint32_t* ConstPtr;
-  const ConstPtr q = (ConstPtr)(const uint32_t*)(tab + 2 * (row * m + opening));
+  const ConstPtr q = (ConstPtr)(const uint32_t*)(st + 2 * (L.scal + row * L.m + opening));
   Fe<FP> r;
 #pragma unroll
-  for (int l = 0; l < 8; l++) r.v[l] = q[l];
+  for (int l = 0; l < 8; l++) r.v[l] = L.m == 1 ? one.v[row][l] : q[l];
   return r;
 }
 
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_begin_batch_kernel(U128* st, IpaBatchLayout L) {
+__global__ void __launch_bounds__(IPA_THREADS) ipa_begin_kernel(U128* st, IpaBatchLayout L, IpaOne one) {
   const size_t o = blockIdx.y;
-  const U128* tab = st + 2 * L.scal;
   typedef const __attribute__((address_space(4))) uint64_t* ConstPtr;
   typedef const __attribute__((address_space(1))) U128* GlobalPtr;       // d_p[o] is device memory: global loads, not flat ones
-  const U128* p = (const U128*)(GlobalPtr)(uintptr_t)((ConstPtr)(const uint64_t*)(tab + 2 * L.m))[o];
+  const uintptr_t p = L.m == 1 ? (uintptr_t)one.p : (uintptr_t)((ConstPtr)(const uint64_t*)(st + 2 * (L.scal + L.m)))[o];
   U128* base = st + 2 * o * L.per;
-  ipa_begin_body<FP>(p, base + 2 * L.a[0], base + 2 * L.b[0], base + 2 * L.s, L.n, ipa_batch_scalar<FP>(tab, L.m, 0, o));
+  ipa_begin_body<FP>((const U128*)(GlobalPtr)p, base + 2 * L.a[0], base + 2 * L.b[0], base + 2 * L.s, L.n,
+                     ipa_scalar<FP>(st, L, one, 0, o));
 }
 
+// S[count + g] = S[g] u per opening: ipa_s_kernel's doubling without its set_init form
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_s_batch_kernel(U128* st, IpaBatchLayout L, uint32_t count) {
+__global__ void __launch_bounds__(IPA_THREADS) ipa_s_double_kernel(U128* st, IpaBatchLayout L, IpaOne one, uint32_t count) {
   const size_t o = blockIdx.y;
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= count) return;
   U128* S = st + 2 * (o * L.per + L.s);
-  fe_store<FP>(S + 2 * ((size_t)count + g), fe_mul(fe_load<FP>(S + 2 * (size_t)g), ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 0, o)));
+  fe_store<FP>(S + 2 * ((size_t)count + g), fe_mul(fe_load<FP>(S + 2 * (size_t)g), ipa_scalar<FP>(st, L, one, 0, o)));
 }
 
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_round_batch_kernel(U128* st, IpaBatchLayout L, uint32_t k, uint32_t j) {
+__global__ void __launch_bounds__(IPA_THREADS) ipa_round_kernel(U128* st, IpaBatchLayout L, IpaOne one, uint32_t k, uint32_t j) {
   const size_t o = blockIdx.y;
   U128* base = st + 2 * o * L.per;
   IpaRound<FP> A;
@@ -356,8 +323,8 @@ __global__ void __launch_bounds__(IPA_THREADS) ipa_round_batch_kernel(U128* st, 
   A.colR = A.colL + 2 * L.col_stride;
   A.partial = base + 2 * L.partial;
   if (j > 0) {
-    A.u = ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 0, o);
-    A.uinv = ipa_batch_scalar<FP>(st + 2 * L.scal, L.m, 1, o);
+    A.u = ipa_scalar<FP>(st, L, one, 0, o);
+    A.uinv = ipa_scalar<FP>(st, L, one, 1, o);
     A.a_old = base + 2 * L.a[(j - 1) & 1];
     A.b_old = base + 2 * L.b[(j - 1) & 1];
     A.a_new = base + 2 * L.a[j & 1];
@@ -373,23 +340,21 @@ __global__ void __launch_bounds__(IPA_THREADS) ipa_round_batch_kernel(U128* st, 
 }
 
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_finish_batch_kernel(U128* st, IpaBatchLayout L, uint32_t count) {
+__global__ void __launch_bounds__(IPA_THREADS) ipa_finish_kernel(U128* st, IpaBatchLayout L, IpaOne one, uint32_t count) {
   const size_t o = blockIdx.y;
-  const U128* tab = st + 2 * L.scal;
   U128* colL = st + 2 * (L.col + 2 * o * L.col_stride);
-  ipa_finish_body<FP>(st + 2 * (o * L.per + L.partial), count, ipa_batch_scalar<FP>(tab, L.m, 2, o),
-                      ipa_batch_scalar<FP>(tab, L.m, 3, o), ipa_batch_scalar<FP>(tab, L.m, 4, o), colL + 2 * L.n,
-                      colL + 2 * (L.col_stride + L.n));
+  ipa_finish_body<FP>(st + 2 * (o * L.per + L.partial), count, ipa_scalar<FP>(st, L, one, 2, o), ipa_scalar<FP>(st, L, one, 3, o),
+                      ipa_scalar<FP>(st, L, one, 4, o), colL + 2 * L.n, colL + 2 * (L.col_stride + L.n));
 }
 
-// d_out: m x (c_i || b_i[0]); the finished table s has no batch form
+// out: m x (c_i || b_i[0]); s_out (or null): m x the finished table of n elements
 template <class FP>
-__global__ void __launch_bounds__(IPA_THREADS) ipa_final_batch_kernel(const U128* st, IpaBatchLayout L, uint32_t k, U128* out) {
+__global__ void __launch_bounds__(IPA_THREADS)
+ipa_final_kernel(const U128* st, IpaBatchLayout L, IpaOne one, uint32_t k, U128* out, U128* s_out) {
   const size_t o = blockIdx.y;
   const U128* base = st + 2 * o * L.per;
-  const U128* tab = st + 2 * L.scal;
-  ipa_final_body<FP>(base + 2 * L.a[(k - 1) & 1], base + 2 * L.b[(k - 1) & 1], base + 2 * L.s, ipa_batch_scalar<FP>(tab, L.m, 0, o),
-                     ipa_batch_scalar<FP>(tab, L.m, 1, o), k, out + 4 * o, nullptr);
+  ipa_final_body<FP>(base + 2 * L.a[(k - 1) & 1], base + 2 * L.b[(k - 1) & 1], base + 2 * L.s, ipa_scalar<FP>(st, L, one, 0, o),
+                     ipa_scalar<FP>(st, L, one, 1, o), k, out + 4 * o, s_out ? s_out + 2 * o * L.n : nullptr);
 }
 
 // ---- launches (one per curve through CurveOps) ----------------------------------------------------------------------------
@@ -400,104 +365,48 @@ inline Fe<FP> ipa_fe(const uint64_t* limbs) {
   return r;
 }
 
+// the launches: for m >= 2 the caller has copied the call's scalar table into the state on `s` (IpaBatchLayout), for m = 1 it
+// has filled `one`; one launch of each kernel serves the m openings
 template <class FP>
-hipError_t ipa_begin_launch(const void* d_p, const uint64_t x3[4], uint32_t k, void* d_state, hipStream_t s) {
-  const IpaLayout L(k);
-  U128* st = (U128*)d_state;
+hipError_t ipa_begin_batch_launch(uint32_t k, size_t m, const IpaOne& one, void* d_state, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
   const size_t threads = (L.n + 7) / 8;
-  hipLaunchKernelGGL(ipa_begin_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s,
-                     (const U128*)d_p, st + 2 * L.a[0], st + 2 * L.b[0], st + 2 * L.s, L.n, ipa_fe<FP>(x3));
+  hipLaunchKernelGGL(ipa_begin_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m), dim3(IPA_THREADS), 0, s,
+                     (U128*)d_state, L, one);
   return hipGetLastError();
 }
 
 template <class FP>
-hipError_t ipa_round_launch(uint32_t k, uint32_t j, void* d_state, const uint64_t* u_prev, const uint64_t* u_prev_inv,
-                            const uint64_t z[4], const uint64_t l_blind[4], const uint64_t r_blind[4], hipStream_t s) {
-  const IpaLayout L(k);
+hipError_t ipa_round_batch_launch(uint32_t k, uint32_t j, size_t m, const IpaOne& one, void* d_state, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
   U128* st = (U128*)d_state;
-  IpaRound<FP> A{};
-  A.k = k;
-  A.j = j;
-  A.S = st + 2 * L.s;
-  A.colL = st + 2 * L.col;
-  A.colR = st + 2 * (L.col + L.col_stride);
-  A.partial = st + 2 * L.partial;
   if (j > 0) {
-    A.u = ipa_fe<FP>(u_prev);
-    A.uinv = ipa_fe<FP>(u_prev_inv);
-    A.a_old = st + 2 * L.a[(j - 1) & 1];
-    A.b_old = st + 2 * L.b[(j - 1) & 1];
-    A.a_new = st + 2 * L.a[j & 1];
-    A.b_new = st + 2 * L.b[j & 1];
     const uint32_t count = 1u << (j - 1);
-    hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, st + 2 * L.s, count,
-                       A.u, Fe<FP>::zero(), 0);
-  } else {
-    A.u = A.uinv = Fe<FP>::zero();
-    A.a_old = st + 2 * L.a[0];
-    A.b_old = st + 2 * L.b[0];
-    A.a_new = nullptr;
-    A.b_new = nullptr;
+    hipLaunchKernelGGL(ipa_s_double_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L,
+                       one, count);
   }
   const size_t half = (size_t)1 << (k - j - 1), nh = (size_t)1 << j;
   const size_t threads = half * ((nh + IPA_H_PER - 1) / IPA_H_PER);
-  hipLaunchKernelGGL(ipa_round_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s, A);
+  hipLaunchKernelGGL(ipa_round_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m), dim3(IPA_THREADS), 0,
+                     s, st, L, one, k, j);
   const uint32_t parts = (uint32_t)((half + IPA_THREADS - 1) / IPA_THREADS);
-  hipLaunchKernelGGL(ipa_finish_kernel<FP>, dim3(1), dim3(IPA_THREADS), 0, s, (const U128*)A.partial, parts, ipa_fe<FP>(z),
-                     ipa_fe<FP>(l_blind), ipa_fe<FP>(r_blind), A.colL + 2 * L.n, A.colR + 2 * L.n);
+  hipLaunchKernelGGL(ipa_finish_kernel<FP>, dim3(1, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L, one, parts);
   return hipGetLastError();
 }
 
+// the last doubling of S only when the finished table is asked for: nothing else reads it any more
 template <class FP>
-hipError_t ipa_final_launch(uint32_t k, void* d_state, const uint64_t u[4], const uint64_t uinv[4], void* d_out, void* d_s_out,
-                            hipStream_t s) {
-  const IpaLayout L(k);
+hipError_t ipa_final_batch_launch(uint32_t k, size_t m, const IpaOne& one, void* d_state, void* d_out, void* d_s_out, hipStream_t s) {
+  const IpaBatchLayout L(k, m);
   U128* st = (U128*)d_state;
-  const Fe<FP> uu = ipa_fe<FP>(u);
-  const uint32_t count = 1u << (k - 1);
-  hipLaunchKernelGGL(ipa_s_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS), dim3(IPA_THREADS), 0, s, st + 2 * L.s, count, uu,
-                     Fe<FP>::zero(), 0);
+  if (d_s_out) {
+    const uint32_t count = 1u << (k - 1);
+    hipLaunchKernelGGL(ipa_s_double_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L,
+                       one, count);
+  }
   const size_t threads = d_s_out ? L.n : 1;
-  hipLaunchKernelGGL(ipa_final_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS)), dim3(IPA_THREADS), 0, s,
-                     (const U128*)(st + 2 * L.a[(k - 1) & 1]), (const U128*)(st + 2 * L.b[(k - 1) & 1]), (const U128*)(st + 2 * L.s), uu,
-                     ipa_fe<FP>(uinv), k, (U128*)d_out, (U128*)d_s_out);
-  return hipGetLastError();
-}
-
-// the batch launches: the caller has copied the call's scalar table into the state on `s` (IpaBatchLayout); one launch of
-// each kernel serves the m openings
-template <class FP>
-hipError_t ipa_begin_batch_launch(uint32_t k, size_t m, void* d_state, hipStream_t s) {
-  const IpaBatchLayout L(k, m);
-  const size_t threads = (L.n + 7) / 8;
-  hipLaunchKernelGGL(ipa_begin_batch_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m),
-                     dim3(IPA_THREADS), 0, s, (U128*)d_state, L);
-  return hipGetLastError();
-}
-
-template <class FP>
-hipError_t ipa_round_batch_launch(uint32_t k, uint32_t j, size_t m, void* d_state, hipStream_t s) {
-  const IpaBatchLayout L(k, m);
-  U128* st = (U128*)d_state;
-  if (j > 0) {
-    const uint32_t count = 1u << (j - 1);
-    hipLaunchKernelGGL(ipa_s_batch_kernel<FP>, dim3((count + IPA_THREADS - 1) / IPA_THREADS, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L,
-                       count);
-  }
-  const size_t half = (size_t)1 << (k - j - 1), nh = (size_t)1 << j;
-  const size_t threads = half * ((nh + IPA_H_PER - 1) / IPA_H_PER);
-  hipLaunchKernelGGL(ipa_round_batch_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m),
-                     dim3(IPA_THREADS), 0, s, st, L, k, j);
-  const uint32_t parts = (uint32_t)((half + IPA_THREADS - 1) / IPA_THREADS);
-  hipLaunchKernelGGL(ipa_finish_batch_kernel<FP>, dim3(1, (unsigned)m), dim3(IPA_THREADS), 0, s, st, L, parts);
-  return hipGetLastError();
-}
-
-template <class FP>
-hipError_t ipa_final_batch_launch(uint32_t k, size_t m, const void* d_state, void* d_out, hipStream_t s) {
-  const IpaBatchLayout L(k, m);
-  hipLaunchKernelGGL(ipa_final_batch_kernel<FP>, dim3(1, (unsigned)m), dim3(IPA_THREADS), 0, s, (const U128*)d_state, L, k,
-                     (U128*)d_out);
+  hipLaunchKernelGGL(ipa_final_kernel<FP>, dim3((unsigned)((threads + IPA_THREADS - 1) / IPA_THREADS), (unsigned)m), dim3(IPA_THREADS), 0,
+                     s, (const U128*)st, L, one, k, (U128*)d_out, (U128*)d_s_out);
   return hipGetLastError();
 }
 

@@ -2,13 +2,13 @@
 
 Upstream (halo2_proofs, src/poly/ipa/commitment.rs and commitment/{prover,verifier}.rs -- un-vendored; the algorithm is
 restated in DESIGN.md section 7.13): the opening proof a halo2 host on the Pasta curves ends `create_proof` with.
-`ParamsIPA` registers the bases ONCE as g || u || w; `create_proof` runs the k rounds on that table through
-h2_ipa_begin_device / h2_ipa_round_device / h2_ipa_final_device -- no generator is ever folded, each round is one
-two-column MSM over the registered table -- and `verify_proof` checks
+`ParamsIPA` registers the bases ONCE as g || u || w; `create_proof` runs the k rounds on that table -- no generator is
+ever folded, each round is one two-column MSM over the registered table -- and `verify_proof` checks
     sum [u_j^-1] L_j + P' + sum [u_j] R_j == [c] <s, G> + [c b_0 z] U + [f] W,   P' = P - [v] G[0] + [xi] S
 with <s, G> and the U, W, G[0] terms as ONE h2_msm_device on the same table (s from h2_ipa_challenge_products_device).
 `create_proofs` runs m openings in lockstep through h2_ipa_*_batch_device -- a round of all of them is ONE MSM of 2 m columns
-on the table -- and returns create_proof's bytes for each.
+on the table; it is the one prover path, `create_proof` is its batch of one (the C ABI's single
+calls h2_ipa_begin_device / h2_ipa_round_device / h2_ipa_final_device are the batch calls at m = 1 too).
 `verify_proofs` checks N such proofs behind ONE combined equation: the N equations are linear in the same table, so with
 random weights r_p they collapse into one table MSM and one points MSM; the 2k + 1 compressed
 points of every proof are decompressed by one kernel launch (h2_pasta_points_decompress_device) and the weighted sum of the
@@ -136,63 +136,9 @@ def create_proof(params, transcript, p, p_blind, x3, rng, s_poly=None):
     s_poly: the caller's column of n random coefficients, or None.  With None it is ONE 32-byte draw of the rng expanded on
     the device by h2_chacha20_scalars_device -- the one deviation from upstream's draw order, which takes the n scalars
     from the rng one by one.  Everything else is drawn in upstream's order: s_blind, then l_j and r_j of every round.
-    Each round reads 128 bytes back (L_j || R_j) for the transcript; the final call reads 64."""
-    import torch
-    L, cv, k, n, P = params._L, params.curve, params.k, params.n, params.p
-    dom = params.domain
-    stream = dom._stream()
-    p = params.column(p)
-    if p.shape[0] != n:
-        raise ValueError("create_proof: p.len() != n")
-    if s_poly is None:
-        seed = bytes(rng(32))
-        s_poly = torch.empty((n, 4), dtype=torch.int64, device=p.device)
-        _lib.check(L.h2_chacha20_scalars_device(cv, seed, 0, n, ctypes.c_void_p(s_poly.data_ptr()), stream),
-                   "h2_chacha20_scalars_device")
-    else:
-        s_poly = params.column(s_poly).clone()
-    # s_poly[0] -= s_poly(x3): the blinding polynomial has a root at x3
-    s_at = dom.eval_polynomial(s_poly.reshape(1, n, 4), x3)[0]
-    poly_lincomb(dom, [(s_poly, [(1, s_poly)], [s_at], [])], n)
-    s_blind = random_scalar(rng, P)
-    transcript.write_point(params.commit(s_poly, s_blind))
-    xi = transcript.squeeze_challenge()
-    z = transcript.squeeze_challenge()
-    # p' = s_poly xi + p, p'[0] -= v with v = p'(x3) = p(x3)
-    v = dom.eval_polynomial(p.reshape(1, n, 4), x3)[0]
-    p_prime = poly_lincomb(dom, [(None, [(xi, s_poly), (1, p)], [v], [])], n)[0]
-    f = (s_blind * xi + p_blind) % P
-
-    need = ctypes.c_size_t(0)
-    _lib.check(L.h2_ipa_state_bytes(k, ctypes.byref(need)), "h2_ipa_state_bytes")
-    state = torch.empty(need.value // 8, dtype=torch.int64, device=p.device)
-    out = torch.empty(16, dtype=torch.int64, device=p.device)
-    _lib.check(L.h2_ipa_begin_device(cv, k, ctypes.c_void_p(p_prime.data_ptr()), params.mont(x3).ctypes.data,
-                                     ctypes.c_void_p(state.data_ptr()), stream), "h2_ipa_begin_device")
-    zm = params.mont(z)
-    u = u_inv = None
-    for j in range(k):
-        l_j = random_scalar(rng, P)
-        r_j = random_scalar(rng, P)
-        um, uim = (params.mont(u), params.mont(u_inv)) if j else (None, None)
-        lm, rm = params.mont(l_j), params.mont(r_j)
-        st = L.h2_ipa_round_device(cv, params.bases.handle, k, j, ctypes.c_void_p(state.data_ptr()),
-                                   um.ctypes.data if j else None, uim.ctypes.data if j else None, zm.ctypes.data,
-                                   lm.ctypes.data, rm.ctypes.data, ctypes.c_void_p(out.data_ptr()), stream)
-        _lib.check(st, "h2_ipa_round_device")
-        lr = out.cpu().numpy().view(np.uint64)
-        transcript.write_point(params.affine_ints(lr[:8]))
-        transcript.write_point(params.affine_ints(lr[8:]))
-        u = transcript.squeeze_challenge()
-        u_inv = pow(u, -1, P)
-        f = (f + l_j * u_inv + r_j * u) % P
-    um, uim = params.mont(u), params.mont(u_inv)
-    _lib.check(L.h2_ipa_final_device(cv, k, ctypes.c_void_p(state.data_ptr()), um.ctypes.data, uim.ctypes.data,
-                                     ctypes.c_void_p(out.data_ptr()), None, stream), "h2_ipa_final_device")
-    c = _ints(out[:4].cpu().numpy().tobytes())[0] * pow(params.R, -1, P) % P
-    transcript.write_scalar(c)
-    transcript.write_scalar(f)
-    return bytes(transcript.bytes)
+    Each round reads 128 bytes back (L_j || R_j) for the transcript; the final call reads 64.  A ValueError for a p or an
+    s_poly that does not have n coefficients.  It is create_proofs' batch of one."""
+    return create_proofs(params, [(transcript, p, p_blind, x3, rng, s_poly)])[0]
 
 
 MAX_BATCH = 64                                      # H2_IPA_MAX_BATCH

@@ -379,9 +379,11 @@ int h2_poly_lincomb_max_rounds(void);
  * ones, G^(j)[i] = sum_{h < 2^j} s^(j)[h] G[h 2^(k-j) + i], so L_j and R_j are MSMs over the ORIGINAL table with expanded
  * scalars.  `bases` holds exactly n + 2 points registered ONCE as  G[0 .. n) || U || W;  a round is one two-column MSM of
  * n + 2 terms on it (slot n: z times the round's inner product, slot n + 1: the blind) and O(n) field products.
- *   h2_ipa_state_bytes      size of the caller-owned, 16-byte aligned device buffer one opening works in: a and b (two
- *                           generations each), the table s of challenge products, two columns of n + 2 and the partial
- *                           sums.  Host only, no h2_init needed.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K or a null out.
+ * These single calls ARE the lockstep calls below with m = 1 (one code path, the same checks): a state begun by one
+ * spelling can be continued by the other.
+ *   h2_ipa_state_bytes      size of the caller-owned, 16-byte aligned device buffer one opening works in:
+ *                           h2_ipa_batch_state_bytes(k, 1), which describes its contents.  Host only, no h2_init needed.
+ *                           H2_EINVAL for k = 0, k > H2_IPA_MAX_K or a null out.
  *   h2_ipa_begin_device     a = the n coefficients d_p (only read), b[i] = x3^i, s = [1].  Whatever an earlier opening
  *                           left in d_state does not matter.
  *   h2_ipa_round_device     round j, 0 <= j < k, half = 2^(k-j-1).  For j > 0 it first folds by the PREVIOUS challenge:
@@ -414,23 +416,27 @@ int h2_ipa_final_device(h2_curve_t curve, uint32_t k, void* d_state, const uint6
                         void* d_out, void* d_s_out, void* stream);
 int h2_ipa_challenge_products_device(h2_curve_t curve, const uint64_t* u, uint32_t k, const uint64_t init[4], void* d_out,
                                      void* stream);
-/* m openings in lockstep: the calls above for m states at once.  ALL m OPENINGS SHARE k, THE CURVE AND THE TABLE `bases`;
+/* m openings in lockstep: the calls above for m openings in one state (the calls above are these at m = 1; an opening
+ * begun with h2_ipa_begin_device may go on through h2_ipa_round_batch_device with m = 1 and the other way round).
+ * ALL m OPENINGS SHARE k, THE CURVE AND THE TABLE `bases`;
  * each has its own polynomial, x3, z, challenges and blinds.  One launch of every kernel serves the m openings and a round is
  * ONE MSM of 2 m columns of n + 2 terms on the registered table (wide batches go through h2_msm_device's column groups), so
  * the launches of a round do not grow with m.  Opening i's outputs are bit for bit what the single-opening calls give.
  *   h2_ipa_batch_state_bytes    size of the caller-owned, 16-byte aligned device buffer m openings work in: per opening a
  *                               and b (two generations each), s and the partial sums; then one block of 2 m columns of
- *                               n + 2; then a table of 5 m scalars every call fills from its host arguments.  Host only, no
- *                               h2_init needed.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K, m = 0, m > H2_IPA_MAX_BATCH, a null out.
+ *                               n + 2; then a table of 5 m scalars every call of m >= 2 fills from its host arguments (at
+ *                               m = 1 the scalars travel in the kernels' arguments and the table is neither written nor
+ *                               read).  Host only, no h2_init needed.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K, m = 0,
+ *                               m > H2_IPA_MAX_BATCH, a null out.
  *   h2_ipa_begin_batch_device   d_p: a HOST array of m device pointers, opening i's n coefficients (only read); x3: m * 4
  *                               limbs.  Whatever an earlier use -- of any m -- left in d_state does not matter.
  *   h2_ipa_round_batch_device   round j of every opening; u_prev, u_prev_inv (both null at j = 0, both required otherwise),
  *                               z, l_blind, r_blind: m * 4 limbs each, entry i for opening i.  d_out_affine: m * 128 bytes,
  *                               L_j || R_j of opening 0, then of opening 1, ...
  *   h2_ipa_final_batch_device   the last fold; u_last, u_last_inv: m * 4 limbs.  d_out: m * 64 bytes, c_i || b_i[0].  The
- *                               finished table s has no batch form.
- * The contract is the single calls': host scalars are canonical Montgomery limbs, read before the call returns (one copy of
- * the scalar table into d_state is enqueued in front of the kernels); the calls of one batch are issued in order on ONE
+ *                               finished table s comes from h2_ipa_final_device only.
+ * The contract is the single calls': host scalars are canonical Montgomery limbs, read before the call returns (for m >= 2
+ * one copy of the scalar table into d_state is enqueued in front of the kernels); the calls of one batch are issued in order on ONE
  * stream; asynchronous on `stream`, no host synchronisation, no device-to-host copy, nothing allocated; the MSM goes through
  * h2_msm_device's launch path with its bounds proof, and what that path refuses with H2_EINVAL (a column too long for the
  * sort's 32-bit indices) is found from the same plans BEFORE the round's table copy and kernels.  H2_EINVAL, before

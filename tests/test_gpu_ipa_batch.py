@@ -165,6 +165,64 @@ def test_stale_state_of_another_batch_size_changes_nothing():
     check(batch, ins[:2], refs[:2])
 
 
+def test_a_stale_scalar_table_is_not_read_at_m_1():
+    """the scalars of a batch of one travel in the kernels' arguments: the table at the end of the m = 1 layout (5 elements)
+    holds what m = 2 left there, then 0xFF bytes, and is neither read nor written"""
+    curve, k = "vesta", 4
+    ins, refs = references(curve, k)
+    batch = Batch(curve, k, 5)
+    check(batch, ins[:2], refs[:2])
+    check(batch, ins[2:3], refs[2:3])                 # m = 1 on what m = 2 left
+    end = state_bytes(k, 1) // 8
+    batch.state[end - 5 * 4:end] = FF
+    check(batch, ins[3:4], refs[3:4])
+    assert (batch.state[end - 5 * 4:end] == FF).all().item(), "m = 1 wrote its scalar table"
+    check(batch, ins[:2], refs[:2])
+
+
+@pytest.mark.parametrize("curve,k", [("pallas", 3), ("vesta", 6)])
+def test_the_two_spellings_are_one_path(curve, k):
+    """one opening on one state, the single calls and the batch calls with m = 1 taking turns: begun by either spelling,
+    every round through the other one than the call before, finished by the spelling that began"""
+    p, _ = T.primes(curve)
+    I = T.inputs(curve, k, 0x2B1 + k)
+    want_lr, c, b0, s = T.reference(curve, k, **I)
+    batch = Batch(curve, k, 1)
+    single = T.Opening(curve, k)
+    assert single.state.numel() == batch.state.numel()
+    single.state = batch.state                        # ONE state under both spellings
+    state = ctypes.c_void_p(batch.state.data_ptr())
+    cid = T.CID[curve]
+    um = T.mont(p, [I["us"][-1], pow(I["us"][-1], -1, p)])
+    for first in ("single", "batch"):
+        batch.state.fill_(FF)
+        if first == "single":
+            d_p = T.to_dev(T.mont(p, I["a"]))
+            assert T.L().h2_ipa_begin_device(cid, k, ctypes.c_void_p(d_p.data_ptr()), T.mont(p, [I["x3"]]).ctypes.data, state,
+                                             None) == H2_OK
+        else:
+            assert batch.begin([I]) == H2_OK
+        for j in range(k):
+            if (j % 2 == 0) == (first == "single"):   # round 0 goes through the spelling that did not begin
+                assert batch.round([I], j) == H2_OK
+                got = T.from_dev(batch.out)[0]
+            else:
+                assert single.round(j, I["z"], I["us"], I["blinds"]) == H2_OK
+                got = T.from_dev(single.out)
+            assert np.array_equal(got[:8], want_lr[j][:8]), "begun by %s: L_%d differs" % (first, j)
+            assert np.array_equal(got[8:], want_lr[j][8:]), "begun by %s: R_%d differs" % (first, j)
+        if first == "single":
+            assert T.L().h2_ipa_final_device(cid, k, state, um[0].ctypes.data, um[1].ctypes.data,
+                                             ctypes.c_void_p(single.out.data_ptr()), ctypes.c_void_p(single.s_out.data_ptr()),
+                                             None) == H2_OK
+            cb = T.from_dev(single.out)[:8]
+            assert np.array_equal(T.from_dev(single.s_out), T.mont(p, s)), "the finished s differs"
+        else:
+            assert batch.final([I]) == H2_OK
+            cb = T.from_dev(batch.out).reshape(-1)[:8]
+        assert np.array_equal(cb.reshape(2, 4), T.mont(p, [c, b0])), "begun by %s: c or b[0] differs" % first
+
+
 def test_argument_errors_then_a_valid_batch():
     import halo2_prover_amd as h2
     curve, k, m = "pallas", 4, 3

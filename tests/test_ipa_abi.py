@@ -76,6 +76,17 @@ def test_state_bytes_grows_with_k_and_refuses_the_ends():
     assert lib.h2_ipa_state_bytes(4, None) == -1
 
 
+@pytest.mark.parametrize("k", [1, 2, 7, "max"])
+def test_the_single_state_is_the_batch_state_of_one(k):
+    import halo2_prover_amd
+    lib = halo2_prover_amd.load()
+    k = max_k() if k == "max" else k
+    one, batch = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert lib.h2_ipa_state_bytes(k, ctypes.byref(one)) == 0
+    assert lib.h2_ipa_batch_state_bytes(k, 1, ctypes.byref(batch)) == 0
+    assert one.value == batch.value > 0
+
+
 def test_they_fail_loudly_without_init():
     """no CPU fallback: before h2_init the calls are H2_ENOTINIT (H2_EINVAL's null pointers if another test of this
     process has initialised a device)"""

@@ -19,6 +19,7 @@
 #include "h2_host.hpp"
 #include "h2_ipa.hpp"
 #include "h2_ipa_verify.hpp"
+#include "h2_ipa_prove.hpp"
 #include "h2_lookup.hpp"
 #include "h2_ntt.hpp"
 #include "h2_permutation.hpp"
@@ -2223,6 +2224,237 @@ int h2_ipa_verify_proofs(h2_curve_t curve, uint64_t bases, uint32_t k_, size_t c
         if (!ok[i]) *all_ok = 0;
     }
     return A.wait();
+  } catch (const std::bad_alloc&) {
+    g_h2.last_error = "ipa: no host memory for the batch";
+    return H2_ENOMEM;
+  }
+}
+
+// ---- the IPA prover behind one call (h2_ipa_prove.hpp) --------------------------------------------------------------------
+int h2_ipa_prove_state_bytes(uint32_t k, size_t m, size_t* out) {
+  if (k == 0 || k > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH || !out) return H2_EINVAL;
+  *out = IpaProveLayout(k, m).total;
+  return H2_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// h2_ipa_prove_rounds_device behind its Call: every refusal first, then ONE upload -- the scalar table as begin and round 0
+// read it, every blind, f, the midstates: one range of the state -- and begin, k x (round, MSM, step), final, step.  No
+// synchronisation and nothing read back
+int ipa_prove_rounds_run(DevCtx& c, hipStream_t stream, int curve, uint64_t bases, uint32_t k_, size_t m, const void* const* d_p,
+                         const uint64_t* x3, const uint64_t* z, const uint64_t* f0, const uint64_t* round_blinds,
+                         const h2_transcript_state_t* states, void* d_state, void* d_tail, void* d_states_out, void* d_status) {
+  if (!curve_ok(curve) || !ops_of(curve)->ipa_prove_step || k_ == 0 || k_ > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH) return H2_EINVAL;
+  if (!d_p || !x3 || !z || !f0 || !round_blinds || !states) return H2_EINVAL;
+  if (!ipa_dev_ptr(d_state) || !ipa_dev_ptr(d_tail) || !d_status || ((uintptr_t)d_status & 3) || (d_states_out && ((uintptr_t)d_states_out & 15)))
+    return H2_EINVAL;
+  for (size_t i = 0; i < m; i++)
+    if (!ipa_dev_ptr(d_p[i]) || states[i].buflen > 128) return H2_EINVAL;
+  if (!H2_BY_SCALAR_FIELD(curve, ipa_canonical)(x3, m) || !H2_BY_SCALAR_FIELD(curve, ipa_canonical)(z, m) ||
+      !H2_BY_SCALAR_FIELD(curve, ipa_canonical)(f0, m) || !H2_BY_SCALAR_FIELD(curve, ipa_canonical)(round_blinds, 2 * k_ * m))
+    return H2_EINVAL;
+  const IpaBatchLayout L(k_, m);
+  const IpaProveLayout P(k_, m);
+  const BasesEntry* be = nullptr;
+  if (int rc = msm_common_checks(curve, bases, 0, L.col_stride, 2 * m, &be); rc != H2_OK) return rc;
+  if (be->n != L.col_stride) return H2_EINVAL;          // exactly G || U || W
+  if (int rc = msm_device_plan_check(*be, L.col_stride, L.col_stride, 2 * m); rc != H2_OK) return rc;
+
+  const size_t up0 = L.scal * 32, row = m * 32;
+  std::vector<uint8_t> host;
+  try {
+    host.assign(P.lr - up0, 0);
+  } catch (const std::bad_alloc&) {
+    g_h2.last_error = "ipa: no host memory for the call's scalars";
+    return H2_ENOMEM;
+  }
+  memcpy(&host[0], x3, row);                             // row 0: begin's x3; row 1: the m pointers d_p
+  for (size_t i = 0; i < m; i++) {
+    const uint64_t p = (uint64_t)(uintptr_t)d_p[i];
+    memcpy(&host[row + 8 * i], &p, 8);
+    memcpy(&host[3 * row + 32 * i], round_blinds + 4 * (i * 2 * k_), 32);       // rows 3, 4: l_0, r_0
+    memcpy(&host[4 * row + 32 * i], round_blinds + 4 * (i * 2 * k_ + 1), 32);
+  }
+  memcpy(&host[2 * row], z, row);                        // row 2 stands for the whole call
+  memcpy(&host[P.blinds - up0], round_blinds, 2 * k_ * row);
+  memcpy(&host[P.f - up0], f0, row);
+  memcpy(&host[P.states - up0], states, m * sizeof(h2_transcript_state_t));
+  char* st = (char*)d_state;
+  // a pageable source: the runtime has read `host` when the call returns (it stages the bytes or waits for the copy)
+  H2_TRY(hipMemcpyAsync(st + up0, host.data(), host.size(), hipMemcpyHostToDevice, stream));
+
+  const CurveOps* ops = ops_of(curve);
+  IpaOne one;
+  memset(&one, 0, sizeof one);
+  one.table = 1;                                         // the step kernel makes the scalars: the table at m = 1 too
+  const int inv = g_knobs.ipa_inv_form;
+  if (int rc = launched(ops->ipa_begin(k_, m, one, d_state, stream), "ipa_begin_kernel"); rc != H2_OK) return rc;
+  for (uint32_t j = 0; j < k_; j++) {
+    if (int rc = launched(ops->ipa_round(k_, j, m, one, d_state, stream), "ipa_round_kernel"); rc != H2_OK) return rc;
+    if (int rc = msm_device_run(c, curve, *be, st + L.col * 32, 0, L.col_stride, L.col_stride, 2 * m, st + P.lr, true, stream); rc != H2_OK)
+      return rc;
+    if (int rc = launched(ops->ipa_prove_step(k_, j, m, d_state, d_tail, nullptr, d_status, inv, stream), "ipa_prove_step_kernel"); rc != H2_OK)
+      return rc;
+  }
+  if (int rc = launched(ops->ipa_final(k_, m, one, d_state, st + P.lr, nullptr, stream), "ipa_final_kernel"); rc != H2_OK) return rc;
+  return launched(ops->ipa_prove_step(k_, k_, m, d_state, d_tail, d_states_out, d_status, inv, stream), "ipa_prove_step_kernel");
+}
+
+// S (affine, Montgomery limbs, (0, 0) the identity) onto a transcript: its wire form, then xi and z squeezed (Montgomery
+// limbs); the state is left behind the two challenges
+template <class CV>
+void ipa_absorb_commitment(const uint64_t aff[8], h2_transcript_state_t* state, uint8_t wire[32], uint64_t xi[4], uint64_t z[4]) {
+  uint8_t msg[65];
+  msg[0] = 1;
+  HF<typename CV::Base>::from_mont_limbs(aff).to_le_bytes(msg + 1);
+  HF<typename CV::Base>::from_mont_limbs(aff + 4).to_le_bytes(msg + 33);
+  memcpy(wire, msg + 1, 32);
+  wire[31] |= (uint8_t)((msg[33] & 1) << 7);
+  Blake2b b;
+  b.import_state((const uint8_t*)state);
+  b.update(msg, 65);
+  for (uint64_t* out : {xi, z}) {
+    const uint8_t zero = 0;
+    uint8_t digest[64];
+    b.update(&zero, 1);
+    b.digest(digest);
+    transcript_reduce<typename CV::Scalar>(digest, out);
+  }
+  b.export_state((uint8_t*)state);
+}
+
+template <class FP>
+void ipa_one_limbs(uint64_t out[4]) {
+  HF<FP>::one().mont_limbs(out);
+}
+
+// s_blind xi + p_blind on Montgomery limbs
+template <class FP>
+void ipa_f0(const uint64_t s_blind[4], const uint64_t xi[4], const uint64_t p_blind[4], uint64_t out[4]) {
+  (HF<FP>::from_mont_limbs(s_blind) * HF<FP>::from_mont_limbs(xi) + HF<FP>::from_mont_limbs(p_blind)).mont_limbs(out);
+}
+}  // namespace
+
+extern "C" {
+
+int h2_ipa_prove_rounds_device(h2_curve_t curve, uint64_t bases, uint32_t k_, size_t m, const void* const* d_p, const uint64_t* x3,
+                               const uint64_t* z, const uint64_t* f0, const uint64_t* round_blinds,
+                               const h2_transcript_state_t* states, void* d_state, void* d_tail, void* d_states_out, void* d_status,
+                               void* stream_) {
+  Call k(stream_);
+  if (k.rc != H2_OK) return k.rc;
+  return ipa_prove_rounds_run(*k.c, k.stream, (int)curve, bases, k_, m, d_p, x3, z, f0, round_blinds, states, d_state, d_tail,
+                              d_states_out, d_status);
+}
+
+int h2_ipa_create_proofs(h2_curve_t curve, uint64_t bases, uint32_t k_, size_t m, const h2_transcript_state_t* states,
+                         const void* const* d_p, const uint64_t* p_blind, const uint64_t* x3, const void* const* d_s_poly,
+                         const uint8_t* seeds, const uint64_t* s_blind, const uint64_t* round_blinds, uint8_t* proofs,
+                         h2_transcript_state_t* states_out, uint32_t* status) {
+  Call k(nullptr);
+  if (k.rc != H2_OK) return k.rc;
+  const int cv = (int)curve;
+  if (!curve_ok(cv) || !ops_of(cv)->ipa_prove_step || k_ == 0 || k_ > IPA_MAX_K || m == 0 || m > IPA_MAX_BATCH) return H2_EINVAL;
+  if (!states || !d_p || !p_blind || !x3 || !d_s_poly || !s_blind || !round_blinds || !proofs || !status) return H2_EINVAL;
+  for (size_t i = 0; i < m; i++) {
+    if (!ipa_dev_ptr(d_p[i]) || states[i].buflen > 128) return H2_EINVAL;
+    if (d_s_poly[i] ? ((uintptr_t)d_s_poly[i] & 15) != 0 : !seeds) return H2_EINVAL;
+  }
+  if (!H2_BY_SCALAR_FIELD(cv, ipa_canonical)(p_blind, m) || !H2_BY_SCALAR_FIELD(cv, ipa_canonical)(x3, m) ||
+      !H2_BY_SCALAR_FIELD(cv, ipa_canonical)(s_blind, m) || !H2_BY_SCALAR_FIELD(cv, ipa_canonical)(round_blinds, 2 * k_ * m))
+    return H2_EINVAL;
+  const size_t n = (size_t)1 << k_, rows = n + 2, per = 2 * (size_t)k_ + 2;
+  const BasesEntry* be = nullptr;
+  if (int rc = msm_common_checks(cv, bases, 0, rows, 2 * m, &be); rc != H2_OK) return rc;
+  if (be->n != rows) return H2_EINVAL;                   // exactly G || U || W
+  if (int rc = msm_device_plan_check(*be, rows, rows, m); rc != H2_OK) return rc;
+  if (int rc = msm_device_plan_check(*be, rows, rows, 2 * m); rc != H2_OK) return rc;
+
+  DevCtx& c = *k.c;
+  hipStream_t stream = k.stream;
+  // the scratch: the columns s_poly_i || 0 || s_blind_i, the polynomials p'_i, the prove state, and what is read back at the
+  // end as one range: the tails, the midstates, the status words
+  size_t off = 0;
+  auto region = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_cols = region(m * rows * 32), o_pp = region(m * n * 32), o_vals = region(2 * m * 32), o_aff = region(m * 64),
+               o_state = region(IpaProveLayout(k_, m).total), o_tail = off, back_tail = m * per * 32,
+               back_states = m * sizeof(h2_transcript_state_t), back = back_tail + back_states + m * 4;
+  region(back);
+  ArenaLease A(c.stage, off, stream);
+  if (A.rc != H2_OK) return A.rc;
+  char* base = (char*)A.a.p;
+  try {
+    // 1. the columns: s_poly_i given or expanded from its seed; the blind in row n + 1, zero in row n
+    std::vector<uint64_t> tails(8 * m, 0);
+    for (size_t i = 0; i < m; i++) memcpy(&tails[8 * i + 4], s_blind + 4 * i, 32);
+    H2_TRY(hipMemcpy2DAsync(base + o_cols + n * 32, rows * 32, tails.data(), 64, 64, m, hipMemcpyHostToDevice, stream));
+    std::vector<const void*> ptrs(2 * m);
+    for (size_t i = 0; i < m; i++) {
+      char* col = base + o_cols + i * rows * 32;
+      if (d_s_poly[i]) {
+        H2_TRY(hipMemcpyAsync(col, d_s_poly[i], n * 32, hipMemcpyDeviceToDevice, stream));
+      } else {
+        if (int rc = h2_chacha20_scalars_device(curve, seeds + 32 * i, 0, n, col, stream); rc != H2_OK) return rc;
+      }
+      ptrs[i] = col;
+      ptrs[m + i] = d_p[i];
+    }
+    // 2. s_poly_i(x3_i) and p_i(x3_i): the first of the call's three synchronisations
+    std::vector<uint64_t> points(8 * m), vals(8 * m);
+    memcpy(&points[0], x3, m * 32);
+    memcpy(&points[4 * m], x3, m * 32);
+    if (int rc = poly_eval_enqueue(c, cv, ptrs.data(), n, points.data(), 2 * m, base + o_vals, stream); rc != H2_OK) return rc;
+    H2_TRY(hipMemcpyAsync(vals.data(), base + o_vals, 2 * m * 32, hipMemcpyDeviceToHost, stream));
+    H2_TRY(hipStreamSynchronize(stream));
+    // 3. s_poly_i[0] -= s_poly_i(x3_i), then the m commitments S_i: the second synchronisation
+    std::vector<h2_lincomb_job_t> jobs(m);
+    std::vector<h2_lincomb_term_t> terms(2 * m);
+    uint64_t one_limbs[4];
+    H2_BY_SCALAR_FIELD(cv, ipa_one_limbs)(one_limbs);
+    for (size_t i = 0; i < m; i++) {
+      jobs[i] = h2_lincomb_job_t{base + o_cols + i * rows * 32, (uint32_t)i, 1, (uint32_t)i, 1, 0, 0};
+      terms[i].d_poly = jobs[i].d_out;
+      memcpy(terms[i].coeff, one_limbs, 32);
+    }
+    if (int rc = h2_poly_lincomb_device(curve, jobs.data(), m, terms.data(), m, vals.data(), m, nullptr, 0, n, stream); rc != H2_OK) return rc;
+    if (int rc = msm_device_run(c, cv, *be, base + o_cols, 0, rows, rows, m, base + o_aff, true, stream); rc != H2_OK) return rc;
+    std::vector<uint64_t> aff(8 * m);
+    H2_TRY(hipMemcpyAsync(aff.data(), base + o_aff, m * 64, hipMemcpyDeviceToHost, stream));
+    H2_TRY(hipStreamSynchronize(stream));
+    // 4. S onto the transcripts, xi and z off them; p'_i = xi_i s_poly_i + p_i, p'_i[0] -= p_i(x3_i); f_i = s_blind_i xi_i + p_blind_i
+    std::vector<h2_transcript_state_t> mid(states, states + m);
+    std::vector<uint64_t> xi(4 * m), z(4 * m), f0(4 * m);
+    std::vector<const void*> d_pp(m);
+    for (size_t i = 0; i < m; i++) {
+      uint8_t* wire = proofs + i * (per + 1) * 32;
+      if (cv == H2_PALLAS)
+        ipa_absorb_commitment<PALLAS_CURVE>(&aff[8 * i], &mid[i], wire, &xi[4 * i], &z[4 * i]);
+      else
+        ipa_absorb_commitment<VESTA_CURVE>(&aff[8 * i], &mid[i], wire, &xi[4 * i], &z[4 * i]);
+      H2_BY_SCALAR_FIELD(cv, ipa_f0)(s_blind + 4 * i, &xi[4 * i], p_blind + 4 * i, &f0[4 * i]);
+      d_pp[i] = base + o_pp + i * n * 32;
+      jobs[i] = h2_lincomb_job_t{base + o_pp + i * n * 32, (uint32_t)(2 * i), 2, (uint32_t)i, 1, 0, 0};
+      terms[2 * i].d_poly = base + o_cols + i * rows * 32;
+      memcpy(terms[2 * i].coeff, &xi[4 * i], 32);
+      terms[2 * i + 1].d_poly = d_p[i];
+      memcpy(terms[2 * i + 1].coeff, one_limbs, 32);
+    }
+    if (int rc = h2_poly_lincomb_device(curve, jobs.data(), m, terms.data(), 2 * m, &vals[4 * m], m, nullptr, 0, n, stream); rc != H2_OK)
+      return rc;
+    // 5. the rounds, nothing through the host; one read-back behind them: the third synchronisation
+    if (int rc = ipa_prove_rounds_run(c, stream, cv, bases, k_, m, d_pp.data(), x3, z.data(), f0.data(), round_blinds, mid.data(),
+                                      base + o_state, base + o_tail, base + o_tail + back_tail, base + o_tail + back_tail + back_states);
+        rc != H2_OK)
+      return rc;
+    std::vector<uint8_t> out(back);
+    H2_TRY(hipMemcpyAsync(out.data(), base + o_tail, back, hipMemcpyDeviceToHost, stream));
+    if (int rc = A.wait(); rc != H2_OK) return rc;
+    for (size_t i = 0; i < m; i++) memcpy(proofs + (i * (per + 1) + 1) * 32, &out[i * per * 32], per * 32);
+    if (states_out) memcpy(states_out, &out[back_tail], back_states);
+    memcpy(status, &out[back_tail + back_states], m * 4);
+    return H2_OK;
   } catch (const std::bad_alloc&) {
     g_h2.last_error = "ipa: no host memory for the batch";
     return H2_ENOMEM;

@@ -12,6 +12,7 @@
 #include "h2_expr_kernel.hpp"
 #include "h2_ipa.hpp"
 #include "h2_ipa_verify.hpp"
+#include "h2_ipa_prove.hpp"
 
 #include <cstring>
 
@@ -556,16 +557,18 @@ int selftest_digits(const uint64_t* scalar_mont, size_t n_for_geometry, uint32_t
 constexpr decltype(CurveOps::ipa_replay) IPA_REPLAY = nullptr;
 constexpr decltype(CurveOps::ipa_verify_prepare) IPA_VERIFY_PREPARE = nullptr;
 constexpr decltype(CurveOps::ipa_verify_finish) IPA_VERIFY_FINISH = nullptr;
+constexpr decltype(CurveOps::ipa_prove_step) IPA_PROVE_STEP = nullptr;
 #else
 constexpr decltype(CurveOps::ipa_replay) IPA_REPLAY = ipa_replay_launch<CV>;
 constexpr decltype(CurveOps::ipa_verify_prepare) IPA_VERIFY_PREPARE = ipa_verify_prepare_launch<FS>;
 constexpr decltype(CurveOps::ipa_verify_finish) IPA_VERIFY_FINISH = ipa_verify_finish_launch<FS>;
+constexpr decltype(CurveOps::ipa_prove_step) IPA_PROVE_STEP = ipa_prove_step_launch<CV>;
 #endif
 
 const CurveOps OPS = {CV::ID,      FS::ID,      FS::NUM_BITS, kernel_setup, table_build, msm_launch_, msm_points_launch_, srs_powers, fixed_base_mul, msm_small,
                       to_affine,   points_sum, points_decompress, selftest_decompress, base_sqrt_, pasta_points_decompress, selftest_base_sqrt, selftest_pasta_decompress, ntt_table_bytes, ntt_scale_in_table, ntt_twiddles, ntt_launch_, ntt_extend_launch_, ntt_coeff_launch_, group_fft_scratch, group_fft, g_to_lagrange, selftest_glv_split, selftest_glv_constants, GLV_BITS, poly_scale, poly_powers, poly_mul_periodic,
                       poly_pointwise, poly_inverse, poly_scan, poly_eval, poly_lincomb, lookup_permute, lookup_ratio, perm_ratio, perm_scan, expr_launch, chacha20_scalars, ipa_begin_batch_launch<FS>, ipa_round_batch_launch<FS>, ipa_final_batch_launch<FS>,
-                      ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, IPA_REPLAY, IPA_VERIFY_PREPARE, IPA_VERIFY_FINISH, selftest_field, selftest_curve,
+                      ipa_s_products_launch<FS>, ipa_s_sum_launch<FS>, IPA_REPLAY, IPA_VERIFY_PREPARE, IPA_VERIFY_FINISH, IPA_PROVE_STEP, selftest_field, selftest_curve,
                       selftest_field_device, selftest_curve_device, selftest_digits, modmul_rate,
                       chain29::covers<FB>(), selftest_xyzz29, selftest_xyzz29_device};
 

@@ -181,6 +181,12 @@ struct CurveOps {
   hipError_t (*ipa_verify_prepare)(const void* d_replay, const void* d_x3, const void* d_v, const void* d_weights, void* d_scal,
                                    void* d_table, void* d_terms, uint32_t k, size_t count, hipStream_t s);
   hipError_t (*ipa_verify_finish)(const void* d_terms, size_t count, void* d_col, uint32_t k, hipStream_t s);
+  // the IPA prover's transcript step (h2_ipa_prove.hpp), one lane per opening: behind round j < k of a state laid out by
+  // IpaProveLayout(k, m) it writes L_j, R_j into the m proofs of d_tail, absorbs them, squeezes u_j and writes the scalar
+  // table for the next round; j == k, behind the final kernel: c and f, the midstates into d_states_out (or null).
+  // inv_form: 0 divsteps, 1 fe_inv (the comparison).  NULL for BN254, whose wire form it does not write
+  hipError_t (*ipa_prove_step)(uint32_t k, uint32_t j, size_t m, void* d_state, void* d_tail, void* d_states_out, void* d_status,
+                               int inv_form, hipStream_t s);
   // host self-test hooks (host instantiation of the same templates)
   int (*selftest_field)(int which /* 0 = base field, 1 = scalar field */, int op, const uint64_t* a,
                         const uint64_t* b, uint64_t* out);

@@ -148,6 +148,7 @@ struct TestKnobs {
   int poseidon_form = 0;                         // the hash kernel's products: 0 = by size, 1 = the compiler's form, 2 = single-chain
   int poseidon_wide_form = 0;                    // the wide permutation kernel's partial rounds: 0 = the width's own, 1 = dense, 2 = sparse
   int poseidon_walk_form = 0;                    // the Merkle walker and update: 0 = by size, 1 = a lane per hash, 2 = a quad per hash
+  int ipa_inv_form = 0;                          // the IPA prover's transcript step inverts by: 0 = divsteps, 1 = fe_inv's Fermat chain
 };
 struct TestCounters {
   uint64_t guard_launches = 0, guard_violations = 0;

@@ -72,10 +72,13 @@ struct IpaBatchLayout {
 };
 
 // The table's rows for a batch of ONE, by value in every kernel's arguments: the call's scalars (Montgomery limbs) and d_p.
-// The host fills it instead of the table and enqueues no copy; the kernels take the argument when L.m == 1 (ipa_scalar).
+// The host fills it instead of the table and enqueues no copy; the kernels take the argument when L.m == 1 (ipa_scalar) --
+// unless `table` is set: the route whose scalars are made on the device (h2_ipa_prove.hpp) reads the table at m = 1 too.
 struct IpaOne {
   uint32_t v[IPA_BATCH_SCALARS][8];
   const void* p;
+  uint32_t table;          // 1: the scalars and d_p come from the state's table whatever m is
+  H2_HD bool by_value(size_t m) const { return m == 1 && !table; }
 };
 
 // h2_ipa_begin_device: a = p, b[i] = x3^i (each thread POLY_RUN-style runs of 8 from x3^first), S[0] = 1
@@ -276,7 +279,7 @@ __device__ __forceinline__ void ipa_final_body(const U128* __restrict__ a, const
 
 // ---- the kernels: blockIdx.y is the opening, blockIdx.x what the bodies above take it for -----------------------------------
 // An opening's scalars come from the table at the end of the state (IpaBatchLayout), or at m = 1 from the kernel's
-// arguments (IpaOne); L.m is an argument, so the choice is uniform across the launch.  No kernel writes the table and a
+// arguments (IpaOne) unless one.table says otherwise; both are arguments, so the choice is uniform across the launch.  No kernel writes the table and a
 // workgroup works on one opening, so the table address is the same in every lane: the loads go through the constant
 // address space, which the back end serves with scalar loads (poseidon_const's way), as it does the arguments.
 template <class FP>
@@ -286,7 +289,7 @@ __device__ __forceinline__ Fe<FP> ipa_scalar(const U128* st, const IpaBatchLayou
   const ConstPtr q = (ConstPtr)(const uint32_t*)(st + 2 * (L.scal + row * L.m + opening));
   Fe<FP> r;
 #pragma unroll
-  for (int l = 0; l < 8; l++) r.v[l] = L.m == 1 ? one.v[row][l] : q[l];
+  for (int l = 0; l < 8; l++) r.v[l] = one.by_value(L.m) ? one.v[row][l] : q[l];
   return r;
 }
 
@@ -295,7 +298,7 @@ __global__ void __launch_bounds__(IPA_THREADS) ipa_begin_kernel(U128* st, IpaBat
   const size_t o = blockIdx.y;
   typedef const __attribute__((address_space(4))) uint64_t* ConstPtr;
   typedef const __attribute__((address_space(1))) U128* GlobalPtr;       // d_p[o] is device memory: global loads, not flat ones
-  const uintptr_t p = L.m == 1 ? (uintptr_t)one.p : (uintptr_t)((ConstPtr)(const uint64_t*)(st + 2 * (L.scal + L.m)))[o];
+  const uintptr_t p = one.by_value(L.m) ? (uintptr_t)one.p : (uintptr_t)((ConstPtr)(const uint64_t*)(st + 2 * (L.scal + L.m)))[o];
   U128* base = st + 2 * o * L.per;
   ipa_begin_body<FP>((const U128*)(GlobalPtr)p, base + 2 * L.a[0], base + 2 * L.b[0], base + 2 * L.s, L.n,
                      ipa_scalar<FP>(st, L, one, 0, o));
@@ -474,7 +477,7 @@ void ipa_sum_fill(const uint64_t* u, const uint64_t* init, uint32_t k, size_t co
 // fn(integral_constant<int, 0>) ... fn(integral_constant<int, N - 1>): the accumulators are indexed by constants from the
 // front end on, so they are registers whatever the unroller decides
 template <int N, class Fn>
-__device__ __forceinline__ void ipa_static_for(Fn&& fn) {
+H2_HD void ipa_static_for(Fn&& fn) {
   if constexpr (N > 0) {
     ipa_static_for<N - 1>(fn);
     fn(std::integral_constant<int, N - 1>{});

@@ -47,7 +47,7 @@ __host__ __device__ constexpr uint32_t blake2b_sigma(int r, int i) {
 template <int R, int I>
 constexpr uint32_t B2B_S = blake2b_sigma(R, I);          // the message schedule as constants: m[] is never indexed at run time
 
-__device__ __forceinline__ uint64_t blake2b_rotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
+H2_HD uint64_t blake2b_rotr(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
 
 #define H2_B2B_G(a, b, c, d, x, y)                              \
   v[a] = v[a] + v[b] + (x); v[d] = blake2b_rotr(v[d] ^ v[a], 32); \
@@ -56,7 +56,7 @@ __device__ __forceinline__ uint64_t blake2b_rotr(uint64_t x, int n) { return (x 
   v[c] = v[c] + v[d];       v[b] = blake2b_rotr(v[b] ^ v[c], 63)
 
 // RFC 7693's F on h with the block m, the byte counter t (below 2^64) and the last-block flag
-__device__ __forceinline__ void blake2b_compress(uint64_t (&h)[8], const uint64_t (&m)[16], uint64_t t, bool last) {
+H2_HD void blake2b_compress(uint64_t (&h)[8], const uint64_t (&m)[16], uint64_t t, bool last) {
   constexpr uint64_t IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
                               0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
   uint64_t v[16];
@@ -83,6 +83,104 @@ __device__ __forceinline__ void blake2b_compress(uint64_t (&h)[8], const uint64_
 }
 #undef H2_B2B_G
 
+// One lane's transcript (the replay below, the prover's step kernel in h2_ipa_prove.hpp): the chaining words and the byte
+// counter in registers, the block buffer the ring of two blocks the header describes, word w at ring[w * STRIDE] -- STRIDE =
+// 64 in LDS with `ring` already at the lane's word 0, STRIDE = 1 for a host instantiation
+template <int STRIDE>
+struct B2bLane {
+  uint64_t h[8], t;
+  uint32_t buflen, cur;
+  uint32_t* ring;
+
+  // byte o (mod 256) of the ring, as an index into its bytes
+  H2_HD uint32_t at(uint32_t o) const { return ((o & 255u) >> 2) * (uint32_t)(4 * STRIDE) + (o & 3u); }
+
+  // st: the 52 words of an exported state (a buflen above 128 is read as 128)
+  H2_HD void load(const uint32_t* st, uint32_t* ring_) {
+    ring = ring_;
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] = (uint64_t)st[2 * i] | ((uint64_t)st[2 * i + 1] << 32);
+    t = (uint64_t)st[16] | ((uint64_t)st[17] << 32);
+#pragma unroll
+    for (int w = 0; w < 32; w++) ring[w * STRIDE] = st[18 + w];
+    buflen = st[50] < 128u ? st[50] : 128u;
+    cur = 0;
+  }
+  // the current block's words, the bytes from `valid` on read as zero
+  H2_HD void block(uint64_t (&m)[16], uint32_t valid) const {
+#pragma unroll
+    for (int i = 0; i < 32; i++) {
+      const uint32_t w = ring[(cur * 32 + i) * STRIDE];
+      const int rem = (int)valid - 4 * i;
+      const uint32_t mask = rem >= 4 ? 0xFFFFFFFFu : rem <= 0 ? 0u : (1u << (8 * rem)) - 1u;
+      if (i & 1)
+        m[i >> 1] |= (uint64_t)(w & mask) << 32;
+      else
+        m[i >> 1] = w & mask;
+    }
+  }
+  // one piece of up to 66 bytes: the tag, then the first len - 1 bytes of d.  A block that is full with more input behind
+  // it is compressed and the other one becomes current: at most one compression per piece
+  H2_HD void absorb(const uint32_t (&d)[16], uint32_t tag, uint32_t len) {
+    uint8_t* ring8 = (uint8_t*)ring;
+    uint32_t pw[17];
+    pw[0] = tag | (d[0] << 8);
+#pragma unroll
+    for (int i = 1; i < 16; i++) pw[i] = (d[i - 1] >> 24) | (d[i] << 8);
+    pw[16] = d[15] >> 24;
+    const uint32_t base = cur * 128 + buflen;
+#pragma unroll
+    for (int i = 0; i < 66; i++)
+      if ((uint32_t)i < len) ring8[at(base + i)] = (uint8_t)(pw[i >> 2] >> (8 * (i & 3)));
+    buflen += len;
+    if (buflen > 128) {
+      uint64_t m[16];
+      block(m, 128);
+      t += 128;
+      blake2b_compress(h, m, t, false);
+      cur ^= 1;
+      buflen -= 128;
+    }
+  }
+  // Challenge255: the digest of a COPY of the state, reduced modulo the field, Montgomery limbs
+  template <class FS>
+  H2_HD Fe<FS> squeeze() const {
+    uint64_t m[16], hc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) hc[i] = h[i];
+    block(m, buflen);
+    blake2b_compress(hc, m, t + buflen, true);
+    Fe<FS> lo, hi;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      lo.v[2 * i] = (uint32_t)hc[i];
+      lo.v[2 * i + 1] = (uint32_t)(hc[i] >> 32);
+      hi.v[2 * i] = (uint32_t)hc[4 + i];
+      hi.v[2 * i + 1] = (uint32_t)(hc[4 + i] >> 32);
+    }
+    return fe_from_wide(lo, hi);
+  }
+  // the state as it stands, exported: the bytes behind buflen zero
+  H2_HD void store(uint32_t* so) const {
+    uint64_t m[16];
+    block(m, buflen);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      so[2 * i] = (uint32_t)h[i];
+      so[2 * i + 1] = (uint32_t)(h[i] >> 32);
+    }
+    so[16] = (uint32_t)t;
+    so[17] = (uint32_t)(t >> 32);
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      so[18 + 2 * i] = (uint32_t)m[i];
+      so[19 + 2 * i] = (uint32_t)(m[i] >> 32);
+    }
+    so[50] = buflen;
+    so[51] = 0;
+  }
+};
+
 // Lane p replays proof p (the lanes behind `count` repeat the last proof and store nothing, so the wave stays whole).
 // states: count x 208 bytes; points: count x (2k + 1) affine points in the API form with their decompression status;
 // scalars: count x 64 bytes, c || f as they stand in the stream; out: count x (k + 4) elements xi, z, u_0 .. u_(k-1), c, f
@@ -94,39 +192,13 @@ ipa_replay_kernel(const uint32_t* __restrict__ states, const U128* __restrict__ 
   using FS = typename CV::Scalar;
   using FB = typename CV::Base;
   __shared__ uint32_t ring[64 * IPA_REPLAY_THREADS];
-  uint8_t* ring8 = (uint8_t*)ring;
   const uint32_t lane = threadIdx.x;
   const uint32_t p_raw = blockIdx.x * IPA_REPLAY_THREADS + lane;
   const bool active = p_raw < count;
   const size_t p = active ? p_raw : count - 1;
   const uint32_t per = 2 * k + 1;
-
-  // byte o (mod 256) of this lane's ring
-  auto at = [&](uint32_t o) { return (((o & 255u) >> 2) << 8) | (lane << 2) | (o & 3u); };
-
-  const uint32_t* st = states + p * (TRANSCRIPT_STATE_BYTES / 4);
-  uint64_t h[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) h[i] = (uint64_t)st[2 * i] | ((uint64_t)st[2 * i + 1] << 32);
-  uint64_t t = (uint64_t)st[16] | ((uint64_t)st[17] << 32);
-#pragma unroll
-  for (int w = 0; w < 32; w++) ring[w * IPA_REPLAY_THREADS + lane] = st[18 + w];
-  uint32_t buflen = st[50] < 128u ? st[50] : 128u;
-  uint32_t cur = 0;                                        // the ring's current block
-
-  // the current block's words, the bytes from `valid` on read as zero
-  auto block = [&](uint64_t (&m)[16], uint32_t valid) {
-#pragma unroll
-    for (int i = 0; i < 32; i++) {
-      const uint32_t w = ring[(cur * 32 + i) * IPA_REPLAY_THREADS + lane];
-      const int rem = (int)valid - 4 * i;
-      const uint32_t mask = rem >= 4 ? 0xFFFFFFFFu : rem <= 0 ? 0u : (1u << (8 * rem)) - 1u;
-      if (i & 1)
-        m[i >> 1] |= (uint64_t)(w & mask) << 32;
-      else
-        m[i >> 1] = w & mask;
-    }
-  };
+  B2bLane<IPA_REPLAY_THREADS> b;
+  b.load(states + p * (TRANSCRIPT_STATE_BYTES / 4), ring + lane);
 
   uint32_t bad_point = 0, bad_scalar = 0, zero_challenge = 0;
   const uint32_t pieces = 2 * k + 4;
@@ -160,40 +232,9 @@ ipa_replay_kernel(const uint32_t* __restrict__ states, const U128* __restrict__ 
       tag = 1;
       len = squeeze ? 66 : 65;                             // the squeeze's 0x00 rides behind the point
     }
-    // the piece's bytes, tag first, packed into words: byte i is byte i & 3 of pw[i >> 2]
-    uint32_t pw[17];
-    pw[0] = tag | (d[0] << 8);
-#pragma unroll
-    for (int i = 1; i < 16; i++) pw[i] = (d[i - 1] >> 24) | (d[i] << 8);
-    pw[16] = d[15] >> 24;
-    const uint32_t base = cur * 128 + buflen;
-#pragma unroll
-    for (int i = 0; i < 66; i++)
-      if ((uint32_t)i < len) ring8[at(base + i)] = (uint8_t)(pw[i >> 2] >> (8 * (i & 3)));
-    buflen += len;
-    if (buflen > 128) {                                    // the block is full and more input has followed
-      uint64_t m[16];
-      block(m, 128);
-      t += 128;
-      blake2b_compress(h, m, t, false);
-      cur ^= 1;
-      buflen -= 128;
-    }
+    b.absorb(d, tag, len);
     if (squeeze) {                                         // the digest of a COPY, reduced: Challenge255
-      uint64_t m[16], hc[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) hc[i] = h[i];
-      block(m, buflen);
-      blake2b_compress(hc, m, t + buflen, true);
-      Fe<FS> lo, hi;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        lo.v[2 * i] = (uint32_t)hc[i];
-        lo.v[2 * i + 1] = (uint32_t)(hc[i] >> 32);
-        hi.v[2 * i] = (uint32_t)hc[4 + i];
-        hi.v[2 * i + 1] = (uint32_t)(hc[4 + i] >> 32);
-      }
-      const Fe<FS> ch = fe_from_wide(lo, hi);
+      const Fe<FS> ch = b.template squeeze<FS>();
       const uint32_t slot = piece < 2 ? piece : 2 + (piece - 3) / 2;
       if (slot >= 2 && ch.is_zero()) zero_challenge = 1;
       if (active) fe_store<FS>(out + 2 * (p * (k + 4) + slot), ch);
@@ -201,25 +242,7 @@ ipa_replay_kernel(const uint32_t* __restrict__ states, const U128* __restrict__ 
   }
   if (!active) return;
   status[p] = bad_point ? 1 : bad_scalar ? 2 : zero_challenge ? 3 : 0;
-  if (states_out) {
-    uint32_t* so = states_out + p * (TRANSCRIPT_STATE_BYTES / 4);
-    uint64_t m[16];
-    block(m, buflen);
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      so[2 * i] = (uint32_t)h[i];
-      so[2 * i + 1] = (uint32_t)(h[i] >> 32);
-    }
-    so[16] = (uint32_t)t;
-    so[17] = (uint32_t)(t >> 32);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      so[18 + 2 * i] = (uint32_t)m[i];
-      so[19 + 2 * i] = (uint32_t)(m[i] >> 32);
-    }
-    so[50] = buflen;
-    so[51] = 0;
-  }
+  if (states_out) b.store(states_out + p * (TRANSCRIPT_STATE_BYTES / 4));
 }
 
 template <class CV>

@@ -527,7 +527,7 @@ __device__ __forceinline__ uint32_t chacha_rotl(uint32_t v, int c) { return (v <
 // ff's from_bytes_wide / Challenge255: the 512-bit integer lo + hi 2^256 reduced, as Montgomery limbs.  lo, hi < 2^256 need
 // not be reduced: a Montgomery product with one factor < p is < 2p before its final subtraction
 template <class FP>
-__device__ __forceinline__ Fe<FP> fe_from_wide(const Fe<FP>& lo, const Fe<FP>& hi) {
+H2_HD Fe<FP> fe_from_wide(const Fe<FP>& lo, const Fe<FP>& hi) {
   Fe<FP> r2;
 #pragma unroll
   for (int k = 0; k < 8; k++) r2.v[k] = FP::R2(k);

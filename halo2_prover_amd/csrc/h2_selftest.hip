@@ -4,6 +4,7 @@
 #include "h2_internal.hpp"
 #include "h2_field29_chain.hpp"
 #include "h2_host.hpp"
+#include "h2_ipa_prove.hpp"
 #include "h2_poseidon.hpp"
 
 #include <cstdio>
@@ -378,6 +379,113 @@ extern "C" int h2_selftest_modmul_rate(int curve, int waves_per_simd, int iters,
   hipDeviceProp_t prop;
   H2_TRY(hipGetDeviceProperties(&prop, c->device));
   return launched(ops->modmul_rate(prop.multiProcessorCount * waves_per_simd, iters, c->stream, modmul_per_s), "modmul_rate_kernel");
+}
+
+// ---- the IPA prover's transcript step (h2_ipa_prove.hpp): the host instantiation of what a lane of the kernel runs -----
+namespace {
+template <class FP>
+void ipa_inv_run(int form, const uint64_t a[4], uint64_t out[4]) {
+  Fe<FP> x;
+  memcpy(x.v, a, 32);
+  const Fe<FP> r = form ? fe_inv(x) : fe_inv_divsteps(x);
+  memcpy(out, r.v, 32);
+}
+template <class CV>
+void ipa_step_run(int form, const uint8_t* state_in, const uint64_t* lr, const uint64_t* lrf, uint8_t* wire, uint8_t* state_out,
+                  uint64_t* out, uint32_t* status) {
+  using FS = typename CV::Scalar;
+  uint32_t ring[64] = {}, st[TRANSCRIPT_STATE_BYTES / 4], w[16];
+  memcpy(st, state_in, TRANSCRIPT_STATE_BYTES);
+  B2bLane<1> b;
+  b.load(st, ring);
+  Fe<typename CV::Base> pts[4];
+  for (int i = 0; i < 4; i++) memcpy(pts[i].v, lr + 4 * i, 32);
+  const Fe<FS> u = ipa_step_points<CV, 1>(b, pts, w);
+  Fe<FS> l, r, f, uinv;
+  memcpy(l.v, lrf, 32);
+  memcpy(r.v, lrf + 4, 32);
+  memcpy(f.v, lrf + 8, 32);
+  *status = form ? ipa_step_fold<FS, 1>(u, l, r, f, uinv) : ipa_step_fold<FS, 0>(u, l, r, f, uinv);
+  b.store(st);
+  memcpy(wire, w, 64);
+  memcpy(state_out, st, TRANSCRIPT_STATE_BYTES);
+  memcpy(out, u.v, 32);
+  memcpy(out + 4, uinv.v, 32);
+  memcpy(out + 8, f.v, 32);
+}
+template <class FS>
+void ipa_fold_run(int form, const uint64_t* in, uint64_t* out, uint32_t* status) {
+  Fe<FS> u, l, r, f, uinv;
+  memcpy(u.v, in, 32);
+  memcpy(l.v, in + 4, 32);
+  memcpy(r.v, in + 8, 32);
+  memcpy(f.v, in + 12, 32);
+  *status = form ? ipa_step_fold<FS, 1>(u, l, r, f, uinv) : ipa_step_fold<FS, 0>(u, l, r, f, uinv);
+  memcpy(out, uinv.v, 32);
+  memcpy(out + 4, f.v, 32);
+}
+template <class FS>
+void ipa_scalar_run(const uint8_t* state_in, const uint64_t* s, uint8_t* canon, uint8_t* state_out) {
+  uint32_t ring[64] = {}, st[TRANSCRIPT_STATE_BYTES / 4], w[8];
+  memcpy(st, state_in, TRANSCRIPT_STATE_BYTES);
+  B2bLane<1> b;
+  b.load(st, ring);
+  Fe<FS> x;
+  memcpy(x.v, s, 32);
+  ipa_step_scalar<FS, 1>(b, x, w);
+  b.store(st);
+  memcpy(canon, w, 32);
+  memcpy(state_out, st, TRANSCRIPT_STATE_BYTES);
+}
+}  // namespace
+extern "C" int h2_selftest_field_inv(int field, int form, const uint64_t a[4], uint64_t out[4]) {
+  if (!a || !out || form < 0 || form > 1) return H2_EINVAL;
+  switch (field) {
+    case 0: ipa_inv_run<BN254_FQ>(form, a, out); return H2_OK;
+    case 1: ipa_inv_run<BN254_FR>(form, a, out); return H2_OK;
+    case 2: ipa_inv_run<PASTA_FP>(form, a, out); return H2_OK;
+    case 3: ipa_inv_run<PASTA_FQ>(form, a, out); return H2_OK;
+  }
+  return H2_EINVAL;
+}
+extern "C" int h2_selftest_ipa_step(int curve, int form, const uint8_t state_in[208], const uint64_t lr[16], const uint64_t lrf[12],
+                                    uint8_t wire[64], uint8_t state_out[208], uint64_t out[12], uint32_t* status) {
+  if (!state_in || !lr || !lrf || !wire || !state_out || !out || !status || form < 0 || form > 1) return H2_EINVAL;
+  if (curve == H2_PALLAS)
+    ipa_step_run<PALLAS_CURVE>(form, state_in, lr, lrf, wire, state_out, out, status);
+  else if (curve == H2_VESTA)
+    ipa_step_run<VESTA_CURVE>(form, state_in, lr, lrf, wire, state_out, out, status);
+  else
+    return H2_EINVAL;
+  return H2_OK;
+}
+extern "C" int h2_selftest_ipa_fold(int curve, int form, const uint64_t in[16], uint64_t out[8], uint32_t* status) {
+  if (!in || !out || !status || form < 0 || form > 1) return H2_EINVAL;
+  if (curve == H2_PALLAS)
+    ipa_fold_run<PALLAS_CURVE::Scalar>(form, in, out, status);
+  else if (curve == H2_VESTA)
+    ipa_fold_run<VESTA_CURVE::Scalar>(form, in, out, status);
+  else
+    return H2_EINVAL;
+  return H2_OK;
+}
+extern "C" int h2_selftest_ipa_step_scalar(int curve, const uint8_t state_in[208], const uint64_t s[4], uint8_t canon[32],
+                                           uint8_t state_out[208]) {
+  if (!state_in || !s || !canon || !state_out) return H2_EINVAL;
+  if (curve == H2_PALLAS)
+    ipa_scalar_run<PALLAS_CURVE::Scalar>(state_in, s, canon, state_out);
+  else if (curve == H2_VESTA)
+    ipa_scalar_run<VESTA_CURVE::Scalar>(state_in, s, canon, state_out);
+  else
+    return H2_EINVAL;
+  return H2_OK;
+}
+// tests and tools only: the inversion of the step kernel (0: divsteps, the product's; 1: fe_inv's Fermat chain)
+extern "C" int h2_selftest_set_ipa_inv_form(int form) {
+  std::lock_guard<std::recursive_mutex> lk(g_h2_mu);
+  if (form < 0 || form > 1) return H2_EINVAL;
+  g_knobs.ipa_inv_form = form;
+  return H2_OK;
 }
 
 // ---- Poseidon (h2_poseidon.hpp) --------------------------------------------------------------------------------------

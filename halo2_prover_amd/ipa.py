@@ -15,6 +15,8 @@ points of every proof are decompressed by one kernel launch (h2_pasta_points_dec
 N compute_s vectors comes from h2_ipa_challenge_products_sum_device, none of them materialised.
 `verify_proofs_bytes` is the same verifier behind ONE C ABI call, h2_ipa_verify_proofs: the transcripts are replayed on the
 device from exported Blake2b midstates and the scalars of every combined check are made there.
+`create_proofs_bytes` is the prover behind ONE C ABI call, h2_ipa_create_proofs: the transcripts run on the device too, a
+lane per opening behind every round's MSM, so no round reads anything back.
 Polynomials are (n, 4) int64 CUDA tensors viewing 4 x u64 Montgomery limbs (numpy uint64 arrays are uploaded); points are
 affine (x, y) pairs of canonical ints, None for the identity.  The transcript is transcript.Blake2bTranscript on the
 curve.  `ParamsIPA::new`'s hash-to-curve is not here: the bases are the caller's.  There is no CPU fallback.
@@ -258,6 +260,72 @@ def _create_proofs_group(params, items):
         tr.write_scalar(f[i])
         proofs.append(bytes(tr.bytes))
     return proofs
+
+
+def create_proofs_bytes(params, items):
+    """create_proofs through ONE C ABI call per group of MAX_BATCH (h2_ipa_create_proofs): items as
+    create_proofs takes them, (transcript, p, p_blind, x3, rng, s_poly or None), each transcript a transcript.Blake2bMidstate
+    standing where create_proof would start -> list[bytes], entry i the (2k + 3) * 32 bytes create_proof writes for the item;
+    midstate i is advanced to where create_proof leaves the transcript (behind f).  The transcripts run on the device, one
+    lane per opening: from round 0 to f nothing goes through the host.
+
+    Every random value is drawn up front from the item's own rng in create_proof's order -- the 32-byte seed when s_poly is
+    None, s_blind, then l_j, r_j for j = 0 .. k - 1; none depends on the transcript, so the stream per item is the one
+    create_proofs draws.  A ValueError for BN254 (the wire form is the Pasta one) and for a p or an s_poly that does not have
+    n coefficients; a RuntimeError if a challenge came out zero (probability about 2^-254 per round)."""
+    if params.curve == 0:
+        raise ValueError("create_proofs_bytes: the Pasta wire form; BN254 openings go through create_proofs")
+    items = list(items)
+    out = []
+    for first in range(0, len(items), MAX_BATCH):
+        out.extend(_create_proofs_bytes_group(params, items[first:first + MAX_BATCH]))
+    return out
+
+
+def _create_proofs_bytes_group(params, items):
+    from .transcript import STATE_BYTES
+    k, n, P, m = params.k, params.n, params.p, len(items)
+    ps = [params.column(it[1]) for it in items]
+    if any(p.shape[0] != n for p in ps):
+        raise ValueError("create_proofs_bytes: p.len() != n")
+    s_polys = [None if it[5] is None else params.column(it[5]) for it in items]
+    if any(s is not None and s.shape[0] != n for s in s_polys):
+        raise ValueError("create_proofs_bytes: s_poly.len() != n")
+    seeds = bytearray(32 * m)
+    s_blind, round_blinds = [], []
+    for i, it in enumerate(items):
+        rng = it[4]
+        if s_polys[i] is None:
+            seeds[32 * i:32 * i + 32] = bytes(rng(32))
+        s_blind.append(random_scalar(rng, P))
+        round_blinds.extend(random_scalar(rng, P) for _ in range(2 * k))
+
+    def scalars(values):
+        return np.ascontiguousarray(np.concatenate([params.mont(v) for v in values]))
+
+    states = bytearray()
+    for it in items:
+        st = it[0].export()
+        if len(st) != STATE_BYTES:
+            raise ValueError("create_proofs_bytes: a midstate is %d bytes" % STATE_BYTES)
+        states += st
+    states = (ctypes.c_char * len(states)).from_buffer(states)
+    seeds = (ctypes.c_char * len(seeds)).from_buffer(seeds)
+    d_p = (ctypes.c_void_p * m)(*[p.data_ptr() for p in ps])
+    d_s = (ctypes.c_void_p * m)(*[None if s is None else s.data_ptr() for s in s_polys])
+    pb, x3, sb, rb = scalars([it[2] for it in items]), scalars([it[3] for it in items]), scalars(s_blind), scalars(round_blinds)
+    per = (2 * k + 3) * 32
+    proofs = ctypes.create_string_buffer(m * per)
+    states_out = ctypes.create_string_buffer(m * STATE_BYTES)
+    status = (ctypes.c_uint32 * m)()
+    st = params._L.h2_ipa_create_proofs(params.curve, params.bases.handle, k, m, states, d_p, pb.ctypes.data, x3.ctypes.data, d_s, seeds,
+                                        sb.ctypes.data, rb.ctypes.data, proofs, states_out, status)
+    _lib.check(st, "h2_ipa_create_proofs")
+    if any(status):
+        raise RuntimeError("create_proofs_bytes: a challenge of opening %d was zero" % list(status).index(1))
+    for i, it in enumerate(items):
+        it[0]._st.raw = states_out.raw[i * STATE_BYTES:(i + 1) * STATE_BYTES]
+    return [proofs.raw[i * per:(i + 1) * per] for i in range(m)]
 
 
 def verify_proof(params, transcript, P, x3, v):

@@ -102,6 +102,9 @@ SYMBOLS = {
     "h2_transcript_challenge": (_I, [_I, _P, _P]),
     "h2_ipa_replay_device": (_I, [_I, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_ipa_verify_proofs": (_I, [_I, _U64, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_prove_state_bytes": (_I, [_U32, _Z, ctypes.POINTER(_Z)]),
+    "h2_ipa_prove_rounds_device": (_I, [_I, _U64, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_ipa_create_proofs": (_I, [_I, _U64, _U32, _Z, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "h2_poseidon_constants": (_I, [_I, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_poseidon_permute_device": (_I, [_I, _U32, _U32, _P, _P, _Z, _P]),
     "h2_poseidon_hash_device": (_I, [_I, _U32, _U32, _P, _Z, _Z, _Z, _P, _P]),
@@ -188,6 +191,11 @@ SELFTEST_SYMBOLS = {
     "h2_selftest_poseidon_wide_table": (_I, [_I, _U32, _U32, _U32, _P, _Z, ctypes.POINTER(_Z)]),
     "h2_selftest_poseidon_wide": (_I, [_I, _U32, _U32, _U32, _I, _I, _U32, _P, _P]),
     "h2_selftest_set_poseidon_wide_form": (_I, [_I]),
+    "h2_selftest_field_inv": (_I, [_I, _I, _P, _P]),
+    "h2_selftest_ipa_step": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "h2_selftest_ipa_fold": (_I, [_I, _I, _P, _P, _P]),
+    "h2_selftest_ipa_step_scalar": (_I, [_I, _P, _P, _P, _P]),
+    "h2_selftest_set_ipa_inv_form": (_I, [_I]),
 }
 
 # the RNG callback of the product surface: void (*)(void* ctx, uint8_t* out, size_t n)

@@ -953,6 +953,62 @@ int h2_ipa_verify_proofs(h2_curve_t curve, uint64_t bases, uint32_t k, size_t co
                          const uint8_t* const* proofs, const size_t* proof_lens, const uint64_t* commitments, const uint64_t* x3,
                          const uint64_t* v, h2_rng_fill_t rng, void* rng_ctx, int* ok, int* all_ok, size_t* checks_out);
 
+/* ---- the IPA prover behind one call, on the Pasta curves -----------------------------------------------------------
+ * create_proof of the inner product argument (poly/ipa/commitment/prover.rs) for m openings of one k in lockstep with the
+ * transcripts on the device: behind every round's MSM one lane per opening writes L_j, R_j in the wire form, absorbs them,
+ * squeezes u_j, inverts it and writes the scalars of the next round, so from round 0 to f nothing goes through the host.
+ * DESIGN.md section 7.20.  h2_version() did not change for these entry points, it stays 1002: a host detects them by their
+ * symbols.
+ *
+ * h2_ipa_prove_state_bytes: host only, no h2_init needed.  The size of the state h2_ipa_prove_rounds_device works in: its
+ * first h2_ipa_batch_state_bytes(k, m) bytes are that call's state, unchanged; behind them what the route keeps resident --
+ * every blind, f, the midstates, the rounds' points.  A multiple of 16.  H2_EINVAL for k = 0, k > H2_IPA_MAX_K, m = 0,
+ * m > H2_IPA_MAX_BATCH or a null out.
+ *
+ * h2_ipa_prove_rounds_device: begin, k rounds and final of h2_ipa_*_batch_device with the transcript step behind each.
+ *   d_p           HOST array of m device pointers: p'_i, 2^k coefficients each, only read
+ *   x3, z, f0     m x 4 limbs each: the opening points, the challenges z_i, and f_i as it stands, s_blind_i xi_i + p_blind_i
+ *   round_blinds  m x 2k x 4 limbs: l_0, r_0, l_1, r_1, ... of opening i
+ *   states        m midstates: each transcript where it stands behind the two challenges squeezed after S
+ *   d_state       h2_ipa_prove_state_bytes(k, m) bytes, 16-byte aligned; what an earlier use left in it does not matter
+ *   d_tail        m x (2k + 2) x 32 bytes, 16-byte aligned: L_0, R_0, ..., L_(k-1), R_(k-1), c, f of opening i in the wire form
+ *   d_states_out  null, or m x 208 bytes, 16-byte aligned: the midstates behind f
+ *   d_status      m x uint32_t: 0, or 1 when some challenge u_j of the opening was zero -- its 1 / u_j is then taken as zero,
+ *                 nothing traps, and the opening's bytes in d_tail are unspecified
+ * All scalars are canonical Montgomery limbs.  Asynchronous on `stream` under h2_ntt_device's rules; the host arrays are read
+ * before the call returns.  ONE upload in front of the kernels; after it no host synchronisation and no device-to-host copy.
+ * Every round's MSM goes through the registered table's own launch path with its bounds proof, and what that path refuses
+ * is found before anything is enqueued.  No device memory is allocated beyond the context's MSM workspace.
+ * H2_EINVAL, before anything is enqueued, for H2_BN254 (the wire form is the Pasta one) or an unknown curve, k = 0,
+ * k > H2_IPA_MAX_K, m = 0, m > H2_IPA_MAX_BATCH, a null array, a null or misaligned device pointer (every d_p[i] included;
+ * d_status 4-byte aligned), a scalar that is not canonical, a state whose buflen is above 128, a handle of another curve or
+ * one that does not hold exactly 2^k + 2 bases (H2_EHANDLE for one that is not registered).
+ *
+ * h2_ipa_create_proofs: upstream's create_proof for m openings with EVERY random value supplied by the caller, so the bytes
+ * are a function of the arguments.  The blinds and the seeds must be uniform and secret: they are what hides the polynomials.
+ *   states        where each item's transcript stands before S
+ *   d_p, p_blind  HOST array of m device pointers to the polynomials (2^k coefficients, only read); their blinds
+ *   d_s_poly      HOST array of m device pointers to the blinding polynomials (only read); entry i null: s_poly_i is
+ *                 expanded from the 32 bytes at seeds + 32 i as h2_chacha20_scalars_device expands them from block 0
+ *   seeds         m x 32 bytes; may be null when no d_s_poly entry is null
+ *   s_blind       m x 4 limbs; round_blinds as above
+ *   proofs        m x (2k + 3) x 32 bytes: S, k x (L_j, R_j), c, f -- what h2_ipa_verify_proofs takes
+ *   states_out    null, or m midstates behind f;  status: m words, as d_status above
+ * The preamble -- the 2 m evaluations, s_poly_i[0] -= s_poly_i(x3_i), the m commitments S_i as one MSM, S absorbed and xi, z
+ * squeezed on the host, p'_i = xi_i s_poly_i + p_i with p'_i[0] -= p_i(x3_i) -- then h2_ipa_prove_rounds_device's work, then one
+ * read-back.  Three stream synchronisations per call whatever k and m are: behind the evaluations, behind S, at the end.
+ * Synchronous, on the context's stream; scratch comes from the context's arenas.  H2_EINVAL as above, and for a null seeds
+ * with a null d_s_poly entry. */
+int h2_ipa_prove_state_bytes(uint32_t k, size_t m, size_t* out);
+int h2_ipa_prove_rounds_device(h2_curve_t curve, uint64_t bases, uint32_t k, size_t m, const void* const* d_p, const uint64_t* x3,
+                               const uint64_t* z, const uint64_t* f0, const uint64_t* round_blinds,
+                               const h2_transcript_state_t* states, void* d_state, void* d_tail, void* d_states_out,
+                               void* d_status, void* stream);
+int h2_ipa_create_proofs(h2_curve_t curve, uint64_t bases, uint32_t k, size_t m, const h2_transcript_state_t* states,
+                         const void* const* d_p, const uint64_t* p_blind, const uint64_t* x3, const void* const* d_s_poly,
+                         const uint8_t* seeds, const uint64_t* s_blind, const uint64_t* round_blinds, uint8_t* proofs,
+                         h2_transcript_state_t* states_out, uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,26 @@ int h2_selftest_poseidon_wide_table(int curve, uint32_t width, uint32_t r_f, uin
 int h2_selftest_poseidon_wide(int curve, uint32_t width, uint32_t r_f, uint32_t r_p, int form, int op, uint32_t len,
                               const uint64_t* in, uint64_t* out);
 int h2_selftest_set_poseidon_wide_form(int form);
+/* The IPA prover's transcript step (h2_ipa_prove_rounds_device; csrc/h2_ipa_prove.hpp): the host instantiation of what one
+ * lane of the step kernel runs, no GPU and no h2_init.  form 0: the inversion by a fixed number of divsteps (the
+ * product's), 1: fe_inv's Fermat chain.
+ * h2_selftest_field_inv: field as h2_selftest_field_op; a, out: 4 x u64 Montgomery limbs; out = 1 / a, and 0 for a = 0.
+ * h2_selftest_ipa_step: the lane's work behind a round on `curve` (H2_PALLAS or H2_VESTA; H2_EINVAL otherwise).  state_in:
+ *   the 208 bytes of the midstate; lr: L || R, affine, 16 Montgomery limbs of the base field, (0, 0) the identity; lrf: the
+ *   round's blinds l, r and f as it stands (Montgomery limbs of the scalar field) -> wire: the two 32-byte wire forms;
+ *   state_out: the midstate behind the squeeze; out = u || 1 / u || f + l / u + r u; *status = 1 if u = 0, else 0.
+ * h2_selftest_ipa_fold: the part of that behind the squeeze on a caller's u: in = u || l || r || f ->
+ *   out = 1 / u || f + l / u + r u, *status as above (u = 0: out = 0 || f, *status = 1).
+ * h2_selftest_ipa_step_scalar: the lane's common_scalar behind the final kernel: s (Montgomery limbs) -> canon, its 32
+ *   canonical little-endian bytes as they go to the proof; state_out: the midstate behind 0x02 || canon.
+ * h2_selftest_set_ipa_inv_form: tests and tools only -- the inversion the step kernel launches with from now on. */
+int h2_selftest_field_inv(int field, int form, const uint64_t a[4], uint64_t out[4]);
+int h2_selftest_ipa_step(int curve, int form, const uint8_t state_in[208], const uint64_t lr[16], const uint64_t lrf[12],
+                         uint8_t wire[64], uint8_t state_out[208], uint64_t out[12], uint32_t* status);
+int h2_selftest_ipa_fold(int curve, int form, const uint64_t in[16], uint64_t out[8], uint32_t* status);
+int h2_selftest_ipa_step_scalar(int curve, const uint8_t state_in[208], const uint64_t s[4], uint8_t canon[32],
+                                uint8_t state_out[208]);
+int h2_selftest_set_ipa_inv_form(int form);
 
 #ifdef __cplusplus
 }
